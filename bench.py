@@ -10,10 +10,14 @@ Nothing crosses to the host inside a step and no stage is replayed from precompu
 N > 1 every rank runs the extract half on its own batch; before clustering the ranks all-gather their treads (RCCL) and
 every rank clusters the (tid, unit) groups it owns (strling_amd/dist.py).
 
-Prints ONE JSON line on rank 0: value = reads of ALL ranks / max-rank time; `roofline` for the slowest kernel launch
-(HIP events on the kernels' own stream); `cpu_baseline` = the oracle's extract + cluster over the same stages, 1 thread;
-`end_to_end` = the `strling extract` -> `strling call` / `strling merge` processes on a BAM FILE on this box (zlib level 6, qualities,
-aux tags, .bai), whole-process wall clock, with a share of the .bin and of -bounds.txt checked against the oracle.
+Prints ONE JSON line on rank 0: value = reads of ALL ranks / max-rank time, ms_per_step = one timed step.  A plain run does
+only that: set up, warm up, time --steps steps, print.  --dump-outputs DIR also writes what the last timed step computed
+(the treads, bounds and unplaced rows a caller of the path receives) as DIR/<array>.<field>.npy.
+--full adds what takes runs of its own: `roofline` for the slowest kernel launch (HIP events on the kernels' own stream) and
+the check that the last pipelined step reproduced the synchronous pass; `cpu_baseline` = the oracle's extract + cluster over
+the same stages, 1 thread; `end_to_end` = the `strling extract` -> `strling call` / `strling merge` processes on a BAM FILE
+the run writes (zlib level 6, qualities, aux tags, .bai), whole-process wall clock, with a share of the .bin and of
+-bounds.txt checked against the oracle; `build` = what the library was built with.
 """
 import argparse
 import json
@@ -47,7 +51,13 @@ def main():
                     "the 30x sample BASELINE.json names; ~8 min to write at zlib level 6 on 16 cores) when the box has the room (>= 75 GB free in the work directory, >= 12 CPUs) and N = 1, "
                     "else 2^26 pairs (1.3e8 reads, ~2 min to write); the line's end_to_end.input says which ran")
     ap.add_argument("--cache", default="", help="directory to keep the generated batch in (profiling runs reload it instead of forking generators)")
+    ap.add_argument("--full", action="store_true", help="also the roofline, the CPU baselines, end_to_end and the build info (the options above "
+                    "that shape those legs take effect only with --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's treads / bounds / unplaced rows as "
+                    "DIR/<array>.<field>.npy (float64; byte strings as float32 rows of bytes; at most 64 MB, a seeded row sample beyond)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs needs --gpus 1 (with N ranks each rank clusters only the groups it owns)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` by itself: become N ranks (one per GPU) under torch.distributed.run, the launch the
@@ -65,7 +75,7 @@ def main():
 
     # ---- end to end first (it forks generators and runs the CLI, which wants the GPU to itself): BAM file -> .bin -----
     e2e = None
-    if rank == 0 and not args.no_e2e:
+    if rank == 0 and args.full and not args.no_e2e:
         # N > 1: rank 0 runs `strling extract --gpus N` (ONE process, a context per device, a contiguous share of the file each)
         # on all N devices while the other ranks wait at the rendezvous below -- they have not touched their device yet
         try:
@@ -76,7 +86,7 @@ def main():
     # When this run's own end_to_end leg was NOT the whole-genome sized file (no room / N > 1), the builder's last run of that size
     # is quoted -- under a key that says it is a quotation, not a measurement of this run
     e2e_full = None
-    if rank == 0 and world == 1 and not (e2e and e2e.get("reads", 0) >= 5e8):
+    if rank == 0 and world == 1 and args.full and not (e2e and e2e.get("reads", 0) >= 5e8):
         for rnd in ("r05", "r04"):
             try:
                 e2e_full = json.load(open(os.path.join(ROOT, "profiles", rnd, "e2e_full.json")))
@@ -222,135 +232,140 @@ def main():
     # the last timed step's results, collected after the fact, are the synchronous pass' results (same batch every step):
     # the pipelined steps computed what the un-pipelined one did
     verified = None
-    if exchange is None and args.steps > 0:
+    if exchange is None and args.steps > 0 and (args.full or args.dump_outputs):
         b_last, u_last, _ = ctx.cluster_collect()
         t_last, _ = ctx.treads_fetch()
-        verified = bool(np.array_equal(b_last, bounds) and np.array_equal(u_last, unplaced) and np.array_equal(t_last, treads))
-        if not verified:
-            raise SystemExit("bench.py: the pipelined steps did not reproduce the synchronous pass' treads / bounds")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"treads": t_last, "bounds": b_last, "unplaced": u_last})
+        if args.full:
+            verified = bool(np.array_equal(b_last, bounds) and np.array_equal(u_last, unplaced) and np.array_equal(t_last, treads))
+            if not verified:
+                raise SystemExit("bench.py: the pipelined steps did not reproduce the synchronous pass' treads / bounds")
     if world > 1:
         t = torch.tensor([el], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
-    # ---- per-launch times: a few instrumented steps with HIP events on the kernels' own stream ----------------------
-    ctx.enable_timing(True)
-    n_inst = 5
-    pair_ms, cl_ms = {}, {}
-    for _ in range(n_inst):
-        ctx.extract_device(cs, cp, n_tail, item_cap, tread_cap)
-        for k, v in ctx.pair_times().items():
-            pair_ms[k] = pair_ms.get(k, 0.0) + v / n_inst
-        ctx.cluster_resident(n_tid, window, min_support=5, max_clip_dist=max_clip_dist, pos_bits=pos_bits, fetch=False)
-        for k, v in ctx.cluster_times().items():
-            cl_ms[k] = cl_ms.get(k, 0.0) + v / n_inst
-    detail, launches = ctx.kernel_times_detail()
-    ctx.enable_timing(False)
-    launches = max(1, launches)
-    ms = {k: v / launches for k, v in detail.items()}
-    ms.update(pair_ms)
-    ms.update(cl_ms)
+    roofline = None
+    if args.full:
+        # ---- per-launch times: a few instrumented steps with HIP events on the kernels' own stream ----------------------
+        ctx.enable_timing(True)
+        n_inst = 5
+        pair_ms, cl_ms = {}, {}
+        for _ in range(n_inst):
+            ctx.extract_device(cs, cp, n_tail, item_cap, tread_cap)
+            for k, v in ctx.pair_times().items():
+                pair_ms[k] = pair_ms.get(k, 0.0) + v / n_inst
+            ctx.cluster_resident(n_tid, window, min_support=5, max_clip_dist=max_clip_dist, pos_bits=pos_bits, fetch=False)
+            for k, v in ctx.cluster_times().items():
+                cl_ms[k] = cl_ms.get(k, 0.0) + v / n_inst
+        detail, launches = ctx.kernel_times_detail()
+        ctx.enable_timing(False)
+        launches = max(1, launches)
+        ms = {k: v / launches for k, v in detail.items()}
+        ms.update(pair_ms)
+        ms.update(cl_ms)
 
-    # ---- roofline of the slowest launch -----------------------------------------------------------------------------
-    # Algorithmic bytes per launch (DESIGN.md "Kernels"):
-    #   classify   13 B of coordinates read + 4 B result word written per read, 4 B id written per kept read
-    #   stage A    4 B id + 16 B row gathered + ceil(L/2) B SEQ read, 16 B queue entry + 4 B result written per item
-    #   stage B    32 B item + ceil(L/2) B SEQ + 4 B result per item that reaches k = 5
-    #   segments   16 B item + the clipped bases (counted as ceil(L/4) B on average) + 16 B result record
-    #   compaction 16 B state read per slot + 32 B item written per survivor; soft items: 1 B flag per slot, 16 B entry
-    #              read + 16 B item written per clipped end
-    #   pair mark + probe  16 B per soft-clip record + 8 B qname hash per read (the one full pass the pair logic adds)
-    #                      + 12 B written per join item
-    #   join sort / order sort  (12 B read + 12 B written) per item per 8-bit pass (4 passes each)
-    #   replay     12 B item + ~40 B of metadata gathered per read item + 40 B per emitted tread
-    #   cluster    32 B tread read + 25 B keys/payload written, 6 sort passes x 24 B, 41 B gathered + written per tread, sweep 16 B
-    seq_b = (L + 1) // 2
-    nbw, nbs = int(st.n_stage_b_whole), int(st.n_stage_b_soft)
-    n_items = int(min(item_cap, 2.3 * n_treads + st.n_soft_items * 0.4))
-    key_passes = (pos_bits + max(n_tid, 1).bit_length() + 15 + 7) // 8
-    alg = {
-        "classify_kernel": 17.0 * n + 4.0 * st.n_scored,          # 13 B read + 4 B written per read, 4 B id per kept read
-        "score_kernel<whole,A>": (40.0 + seq_b) * st.n_scored,     # 4 B id + 16 B row gathered + SEQ + 16 B entry + 4 B result written
-        "compact_kernel<whole>": 16.0 * st.n_scored + 32.0 * nbw,
-        "score_kernel<whole,B>": (36.0 + seq_b) * nbw,
-        "soft_compact_kernel": 1.0 * st.n_scored + 32.0 * st.n_soft_items,
-        "score_kernel<segment,A>": (32.0 + (L + 3) // 4) * st.n_soft_items,
-        "compact_kernel<segment>": 16.0 * st.n_soft_items + 32.0 * nbs,
-        "score_kernel<segment,B>": (48.0 + (L + 3) // 4) * nbs,
-        "pair_soft_items_kernel": 16.0 * st.n_soft_items + 0.4 * 20.0 * st.n_soft_items,
-        "pair_probe_kernel": 8.0 * n + 20.0 * n_items,
-        "pair_join_sort": 4 * 24.0 * n_items,
-        "pair_groups_kernel": 52.0 * n_items + 44.0 * n_treads,
-        "pair_order": 0.0,   # the .bin-order sort of the treads is deferred to a fetch: clustering works from the emission keys
-        "cluster_keys_sort_groups": (57.0 + key_passes * 24.0 + 41.0) * n_treads,
-        "cluster_sweep": 16.0 * n_treads,
-        "cluster_bounds": 8.0 * n_treads + 44.0 * len(bounds),
-    }
-    if L <= 160 and not os.environ.get("STRL_SPLIT_SEGMENTS"):
-        # segments of the short-read class: stage A and B in ONE launch (no hand-over, no compaction, one fetch of the bases);
-        # the library reports it in stage A's slot, the two slots behind it hold nothing but the gap between two events
-        ms["score_kernel<segment,A+B>"] = ms.pop("score_kernel<segment,A>") + ms.pop("compact_kernel<segment>") + ms.pop("score_kernel<segment,B>")
-        alg["score_kernel<segment,A+B>"] = alg.pop("score_kernel<segment,A>")      # 16 B item + the clipped bases + 16 B result record
-        alg.pop("compact_kernel<segment>"); alg.pop("score_kernel<segment,B>")
-    grouped = ("pair_join_sort", "pair_order", "cluster_keys_sort_groups", "cluster_sweep", "cluster_bounds")   # several launches each
-    kernels = {k: (ms[k], alg[k]) for k in ms if k not in grouped}
-    groups = {"classify_kernel": ms["classify_kernel"],
-              "score_kernel<whole>": ms["score_kernel<whole,A>"] + ms["compact_kernel<whole>"] + ms["score_kernel<whole,B>"],
-              "score_kernel<soft>": ms["soft_compact_kernel"] + sum(v for k, v in ms.items() if "segment" in k),
-              "pair_logic": sum(pair_ms.values()), "cluster_pass": sum(cl_ms.values())}
-    groups.update({k: ms[k] for k in grouped})
-    dom = max(kernels, key=lambda k: kernels[k][0])     # slowest single launch
-    dom_ms, dom_bytes = kernels[dom]
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    traffic = None
-    tj, pick = {}, {}
-    try:
-        tj = json.load(open(os.path.join(ROOT, "profiles", PROFILE_ROUND, "traffic.json")))["kernels"]
-        pick = {"classify_kernel": "classify_kernel", "score_kernel<whole,A>": "<10, 64, 0, 0", "score_kernel<segment,A>": "<10, 64, 1, 0", "score_kernel<segment,A+B>": "<10, 64, 1, 2",
-                "pair_probe_kernel": "pair_probe_kernel", "pair_groups_kernel": "pair_groups_kernel"}
-        if dom in pick and n == 2 ** 25 and L == 150:
-            traffic = sum(v["hbm_bytes_corrected"] for name, v in tj.items() if pick[dom] in name) or None
-    except Exception:
+        # ---- roofline of the slowest launch -----------------------------------------------------------------------------
+        # Algorithmic bytes per launch (DESIGN.md "Kernels"):
+        #   classify   13 B of coordinates read + 4 B result word written per read, 4 B id written per kept read
+        #   stage A    4 B id + 16 B row gathered + ceil(L/2) B SEQ read, 16 B queue entry + 4 B result written per item
+        #   stage B    32 B item + ceil(L/2) B SEQ + 4 B result per item that reaches k = 5
+        #   segments   16 B item + the clipped bases (counted as ceil(L/4) B on average) + 16 B result record
+        #   compaction 16 B state read per slot + 32 B item written per survivor; soft items: 1 B flag per slot, 16 B entry
+        #              read + 16 B item written per clipped end
+        #   pair mark + probe  16 B per soft-clip record + 8 B qname hash per read (the one full pass the pair logic adds)
+        #                      + 12 B written per join item
+        #   join sort / order sort  (12 B read + 12 B written) per item per 8-bit pass (4 passes each)
+        #   replay     12 B item + ~40 B of metadata gathered per read item + 40 B per emitted tread
+        #   cluster    32 B tread read + 25 B keys/payload written, 6 sort passes x 24 B, 41 B gathered + written per tread, sweep 16 B
+        seq_b = (L + 1) // 2
+        nbw, nbs = int(st.n_stage_b_whole), int(st.n_stage_b_soft)
+        n_items = int(min(item_cap, 2.3 * n_treads + st.n_soft_items * 0.4))
+        key_passes = (pos_bits + max(n_tid, 1).bit_length() + 15 + 7) // 8
+        alg = {
+            "classify_kernel": 17.0 * n + 4.0 * st.n_scored,          # 13 B read + 4 B written per read, 4 B id per kept read
+            "score_kernel<whole,A>": (40.0 + seq_b) * st.n_scored,     # 4 B id + 16 B row gathered + SEQ + 16 B entry + 4 B result written
+            "compact_kernel<whole>": 16.0 * st.n_scored + 32.0 * nbw,
+            "score_kernel<whole,B>": (36.0 + seq_b) * nbw,
+            "soft_compact_kernel": 1.0 * st.n_scored + 32.0 * st.n_soft_items,
+            "score_kernel<segment,A>": (32.0 + (L + 3) // 4) * st.n_soft_items,
+            "compact_kernel<segment>": 16.0 * st.n_soft_items + 32.0 * nbs,
+            "score_kernel<segment,B>": (48.0 + (L + 3) // 4) * nbs,
+            "pair_soft_items_kernel": 16.0 * st.n_soft_items + 0.4 * 20.0 * st.n_soft_items,
+            "pair_probe_kernel": 8.0 * n + 20.0 * n_items,
+            "pair_join_sort": 4 * 24.0 * n_items,
+            "pair_groups_kernel": 52.0 * n_items + 44.0 * n_treads,
+            "pair_order": 0.0,   # the .bin-order sort of the treads is deferred to a fetch: clustering works from the emission keys
+            "cluster_keys_sort_groups": (57.0 + key_passes * 24.0 + 41.0) * n_treads,
+            "cluster_sweep": 16.0 * n_treads,
+            "cluster_bounds": 8.0 * n_treads + 44.0 * len(bounds),
+        }
+        if L <= 160 and not os.environ.get("STRL_SPLIT_SEGMENTS"):
+            # segments of the short-read class: stage A and B in ONE launch (no hand-over, no compaction, one fetch of the bases);
+            # the library reports it in stage A's slot, the two slots behind it hold nothing but the gap between two events
+            ms["score_kernel<segment,A+B>"] = ms.pop("score_kernel<segment,A>") + ms.pop("compact_kernel<segment>") + ms.pop("score_kernel<segment,B>")
+            alg["score_kernel<segment,A+B>"] = alg.pop("score_kernel<segment,A>")      # 16 B item + the clipped bases + 16 B result record
+            alg.pop("compact_kernel<segment>"); alg.pop("score_kernel<segment,B>")
+        grouped = ("pair_join_sort", "pair_order", "cluster_keys_sort_groups", "cluster_sweep", "cluster_bounds")   # several launches each
+        kernels = {k: (ms[k], alg[k]) for k in ms if k not in grouped}
+        groups = {"classify_kernel": ms["classify_kernel"],
+                  "score_kernel<whole>": ms["score_kernel<whole,A>"] + ms["compact_kernel<whole>"] + ms["score_kernel<whole,B>"],
+                  "score_kernel<soft>": ms["soft_compact_kernel"] + sum(v for k, v in ms.items() if "segment" in k),
+                  "pair_logic": sum(pair_ms.values()), "cluster_pass": sum(cl_ms.values())}
+        groups.update({k: ms[k] for k in grouped})
+        dom = max(kernels, key=lambda k: kernels[k][0])     # slowest single launch
+        dom_ms, dom_bytes = kernels[dom]
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
         traffic = None
-    # The slowest launch may be one that HBM does not bound at all (the scorer stages issue integer VALU instructions ~88 % of
-    # the time): report its VALU issue utilisation from the committed PMC pass next to the HBM figure, and the slowest launch
-    # that IS bound by HBM traffic (the skip-predicate pass) separately.
-    valu_frac = None
-    try:
-        pj = json.load(open(os.path.join(ROOT, "profiles", PROFILE_ROUND, "pmc_counters.json")))
-        if dom in pick and n == 2 ** 25 and L == 150:
-            insts = [v["SQ_INSTS_VALU"] for name, v in pj.items() if pick[dom] in name and "SQ_INSTS_VALU" in v]
-            if insts and dom_ms > 0:      # a wave64 VALU instruction occupies its SIMD for 4 cycles; 256 CUs x 4 SIMDs at 2.4 GHz
-                valu_frac = round(insts[0] * 4.0 / (dom_ms * 1e-3 * 2.4e9 * 1024), 3)
-    except Exception:
+        tj, pick = {}, {}
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", PROFILE_ROUND, "traffic.json")))["kernels"]
+            pick = {"classify_kernel": "classify_kernel", "score_kernel<whole,A>": "<10, 64, 0, 0", "score_kernel<segment,A>": "<10, 64, 1, 0", "score_kernel<segment,A+B>": "<10, 64, 1, 2",
+                    "pair_probe_kernel": "pair_probe_kernel", "pair_groups_kernel": "pair_groups_kernel"}
+            if dom in pick and n == 2 ** 25 and L == 150:
+                traffic = sum(v["hbm_bytes_corrected"] for name, v in tj.items() if pick[dom] in name) or None
+        except Exception:
+            traffic = None
+        # The slowest launch may be one that HBM does not bound at all (the scorer stages issue integer VALU instructions ~88 % of
+        # the time): report its VALU issue utilisation from the committed PMC pass next to the HBM figure, and the slowest launch
+        # that IS bound by HBM traffic (the skip-predicate pass) separately.
         valu_frac = None
-    c_ms, c_bytes = kernels["classify_kernel"]
-    c_traffic = None
-    try:
-        if n == 2 ** 25 and L == 150:
-            c_traffic = sum(v["hbm_bytes_corrected"] for name, v in tj.items() if "classify_kernel" in name) or None
-    except Exception:
+        try:
+            pj = json.load(open(os.path.join(ROOT, "profiles", PROFILE_ROUND, "pmc_counters.json")))
+            if dom in pick and n == 2 ** 25 and L == 150:
+                insts = [v["SQ_INSTS_VALU"] for name, v in pj.items() if pick[dom] in name and "SQ_INSTS_VALU" in v]
+                if insts and dom_ms > 0:      # a wave64 VALU instruction occupies its SIMD for 4 cycles; 256 CUs x 4 SIMDs at 2.4 GHz
+                    valu_frac = round(insts[0] * 4.0 / (dom_ms * 1e-3 * 2.4e9 * 1024), 3)
+        except Exception:
+            valu_frac = None
+        c_ms, c_bytes = kernels["classify_kernel"]
         c_traffic = None
-    c_ach = c_bytes / (c_ms * 1e-3) / 1e9 if c_ms > 0 else 0.0
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
-                "traffic_note": f"HBM bytes per launch of that kernel from profiles/{PROFILE_ROUND}/traffic.json (rocprofv3 PMC passes of the same workload and build, committed; not measured in this run)", "from_committed_profile": True,
-                "valu_issue_frac": valu_frac,
-                "valu_note": f"SQ_INSTS_VALU (profiles/{PROFILE_ROUND}/pmc_counters.json, committed) x 4 cycles / (launch time x 1024 SIMDs x 2.4 GHz): the scorer launches are bound by integer VALU issue, not by HBM",
-                "hbm_bound_launch": {"kernel": "classify_kernel", "achieved": round(c_ach, 2), "frac": round(c_ach / HBM_PEAK_GBPS, 5), "traffic": c_traffic,
-                                     "note": "slowest launch that HBM traffic bounds (13 B read + 4 B written per read, algorithmic)"},
-                "times_note": "kernel_ms / group_ms: un-overlapped launch times from instrumented steps (HIP events, one stream); ms_per_step is the "
-                              "pipelined period: pair logic + clustering of step i run on side streams beside classify + scorer of step i + 1 and the tail of step i - 1",
-                "kernel_ms": {k: round(v[0], 4) for k, v in kernels.items()},
-                "kernel_alg_bytes": {k: int(v[1]) for k, v in kernels.items()},
-                "kernel_alg_GBps": {k: round(v[1] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else 0.0 for k, v in kernels.items()},
-                "group_ms": {k: round(v, 4) for k, v in groups.items()},
-                "pipeline_alg_GBps": round(sum(alg.values()) / (el / args.steps) / 1e9, 2),
-                "survey_115B_per_read_GBps": round(115.0 * n / (el / args.steps) / 1e9, 2)}
+        try:
+            if n == 2 ** 25 and L == 150:
+                c_traffic = sum(v["hbm_bytes_corrected"] for name, v in tj.items() if "classify_kernel" in name) or None
+        except Exception:
+            c_traffic = None
+        c_ach = c_bytes / (c_ms * 1e-3) / 1e9 if c_ms > 0 else 0.0
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
+                    "traffic_note": f"HBM bytes per launch of that kernel from profiles/{PROFILE_ROUND}/traffic.json (rocprofv3 PMC passes of the same workload and build, committed; not measured in this run)", "from_committed_profile": True,
+                    "valu_issue_frac": valu_frac,
+                    "valu_note": f"SQ_INSTS_VALU (profiles/{PROFILE_ROUND}/pmc_counters.json, committed) x 4 cycles / (launch time x 1024 SIMDs x 2.4 GHz): the scorer launches are bound by integer VALU issue, not by HBM",
+                    "hbm_bound_launch": {"kernel": "classify_kernel", "achieved": round(c_ach, 2), "frac": round(c_ach / HBM_PEAK_GBPS, 5), "traffic": c_traffic,
+                                         "note": "slowest launch that HBM traffic bounds (13 B read + 4 B written per read, algorithmic)"},
+                    "times_note": "kernel_ms / group_ms: un-overlapped launch times from instrumented steps (HIP events, one stream); ms_per_step is the "
+                                  "pipelined period: pair logic + clustering of step i run on side streams beside classify + scorer of step i + 1 and the tail of step i - 1",
+                    "kernel_ms": {k: round(v[0], 4) for k, v in kernels.items()},
+                    "kernel_alg_bytes": {k: int(v[1]) for k, v in kernels.items()},
+                    "kernel_alg_GBps": {k: round(v[1] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else 0.0 for k, v in kernels.items()},
+                    "group_ms": {k: round(v, 4) for k, v in groups.items()},
+                    "pipeline_alg_GBps": round(sum(alg.values()) / (el / args.steps) / 1e9, 2),
+                    "survey_115B_per_read_GBps": round(115.0 * n / (el / args.steps) / 1e9, 2)}
 
     # ---- CPU baseline: the oracle ("port" of the reference algorithm) over the SAME stages, 1 thread, bounded sample ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         srec, sg = synth.synth_wgs(2 ** 17, seed=1234)
         sfrag = synth.frag_hist(srec)
@@ -370,7 +385,7 @@ def main():
     # ---- ... the same on every core the box grants (process-sharded: the reference is single-threaded per sample, a pipeline
     #      runs one process per sample), and a decode-inclusive single-thread leg to put beside end_to_end ----
     cpu_nproc, cpu_e2e = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu_nproc = cpu_baseline_nproc(max(4.0, args.cpu_seconds / 2))
             cpu_e2e = cpu_baseline_e2e(cpu["value"])
@@ -408,12 +423,50 @@ def main():
                        "parallelism": (f"records sharded over {world} GPU(s), no data-path collective" if exchange is None else
                                        f"records sharded over {world} GPUs; per step one RCCL all-gather of the tread arrays [{type(exchange).__name__}] "
                                        f"({exchange.pad * 32} B per rank) before clustering, every rank clusters the (tid, unit) groups it owns")},
-            "build": build_info(),
-            "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_nproc": cpu_nproc, "cpu_baseline_e2e": cpu_e2e, "end_to_end": e2e, "quoted_not_measured_end_to_end_full_size": e2e_full,
         }
+        if args.full:
+            out.update({"build": build_info(), "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_nproc": cpu_nproc, "cpu_baseline_e2e": cpu_e2e,
+                        "end_to_end": e2e, "quoted_not_measured_end_to_end_full_size": e2e_full})
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = (64 << 20) - (64 << 10)      # --dump-outputs cap, less room for the .npy headers
+DUMP_SEED = 20250101
+
+
+def dump_outputs(d, tables):
+    """tables = {name: structured array}: one file per field, d/<name>.<field>.npy.  Integer fields are written as float64 (checked
+    exact), byte strings (the repeat units) as float32 rows of their bytes.  The smaller tables are written first; a table that
+    does not fit in its share of what is left of DUMP_BYTES is written as a fixed seeded sample of its rows, kept in row order,
+    whose indices are d/<name>.rows.npy."""
+    os.makedirs(d, exist_ok=True)
+
+    def row_bytes(dt):
+        return sum(4 * dt[f].itemsize if dt[f].kind == "S" else 8 for f in dt.names)
+
+    left = DUMP_BYTES
+    names = sorted(tables, key=lambda k: tables[k].size * row_bytes(tables[k].dtype))
+    for i, name in enumerate(names):
+        a = tables[name]
+        per_row = row_bytes(a.dtype)
+        keep = min(a.size, (left // (len(names) - i)) // (per_row + 8))
+        if keep < a.size:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(d, f"{name}.rows.npy"), rows.astype(np.float64))
+            left -= 8 * keep
+        for f in a.dtype.names:
+            col = a[f]
+            if col.dtype.kind == "S":
+                v = np.ascontiguousarray(col).view(np.uint8).reshape(col.size, col.dtype.itemsize).astype(np.float32)
+            else:
+                v = col.astype(np.float64)
+                if not np.array_equal(v.astype(col.dtype), col):
+                    raise SystemExit(f"bench.py: {name}.{f} does not convert to float64 exactly")
+            np.save(os.path.join(d, f"{name}.{f}.npy"), v)
+        left -= per_row * a.size
 
 
 def _cpu_quota():

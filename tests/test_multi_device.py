@@ -117,7 +117,7 @@ def test_bench_two_ranks_native_exchange_and_file_leg():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--reads-per-gpu", str(2 ** 20),
-                        "--no-cpu-baseline", "--e2e-pairs", str(2 ** 20)], capture_output=True, text=True, env=env, timeout=1500, cwd=ROOT)
+                        "--no-cpu-baseline", "--e2e-pairs", str(2 ** 20), "--full"], capture_output=True, text=True, env=env, timeout=1500, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
     out = json.loads(lines[0])

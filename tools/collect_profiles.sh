@@ -6,7 +6,7 @@ TAG=${1:-x}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
-cd $R && python bench.py --cache /tmp --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err
+cd $R && python bench.py --cache /tmp --steps 20 --warmup 3 --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 run() { d=$1; shift; STEPS=${STEPS:-30} timeout 900 rocprofv3 "$@" --output-format csv -d $O/$d -o run -- python $R/tools/prof_run.py > $O/$d.log 2>&1; }
 run kt --kernel-trace --stats

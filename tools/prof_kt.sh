@@ -4,7 +4,7 @@ TAG=${1:-x}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
-cd $R && python bench.py --cache /tmp --steps 5 --warmup 1 --no-cpu-baseline --no-e2e > $O/bench.json 2> $O/bench.err
+cd $R && python bench.py --cache /tmp --steps 5 --warmup 1 --full --no-cpu-baseline --no-e2e > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 STEPS=${2:-20} timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o run -- python $R/tools/prof_run.py > $O/kt.log 2>&1
 cd $R

@@ -3,6 +3,6 @@ previous un-profiled `python bench.py --cache /tmp ...` run, so that nothing for
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.argv = [sys.argv[0], "--steps", os.environ.get("STEPS", "50"), "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--cache", "/tmp",
-            "--reads-per-gpu", os.environ.get("READS", str(2 ** 25))]
+            "--reads-per-gpu", os.environ.get("READS", str(2 ** 25)), "--full"]
 import bench
 bench.main()
