@@ -294,6 +294,37 @@ int strl_ctx_pair_times(strl_ctx *ctx, double ms[5]);
  * only knows an upper bound of the count would. */
 int strl_sort_pairs(strl_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n, uint64_t n_max, int bit_lo, int bits);
 
+/* ---- the outlier stage (scripts/strling-outliers.py, the reference's fifth step; csrc/outliers.hip) ----
+ * Matrices are row-major doubles with NaN holes; `mem` (STRL_MEM_HOST / STRL_MEM_DEVICE) says where ALL array arguments of a
+ * call live, so a pipeline can keep its data on the device between the stages (strl_dev_alloc / strl_copy).  fp64 throughout,
+ * IEEE division and sqrt, fixed reduction orders: two runs give the same bits.  Each call returns when its results are in place. */
+int strl_dev_alloc(strl_ctx *ctx, uint64_t bytes, void **p);
+int strl_dev_free(strl_ctx *ctx, void *p);
+/* synchronous copy of `bytes` host -> device (to_device = 1) or device -> host (0) on the context's stream */
+int strl_copy(strl_ctx *ctx, void *dst, const void *src, uint64_t bytes, int to_device);
+/* Medians of the rows of x (rows x cols), NaN skipped, numpy's rule for an even count (the mean of the two middle values), by
+ * exact selection.  The per-sample depth medians of strling-outliers.py:247 (m_all: every value), :280-282 (m_kept: over the
+ * columns with keep[c] != 0, zeros as NaN) and :296 (m_filled: the same columns with NaN / 0 filled by m_kept).  keep may be
+ * NULL (every column); any of the three outputs may be NULL. */
+int strl_outliers_row_medians(strl_ctx *ctx, const double *x, uint64_t rows, uint64_t cols, const uint8_t *keep, double *m_all,
+                              double *m_kept, double *m_filled, int mem);
+/* hubers_est (strling-outliers.py:115-136) of every row of x (rows x cols): statsmodels 0.12.2 robust.scale.Huber(maxiter=1000)
+ * over the row's non-NaN values; where numpy would warn (divide by zero, invalid, overflow) or the loop does not converge, the
+ * median and MAD instead (method[r] = 1 'MAD', else 0 'Huber'); sd 0 -> NaN.  Rows wider than 4096 columns take the
+ * global-memory path (STRL_OUTLIERS_WIDE=1 forces it for every row). */
+int strl_outliers_huber(strl_ctx *ctx, const double *x, uint64_t rows, uint64_t cols, double *mu, double *sd, uint8_t *method, int mem);
+/* z = (x - mu[r]) / sd[r] (z_score :138-141, :359), p = norm.sf(z) (:395), p_adj = Benjamini-Hochberg per column over the finite p
+ * (p_adj_bh :143-168 via :402), every other value passed through.  n_null control-only rows (:340-373) join each column's BH
+ * with the values null_x[c] (NULL: NaN, which is what the script's :368 leaves there) against (null_mu[j], null_sd[j]); they
+ * produce no output.  z, p, p_adj: rows x cols.  (rows + n_null) * cols < 2^31. */
+int strl_outliers_scores(strl_ctx *ctx, const double *x, const double *mu, const double *sd, uint64_t rows, uint64_t cols,
+                         const double *null_x, const double *null_mu, const double *null_sd, uint64_t n_null, double *z, double *p,
+                         double *p_adj, int mem);
+/* The row order of STRs.tsv (:451, sort_values(['outlier', 'allele2_est'], ascending=False), NaN last) over the cells of two
+ * rows x cols matrices: order[k] = row-major index r * cols + c of the k-th output row.  Ties keep column-major order (column =
+ * sample in name order, then row = locus), the order this build defines where the script's depends on Python set order. */
+int strl_outliers_order(strl_ctx *ctx, const double *outlier, const double *allele2, uint64_t rows, uint64_t cols, uint32_t *order, int mem);
+
 /* The pair rules on single treads, so that known-answer vectors (the reference's tests/test_extract.nim:7-19,
  * tests/test_strling.nim:91-107, tests/test_utils.nim:66-74) can be run through the product's own code: with a context the
  * DEVICE functions the replay kernel calls, with ctx == NULL the host twins the streaming pairer (strl_pairer_*) calls.

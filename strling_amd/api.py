@@ -112,7 +112,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 MODE_MERGE, MODE_CALL = 0, 1
 
 # every symbol include/strling_amd.h declares
-EXPORTS = ["strl_version", "strl_last_error", "strl_device_count", "strl_ctx_create", "strl_ctx_destroy", "strl_ctx_stream",
+EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_medians", "strl_outliers_huber", "strl_outliers_scores",
+           "strl_outliers_order", "strl_version", "strl_last_error", "strl_device_count", "strl_ctx_create", "strl_ctx_destroy", "strl_ctx_stream",
            "strl_ctx_sync", "strl_ctx_set_opts", "strl_ctx_set_genome", "strl_soa_from_records", "strl_score_reads", "strl_index_chrom", "strl_index_regions",
            "strl_ctx_enable_timing", "strl_ctx_kernel_times", "strl_ctx_kernel_times_detail", "strl_pair_reads", "strl_pairer_create", "strl_pairer_destroy", "strl_pairer_add",
            "strl_pairer_result", "strl_qname_hash", "strl_extract", "strl_cluster", "strl_cluster_replay", "strl_frag_median",
@@ -227,6 +228,12 @@ def load(build_if_missing=True):
     L.strl_pair_rows.argtypes = [C.POINTER(CRecords)] + [C.c_void_p] * 5
     L.strl_ctx_cluster_times.argtypes = [C.c_void_p, C.POINTER(C.c_double * 3)]
     L.strl_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int]
+    L.strl_outliers_row_medians.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int]
+    L.strl_outliers_huber.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.strl_outliers_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.strl_outliers_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int]
     _LIB = L
     return L
 
@@ -421,6 +428,49 @@ class Context:
         v = np.ascontiguousarray(vals, np.uint32).copy()
         _check(self.L.strl_sort_pairs(self.h, _ptr(k), _ptr(v), k.size, n_max or k.size, bit_lo, bits))
         return k, v
+
+    # ---- the outlier stage (strling-outliers.py; csrc/outliers.hip): host arrays in and out
+
+    def outliers_row_medians(self, x, keep=None):
+        """per-row medians of a (rows, cols) float64 matrix, NaN skipped -> (m_all, m_kept, m_filled); keep: per-column mask
+        (strl_outliers_row_medians: the depth medians of :247, :281-282, :296)"""
+        x = np.ascontiguousarray(x, np.float64)
+        r, c = x.shape
+        k = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        out = [np.empty(r, np.float64) for _ in range(3)]
+        _check(self.L.strl_outliers_row_medians(self.h, _ptr(x), r, c, _ptr(k), *[o.ctypes.data for o in out], MEM_HOST))
+        return tuple(out)
+
+    def outliers_huber(self, x):
+        """hubers_est (:115-136) of every row -> (mu, sd, method) with method 'Huber' / 'MAD' (strl_outliers_huber)"""
+        x = np.ascontiguousarray(x, np.float64)
+        r, c = x.shape
+        mu, sd, m = np.empty(r, np.float64), np.empty(r, np.float64), np.empty(r, np.uint8)
+        _check(self.L.strl_outliers_huber(self.h, _ptr(x), r, c, mu.ctypes.data, sd.ctypes.data, m.ctypes.data, MEM_HOST))
+        return mu, sd, np.where(m == 0, "Huber", "MAD")
+
+    def outliers_scores(self, x, mu, sd, null_x=None, null_mu=None, null_sd=None):
+        """z, p, p_adj (:138-141, :359-404) of a (loci, samples) matrix; null_*: control-only rows that count in BH only
+        (strl_outliers_scores)"""
+        x = np.ascontiguousarray(x, np.float64)
+        r, c = x.shape
+        mu, sd = np.ascontiguousarray(mu, np.float64), np.ascontiguousarray(sd, np.float64)
+        nx = None if null_x is None else np.ascontiguousarray(null_x, np.float64)
+        nm = np.ascontiguousarray(null_mu if null_mu is not None else [], np.float64)
+        ns = np.ascontiguousarray(null_sd if null_sd is not None else [], np.float64)
+        z, p, q = (np.empty((r, c), np.float64) for _ in range(3))
+        _check(self.L.strl_outliers_scores(self.h, _ptr(x), _ptr(mu), _ptr(sd), r, c, _ptr(nx), _ptr(nm), _ptr(ns), nm.size,
+                                           z.ctypes.data, p.ctypes.data, q.ctypes.data, MEM_HOST))
+        return z, p, q
+
+    def outliers_order(self, outlier, allele2):
+        """STRs.tsv row order (:451) over two (loci, samples) matrices -> row-major cell indices (strl_outliers_order)"""
+        z = np.ascontiguousarray(outlier, np.float64)
+        a = np.ascontiguousarray(allele2, np.float64)
+        r, c = z.shape
+        o = np.empty(r * c, np.uint32)
+        _check(self.L.strl_outliers_order(self.h, _ptr(z), _ptr(a), r, c, o.ctypes.data, MEM_HOST))
+        return o
 
     def extract_device(self, cs: CReadSoa, cp: CPairSoa, n_tail, item_cap=0, tread_cap=0):
         """scoring + pair logic of one batch, asynchronous for device-resident batches (strl_extract_device)"""

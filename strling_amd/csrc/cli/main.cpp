@@ -2550,18 +2550,22 @@ static double since_exec() {
   if (!start || clock_gettime(CLOCK_BOOTTIME, &ts) != 0) return -1;
   return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec - (double)start / (double)sysconf(_SC_CLK_TCK);
 }
+int outliers_main(int argc, char **argv);   // outliers_cli.cpp
+
 int main(int argc, char **argv) {
   g_main_at = since_exec();
   const char *top =
       "strling version: 0.6.0 (MI355X-native hot path)\n\nCommands:\n  extract  :   extract informative STR reads from a BAM/CRAM. This is a required first step.\n"
       "  merge    :   merge putitive STR loci from multiple samples. Only required for joint calling.\n  call     :   call STRs\n"
-      "  index    :   identify large STRs in the reference genome, to produce ref.fasta.str.\n";      // strling.nim:19-22 (pull_region, a debugging writer, is out of scope)
+      "  index    :   identify large STRs in the reference genome, to produce ref.fasta.str.\n"
+      "  outliers :   cohort STR outlier scores from the call outputs of many samples (scripts/strling-outliers.py).\n";      // strling.nim:19-22 (pull_region, a debugging writer, is out of scope)
   if (argc < 2) { fputs(top, stdout); return 1; }
   const std::string cmd = argv[1];
   if (cmd == "extract") return extract_main(argc, argv);
   if (cmd == "merge") return merge_main(argc, argv);
   if (cmd == "index") return index_main(argc, argv);
   if (cmd == "call") return call_main(argc, argv);
+  if (cmd == "outliers") return outliers_main(argc, argv);
   if (cmd == "_dump") return dump_main(argc, argv);
   if (cmd == "_decode") return decode_main(argc, argv);
   if (cmd == "_region") return region_main(argc, argv);
