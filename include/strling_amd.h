@@ -552,6 +552,35 @@ int strl_regions_fetch(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, 
                        const uint32_t *crc32, uint32_t n_blocks, const strl_region_req *req, uint32_t n_regions, uint8_t *out, uint64_t out_cap,
                        uint64_t *out_off, uint64_t *out_len, uint8_t *status);
 
+/* ---- `strling call`'s evidence around a bound on the device (replaces the per-record work of spanners(), collect.nim:130-182:
+ * the loop over the query's records with bam_endpos and the flag / mapq filter (:138-141), expected_spanning_probability
+ * (spanning.nim:22-49), the depth array and median_depth (collect.nim:154-155, utils.nim:148-158), overlapping_read with
+ * find_read_position and the unit count (collect.nim:50-119), the pair table's eligibility (:161-166); the steps that follow
+ * the order of Nim's tables are finished on the host inside the call).  Bit for bit what strl_spanners returns for the same
+ * records and bound.
+ * Input: the records of n_regions regions as block_size-prefixed BAM records in host memory, region r at
+ * bytes[off[r], off[r] + len[r]) -- what strl_regions_fetch writes to `out` (the span from the lowest to the highest region is
+ * copied to the device in one piece).  bounds[r] is region r's bound; window, frag, min_mapq as for strl_spanners.
+ * Output: region r's Support list at support_out[support_off[r], support_off[r + 1]) (support_off has n_regions + 1 entries;
+ * `rec` = the ordinal of the record in the region's bytes) and its summary[r]; status[r] = 0: answered; 2: passed on -- more
+ * than 4096 records in the region's bytes, right - left + 2 * window outside 1 .. 9190 (1000, callclusters.nim:52-66, plus
+ * twice the 4095 the fragment histogram allows a window), bytes that do not parse as records, or a pair whose first record
+ * starts behind its second (doAssert collect.nim:37): ask strl_spanners, which has the last word.  Nothing is answered
+ * approximately.  STRL_ERR_CAPACITY when support_cap is too small: support_off[n_regions] = the entries needed.
+ * STRL_ERR_ARG for a bound with left > right, like strl_spanners. */
+int strl_evidence_records(strl_ctx *ctx, const uint8_t *bytes, const uint64_t *off, const uint64_t *len, const strl_bounds *bounds, uint32_t n_regions,
+                          int32_t window, const uint32_t frag[4096], uint8_t min_mapq, strl_support *support_out, uint64_t support_cap,
+                          uint64_t *support_off, strl_span_summary *summary, uint8_t *status);
+/* The fused form `strling call` uses (replaces call.nim:196-218 from the query to the Support list: htslib's indexed iterator
+ * and spanners(), collect.nim:130-182): strl_regions_fetch's inputs plus the bounds; inflate, CRC, the walk and the evidence
+ * run on one stream of the context and no record bytes come back.  status[r] = 0: answered; 1: as strl_regions_fetch (read
+ * the region on the host); 2: as strl_evidence_records.  Errors as for both.  kernel_ms (may be NULL): HIP-event time of the
+ * evidence kernel of this call. */
+int strl_regions_evidence(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                          const uint32_t *crc32, uint32_t n_blocks, const strl_region_req *req, const strl_bounds *bounds, uint32_t n_regions,
+                          int32_t window, const uint32_t frag[4096], uint8_t min_mapq, strl_support *support_out, uint64_t support_cap,
+                          uint64_t *support_off, strl_span_summary *summary, uint8_t *status, double *kernel_ms);
+
 /* ---- `strling extract` with the whole BAM front end on the device (replaces extract.nim:275-329: bam open / `for aln in ibam`
  * / `query("*")`, i.e. htslib's inflate + bam_read1 + the hts-nim accessors, for the whole file).  The host walks the BGZF
  * block headers and hands over compressed bytes; inflate, record boundaries, record parsing, the fragment-length words and

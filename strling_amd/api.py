@@ -97,6 +97,10 @@ assert SUPPORT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 96, (SUPPORT_DTYP
 SUPPORT_TYPES = ["SpanningFragment", "SpanningRead", "OverlappingRead"]
 
 
+SPAN_SUMMARY_DTYPE = np.dtype([("median_depth", "<i4"), ("expected_spanners", "<f4"), ("n_support", "<u8")], align=True)
+assert SPAN_SUMMARY_DTYPE.itemsize == 16
+
+
 class SpanSummary(C.Structure):
     _fields_ = [("median_depth", C.c_int32), ("expected_spanners", C.c_float), ("n_support", C.c_uint64)]
 
@@ -119,7 +123,7 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_pairer_result", "strl_qname_hash", "strl_extract", "strl_cluster", "strl_cluster_replay", "strl_frag_median",
            "strl_bin_write", "strl_bin_read", "strl_bounds_row", "strl_cluster_members", "strl_spanners", "strl_genotype",
            "strl_calls_finish", "strl_unplaced_order", "strl_call_row", "strl_canonical_repeat", "strl_assign_reads_loci", "strl_group_order",
-           "strl_extract_device", "strl_treads_fetch", "strl_ctx_pair_times", "strl_sort_pairs", "strl_cluster_resident", "strl_ctx_cluster_times", "strl_pair_rows", "strl_extract_begin", "strl_extract_add", "strl_extract_finish", "strl_pair_rule", "strl_bounds_bare", "strl_ctx_treads_device", "strl_cluster_gathered", "strl_inflate_blocks", "strl_ctx_inflate_ms", "strl_regions_fetch", "strl_front_begin", "strl_front_push", "strl_front_push_after", "strl_front_reserve", "strl_front_stage", "strl_front_enqueue_after", "strl_front_collect", "strl_ctxs_extract_gather", "strl_front_finish", "strl_front_fragwords", "strl_front_fragwords_async", "strl_event_wait", "strl_front_records", "strl_front_tids", "strl_front_qnames", "strl_front_treads_named", "strl_pinned_alloc", "strl_pinned_free", "strl_comm_unique_id", "strl_ctx_comm_init", "strl_ctxs_comm_init", "strl_ctx_comm_info", "strl_cluster_exchange", "strl_ctxs_cluster_exchange", "strl_exchange_treads", "strl_ctx_set_treads", "strl_cluster_collect", "strl_ctx_tail_stream", "strl_ctx_mem_info", "strl_bin_peek", "strl_front_trim_next", "strl_front_tail_bytes", "strl_ctx_blocking_waits", "strl_score_read_host", "strl_front_end"]
+           "strl_extract_device", "strl_treads_fetch", "strl_ctx_pair_times", "strl_sort_pairs", "strl_cluster_resident", "strl_ctx_cluster_times", "strl_pair_rows", "strl_extract_begin", "strl_extract_add", "strl_extract_finish", "strl_pair_rule", "strl_bounds_bare", "strl_ctx_treads_device", "strl_cluster_gathered", "strl_inflate_blocks", "strl_ctx_inflate_ms", "strl_regions_fetch", "strl_evidence_records", "strl_regions_evidence", "strl_front_begin", "strl_front_push", "strl_front_push_after", "strl_front_reserve", "strl_front_stage", "strl_front_enqueue_after", "strl_front_collect", "strl_ctxs_extract_gather", "strl_front_finish", "strl_front_fragwords", "strl_front_fragwords_async", "strl_event_wait", "strl_front_records", "strl_front_tids", "strl_front_qnames", "strl_front_treads_named", "strl_pinned_alloc", "strl_pinned_free", "strl_comm_unique_id", "strl_ctx_comm_init", "strl_ctxs_comm_init", "strl_ctx_comm_info", "strl_cluster_exchange", "strl_ctxs_cluster_exchange", "strl_exchange_treads", "strl_ctx_set_treads", "strl_cluster_collect", "strl_ctx_tail_stream", "strl_ctx_mem_info", "strl_bin_peek", "strl_front_trim_next", "strl_front_tail_bytes", "strl_ctx_blocking_waits", "strl_score_read_host", "strl_front_end"]
 
 
 def lib_path():
@@ -204,6 +208,11 @@ def load(build_if_missing=True):
     L.strl_ctx_inflate_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.strl_regions_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                      C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.strl_evidence_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8, C.c_void_p,
+                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.strl_regions_evidence.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_double)]
     L.strl_front_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64]
     L.strl_front_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_int)]
     L.strl_front_finish.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
@@ -609,6 +618,61 @@ class Context:
         _check(self.L.strl_regions_fetch(self.h, comp.ctypes.data, int(clen.sum()), _ptr(coff), _ptr(clen), _ptr(isz), None if crc is None else _ptr(crc), len(streams),
                                          req.ctypes.data, len(regions), out.ctypes.data, cap, _ptr(off), _ptr(ln), _ptr(st)))
         return [(out[int(o):int(o) + int(n)].tobytes(), int(x)) for o, n, x in zip(off, ln, st)]
+
+    def _evidence_call(self, n, call, cap):
+        """the support / summary / status buffers of the evidence entry points, grown once if `cap` proves short"""
+        while True:
+            sup = np.zeros(max(1, cap), SUPPORT_DTYPE)
+            off = np.zeros(n + 1, np.uint64)
+            sm = np.zeros(max(1, n), SPAN_SUMMARY_DTYPE)
+            st = np.zeros(max(1, n), np.uint8)
+            rc = call(sup, cap, off, sm, st)
+            if rc == -4 and int(off[n]) > cap:
+                cap = int(off[n])
+                continue
+            _check(rc)
+            return [(sup[int(off[r]):int(off[r + 1])].copy(), int(sm["median_depth"][r]), np.float32(sm["expected_spanners"][r]), int(st[r])) for r in range(n)]
+
+    def evidence_records(self, regions, bounds, window, frag, min_mapq=20):
+        """strl_evidence_records: regions = list of bytes (block_size-prefixed BAM records, what regions_fetch returns), bounds =
+        one BOUNDS_DTYPE record per region -> list of (support array, median_depth, expected_spanners, status); status 2 = passed
+        on to spanners()"""
+        n = len(regions)
+        raw = b"".join(regions)
+        buf = np.frombuffer(raw + b"\0" * 8, np.uint8)
+        ln = np.array([len(x) for x in regions], np.uint64)
+        off = np.zeros(n, np.uint64)
+        off[1:] = np.cumsum(ln[:-1], dtype=np.uint64)
+        bb = np.ascontiguousarray(bounds, BOUNDS_DTYPE).reshape(n)
+        frag = np.ascontiguousarray(frag, np.uint32)
+
+        def call(sup, cap, soff, sm, st):
+            return self.L.strl_evidence_records(self.h, buf.ctypes.data, _ptr(off), _ptr(ln), bb.ctypes.data, n, window, frag.ctypes.data, min_mapq,
+                                                sup.ctypes.data, cap, _ptr(soff), sm.ctypes.data, _ptr(st))
+        return self._evidence_call(n, call, len(raw) // 128 + 64 * n + 64)
+
+    def regions_evidence(self, streams, sizes, regions, bounds, window, frag, min_mapq=20, crcs=None):
+        """strl_regions_evidence: regions_fetch's arguments plus one bound per region -> list of (support array, median_depth,
+        expected_spanners, status); status 1 = the blocks end before the query does, 2 = passed on to spanners()"""
+        comp = np.frombuffer(b"".join(streams) + b"\0" * 8, np.uint8)
+        clen = np.array([len(x) for x in streams], np.uint32)
+        coff = np.zeros(len(streams), np.uint64)
+        coff[1:] = np.cumsum(clen[:-1], dtype=np.uint64)
+        isz = np.asarray(sizes, np.uint32)
+        n = len(regions)
+        req = np.zeros(n, REGION_REQ_DTYPE)
+        for k, r in enumerate(regions):
+            req[k] = tuple(r)
+        bb = np.ascontiguousarray(bounds, BOUNDS_DTYPE).reshape(n)
+        frag = np.ascontiguousarray(frag, np.uint32)
+        crc = None if crcs is None else np.asarray(crcs, np.uint32)
+        ms = C.c_double(0)
+
+        def call(sup, cap, soff, sm, st):
+            return self.L.strl_regions_evidence(self.h, comp.ctypes.data, int(clen.sum()), _ptr(coff), _ptr(clen), _ptr(isz), None if crc is None else _ptr(crc),
+                                                len(streams), req.ctypes.data, bb.ctypes.data, n, window, frag.ctypes.data, min_mapq, sup.ctypes.data, cap,
+                                                _ptr(soff), sm.ctypes.data, _ptr(st), C.byref(ms))
+        return self._evidence_call(n, call, sum(int(isz[r[0]:r[0] + r[1]].sum()) for r in regions) // 128 + 64 * n + 64)
 
     def inflate_blocks(self, streams, sizes):
         """raw DEFLATE streams (list of bytes) with their inflated sizes -> list of inflated bytes (strl_inflate_blocks)"""

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "device_util.h"
 #include "inflate_wave.h"
+#include "regions.h"
 // The grouped form of the decoder (inflate_group.h: a block per 8 lanes) measured slower than the wave form everywhere it was
 // tried (profiles/r05/inflate_group/): it is an experiment, kept with its logs and its CPU tests, and NOT part of the shipped
 // library -- a second decoder of untrusted input nobody benefits from.  `STRL_WITH_INFLATE_GROUP=1 python -m strling_amd.build`
@@ -145,7 +146,6 @@ __global__ __launch_bounds__(256) void crc32_kernel(const uint8_t *out, const ui
 // offset on -- htslib's iterator does the same walk -- and notes the byte range from the first record that can reach past `beg`
 // to the first record at or behind `end` (or on another reference); a second launch copies exactly those bytes out.  What goes
 // back to the host is the tenth of the inflated bytes the query returns, not all the index makes one read.
-struct RegionWalk { uint64_t start, stop; };
 __device__ __forceinline__ uint32_t rg_ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 // One WAVE per region.  The walk is serial (a record's place follows from the length of the one before it) and, lane per
 // region straight out of global memory, every step was a dependent miss: 5 - 6 ms for ~4600 records.  Here the wave copies a
@@ -383,53 +383,50 @@ extern "C" int strl_ctx_inflate_ms(strl_ctx *c, double *ms) {
   return STRL_OK;
 }
 
-// C ABI: the records of many region queries of one BAM (call.nim:196-218), inflated and cut out on the device.
-extern "C" int strl_regions_fetch(strl_ctx *c, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
-                                  const uint32_t *crc32, uint32_t n_blocks, const strl_region_req *req, uint32_t n_regions, uint8_t *out, uint64_t out_cap,
-                                  uint64_t *out_off, uint64_t *out_len, uint8_t *status) {
-  if (!c || (n_blocks && (!comp || !coff || !clen || !isize)) || (n_regions && (!req || !out_off || !out_len || !status)) || (out_cap && !out)) { set_error("null argument"); return STRL_ERR_ARG; }
-  if (!n_regions) return STRL_OK;
-  STRL_HIP(hipSetDevice(c->device));
-  std::vector<uint64_t> uoff(n_blocks);
-  uint64_t tot = 0;
-  for (uint32_t i = 0; i < n_blocks; ++i) {
-    if (coff[i] + clen[i] > comp_bytes) { set_error("block %u reaches past the compressed buffer", i); return STRL_ERR_ARG; }
-    if (isize[i] > 65536u) { set_error("block %u: ISIZE %u", i, isize[i]); return STRL_ERR_FORMAT; }
-    uoff[i] = tot;
-    tot += isize[i];
-  }
-  for (uint32_t r = 0; r < n_regions; ++r)
-    if (!req[r].n_blocks || (uint64_t)req[r].first_block + req[r].n_blocks > n_blocks) { set_error("region %u names blocks that were not handed over", r); return STRL_ERR_ARG; }
-  // a slot of the context: its stream, its buffers (kept between calls: freeing gigabytes synchronises the device)
-  strl_ctx::RegionSlot *slot = nullptr;
+// ---- the slot, stream and buffer machinery the region entry points share (regions.h) ----
+int strl::RegionJob::acquire(strl_ctx *ctx, bool want_crc) {
+  c = ctx;
   {
     std::unique_lock<std::mutex> lk(c->rg_mu);
     c->rg_cv.wait(lk, [&] { return !c->rg[0].busy || !c->rg[1].busy; });
     slot = !c->rg[0].busy ? &c->rg[0] : &c->rg[1];
     slot->busy = true;
-    if (crc32 && !c->crc_tab.p) {                       // (made once, by whichever call comes first)
+    if (want_crc && !c->crc_tab.p) {                    // (made once, by whichever call comes first)
       if (c->crc_tab.reserve(sizeof(CrcTables)) != STRL_OK || hipMemcpy(c->crc_tab.p, &crc_tables(), sizeof(CrcTables), hipMemcpyHostToDevice) != hipSuccess) {
         slot->busy = false;
+        slot = nullptr;
         set_error("CRC tables");
         return STRL_ERR_HIP;
       }
     }
   }
-  // (the slot's stream is drained before the slot -- and the stack memory its copies read and write: uoff, err, range -- is given
-  // up, whichever way the function is left: an early error return must not leave DMA pending on destroyed memory; round-4 advisor)
-  struct Rel {
-    strl_ctx *c; strl_ctx::RegionSlot *s;
-    ~Rel() {
-      if (s->st) (void)hipStreamSynchronize(s->st);
-      { std::lock_guard<std::mutex> lk(c->rg_mu); s->busy = false; }
-      c->rg_cv.notify_all();
-    }
-  };
-  std::vector<RegionWalk> range(n_regions);          // declared ahead of `rel`: destroyed after its destructor has drained the stream
-  uint32_t err = 0;
-  Rel rel{c, slot};
   if (!slot->st) STRL_HIP(hipStreamCreateWithFlags(&slot->st, hipStreamNonBlocking));
-  DevBuf &d_comp = slot->comp, &d_meta = slot->meta, &d_u = slot->u, &d_out = slot->out, &d_rq = slot->rq, &d_work = slot->work;
+  return STRL_OK;
+}
+strl::RegionJob::~RegionJob() {
+  if (!slot) return;
+  if (slot->st) (void)hipStreamSynchronize(slot->st);
+  { std::lock_guard<std::mutex> lk(c->rg_mu); slot->busy = false; }
+  c->rg_cv.notify_all();
+}
+
+int strl::regions_inflate_walk(RegionJob &J, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                               const uint32_t *crc32, uint32_t n_blocks, const strl_region_req *req, uint32_t n_regions, uint8_t *status) {
+  strl_ctx *c = J.c;
+  J.uoff.resize(n_blocks);
+  uint64_t tot = 0;
+  for (uint32_t i = 0; i < n_blocks; ++i) {
+    if (coff[i] + clen[i] > comp_bytes) { set_error("block %u reaches past the compressed buffer", i); return STRL_ERR_ARG; }
+    if (isize[i] > 65536u) { set_error("block %u: ISIZE %u", i, isize[i]); return STRL_ERR_FORMAT; }
+    J.uoff[i] = tot;
+    tot += isize[i];
+  }
+  J.tot = tot;
+  for (uint32_t r = 0; r < n_regions; ++r)
+    if (!req[r].n_blocks || (uint64_t)req[r].first_block + req[r].n_blocks > n_blocks) { set_error("region %u names blocks that were not handed over", r); return STRL_ERR_ARG; }
+  J.range.assign(n_regions, RegionWalk{0, 0});
+  strl_ctx::RegionSlot *slot = J.slot;
+  DevBuf &d_comp = slot->comp, &d_meta = slot->meta, &d_u = slot->u, &d_rq = slot->rq, &d_work = slot->work;
   int rc;
   const uint64_t readable = (comp_bytes + 3) & ~(uint64_t)3;
   const size_t meta = (size_t)n_blocks * (8 + 8 + 4 + 4 + 4) + 64;
@@ -438,15 +435,15 @@ extern "C" int strl_regions_fetch(strl_ctx *c, const uint8_t *comp, uint64_t com
   if ((rc = d_comp.reserve(readable + 16)) || (rc = d_meta.reserve(meta)) || (rc = d_u.reserve(tot + 64)) || (rc = d_rq.reserve(rq_bytes)) || (work && (rc = d_work.reserve(work)))) return rc;
   uint64_t *m_coff = d_meta.as<uint64_t>(), *m_uoff = m_coff + n_blocks;
   uint32_t *m_clen = reinterpret_cast<uint32_t *>(m_uoff + n_blocks), *m_isize = m_clen + n_blocks, *m_crc = m_isize + n_blocks, *m_err = m_crc + n_blocks;
-  RegionWalk *d_range = d_rq.as<RegionWalk>();
-  uint64_t *d_off = reinterpret_cast<uint64_t *>(d_range + n_regions);
-  strl_region_req *d_req = reinterpret_cast<strl_region_req *>(d_off + n_regions);
-  uint8_t *d_status = reinterpret_cast<uint8_t *>(d_req + n_regions);
+  J.d_range = d_rq.as<RegionWalk>();
+  J.d_off = reinterpret_cast<uint64_t *>(J.d_range + n_regions);
+  strl_region_req *d_req = reinterpret_cast<strl_region_req *>(J.d_off + n_regions);
+  J.d_status = reinterpret_cast<uint8_t *>(d_req + n_regions);
   hipStream_t st = slot->st;
   STRL_HIP(hipMemcpyAsync(d_comp.p, comp, comp_bytes, hipMemcpyHostToDevice, st));
   STRL_HIP(hipMemsetAsync(static_cast<uint8_t *>(d_comp.p) + comp_bytes, 0, 16, st));
   STRL_HIP(hipMemcpyAsync(m_coff, coff, (size_t)n_blocks * 8, hipMemcpyHostToDevice, st));
-  STRL_HIP(hipMemcpyAsync(m_uoff, uoff.data(), (size_t)n_blocks * 8, hipMemcpyHostToDevice, st));
+  STRL_HIP(hipMemcpyAsync(m_uoff, J.uoff.data(), (size_t)n_blocks * 8, hipMemcpyHostToDevice, st));
   STRL_HIP(hipMemcpyAsync(m_clen, clen, (size_t)n_blocks * 4, hipMemcpyHostToDevice, st));
   STRL_HIP(hipMemcpyAsync(m_isize, isize, (size_t)n_blocks * 4, hipMemcpyHostToDevice, st));
   if (crc32) STRL_HIP(hipMemcpyAsync(m_crc, crc32, (size_t)n_blocks * 4, hipMemcpyHostToDevice, st));
@@ -454,14 +451,30 @@ extern "C" int strl_regions_fetch(strl_ctx *c, const uint8_t *comp, uint64_t com
   STRL_HIP(hipMemsetAsync(m_err, 0, 4, st));
   if ((rc = strl_inflate_device(c, d_comp.as<uint8_t>(), readable, m_coff, m_clen, m_uoff, m_isize, n_blocks, d_u.as<uint8_t>(), m_err, nullptr, st, tot, d_work.as<uint8_t>(), work))) return rc;
   if (crc32 && (rc = strl_crc_device(c, d_u.as<uint8_t>(), m_uoff, m_isize, m_crc, n_blocks, nullptr, m_err, st))) return rc;
-  hipLaunchKernelGGL(region_walk_kernel, dim3(n_regions), dim3(64), 0, st, d_u.as<uint8_t>(), (tot + 64) & ~(uint64_t)15, m_uoff, m_isize, d_req, n_regions, d_range, d_status);
+  hipLaunchKernelGGL(region_walk_kernel, dim3(n_regions), dim3(64), 0, st, d_u.as<uint8_t>(), (tot + 64) & ~(uint64_t)15, m_uoff, m_isize, d_req, n_regions, J.d_range, J.d_status);
   STRL_HIP(hipGetLastError());
-  STRL_HIP(hipMemcpyAsync(&err, m_err, 4, hipMemcpyDeviceToHost, st));
-  STRL_HIP(hipMemcpyAsync(range.data(), d_range, (size_t)n_regions * sizeof(RegionWalk), hipMemcpyDeviceToHost, st));
-  STRL_HIP(hipMemcpyAsync(status, d_status, n_regions, hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipMemcpyAsync(&J.err, m_err, 4, hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipMemcpyAsync(J.range.data(), J.d_range, (size_t)n_regions * sizeof(RegionWalk), hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipMemcpyAsync(status, J.d_status, n_regions, hipMemcpyDeviceToHost, st));
   STRL_HIP(hipStreamSynchronize(st));
-  if (err & IW_ERR_CRC) { set_error("a BGZF block inflates, but not to the bytes its CRC-32 names"); return STRL_ERR_CRC; }
-  if (err) { set_error("device inflate: %s", (err & IW_ERR_DATA) ? "invalid DEFLATE data" : "inflated size differs from the block's ISIZE"); return STRL_ERR_FORMAT; }
+  if (J.err & IW_ERR_CRC) { set_error("a BGZF block inflates, but not to the bytes its CRC-32 names"); return STRL_ERR_CRC; }
+  if (J.err) { set_error("device inflate: %s", (J.err & IW_ERR_DATA) ? "invalid DEFLATE data" : "inflated size differs from the block's ISIZE"); return STRL_ERR_FORMAT; }
+  return STRL_OK;
+}
+
+// C ABI: the records of many region queries of one BAM (call.nim:196-218), inflated and cut out on the device.
+extern "C" int strl_regions_fetch(strl_ctx *c, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                                  const uint32_t *crc32, uint32_t n_blocks, const strl_region_req *req, uint32_t n_regions, uint8_t *out, uint64_t out_cap,
+                                  uint64_t *out_off, uint64_t *out_len, uint8_t *status) {
+  if (!c || (n_blocks && (!comp || !coff || !clen || !isize)) || (n_regions && (!req || !out_off || !out_len || !status)) || (out_cap && !out)) { set_error("null argument"); return STRL_ERR_ARG; }
+  if (!n_regions) return STRL_OK;
+  STRL_HIP(hipSetDevice(c->device));
+  RegionJob J;
+  int rc;
+  if ((rc = J.acquire(c, crc32 != nullptr)) || (rc = regions_inflate_walk(J, comp, comp_bytes, coff, clen, isize, crc32, n_blocks, req, n_regions, status))) return rc;
+  const std::vector<RegionWalk> &range = J.range;
+  DevBuf &d_u = J.slot->u, &d_out = J.slot->out;
+  hipStream_t st = J.stream();
   // where each region's bytes go: back to back, every piece starting at its source's offset modulo 16 (16-byte copies)
   uint64_t at = 0;
   for (uint32_t r = 0; r < n_regions; ++r) {
@@ -478,8 +491,8 @@ extern "C" int strl_regions_fetch(strl_ctx *c, const uint8_t *comp, uint64_t com
   }
   if (at) {
     if ((rc = d_out.reserve(at + 64))) return rc;
-    STRL_HIP(hipMemcpyAsync(d_off, out_off, (size_t)n_regions * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(region_copy_kernel, dim3(std::min<uint32_t>(n_regions, 4096u)), dim3(256), 0, st, d_u.as<uint8_t>(), d_range, d_off, n_regions, d_out.as<uint8_t>());
+    STRL_HIP(hipMemcpyAsync(J.d_off, out_off, (size_t)n_regions * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(region_copy_kernel, dim3(std::min<uint32_t>(n_regions, 4096u)), dim3(256), 0, st, d_u.as<uint8_t>(), J.d_range, J.d_off, n_regions, d_out.as<uint8_t>());
     STRL_HIP(hipGetLastError());
     STRL_HIP(hipMemcpyAsync(out, d_out.p, at, hipMemcpyDeviceToHost, st));
     STRL_HIP(hipStreamSynchronize(st));

@@ -1,7 +1,9 @@
 // call_logic.cpp -- host side of `strling call` above the clustering kernels: the evidence collected around one
 // bound (collect.nim:36-182, spanning.nim:7-49, utils.nim:129-158) and the genotype record built from it
-// (genotyper.nim:56-199, call.nim:29-48,264-281).  Sequential, hash-table shaped work on a few hundred records per
-// bound: it stays on the host (the region's records come from an indexed BAM read, which is what bounds it).
+// (genotyper.nim:56-199, call.nim:29-48,264-281).  strl_spanners is the whole of spanners() over parsed records: the path of
+// CRAM input, of STRL_CALL_EVIDENCE=host and of every region the device passes on.  For the regions the device answers
+// (evidence.hip) the per-record work -- CIGAR walks, base access, hashing, depths -- is done there, and only the steps that
+// follow the order of Nim's tables are finished here from one compact row per record (evidence_finish below).
 // Nim stdlib order effects that reach the output text are reproduced with nim_tables.h.
 #include <math.h>
 #include <stdio.h>
@@ -14,6 +16,7 @@
 #include "../../include/strling_amd.h"
 #include "common.h"
 #include "nim_tables.h"
+#include "regions.h"
 
 using strl::set_error;
 namespace nim { std::vector<int64_t> table_slot_order(const std::vector<uint64_t> &hcodes, uint64_t initial_size); }
@@ -516,3 +519,68 @@ int strl_call_row(char *buf, int cap, const strl_call *c, const char *chrom) {
 }
 
 }  // extern "C"
+
+// ---- the host half of the device evidence (regions.h) ----
+const float *strl::frag_cd(const uint32_t frag[4096]) { return frag_tables(frag).cd; }
+
+// strl_spanners from `if prob > 0` on (collect.nim:145-182), over the rows the device kept: the same tables, filled in the
+// same order, with a row's name_id in the place of the qname look-up.
+int strl::evidence_finish(const EvRow *rows, uint32_t n, const strl_bounds &b, const uint32_t frag[4096], strl_support *out, uint64_t cap, uint64_t *n_out_p,
+                          float *expected_spanners) {
+  const FragTables &FT = frag_tables(frag);
+  thread_local std::vector<int32_t> exp_id, pair_id;
+  exp_id.assign(n, -1);
+  pair_id.assign(n, -1);
+  std::vector<double> exp_val;
+  std::vector<uint64_t> exp_hc, pair_hc;
+  struct Pair { uint32_t first, second; int n; };
+  std::vector<Pair> pairs;
+  uint64_t n_out = 0;
+  auto emit = [&](const strl_support &s) { if (out && n_out < cap) out[n_out] = s; ++n_out; };
+  for (uint32_t i = 0; i < n; ++i) {
+    const EvRow &w = rows[i];
+    const uint32_t nm = w.name_id;
+    const double prob = (double)w.prob;
+    if (prob > 0) {                                                                  // :145-152
+      if (exp_id[nm] >= 0) exp_val[(size_t)exp_id[nm]] = 0.5 * (exp_val[(size_t)exp_id[nm]] + prob);
+      else {
+        exp_id[nm] = (int32_t)exp_val.size();
+        exp_val.push_back(prob);
+        exp_hc.push_back(w.hash);
+      }
+    }
+    if (w.flags & EV_OVERLAP) {                                                      // :157-159
+      strl_support s{};
+      s.type = w.type; s.repeat_count = w.repeat_count; s.cigar_ins = w.cigar_ins; s.cigar_del = w.cigar_del;
+      s.rec = w.ord;
+      emit(s);
+    }
+    if (!(w.flags & EV_PAIR)) continue;
+    if (pair_id[nm] >= 0) { Pair &p = pairs[(size_t)pair_id[nm]]; if (p.n == 1) p.second = i; ++p.n; }
+    else {
+      pair_id[nm] = (int32_t)pairs.size();
+      pairs.push_back(Pair{i, 0, 1});
+      pair_hc.push_back(w.hash);
+    }
+  }
+  float es = 0;                                                                      // :176-177
+  for (int64_t id : nim::table_slot_order(exp_hc, 32)) es += (float)exp_val[(size_t)id];
+  *expected_spanners = es;
+  const int64_t slop = bound_slop(b);
+  for (int64_t id : nim::table_slot_order(pair_hc, 32)) {                            // :179-183
+    const Pair &p = pairs[(size_t)id];
+    if (p.n != 2) continue;
+    const EvRow &L = rows[p.first], &R = rows[p.second];
+    if (!(L.start <= R.start)) return 2;                                             // doAssert collect.nim:37: the host path reports it
+    if ((int64_t)L.start < (int64_t)b.left - slop && R.stop > (int64_t)b.right + slop) {
+      strl_support s{};
+      s.type = STRL_SPANNING_FRAGMENT;
+      s.fragment_length = std::max<uint32_t>(1u, (uint32_t)std::abs((int64_t)L.isize));
+      s.fragment_percentile = percentile_cached(FT, (int64_t)s.fragment_length);
+      s.rec = L.ord;
+      emit(s);
+    }
+  }
+  *n_out_p = n_out;
+  return 0;
+}

@@ -1925,19 +1925,16 @@ static int call_main(int argc, char **argv) {
   double t_evidence = 0;
   std::atomic<uint64_t> ns_region{0}, ns_rules{0};      // summed over the workers: region reads (seek + inflate + parse) / spanners + genotype
   // What a worker does with a bound once its region's records are in w.region: spanners(), genotype(), the row.
-  auto rules = [&](Worker &w, const Task &t, Done &d, std::string &werr) -> bool {
+  // ... with the evidence in hand (from strl_spanners, or from the device: strl_regions_evidence): genotype(), the row
+  auto genotype_row = [&](Worker &w, const Task &t, Done &d, const strl_support *sup, const strl_span_summary &sm, std::string &werr) -> bool {
     const strl_bounds &b = t.b;
     char row[2048];
-    const strl_records rv = w.region.view();
-    w.sup.resize(2 * w.region.size() + 16);
-    strl_span_summary sm{};
-    if (strl_spanners(&rv, w.region.isize.data(), &b, window, frag, min_mapq, w.sup.data(), w.sup.size(), &sm) != STRL_OK) { werr = std::string("[strling] ") + strl_last_error(); return false; }
     if (sm.n_support > 5000) return true;                                              // spans.len > 5_000
     if (sm.median_depth == -1) return true;
     w.cl.clear();
     for (uint64_t k = t.i0; k < t.i1; ++k) w.cl.push_back(t.src[(*t.idx)[(size_t)k]]);
     memset(&d.c, 0, sizeof d.c);
-    if (strl_genotype(&b, w.cl.data(), w.cl.size(), qoff.data(), qnames.data(), w.sup.data(), sm.n_support, &copts, (double)sm.median_depth, &d.c) != STRL_OK) {
+    if (strl_genotype(&b, w.cl.data(), w.cl.size(), qoff.data(), qnames.data(), sup, sm.n_support, &copts, (double)sm.median_depth, &d.c) != STRL_OK) {
       werr = std::string("[strling] ") + strl_last_error();
       return false;
     }
@@ -1951,12 +1948,23 @@ static int call_main(int argc, char **argv) {
     d.keep = true;
     return true;
   };
+  auto rules = [&](Worker &w, const Task &t, Done &d, std::string &werr) -> bool {
+    const strl_records rv = w.region.view();
+    w.sup.resize(2 * w.region.size() + 16);
+    strl_span_summary sm{};
+    if (strl_spanners(&rv, w.region.isize.data(), &t.b, window, frag, min_mapq, w.sup.data(), w.sup.size(), &sm) != STRL_OK) { werr = std::string("[strling] ") + strl_last_error(); return false; }
+    return genotype_row(w, t, d, w.sup.data(), sm, werr);
+  };
   // The regions of many bounds through the device (strl_regions_fetch): the .bai linear index gives every region's run of
   // BGZF blocks; their compressed bytes are read into page-locked memory, inflated on the GPU -- which also cuts out the
   // records the query returns -- and the workers are left with parsing a few hundred records and the rules per bound.  The
   // host path inflates ~10 blocks per bound on a CPU (2 - 3 ms): that was the whole evidence step.  Batches of 384 MB of
   // inflated bytes (128 ... 768 MB measured alike); one batch is being read while two are on the device and one with the workers.  STRL_CALL_REGIONS=host keeps the
   // host path; a region whose blocks the index cannot bound, and CRAM input, take it by themselves.
+  // The evidence itself is computed where the records are (strl_regions_evidence: no record bytes come back, the workers are
+  // left with genotype() and the row); a region the device passes on (status 2: more records or a wider span than its
+  // capacity rule takes) goes to the host path like one the index cannot bound.  Asked for with STRL_CALL_EVIDENCE=device;
+  // without it (or with =host) the records come back to strl_spanners on the workers.
   struct Batch {
     size_t t0 = 0, t1 = 0;
     std::vector<uint32_t> which;            // tasks of [t0, t1) that go through the device
@@ -1964,12 +1972,21 @@ static int call_main(int argc, char **argv) {
     std::vector<uint32_t> clen, isize, crc;
     std::vector<strl_region_req> req;
     std::vector<uint8_t> status;
+    std::vector<strl_bounds> bnd;           // device evidence: the regions' bounds, their Support lists and summaries
+    std::vector<strl_support> sup;
+    std::vector<uint64_t> sup_off;
+    std::vector<strl_span_summary> sum;
+    double ev_ms = 0;
     uint64_t comp_bytes = 0, inflated = 0;
     int rc = 0;
     std::string err;
   };
   const char *regions_env = getenv("STRL_CALL_REGIONS");
   const bool device_regions = !rd.is_cram() && !(regions_env && !strcmp(regions_env, "host"));
+  const char *evidence_env = getenv("STRL_CALL_EVIDENCE");
+  const bool device_evidence = device_regions && evidence_env && !strcmp(evidence_env, "device");   // opt-in until measured on a device
+  uint64_t n_ev_device = 0, n_ev_passed = 0;
+  double t_ev_kernels = 0;
   const uint64_t batch_inflated = getenv("STRL_CALL_BATCH_MB") ? (uint64_t)atoll(getenv("STRL_CALL_BATCH_MB")) << 20 : (uint64_t)384 << 20;
   int region_fd = -1;
   constexpr size_t NSETS = 4;      // batches in flight: one being read, two on the device (its two region slots), one with the workers
@@ -1986,7 +2003,8 @@ static int call_main(int argc, char **argv) {
         pin_comp_cap[k] = batch_inflated / 2 + (16 << 20);
         pin_out_cap[k] = (uint64_t)((double)batch_inflated * 0.75) + (16 << 20);
         pin_comp[k] = static_cast<uint8_t *>(strl_pinned_alloc(pin_comp_cap[k]));
-        pin_out[k] = static_cast<uint8_t *>(strl_pinned_alloc(pin_out_cap[k]));
+        if (device_evidence) pin_out_cap[k] = 0;       // (no record bytes come back)
+        else pin_out[k] = static_cast<uint8_t *>(strl_pinned_alloc(pin_out_cap[k]));
         if (!pin_comp[k]) pin_comp_cap[k] = 0;
         if (!pin_out[k]) pin_out_cap[k] = 0;
       }
@@ -2070,6 +2088,7 @@ static int call_main(int argc, char **argv) {
             }
             B.comp_bytes += (o + 15) & ~(uint64_t)15;
             B.req.push_back(q);
+            if (device_evidence) B.bnd.push_back(tasks[j].b);
             B.which.push_back((uint32_t)j);
           }
           ++j;
@@ -2100,14 +2119,14 @@ static int call_main(int argc, char **argv) {
               pin_comp_cap[s] = B.comp_bytes + B.comp_bytes / 4 + 64;
               pin_comp[s] = static_cast<uint8_t *>(strl_pinned_alloc(pin_comp_cap[s]));
             }
-            if (pin_out_cap[s] < want_out) {
+            if (!device_evidence && pin_out_cap[s] < want_out) {
               if (pin_out[s]) strl_pinned_free(pin_out[s]);
               pin_out_cap[s] = want_out + want_out / 4;
               pin_out[s] = static_cast<uint8_t *>(strl_pinned_alloc(pin_out_cap[s]));
             }
             const auto tr1 = std::chrono::steady_clock::now();
             t_pin += std::chrono::duration<double>(tr1 - tr0).count();
-            if (!pin_comp[s] || !pin_out[s]) { B.rc = STRL_ERR_HIP; B.err = "page-locked memory for the region reads"; }
+            if (!pin_comp[s] || (!device_evidence && !pin_out[s])) { B.rc = STRL_ERR_HIP; B.err = "page-locked memory for the region reads"; }
             else {
               std::atomic<bool> io_bad{false};
               io_pool.parallel_for((B.which.size() + 15) / 16, [&](size_t blk) {
@@ -2138,9 +2157,23 @@ static int call_main(int argc, char **argv) {
           if (!B.which.empty() && !B.rc) {
             const auto tf0 = std::chrono::steady_clock::now();
             B.out_off.assign(B.which.size(), 0); B.out_len.assign(B.which.size(), 0); B.status.assign(B.which.size(), 1);
+            if (device_evidence) {
+              // the Support lists: a few per record over the bound, sized by a guess and by what it took if the guess proves short
+              B.sup.resize((size_t)(B.inflated / 512) + 64 * B.which.size() + 1024);
+              B.sup_off.assign(B.which.size() + 1, 0);
+              B.sum.assign(B.which.size(), strl_span_summary{});
+              for (int attempt = 0; attempt < 2; ++attempt) {
+                B.status.assign(B.which.size(), 1);
+                B.rc = strl_regions_evidence(ctx, pin_comp[s], B.comp_bytes, B.coff.data(), B.clen.data(), B.isize.data(), B.crc.data(), (uint32_t)B.clen.size(), B.req.data(),
+                                             B.bnd.data(), (uint32_t)B.req.size(), window, frag, min_mapq, B.sup.data(), B.sup.size(), B.sup_off.data(), B.sum.data(),
+                                             B.status.data(), &B.ev_ms);
+                if (B.rc != STRL_ERR_CAPACITY || B.sup_off.back() <= B.sup.size()) break;
+                B.sup.resize((size_t)B.sup_off.back() + 64);
+              }
+            } else
             B.rc = strl_regions_fetch(ctx, pin_comp[s], B.comp_bytes, B.coff.data(), B.clen.data(), B.isize.data(), B.crc.data(), (uint32_t)B.clen.size(), B.req.data(),
                                       (uint32_t)B.req.size(), pin_out[s], pin_out_cap[s], B.out_off.data(), B.out_len.data(), B.status.data());
-            if (B.rc == STRL_ERR_CAPACITY && !B.out_off.empty() && B.out_off[0] > pin_out_cap[s]) {
+            if (!device_evidence && B.rc == STRL_ERR_CAPACITY && !B.out_off.empty() && B.out_off[0] > pin_out_cap[s]) {
               const uint64_t need = B.out_off[0] + B.out_off[0] / 16 + 64;
               strl_pinned_free(pin_out[s]);
               pin_out[s] = static_cast<uint8_t *>(strl_pinned_alloc(need));
@@ -2180,7 +2213,9 @@ static int call_main(int argc, char **argv) {
         std::vector<int64_t> slot(B.t1 - B.t0, -1);
         for (size_t k = 0; k < B.which.size(); ++k) {
           if (B.status[k] == 0) { slot[B.which[k] - B.t0] = (int64_t)k; ++n_dev_regions; dev_kept += B.out_len[k]; }
+          if (device_evidence) { n_ev_device += B.status[k] == 0; n_ev_passed += B.status[k] == 2; }
         }
+        t_ev_kernels += B.ev_ms * 1e-3;
         dev_comp_bytes += B.comp_bytes; dev_inflated += B.inflated;
         ev_pool.parallel_for((B.t1 - B.t0 + per - 1) / per, [&](size_t blk) {
           with_worker([&](Worker &w) {
@@ -2188,6 +2223,13 @@ static int call_main(int argc, char **argv) {
               const int64_t k = slot[j - B.t0];
               if (k < 0) { { std::lock_guard<std::mutex> lk(wm); ++n_host_regions; } if (!host_task(w, j)) break; continue; }
               std::string werr;
+              if (device_evidence) {
+                const auto tw1 = std::chrono::steady_clock::now();
+                const bool ok = genotype_row(w, tasks[j], done[j], B.sup.data() + B.sup_off[(size_t)k], B.sum[(size_t)k], werr);
+                ns_rules += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tw1).count();
+                if (!ok) { fail(werr); break; }
+                continue;
+              }
               w.region.clear();
               const auto tw0 = std::chrono::steady_clock::now();
               if (BamReader::append_records(w.region, pin_out[s] + B.out_off[(size_t)k], (size_t)B.out_len[(size_t)k], werr) < 0) { fail("[strling] error reading " + bam + ": " + werr); break; }
@@ -2278,6 +2320,9 @@ static int call_main(int argc, char **argv) {
             t_start_up, t_up_ctx, t_up_bin, t_up_bam, std::chrono::duration<double>(tc2 - tc1).count(), (unsigned long long)nb, n_workers, t_evidence, (double)ns_region.load() * 1e-9, (double)ns_rules.load() * 1e-9,
             (unsigned long long)n_dev_regions, (unsigned long long)n_host_regions, t_plan, t_pin, t_pread, t_fetch, t_wait_fetch, (double)dev_comp_bytes / 1e6, (double)dev_inflated / 1e6, (double)dev_kept / 1e6,
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call0).count());
+  if (verbose && device_regions)
+    fprintf(stderr, "[strling] evidence of the regions through the device: %s -- computed on the device %llu, passed on to the host (beyond 4096 records or a span of 9190) %llu, evidence kernels %.3f s\n",
+            device_evidence ? "device (STRL_CALL_EVIDENCE=device)" : "host", (unsigned long long)n_ev_device, (unsigned long long)n_ev_passed, t_ev_kernels);
   char row[2048];
   std::vector<uint64_t> order(std::max<size_t>(calls.size(), 1)), uorder(std::max<size_t>((size_t)nu, 1));
   CHECK(strl_calls_finish(calls.data(), calls.size(), unplaced.data(), nu, order.data()));   // :264-278
