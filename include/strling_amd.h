@@ -679,6 +679,48 @@ int strl_front_treads_named(strl_ctx *ctx, strl_tread *treads, uint64_t cap, uin
 void *strl_pinned_alloc(uint64_t bytes);
 void strl_pinned_free(void *p);
 
+/* ---- the BAM index (.bai) built on the device ----
+ * What `samtools index` does on one thread through htslib (sam_index_build: bam_read1 + hts_idx_push per record, then
+ * hts_idx_finish); the reference only consumes an index (call.nim:101-102 opens the BAM with index=true).  The chunks go through
+ * the front end's copy + inflate + CRC + record scan (the same kernels as strl_front_push, and the same block tables), then one
+ * lane per record computes end (CIGAR ops M, D, N, =, X; 1 for flag 0x4 or an empty CIGAR), bin (reg2bin, SAM spec 5.3) and the
+ * virtual offsets of its first byte and of the byte behind it; consecutive records of one (reference, bin) collapse into a run
+ * and only the runs stay resident (40 B each).  No record is parsed for the scorer and none of strl_front_begin's per-read,
+ * pair-pass or name state is allocated.  Chunks are pipelined like strl_front_push: push(i) enqueues chunk i's copy + inflate +
+ * scan, then indexes chunk i - 1.  Records may straddle blocks and chunks.
+ *   l_ref                 [n_ref] reference lengths of the BAM header: they size the linear index (one 64-bit word per 16 KiB, and
+ *                         64 windows = 1 Mbase behind l_ref: reads that hang over the end of a contig are indexed like any other)
+ *   first_record_offset   bytes between the start of the first pushed block's inflated data and the first record
+ *   comp .. crc32         as strl_front_push (crc32 may be NULL: not checked); blocks in file order, each once, none empty
+ *   block_off             per block: file offset of its first byte (the gzip header), what a virtual offset names
+ *   end_off               file offset behind the chunk's last block
+ *   strl_bamindex_reserve (optional, after _begin) as strl_front_reserve
+ *   strl_bamindex_finish  indexes what is in flight, sorts the runs by (reference, bin) (the library's own radix sort), merges
+ *                         runs that have become neighbours and serializes: *bai_bytes = size of the .bai
+ *   strl_bamindex_fetch   the bytes of the .bai file (SAM spec 5.2): bins ascending per reference, the metadata pseudo-bin 37450
+ *                         (file span, mapped / placed-unmapped counts) last, n_intv = last window touched + 1, windows no
+ *                         record overlaps 0, n_no_coor at the end.  A valid index for htslib-style readers; byte identity with
+ *                         samtools' file is not claimed (a chunk that ends at the end of a block may name it either way).
+ * Refused, never indexed wrongly: STRL_ERR_FORMAT a file that is not coordinate sorted (the message names the record), a record
+ * that reaches more than 1 Mbase past its reference's l_ref or has a refID outside the header, a malformed record, invalid DEFLATE data, a file
+ * that ends inside a record; STRL_ERR_LIMIT a position or end >= 2^29 (a .bai cannot hold it; CSI is not written);
+ * STRL_ERR_CRC; STRL_ERR_NOMEM. */
+typedef struct {
+  uint64_t n_records;  /* records of the file */
+  uint64_t n_no_coor;  /* those without a reference (the index's last word) */
+  uint64_t n_runs;     /* runs of consecutive records of one (reference, bin): what stayed resident */
+  uint64_t n_chunks;   /* chunks written to the bins (runs merged again behind the sort) */
+} strl_bamindex_info;
+int strl_bamindex_begin(strl_ctx *ctx, int32_t n_ref, const int32_t *l_ref, uint64_t first_record_offset);
+int strl_bamindex_reserve(strl_ctx *ctx, uint32_t max_blocks, uint64_t max_comp_bytes);
+int strl_bamindex_push(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                       const uint32_t *crc32, const uint64_t *block_off, uint64_t end_off, uint32_t n_blocks);
+int strl_bamindex_finish(strl_ctx *ctx, uint64_t *bai_bytes, strl_bamindex_info *info);
+int strl_bamindex_fetch(strl_ctx *ctx, uint8_t *out, uint64_t cap);
+/* gives the builder up (also after an error): what it had in flight has completed on return, its tables are freed; the front
+ * end's chunk buffers stay with the context */
+int strl_bamindex_end(strl_ctx *ctx);
+
 /* ---- fragment-length statistics (utils.nim:139-146) ---- */
 int strl_frag_median(const uint32_t frag[4096], double pct);
 

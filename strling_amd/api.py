@@ -55,6 +55,10 @@ class FrontChunk(C.Structure):
                 ("max_l_seq", C.c_uint32), ("scan_slow_segments", C.c_uint32)]
 
 
+class BamindexInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_no_coor", C.c_uint64), ("n_runs", C.c_uint64), ("n_chunks", C.c_uint64)]
+
+
 def _front_chunk(c):
     return {k: int(getattr(c, k)) for k, _ in FrontChunk._fields_}
 
@@ -123,7 +127,8 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_pairer_result", "strl_qname_hash", "strl_extract", "strl_cluster", "strl_cluster_replay", "strl_frag_median",
            "strl_bin_write", "strl_bin_read", "strl_bounds_row", "strl_cluster_members", "strl_spanners", "strl_genotype",
            "strl_calls_finish", "strl_unplaced_order", "strl_call_row", "strl_canonical_repeat", "strl_assign_reads_loci", "strl_group_order",
-           "strl_extract_device", "strl_treads_fetch", "strl_ctx_pair_times", "strl_sort_pairs", "strl_cluster_resident", "strl_ctx_cluster_times", "strl_pair_rows", "strl_extract_begin", "strl_extract_add", "strl_extract_finish", "strl_pair_rule", "strl_bounds_bare", "strl_ctx_treads_device", "strl_cluster_gathered", "strl_inflate_blocks", "strl_ctx_inflate_ms", "strl_regions_fetch", "strl_evidence_records", "strl_regions_evidence", "strl_front_begin", "strl_front_push", "strl_front_push_after", "strl_front_reserve", "strl_front_stage", "strl_front_enqueue_after", "strl_front_collect", "strl_ctxs_extract_gather", "strl_front_finish", "strl_front_fragwords", "strl_front_fragwords_async", "strl_event_wait", "strl_front_records", "strl_front_tids", "strl_front_qnames", "strl_front_treads_named", "strl_pinned_alloc", "strl_pinned_free", "strl_comm_unique_id", "strl_ctx_comm_init", "strl_ctxs_comm_init", "strl_ctx_comm_info", "strl_cluster_exchange", "strl_ctxs_cluster_exchange", "strl_exchange_treads", "strl_ctx_set_treads", "strl_cluster_collect", "strl_ctx_tail_stream", "strl_ctx_mem_info", "strl_bin_peek", "strl_front_trim_next", "strl_front_tail_bytes", "strl_ctx_blocking_waits", "strl_score_read_host", "strl_front_end"]
+           "strl_extract_device", "strl_treads_fetch", "strl_ctx_pair_times", "strl_sort_pairs", "strl_cluster_resident", "strl_ctx_cluster_times", "strl_pair_rows", "strl_extract_begin", "strl_extract_add", "strl_extract_finish", "strl_pair_rule", "strl_bounds_bare", "strl_ctx_treads_device", "strl_cluster_gathered", "strl_inflate_blocks", "strl_ctx_inflate_ms", "strl_regions_fetch", "strl_evidence_records", "strl_regions_evidence", "strl_front_begin", "strl_front_push", "strl_front_push_after", "strl_front_reserve", "strl_front_stage", "strl_front_enqueue_after", "strl_front_collect", "strl_ctxs_extract_gather", "strl_front_finish", "strl_front_fragwords", "strl_front_fragwords_async", "strl_event_wait", "strl_front_records", "strl_front_tids", "strl_front_qnames", "strl_front_treads_named", "strl_pinned_alloc", "strl_pinned_free", "strl_comm_unique_id", "strl_ctx_comm_init", "strl_ctxs_comm_init", "strl_ctx_comm_info", "strl_cluster_exchange", "strl_ctxs_cluster_exchange", "strl_exchange_treads", "strl_ctx_set_treads", "strl_cluster_collect", "strl_ctx_tail_stream", "strl_ctx_mem_info", "strl_bin_peek", "strl_front_trim_next", "strl_front_tail_bytes", "strl_ctx_blocking_waits", "strl_score_read_host", "strl_front_end",
+           "strl_bamindex_begin", "strl_bamindex_reserve", "strl_bamindex_push", "strl_bamindex_finish", "strl_bamindex_fetch", "strl_bamindex_end"]
 
 
 def lib_path():
@@ -223,6 +228,12 @@ def load(build_if_missing=True):
     L.strl_front_fragwords.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     L.strl_front_tids.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     L.strl_front_qnames.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.strl_bamindex_begin.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64]
+    L.strl_bamindex_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    L.strl_bamindex_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+    L.strl_bamindex_finish.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(BamindexInfo)]
+    L.strl_bamindex_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_bamindex_end.argtypes = [C.c_void_p]
     L.strl_pinned_alloc.argtypes = [C.c_uint64]
     L.strl_pinned_alloc.restype = C.c_void_p
     L.strl_pinned_free.argtypes = [C.c_void_p]
@@ -693,17 +704,19 @@ class Context:
     @staticmethod
     def _bam_blocks(path):
         """the host side of the device front end in Python: BGZF block table (payload offset, payload length, isize, crc), the
-        header (inflated here) -> dict(data, blocks, n_ref, targets, text, b0 = the block the first record starts in, first_off)"""
+        header (inflated here) -> dict(data, blocks, block_off = file offset of each block of the table, n_ref, targets, text, b0 = the block the first record
+        starts in, first_off)"""
         import struct, zlib
         data = np.fromfile(path, np.uint8)
         raw = data.tobytes()
-        blocks, o = [], 0
+        blocks, block_off, o = [], [], 0
         while o < len(raw):
             xlen = struct.unpack_from("<H", raw, o + 10)[0]
             bsize = struct.unpack_from("<H", raw, o + 16)[0] + 1
             isz = struct.unpack_from("<I", raw, o + bsize - 4)[0]
             if isz:
                 blocks.append((o + 12 + xlen, bsize - 12 - xlen - 8, isz, struct.unpack_from("<I", raw, o + bsize - 8)[0]))
+                block_off.append(o)
             o += bsize
         hdr, k = b"", 0
 
@@ -732,7 +745,7 @@ class Context:
         while b0 < len(blocks) and cum + blocks[b0][2] <= at:
             cum += blocks[b0][2]
             b0 += 1
-        return dict(data=data, raw=raw, blocks=blocks, n_ref=n_ref, targets=targets, text=text, b0=b0, first_off=at - cum)
+        return dict(data=data, raw=raw, blocks=blocks, block_off=block_off, n_ref=n_ref, targets=targets, text=text, b0=b0, first_off=at - cum)
 
     def _front_push_blocks(self, B, c0, c1, chunk_blocks, check_crc, trim=0):
         """blocks [c0, c1) of the table through strl_front_push in chunks; trim = inflated bytes at the end of the LAST block that
@@ -793,6 +806,35 @@ class Context:
         _check(self.L.strl_front_begin(self.h, B["n_ref"], B["first_off"], n_reads_hint))
         chunks = self._front_push_blocks(B, B["b0"], len(B["blocks"]), chunk_blocks, check_crc)
         return self._front_results(B, chunks)
+
+    def bamindex(self, path, chunk_blocks=16384, check_crc=True):
+        """the .bai of a coordinate-sorted BAM FILE built on the device (strl_bamindex_begin / _push / _finish / _fetch; what
+        `samtools index` writes).  -> (bytes of the .bai, dict(n_records, n_no_coor, n_runs, n_chunks))"""
+        B = self._bam_blocks(path)
+        l_ref = np.array([t[1] for t in B["targets"]], np.int32)
+        _check(self.L.strl_bamindex_begin(self.h, B["n_ref"], _ptr(l_ref) if l_ref.size else None, B["first_off"]))
+        try:
+            data, blocks, keep = B["data"], B["blocks"], []
+            for s0 in range(B["b0"], len(blocks), chunk_blocks):
+                cb = blocks[s0:s0 + chunk_blocks]
+                lo, hi = cb[0][0], cb[-1][0] + cb[-1][1]
+                comp = np.ascontiguousarray(data[lo:hi])
+                coff = np.array([b[0] - lo for b in cb], np.uint64)
+                clen = np.array([b[1] for b in cb], np.uint32)
+                isz = np.array([b[2] for b in cb], np.uint32)
+                crc = np.array([b[3] for b in cb], np.uint32)
+                boff = np.array(B["block_off"][s0:s0 + chunk_blocks], np.uint64)
+                keep = (keep + [(comp, coff, clen, isz, crc, boff)])[-3:]      # pageable memory: the copy is staged by the runtime
+                _check(self.L.strl_bamindex_push(self.h, comp.ctypes.data, comp.size, _ptr(coff), _ptr(clen), _ptr(isz), _ptr(crc) if check_crc else None,
+                                                 _ptr(boff), hi + 8, len(cb)))
+            nbytes = C.c_uint64(0)
+            info = BamindexInfo()
+            _check(self.L.strl_bamindex_finish(self.h, C.byref(nbytes), C.byref(info)))
+            out = np.zeros(max(1, nbytes.value), np.uint8)
+            _check(self.L.strl_bamindex_fetch(self.h, out.ctypes.data, out.size))
+        finally:
+            self.L.strl_bamindex_end(self.h)
+        return out[:nbytes.value].tobytes(), {k: int(getattr(info, k)) for k, _ in BamindexInfo._fields_}
 
     def inflate_ms(self):
         """kernel time (ms) of the last inflate_blocks call"""

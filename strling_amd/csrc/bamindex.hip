@@ -1,0 +1,585 @@
+// bamindex.hip -- `strling bamindex`: the BAM index (.bai, SAM spec 5.2) built on the GPU (gfx950) behind the front end's record
+// scan.  What `samtools index` does on one thread through htslib (sam_index_build: inflate, bam_read1, hts_idx_push per record,
+// hts_idx_finish); the reference only consumes an index (call.nim:101-102).  A chunk of BGZF blocks goes through
+//   front_stage_a        (front.hip)   copy + inflate + CRC + rec_guess / rec_walk / rec_link / rec_emit: recoff[] of the chunk
+//   bai_record_kernel                  one lane per record: refID, pos, flag, CIGAR -> end, bin (reg2bin), virtual offsets of its
+//                                      first byte and of the byte behind it, sortedness, the linear index's windows (a 64-bit
+//                                      atomicMin only from the first record that reaches a window), the per-reference span and
+//                                      counts (one set of atomics per wave), and a flag where (tid, bin) changes: a run starts
+//   bai_scan_kernel                    one block: exclusive sums of the flags per 256 records
+//   bai_emit_kernel                    the flagged records write their run into the resident table, in file order, and close
+//                                      the run in front of them (records lie back to back: a run ends where the next begins)
+// and nothing of a chunk but its runs stays: the table grows with the number of (tid, bin) changes, not with the records.
+// At the end one stable radix sort (sort.hip) of the runs by (tid, bin), a second merge of runs that have become neighbours
+// (prev.end == cur.beg in the inflated stream), and the host packs the bytes from the sorted chunks.
+// rec_parse_kernel, the scorer and strl_front_begin's per-read state are not involved.
+#include <string.h>
+#include <algorithm>
+#include "front.h"
+#include "sort.h"
+#include "device_util.h"
+
+namespace strl {
+
+constexpr uint32_t BAI_ERR_KINDS = 5;
+constexpr uint32_t BAI_E_UNSORTED = 0, BAI_E_RANGE = 1, BAI_E_TID = 2, BAI_E_LREF = 3, BAI_E_NEGPOS = 4;
+constexpr uint64_t BAI_KEY_NONE = ~0ull;
+constexpr int32_t BAI_MAX_POS = 1 << 29;       // what the five-level binning scheme of a .bai addresses
+constexpr uint32_t BAI_META_BIN = 37450;
+constexpr int64_t BAI_LREF_SLACK = 64;         // windows of the linear index kept behind l_ref (1 Mbase)
+
+struct BaiRun { uint64_t key, beg_v, end_v, beg_abs, end_abs; };   // key = tid << 16 | bin; virtual offsets; offsets in the inflated stream
+struct BaiChunk { uint64_t key, beg_v, end_v; };
+struct BaiLast {          // the last record so far
+  uint64_t key, end_v, end_abs;
+  int32_t tid, pos, end_win, pad;
+};
+struct BaiState {         // device words of the builder; the host reads them back behind every chunk
+  uint64_t err_ord[BAI_ERR_KINDS];   // ordinal of the first record of each kind of refusal, ~0 = none
+  uint64_t n_no_coor;
+  uint32_t n_heads, pad;             // runs that start in the chunk just scanned / chunks after the merge
+  BaiLast last[2];                   // [parity of the chunk]: read from one, written to the other
+};
+
+struct BaiPush {
+  const uint8_t *U;
+  const uint32_t *recoff;
+  uint32_t n;
+  const int64_t *vrel;      // [vm + 1] offset in the chunk's buffer of each block's first inflated byte (blocks of the previous
+  const uint64_t *vfoff;    //          chunks that the carried record may start in come first); file offset of the block.  [vm]: the end
+  uint32_t vm;
+  int64_t abs0;             // offset in the file's inflated stream of the buffer's byte 0
+  uint64_t ord0;            // ordinal of the chunk's first record
+  int32_t n_ref;
+  const uint64_t *win_off;  // [n_ref + 1] first window of each reference in lin[]
+  uint64_t *lin, *ref_beg, *ref_end, *ref_cnt;
+  BaiState *S;
+  uint32_t par;
+  uint8_t *flag;
+  uint32_t *blk_cnt;
+  BaiRun *runs;
+  uint64_t run_base;
+};
+
+struct BaiRec { int32_t tid, pos, end; uint32_t flag, bs; };
+
+__device__ __forceinline__ void bai_read(const uint8_t *U, uint32_t q, BaiRec &r) {
+  const uint8_t *R = U + q;
+  r.bs = ld32u(R);
+  r.tid = (int32_t)ld32u(R + 4); r.pos = (int32_t)ld32u(R + 8);
+  const uint32_t l_qname = R[12], n_cigar = ld16u(R + 16);
+  r.flag = ld16u(R + 18);
+  int64_t rl = 0;
+  if (!(r.flag & 4u)) {
+    const uint8_t *cg = R + 36 + l_qname;       // (inside the record: rec_header's rule, checked by the scan's walk)
+    for (uint32_t j = 0; j < n_cigar; ++j) {
+      const uint32_t c = ld32u(cg + 4u * j), op = c & 15u;
+      if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) rl += c >> 4;
+    }
+  }
+  const int64_t e = (int64_t)r.pos + (rl ? rl : 1);
+  r.end = e > 0x7fffffffll ? 0x7fffffff : (int32_t)e;
+}
+__device__ __forceinline__ uint32_t bai_reg2bin(int32_t beg, int32_t end) {      // SAM spec 5.3
+  --end;
+  if (beg >> 14 == end >> 14) return 4681u + (uint32_t)(beg >> 14);
+  if (beg >> 17 == end >> 17) return 585u + (uint32_t)(beg >> 17);
+  if (beg >> 20 == end >> 20) return 73u + (uint32_t)(beg >> 20);
+  if (beg >> 23 == end >> 23) return 9u + (uint32_t)(beg >> 23);
+  if (beg >> 26 == end >> 26) return 1u + (uint32_t)(beg >> 26);
+  return 0u;
+}
+// a record the index can hold: a reference of the header, 0 <= pos, end <= 2^29, its last window one of the reference's
+// (l_ref and BAI_LREF_SLACK windows behind it: aligners do leave reads that hang over the end of a contig).  else the kind of refusal
+__device__ __forceinline__ int bai_refusal(const BaiRec &r, int32_t n_ref, const uint64_t *win_off) {
+  if (r.tid < -1 || r.tid >= n_ref) return (int)BAI_E_TID;
+  if (r.tid < 0) return -1;
+  if (r.pos < 0) return (int)BAI_E_NEGPOS;
+  if (r.pos >= BAI_MAX_POS || r.end > BAI_MAX_POS) return (int)BAI_E_RANGE;
+  if ((uint64_t)((r.end - 1) >> 14) >= win_off[r.tid + 1] - win_off[r.tid]) return (int)BAI_E_LREF;
+  return -1;
+}
+__device__ __forceinline__ uint64_t bai_key(const BaiRec &r, int32_t n_ref, bool indexable) {
+  return (r.tid < 0 || !indexable) ? (uint64_t)(uint32_t)n_ref << 16 : ((uint64_t)(uint32_t)r.tid << 16) | bai_reg2bin(r.pos, r.end);
+}
+// virtual offset of the byte at buffer offset q: the last block that starts at or in front of it (vrel[0] <= q <= vrel[m])
+__device__ __forceinline__ uint64_t bai_voff(const int64_t *vrel, const uint64_t *vfoff, uint32_t m, int64_t q) {
+  uint32_t lo = 0, hi = m;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1u) >> 1;
+    if (vrel[mid] <= q) lo = mid; else hi = mid - 1u;
+  }
+  return (vfoff[lo] << 16) | (uint64_t)(q - vrel[lo]);
+}
+
+__global__ __launch_bounds__(256) void bai_record_kernel(BaiPush P) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+  const bool act = i < P.n;
+  BaiRec r{-1, -1, 0, 0, 0};
+  uint32_t q = 0;
+  int bad = -1;
+  if (act) { q = P.recoff[i]; bai_read(P.U, q, r); bad = bai_refusal(r, P.n_ref, P.win_off); }
+  const bool placed = act && r.tid >= 0 && bad < 0;
+  const uint64_t key = act ? bai_key(r, P.n_ref, bad < 0) : BAI_KEY_NONE;
+  const int32_t end_win = placed ? (r.end - 1) >> 14 : -1;
+  // the record in front: the lane below, or (first lane of a wave) read again / the previous chunk's last
+  int32_t ptid = __shfl_up(r.tid, 1), ppos = __shfl_up(r.pos, 1), pwin = __shfl_up(end_win, 1);
+  uint64_t pkey = __shfl_up(key, 1);
+  if (act && lane == 0) {
+    if (i == 0) { const BaiLast &L = P.S->last[P.par]; ptid = L.tid; ppos = L.pos; pwin = L.end_win; pkey = L.key; }
+    else {
+      BaiRec p;
+      bai_read(P.U, P.recoff[i - 1], p);
+      const bool pok = bai_refusal(p, P.n_ref, P.win_off) < 0;
+      ptid = p.tid; ppos = p.pos; pkey = bai_key(p, P.n_ref, pok);
+      pwin = (p.tid >= 0 && pok) ? (p.end - 1) >> 14 : -1;
+    }
+  }
+  uint64_t beg_v = 0, end_v = 0;
+  if (act) {
+    const uint64_t ord = P.ord0 + i;
+    if (bad >= 0) atomicMin(reinterpret_cast<unsigned long long *>(&P.S->err_ord[bad]), (unsigned long long)ord);
+    // coordinate order: (tid, pos) does not decrease, tid = -1 only at the end
+    const uint32_t uc = (uint32_t)r.tid, up = (uint32_t)ptid;
+    if (pkey != BAI_KEY_NONE && (uc < up || (uc == up && r.tid >= 0 && r.pos < ppos)))
+      atomicMin(reinterpret_cast<unsigned long long *>(&P.S->err_ord[BAI_E_UNSORTED]), (unsigned long long)ord);
+    beg_v = bai_voff(P.vrel, P.vfoff, P.vm, (int64_t)q);
+    end_v = bai_voff(P.vrel, P.vfoff, P.vm, (int64_t)q + 4 + (int64_t)r.bs);
+  }
+  // linear index: the windows no record in front of this one has reached (in a sorted stream the lane below covers all
+  // but the window a record is the first to enter; an N skip of hundreds of kilobases enters many)
+  if (placed) {
+    const int32_t w0 = r.pos >> 14, from = (ptid == r.tid && pwin >= w0) ? pwin + 1 : w0;
+    uint64_t *lin = P.lin + P.win_off[r.tid];
+    for (int32_t w = from; w <= end_win; ++w) atomicMin(reinterpret_cast<unsigned long long *>(&lin[w]), (unsigned long long)beg_v);
+  }
+  // per reference: span, mapped / placed-unmapped counts -- one lane of a wave whose records share a reference
+  const unsigned long long pm = __ballot(placed);
+  if (pm) {
+    const int first = __ffsll((long long)pm) - 1, last = 63 - __clzll((long long)pm);
+    const int32_t t0 = __shfl(r.tid, first);
+    const unsigned long long same = __ballot(placed && r.tid == t0), un = __ballot(placed && (r.flag & 4u));
+    const uint64_t last_end = __shfl(end_v, last);
+    if (same == pm) {
+      if ((int)lane == first) {
+        atomicMin(reinterpret_cast<unsigned long long *>(&P.ref_beg[t0]), (unsigned long long)beg_v);
+        atomicMax(reinterpret_cast<unsigned long long *>(&P.ref_end[t0]), (unsigned long long)last_end);
+        const unsigned n_un = (unsigned)__popcll(un), n_map = (unsigned)__popcll(pm) - n_un;
+        if (n_map) atomicAdd(reinterpret_cast<unsigned long long *>(&P.ref_cnt[2 * t0]), (unsigned long long)n_map);
+        if (n_un) atomicAdd(reinterpret_cast<unsigned long long *>(&P.ref_cnt[2 * t0 + 1]), (unsigned long long)n_un);
+      }
+    } else if (placed) {
+      atomicMin(reinterpret_cast<unsigned long long *>(&P.ref_beg[r.tid]), (unsigned long long)beg_v);
+      atomicMax(reinterpret_cast<unsigned long long *>(&P.ref_end[r.tid]), (unsigned long long)end_v);
+      atomicAdd(reinterpret_cast<unsigned long long *>(&P.ref_cnt[2 * r.tid + ((r.flag & 4u) ? 1 : 0)]), 1ull);
+    }
+  }
+  const unsigned long long nc = __ballot(act && r.tid < 0);
+  if (nc && lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&P.S->n_no_coor), (unsigned long long)__popcll(nc));
+  const bool head = act && key != pkey;
+  if (act) P.flag[i] = head ? 1 : 0;
+  const int heads = __syncthreads_count(head);
+  if (threadIdx.x == 0) P.blk_cnt[blockIdx.x] = (uint32_t)heads;
+  if (act && i == P.n - 1) {
+    BaiLast L;
+    L.key = key; L.end_v = end_v; L.end_abs = (uint64_t)(P.abs0 + (int64_t)q + 4 + (int64_t)r.bs);
+    L.tid = r.tid; L.pos = r.pos; L.end_win = end_win; L.pad = 0;
+    P.S->last[P.par ^ 1u] = L;
+  }
+}
+
+// One block: cnt[0, n) -> exclusive sums in place, the total to *total
+__global__ __launch_bounds__(1024) void bai_scan_kernel(uint32_t *cnt, uint32_t n, uint32_t *total) {
+  __shared__ uint32_t part[1024];
+  const uint32_t t = threadIdx.x, per = (n + 1023u) / 1024u, a = min(n, t * per), b = min(n, a + per);
+  uint32_t s = 0;
+  for (uint32_t k = a; k < b; ++k) s += cnt[k];
+  part[t] = s;
+  __syncthreads();
+  if (t == 0) { uint32_t run = 0; for (int k = 0; k < 1024; ++k) { const uint32_t v = part[k]; part[k] = run; run += v; } *total = run; }
+  __syncthreads();
+  uint32_t run = part[t];
+  for (uint32_t k = a; k < b; ++k) { const uint32_t v = cnt[k]; cnt[k] = run; run += v; }
+}
+
+// rank of a flagged thread among the flagged threads of its 256-thread block
+__device__ __forceinline__ uint32_t bai_block_rank(bool f) {
+  __shared__ uint32_t wsum[4];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(f);
+  if (lane == 0) wsum[w] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t r = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  for (uint32_t k = 0; k < w; ++k) r += wsum[k];
+  return r;
+}
+
+__global__ __launch_bounds__(256) void bai_emit_kernel(BaiPush P) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const bool head = i < P.n && P.flag[i];
+  const uint32_t rank = bai_block_rank(head);
+  if (!head) return;
+  const uint64_t slot = P.run_base + P.blk_cnt[blockIdx.x] + rank;
+  const uint32_t q = P.recoff[i];
+  BaiRec r;
+  bai_read(P.U, q, r);
+  const uint64_t beg_v = bai_voff(P.vrel, P.vfoff, P.vm, (int64_t)q), beg_abs = (uint64_t)(P.abs0 + (int64_t)q);
+  BaiRun &R = P.runs[slot];
+  R.key = bai_key(r, P.n_ref, bai_refusal(r, P.n_ref, P.win_off) < 0); R.beg_v = beg_v; R.beg_abs = beg_abs;
+  if (slot) { BaiRun &B = P.runs[slot - 1]; B.end_v = beg_v; B.end_abs = beg_abs; }
+}
+
+// finish: the open run ends behind the last record; sort keys of the runs
+__global__ void bai_keys_kernel(BaiRun *runs, uint32_t n, const BaiState *S, uint32_t par, uint64_t *keys, uint32_t *vals) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (i == n - 1) { runs[i].end_v = S->last[par].end_v; runs[i].end_abs = S->last[par].end_abs; }
+  keys[i] = runs[i].key; vals[i] = i;
+}
+// sorted by (tid, bin), file order kept inside a key: a chunk starts where the key changes or the run in front does not end here
+__global__ __launch_bounds__(256) void bai_merge_flag_kernel(const BaiRun *runs, const uint64_t *keys, const uint32_t *vals, uint32_t n, uint8_t *flag, uint32_t *blk_cnt) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  bool head = false;
+  if (j < n) {
+    head = j == 0 || keys[j] != keys[j - 1] || runs[vals[j - 1]].end_abs != runs[vals[j]].beg_abs;
+    flag[j] = head ? 1 : 0;
+  }
+  const int heads = __syncthreads_count(head);
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (uint32_t)heads;
+}
+__global__ __launch_bounds__(256) void bai_merge_emit_kernel(const BaiRun *runs, const uint64_t *keys, const uint32_t *vals, uint32_t n, const uint8_t *flag,
+                                                             const uint32_t *blk_cnt, const uint32_t *total, BaiChunk *out) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  const bool head = j < n && flag[j];
+  const uint32_t rank = bai_block_rank(head);
+  if (j < n && j == n - 1) out[*total - 1].end_v = runs[vals[j]].end_v;
+  if (!head) return;
+  const uint32_t slot = blk_cnt[blockIdx.x] + rank;
+  out[slot].key = keys[j]; out[slot].beg_v = runs[vals[j]].beg_v;
+  if (j) out[slot - 1].end_v = runs[vals[j - 1]].end_v;
+}
+__global__ void bai_fill_kernel(uint64_t *p, size_t n, uint64_t v) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
+}
+
+struct BaiBlock { int64_t abs; uint64_t foff; };       // a pushed block: offset of its first byte in the inflated stream, file offset
+struct strl_bai {
+  int32_t n_ref = 0;
+  std::vector<int32_t> l_ref;
+  std::vector<uint64_t> win_off;                      // [n_ref + 1]
+  DevBuf d_winoff, lin, ref_beg, ref_end, ref_cnt, state, runs, flag, blk_cnt;
+  DevBuf vt[2];                                       // [slot] block table of the chunk: vrel[m + 1] | vfoff[m + 1]
+  uint8_t *h_vt[2] = {nullptr, nullptr};              // pinned source of it
+  size_t h_vt_cap[2] = {0, 0};
+  uint32_t vm[2] = {0, 0};
+  int64_t abs0[2] = {0, 0};
+  BaiState *h_state = nullptr;                        // pinned
+  std::vector<BaiBlock> tail;                         // blocks that hold the last FRONT_CARRY_MAX inflated bytes pushed so far
+  int64_t abs_total = 0;                              // inflated bytes pushed so far
+  uint64_t end_off = 0;                               // file offset behind the last block pushed
+  uint64_t chunks = 0, done = 0;                      // pushed / indexed
+  uint64_t n_records = 0, n_runs = 0, n_chunks = 0;
+  uint32_t par = 0;
+  bool finished = false;
+  std::vector<uint8_t> bytes;                         // the serialized index
+};
+
+void bai_destroy(strl_bai *B) {
+  if (!B) return;
+  for (DevBuf *b : {&B->d_winoff, &B->lin, &B->ref_beg, &B->ref_end, &B->ref_cnt, &B->state, &B->runs, &B->flag, &B->blk_cnt, &B->vt[0], &B->vt[1]}) b->release();
+  for (uint8_t *p : B->h_vt) if (p) (void)hipHostFree(p);
+  if (B->h_state) (void)hipHostFree(B->h_state);
+  delete B;
+}
+
+static int bai_refuse(const strl_bai *B, const BaiState &S) {
+  uint32_t kind = BAI_ERR_KINDS;
+  for (uint32_t k = 0; k < BAI_ERR_KINDS; ++k)
+    if (S.err_ord[k] != ~0ull && (kind == BAI_ERR_KINDS || S.err_ord[k] < S.err_ord[kind])) kind = k;
+  if (kind == BAI_ERR_KINDS) return STRL_OK;
+  const unsigned long long at = (unsigned long long)S.err_ord[kind];
+  switch (kind) {
+    case BAI_E_UNSORTED: set_error("the BAM is not coordinate sorted: record %llu comes behind a record of a later position (or behind an unplaced one); sort it first", at); return STRL_ERR_FORMAT;
+    case BAI_E_RANGE: set_error("record %llu lies at or reaches past position 2^29 = 536870912, which a .bai cannot address (a CSI index can; writing CSI is not supported)", at); return STRL_ERR_LIMIT;
+    case BAI_E_TID: set_error("malformed BAM record %llu: its refID is not one of the header's %d references", at, B->n_ref); return STRL_ERR_FORMAT;
+    case BAI_E_LREF: set_error("record %llu reaches more than %lld bases past the end of its reference as the header gives it (l_ref); not indexed", at, (long long)(BAI_LREF_SLACK << 14)); return STRL_ERR_FORMAT;
+    default: set_error("record %llu has a reference but a negative position; not indexed", at); return STRL_ERR_FORMAT;
+  }
+}
+
+// the runs of the chunk in slot si (its record scan was enqueued by the push before): waits on the host for the scan's counts
+static int bai_index_chunk(strl_ctx *c, strl_front *F, strl_bai *B, int si) {
+  FrontSlot &S = F->slot[si];
+  STRL_HIP(hipEventSynchronize(S.ev_a));
+  const FrontInfo I = S.h_info[0];
+  if (I.err & FRONT_ERR_INFLATE) { set_error("invalid BGZF block (DEFLATE data or ISIZE)"); return STRL_ERR_FORMAT; }
+  if (I.err & FRONT_ERR_CRC) { set_error("CRC32 checksum mismatch in a BGZF block"); return STRL_ERR_CRC; }
+  if (I.err & FRONT_ERR_RECORD) { set_error("malformed BAM record"); return STRL_ERR_FORMAT; }
+  if (I.err & FRONT_ERR_CARRY) { set_error("BAM record of more than %u bytes", FRONT_CARRY_MAX); return STRL_ERR_FORMAT; }
+  const uint32_t n = I.n_records;
+  hipStream_t st = c->stream;
+  int rc;
+  if (n) {
+    const uint32_t nblk = (n + 255u) / 256u, m = B->vm[si];
+    if ((rc = B->flag.reserve((size_t)n + 64)) || (rc = B->blk_cnt.reserve((size_t)nblk * 4 + 64)) || (rc = B->vt[si].reserve((size_t)(m + 1) * 16))) return rc;
+    STRL_HIP(hipMemcpyAsync(B->vt[si].p, B->h_vt[si], (size_t)(m + 1) * 16, hipMemcpyHostToDevice, st));
+    BaiPush P{};
+    P.U = S.infl.as<uint8_t>(); P.recoff = S.recoff.as<uint32_t>(); P.n = n;
+    P.vrel = B->vt[si].as<int64_t>(); P.vfoff = B->vt[si].as<uint64_t>() + (m + 1); P.vm = m;
+    P.abs0 = B->abs0[si]; P.ord0 = B->n_records;
+    P.n_ref = B->n_ref; P.win_off = B->d_winoff.as<uint64_t>();
+    P.lin = B->lin.as<uint64_t>(); P.ref_beg = B->ref_beg.as<uint64_t>(); P.ref_end = B->ref_end.as<uint64_t>(); P.ref_cnt = B->ref_cnt.as<uint64_t>();
+    P.S = B->state.as<BaiState>(); P.par = B->par; P.flag = B->flag.as<uint8_t>(); P.blk_cnt = B->blk_cnt.as<uint32_t>();
+    hipLaunchKernelGGL(bai_record_kernel, dim3(nblk), dim3(256), 0, st, P);
+    STRL_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, P.blk_cnt, nblk, &P.S->n_heads);
+    STRL_HIP(hipGetLastError());
+    STRL_HIP(hipMemcpyAsync(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost, st));
+    STRL_HIP(hipStreamSynchronize(st));                 // the number of runs that start in the chunk: the table grows by exactly that
+    if ((rc = bai_refuse(B, *B->h_state))) return rc;
+    const uint64_t heads = B->h_state->n_heads;
+    if (B->n_runs + heads > 0x7ffffff0ull) { set_error("more than 2^31 runs of equal (reference, bin): beyond one device sort"); return STRL_ERR_LIMIT; }
+    if (heads) {
+      if ((rc = B->runs.grow((size_t)(B->n_runs + heads) * sizeof(BaiRun), (size_t)B->n_runs * sizeof(BaiRun), st))) return rc;
+      P.runs = B->runs.as<BaiRun>(); P.run_base = B->n_runs;
+      hipLaunchKernelGGL(bai_emit_kernel, dim3(nblk), dim3(256), 0, st, P);
+      STRL_HIP(hipGetLastError());
+      B->n_runs += heads;
+    }
+    B->n_records += n;
+    B->par ^= 1u;
+  }
+  STRL_HIP(hipEventRecord(S.ev_b, st));      // the slot's inflated bytes and record table may be overwritten behind this
+  S.b_pending = true;
+  return STRL_OK;
+}
+
+static void put32(std::vector<uint8_t> &o, uint32_t v) { for (int k = 0; k < 4; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
+static void put64(std::vector<uint8_t> &o, uint64_t v) { for (int k = 0; k < 8; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
+
+}  // namespace strl
+
+using namespace strl;
+
+extern "C" int strl_bamindex_begin(strl_ctx *c, int32_t n_ref, const int32_t *l_ref, uint64_t first_record_offset) {
+  if (!c || n_ref < 0 || (n_ref && !l_ref)) { set_error("strl_bamindex_begin: bad argument"); return STRL_ERR_ARG; }
+  int rc;
+  if ((rc = front_begin_scan(c, n_ref, first_record_offset))) return rc;
+  if (c->bai) { bai_destroy(c->bai); c->bai = nullptr; }
+  strl_bai *B = new strl_bai();
+  c->bai = B;
+  B->n_ref = n_ref;
+  B->l_ref.assign(l_ref, l_ref + n_ref);
+  B->win_off.assign((size_t)n_ref + 1, 0);
+  for (int32_t t = 0; t < n_ref; ++t) {
+    const int64_t len = std::min<int64_t>(std::max<int64_t>(l_ref[t], 0), BAI_MAX_POS);
+    B->win_off[(size_t)t + 1] = B->win_off[(size_t)t] + (uint64_t)std::min<int64_t>(((len + 16383) >> 14) + BAI_LREF_SLACK, BAI_MAX_POS >> 14);
+  }
+  const size_t nw = (size_t)B->win_off[(size_t)n_ref], nr = (size_t)n_ref;
+  if ((rc = B->d_winoff.reserve((nr + 1) * 8)) || (rc = B->lin.reserve(nw * 8 + 16)) || (rc = B->ref_beg.reserve(nr * 8 + 16)) ||
+      (rc = B->ref_end.reserve(nr * 8 + 16)) || (rc = B->ref_cnt.reserve(nr * 16 + 16)) || (rc = B->state.reserve(sizeof(BaiState))))
+    return rc;
+  STRL_HIP(hipHostMalloc(reinterpret_cast<void **>(&B->h_state), sizeof(BaiState), hipHostMallocDefault));
+  hipStream_t st = c->stream;
+  STRL_HIP(hipMemcpyAsync(B->d_winoff.p, B->win_off.data(), (nr + 1) * 8, hipMemcpyHostToDevice, st));
+  if (nw) hipLaunchKernelGGL(bai_fill_kernel, dim3((unsigned)std::min<size_t>((nw + 255) / 256, 1024)), dim3(256), 0, st, B->lin.as<uint64_t>(), nw, ~0ull);
+  if (nr) hipLaunchKernelGGL(bai_fill_kernel, dim3((unsigned)std::min<size_t>((nr + 255) / 256, 1024)), dim3(256), 0, st, B->ref_beg.as<uint64_t>(), nr, ~0ull);
+  STRL_HIP(hipGetLastError());
+  if (nr) { STRL_HIP(hipMemsetAsync(B->ref_end.p, 0, nr * 8, st)); STRL_HIP(hipMemsetAsync(B->ref_cnt.p, 0, nr * 16, st)); }
+  BaiState &H = *B->h_state;
+  memset(&H, 0, sizeof H);
+  for (uint64_t &e : H.err_ord) e = ~0ull;
+  for (BaiLast &L : H.last) { L.key = BAI_KEY_NONE; L.tid = 0; L.pos = -1; L.end_win = -1; }
+  STRL_HIP(hipMemcpyAsync(B->state.p, &H, sizeof H, hipMemcpyHostToDevice, st));
+  STRL_HIP(hipStreamSynchronize(st));
+  return STRL_OK;
+}
+
+extern "C" int strl_bamindex_reserve(strl_ctx *c, uint32_t max_blocks, uint64_t max_comp_bytes) {
+  if (!c || !c->bai || !c->front || !max_blocks) { set_error("strl_bamindex_reserve: bad argument / no strl_bamindex_begin"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  int rc;
+  const uint64_t rec_cap = (uint64_t)max_blocks * 65280u / 36 + 16;      // no record is shorter than 36 bytes (front_reserve's bound)
+  if ((rc = c->bai->flag.reserve((size_t)rec_cap + 64)) || (rc = c->bai->blk_cnt.reserve((size_t)(rec_cap / 256 + 2) * 4 + 64))) return rc;
+  return front_reserve(c, c->front, max_blocks, max_comp_bytes);
+}
+
+extern "C" int strl_bamindex_push(strl_ctx *c, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                                  const uint32_t *crc32, const uint64_t *block_off, uint64_t end_off, uint32_t n_blocks) {
+  if (!c || !c->bai || !c->front || c->bai->finished || (n_blocks && (!comp || !coff || !clen || !isize || !block_off))) {
+    set_error("strl_bamindex_push: bad argument / no strl_bamindex_begin");
+    return STRL_ERR_ARG;
+  }
+  if (!n_blocks) return STRL_OK;
+  STRL_HIP(hipSetDevice(c->device));
+  strl_front *F = c->front;
+  strl_bai *B = c->bai;
+  const int si = (int)(B->chunks & 1);
+  FrontSlot &S = F->slot[si];
+  int rc;
+  for (uint32_t i = 0; i < n_blocks; ++i)
+    if (block_off[i] >= (1ull << 48) || (i && block_off[i] <= block_off[i - 1]) || block_off[i] < B->end_off || isize[i] > 65536u || !isize[i]) {
+      set_error("strl_bamindex_push: block %u: file offsets must ascend and fit 48 bits, ISIZE must be in [1, 65536]", i);
+      return STRL_ERR_ARG;
+    }
+  if (end_off <= block_off[n_blocks - 1] || end_off >= (1ull << 48)) { set_error("strl_bamindex_push: end_off is not behind the last block"); return STRL_ERR_ARG; }
+  // the chunk two back has left the slot (its table in h_vt was copied in front of its kernels)
+  if (S.b_pending) { STRL_HIP(hipEventSynchronize(S.ev_b)); S.b_pending = false; }
+  // block table of the chunk, with the blocks a carried record may start in
+  const size_t m = B->tail.size() + n_blocks;
+  if (B->h_vt_cap[si] < (m + 1) * 16) {
+    if (B->h_vt[si]) { (void)hipHostFree(B->h_vt[si]); B->h_vt[si] = nullptr; }
+    B->h_vt_cap[si] = (m + 1) * 16 + (m + 1) * 4 + 4096;
+    STRL_HIP(hipHostMalloc(reinterpret_cast<void **>(&B->h_vt[si]), B->h_vt_cap[si], hipHostMallocDefault));
+  }
+  int64_t *vrel = reinterpret_cast<int64_t *>(B->h_vt[si]);
+  uint64_t *vfoff = reinterpret_cast<uint64_t *>(B->h_vt[si]) + (m + 1);
+  const int64_t base = (int64_t)FRONT_CARRY_MAX - B->abs_total;      // buffer offset of the inflated stream's byte 0
+  size_t k = 0;
+  for (const BaiBlock &t : B->tail) { vrel[k] = base + t.abs; vfoff[k] = t.foff; ++k; }
+  int64_t at = B->abs_total;
+  for (uint32_t i = 0; i < n_blocks; ++i) {
+    vrel[k] = base + at; vfoff[k] = block_off[i]; ++k;
+    B->tail.push_back(BaiBlock{at, block_off[i]});
+    at += isize[i];
+  }
+  vrel[m] = base + at; vfoff[m] = end_off;
+  B->vm[si] = (uint32_t)m;
+  B->abs0[si] = -base;
+  B->abs_total = at;
+  B->end_off = end_off;
+  size_t drop = 0;                                                    // keep the blocks that hold the last FRONT_CARRY_MAX bytes
+  while (drop + 1 < B->tail.size() && B->tail[drop + 1].abs <= at - (int64_t)FRONT_CARRY_MAX) ++drop;
+  B->tail.erase(B->tail.begin(), B->tail.begin() + (ptrdiff_t)drop);
+  const FrontChunkDesc d{comp, comp_bytes, coff, clen, isize, crc32, n_blocks};
+  if ((rc = front_stage_a(c, F, si, d, B->chunks == 0))) return rc;
+  ++B->chunks;
+  // ... and beside this chunk's inflate, the runs of the previous one
+  while (B->done + 1 < B->chunks) {
+    if ((rc = bai_index_chunk(c, F, B, (int)(B->done & 1)))) return rc;
+    ++B->done;
+  }
+  return STRL_OK;
+}
+
+extern "C" int strl_bamindex_finish(strl_ctx *c, uint64_t *bai_bytes, strl_bamindex_info *info) {
+  if (!c || !c->bai || !c->front) { set_error("strl_bamindex_finish without strl_bamindex_begin"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  strl_front *F = c->front;
+  strl_bai *B = c->bai;
+  hipStream_t st = c->stream;
+  int rc;
+  if (!B->finished) {
+    for (; B->done < B->chunks; ++B->done)
+      if ((rc = bai_index_chunk(c, F, B, (int)(B->done & 1)))) return rc;
+    STRL_HIP(hipStreamSynchronize(st));
+    if (F->last_slot >= 0 && F->slot[F->last_slot].h_info[0].carry_len) { set_error("the BAM ends inside a record (truncated file)"); return STRL_ERR_FORMAT; }
+    // one stable sort of the runs by (tid, bin), the second merge, the chunks to the host
+    const uint32_t n = (uint32_t)B->n_runs;
+    std::vector<BaiChunk> ch;
+    if (n) {
+      int bits = 17;
+      while (bits < 48 && ((uint64_t)B->n_ref >> (bits - 16))) ++bits;
+      const size_t sb = radix_sort_scratch_bytes(n, bits);
+      const uint32_t nblk = (n + 255u) / 256u;
+      DevBuf k0, k1, v0, v1, sc, out;
+      auto drop = [&] { for (DevBuf *b : {&k0, &k1, &v0, &v1, &sc, &out}) b->release(); };
+      if ((rc = k0.reserve((size_t)n * 8)) || (rc = k1.reserve((size_t)n * 8)) || (rc = v0.reserve((size_t)n * 4)) || (rc = v1.reserve((size_t)n * 4)) || (rc = sc.reserve(sb)) ||
+          (rc = out.reserve((size_t)n * sizeof(BaiChunk))) || (rc = B->flag.reserve((size_t)n + 64)) || (rc = B->blk_cnt.reserve((size_t)nblk * 4 + 64))) {
+        drop();
+        return rc;
+      }
+      BaiState *S = B->state.as<BaiState>();
+      hipLaunchKernelGGL(bai_keys_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), n, S, B->par, k0.as<uint64_t>(), v0.as<uint32_t>());
+      uint32_t *d_n = &S->n_heads;                         // (the device-side count the sort reads)
+      hipError_t e = hipMemcpyAsync(d_n, &n, 4, hipMemcpyHostToDevice, st);
+      uint64_t *ok = nullptr;
+      uint32_t *ov = nullptr;
+      int se = 0;
+      if (e == hipSuccess) se = radix_sort_pairs(st, d_n, n, k0.as<uint64_t>(), v0.as<uint32_t>(), k1.as<uint64_t>(), v1.as<uint32_t>(), sc.p, sb, 0, bits, &ok, &ov);
+      if (e == hipSuccess && !se) {
+        hipLaunchKernelGGL(bai_merge_flag_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), ok, ov, n, B->flag.as<uint8_t>(), B->blk_cnt.as<uint32_t>());
+        hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, B->blk_cnt.as<uint32_t>(), nblk, d_n);
+        hipLaunchKernelGGL(bai_merge_emit_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), ok, ov, n, B->flag.as<uint8_t>(), B->blk_cnt.as<uint32_t>(), d_n, out.as<BaiChunk>());
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) {
+          ch.resize(B->h_state->n_heads);
+          if (!ch.empty()) e = hipMemcpy(ch.data(), out.p, ch.size() * sizeof(BaiChunk), hipMemcpyDeviceToHost);
+        }
+      }
+      drop();
+      if (se) { set_error("radix_sort_pairs failed: %s", hipGetErrorString((hipError_t)se)); return STRL_ERR_HIP; }
+      if (e != hipSuccess) { set_error("strl_bamindex_finish: %s", hipGetErrorString(e)); return STRL_ERR_HIP; }
+    } else {
+      STRL_HIP(hipMemcpy(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost));
+    }
+    const size_t nr = (size_t)B->n_ref, nw = (size_t)B->win_off[nr];
+    std::vector<uint64_t> lin(nw), rb(nr), re(nr), cnt(2 * nr);
+    if (nw) STRL_HIP(hipMemcpy(lin.data(), B->lin.p, nw * 8, hipMemcpyDeviceToHost));
+    if (nr) {
+      STRL_HIP(hipMemcpy(rb.data(), B->ref_beg.p, nr * 8, hipMemcpyDeviceToHost));
+      STRL_HIP(hipMemcpy(re.data(), B->ref_end.p, nr * 8, hipMemcpyDeviceToHost));
+      STRL_HIP(hipMemcpy(cnt.data(), B->ref_cnt.p, nr * 16, hipMemcpyDeviceToHost));
+    }
+    // the bytes (SAM spec 5.2): per reference the bins ascending with their chunks, the pseudo-bin last, the linear index up to
+    // the last window touched (empty windows 0), n_no_coor at the end
+    std::vector<uint8_t> &o = B->bytes;
+    o.clear();
+    o.reserve(8 + ch.size() * 24 + nw * 8 + nr * 64 + 8);
+    o.insert(o.end(), {'B', 'A', 'I', 1});
+    put32(o, (uint32_t)B->n_ref);
+    size_t at = 0;
+    uint64_t n_chunks = 0;
+    for (size_t t = 0; t < nr; ++t) {
+      size_t e = at, n_bin = 0;
+      while (e < ch.size() && (ch[e].key >> 16) == t) { if (e == at || ch[e].key != ch[e - 1].key) ++n_bin; ++e; }
+      const bool meta = cnt[2 * t] + cnt[2 * t + 1] != 0;
+      put32(o, (uint32_t)(n_bin + (meta ? 1 : 0)));
+      for (size_t a = at; a < e;) {
+        size_t b = a;
+        while (b < e && ch[b].key == ch[a].key) ++b;
+        put32(o, (uint32_t)(ch[a].key & 0xffffu));
+        put32(o, (uint32_t)(b - a));
+        for (size_t k = a; k < b; ++k) { put64(o, ch[k].beg_v); put64(o, ch[k].end_v); }
+        n_chunks += b - a;
+        a = b;
+      }
+      if (meta) { put32(o, BAI_META_BIN); put32(o, 2); put64(o, rb[t]); put64(o, re[t]); put64(o, cnt[2 * t]); put64(o, cnt[2 * t + 1]); }
+      const uint64_t w0 = B->win_off[t], w1 = B->win_off[t + 1];
+      uint64_t n_intv = 0;
+      for (uint64_t w = w1; w > w0; --w) if (lin[(size_t)w - 1] != ~0ull) { n_intv = w - w0; break; }
+      put32(o, (uint32_t)n_intv);
+      for (uint64_t w = 0; w < n_intv; ++w) { const uint64_t v = lin[(size_t)(w0 + w)]; put64(o, v == ~0ull ? 0 : v); }
+      at = e;
+    }
+    put64(o, B->h_state->n_no_coor);
+    B->n_chunks = n_chunks;
+    B->finished = true;
+  }
+  if (bai_bytes) *bai_bytes = B->bytes.size();
+  if (info) { info->n_records = B->n_records; info->n_no_coor = B->h_state->n_no_coor; info->n_runs = B->n_runs; info->n_chunks = B->n_chunks; }
+  return STRL_OK;
+}
+
+extern "C" int strl_bamindex_fetch(strl_ctx *c, uint8_t *out, uint64_t cap) {
+  if (!c || !c->bai || !c->bai->finished || !out) { set_error("strl_bamindex_fetch without strl_bamindex_finish"); return STRL_ERR_ARG; }
+  const std::vector<uint8_t> &b = c->bai->bytes;
+  if (cap < b.size()) { set_error("strl_bamindex_fetch: %llu bytes, room for %llu", (unsigned long long)b.size(), (unsigned long long)cap); return STRL_ERR_CAPACITY; }
+  memcpy(out, b.data(), b.size());
+  return STRL_OK;
+}
+
+extern "C" int strl_bamindex_end(strl_ctx *c) {
+  if (!c) { set_error("null argument"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  if (c->front) {
+    for (hipStream_t q : c->front->st_i) if (q) (void)hipStreamSynchronize(q);
+    if (c->front->st_a) (void)hipStreamSynchronize(c->front->st_a);
+    if (c->front->st_c) (void)hipStreamSynchronize(c->front->st_c);
+  }
+  STRL_HIP(hipStreamSynchronize(c->stream));
+  if (c->bai) { bai_destroy(c->bai); c->bai = nullptr; }
+  return STRL_OK;
+}

@@ -271,12 +271,12 @@ void BgzfFeed::walk_from(size_t start, uint64_t end_coff, uint32_t end_uoff) {
       if (isz > 65536u) { state = 2; werr = "BGZF block inflates to more than 64 KiB"; break; }
       if (end_coff && pos == end_coff) {               // the share's last block: the record boundary lies inside it
         if (end_uoff > isz) { state = 2; werr = "the index names an offset behind its block's end"; break; }
-        if (isz) local.push_back(Block{pos + 12 + xlen, bsize - 12 - xlen - 8, isz, crc});
+        if (isz) local.push_back(Block{pos + 12 + xlen, bsize - 12 - xlen - 8, isz, crc, 12 + xlen});
         trim_ = isz - end_uoff;                        // (published with state_ under the lock below)
         state = 1;
         break;
       }
-      if (isz) local.push_back(Block{pos + 12 + xlen, bsize - 12 - xlen - 8, isz, crc});
+      if (isz) local.push_back(Block{pos + 12 + xlen, bsize - 12 - xlen - 8, isz, crc, 12 + xlen});
       have = want == 8 + 18;
       if (have) memcpy(h, tail + 8, 18);
       pos = next;

@@ -57,7 +57,8 @@ class BgzfFeed {
   // thread that stages the next chunk made the feed the bottleneck of a one-device run (loop 2.0 -> 2.5 s); inside the copy threads it
   // took an eighth off the rate of eight CPU-bound shares.)
   void done_with(size_t off, size_t n) const;
-  struct Block { size_t c_off; uint32_t clen, isize, crc; };     // DEFLATE payload at file offset c_off; CRC-32 of the inflated bytes (trailer)
+  struct Block { size_t c_off; uint32_t clen, isize, crc; uint32_t hdr = 0; };   // DEFLATE payload at file offset c_off; CRC-32 of the inflated bytes (trailer);
+                                                                               // hdr = bytes of gzip header in front of the payload (the block starts at c_off - hdr)
   // Next run of consecutive non-empty blocks: at most max_blocks and max_bytes of file (first block's payload to the last
   // block's end).  Returns the number of blocks (0 at the end of the file), -1 on a malformed file.
   // *last (if given): this run reaches the end of the file / share (the call waits until the walker can tell).

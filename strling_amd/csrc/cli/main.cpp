@@ -1799,6 +1799,123 @@ static void plan_region(const BamReader &rd, int fd, int32_t tid, int64_t beg, i
   P.ok = good && beyond >= 1 && !P.bsize.empty() && P.in_block <= P.isz[0];
 }
 
+// `strling bamindex` / `strling call --make-index`: the .bai of a BAM built on the device (strl_bamindex_*; what `samtools index`
+// does on one thread) and written to `out` through a temporary name, so a failed run leaves no half index.  Fed like extract's
+// front end: BgzfFeed walks the block headers, the compressed bytes go into page-locked buffers, chunk ci + 1 is read beside the
+// push of chunk ci.  get_ctx is asked for the context only once the file is open, the buffers are there and the first chunk is
+// read: a caller brings the context up on a thread beside that.  last_use: the process ends behind this (nothing is freed).
+// false: `why` says what the file was refused for (status = the library's, STRL_ERR_IO for the output)
+static bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::string &out, bool verbose, bool last_use, std::string &why,
+                      int &status) {
+  const auto t0 = std::chrono::steady_clock::now();
+  status = STRL_ERR_IO;
+  BgzfFeed feed;
+  std::string err;
+  if (!feed.open(bam, err)) { why = err.empty() ? "couldn't open bam" : "couldn't open bam: " + err; return false; }
+  static const char *env_blocks = getenv("STRL_CHUNK_BLOCKS");     // tests: tiny chunks put runs and records across pushes
+  const size_t auto_blocks = std::min<size_t>(16384, std::max<size_t>(2048, feed.file_bytes() / 16384 / 12));
+  const size_t chunk_blocks = env_blocks && atoi(env_blocks) > 0 ? (size_t)atoi(env_blocks) : auto_blocks;
+  const size_t chunk_bytes = std::max<size_t>((size_t)1 << 20, chunk_blocks * 20000);
+  uint8_t *pin[3] = {nullptr, nullptr, nullptr}, *pin_meta[3] = {nullptr, nullptr, nullptr};   // tables: coff, block offset u64 | clen | isize | crc u32
+  auto release = [&] { for (int k = 0; k < 3; ++k) { if (pin[k]) strl_pinned_free(pin[k]); if (pin_meta[k]) strl_pinned_free(pin_meta[k]); } };
+  {
+    std::vector<std::thread> each;            // (the time is the kernel's, faulting and locking the pages: a thread per buffer)
+    for (int k = 0; k < 3; ++k) each.emplace_back([&, k] { pin[k] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_bytes + 64)); pin_meta[k] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_blocks * 28 + 64)); });
+    for (auto &t : each) t.join();
+  }
+  for (int k = 0; k < 3; ++k)
+    if (!pin[k] || !pin_meta[k]) { why = "page-locked memory for the chunks"; release(); return false; }
+  strl_ctx *ctx = nullptr;
+  auto fail = [&](int rc) { why = strl_last_error(); status = rc; (void)strl_bamindex_end(ctx); release(); return false; };
+  ThreadPool pool(std::min(decode_threads(), 12));
+  struct St { int64_t nb = 0; size_t lo = 0, hi = 0, end_off = 0; bool short_read = false; std::string err; };
+  St ring[3];
+  std::vector<BgzfFeed::Block> bl;
+  struct Tab { uint64_t *coff, *boff; uint32_t *clen, *isz, *crc; };
+  auto tab = [&](uint64_t ci) { Tab t; t.coff = reinterpret_cast<uint64_t *>(pin_meta[ci % 3]); t.boff = t.coff + chunk_blocks;
+                                t.clen = reinterpret_cast<uint32_t *>(t.boff + chunk_blocks); t.isz = t.clen + chunk_blocks; t.crc = t.isz + chunk_blocks; return t; };
+  auto stage = [&](uint64_t ci, St &S) {
+    S = St{};
+    S.nb = feed.next(bl, chunk_blocks, chunk_bytes, S.err);
+    if (S.nb <= 0) return;
+    uint8_t *dst = pin[ci % 3];
+    S.lo = bl.front().c_off; S.hi = bl.back().c_off + bl.back().clen; S.end_off = S.hi + 8;      // (CRC-32 and ISIZE close a block)
+    const size_t lo = S.lo, hi = S.hi, piece = (size_t)4 << 20, pieces = (hi - lo + piece - 1) / piece;
+    std::atomic<int> short_reads{0};
+    pool.parallel_for(pieces, [&](size_t k) { if (!feed.copy_at(dst + k * piece, lo + k * piece, std::min(piece, hi - lo - k * piece))) ++short_reads; });
+    feed.done_with(lo, hi - lo);
+    S.short_read = short_reads.load() != 0;
+    const Tab t = tab(ci);
+    for (size_t k = 0; k < (size_t)S.nb; ++k) { t.coff[k] = bl[k].c_off - lo; t.boff[k] = bl[k].c_off - bl[k].hdr; t.clen[k] = bl[k].clen; t.isz[k] = bl[k].isize; t.crc[k] = bl[k].crc; }
+  };
+  stage(0, ring[0]);
+  if (!(ctx = get_ctx(why))) { status = STRL_ERR_NO_DEVICE; release(); return false; }
+  std::vector<int32_t> l_ref;
+  for (const BamTarget &t : feed.targets()) l_ref.push_back((int32_t)std::min<uint64_t>(t.length, 0x7fffffffu));
+  int rc = strl_bamindex_begin(ctx, (int32_t)l_ref.size(), l_ref.data(), feed.first_record_offset());
+  if (!rc) rc = strl_bamindex_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes);
+  if (rc) return fail(rc);
+  for (uint64_t ci = 0;; ++ci) {
+    const St cur = ring[ci % 3];
+    if (cur.nb < 0 || cur.short_read) { why = cur.nb < 0 ? cur.err : "short read"; status = STRL_ERR_FORMAT; (void)strl_bamindex_end(ctx); release(); return false; }
+    if (cur.nb == 0) break;
+    std::thread ahead([&, ci] { stage(ci + 1, ring[(ci + 1) % 3]); });
+    const Tab t = tab(ci);
+    rc = strl_bamindex_push(ctx, pin[ci % 3], cur.hi - cur.lo, t.coff, t.clen, t.isz, t.crc, t.boff, cur.end_off, (uint32_t)cur.nb);
+    ahead.join();
+    if (rc) return fail(rc);
+  }
+  uint64_t nbytes = 0;
+  strl_bamindex_info info;
+  if ((rc = strl_bamindex_finish(ctx, &nbytes, &info))) return fail(rc);
+  std::vector<uint8_t> bytes((size_t)nbytes);
+  if ((rc = strl_bamindex_fetch(ctx, bytes.data(), nbytes))) return fail(rc);
+  if (!last_use) (void)strl_bamindex_end(ctx);
+  // (the page-locked buffers are left to the end of the process: unlocking them stalls the device -- as `call` leaves its own)
+  status = STRL_ERR_IO;
+  const std::string tmp = out + ".tmp." + std::to_string((long long)getpid());
+  FILE *f = fopen(tmp.c_str(), "wb");
+  if (!f) { why = "cannot write " + tmp + ": " + strerror(errno); return false; }
+  const bool wrote = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+  const bool closed = fclose(f) == 0;
+  if (!wrote || !closed || rename(tmp.c_str(), out.c_str()) != 0) { why = "cannot write " + out + ": " + strerror(errno); (void)unlink(tmp.c_str()); return false; }
+  if (verbose)
+    fprintf(stderr, "[strling] bamindex: %llu records (%llu without a reference), %llu runs resident on the device, %llu chunks, %llu bytes -> %s in %.3f s\n",
+            (unsigned long long)info.n_records, (unsigned long long)info.n_no_coor, (unsigned long long)info.n_runs, (unsigned long long)info.n_chunks,
+            (unsigned long long)nbytes, out.c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  status = 0;
+  return true;
+}
+
+// the index `samtools index` writes (htslib sam_index_build); the reference only reads one (call.nim:101-102)
+static int bamindex_main(int argc, char **argv) {
+  const char *usage =
+      "strling bamindex\n\nUsage:\n  strling bamindex [options] bam\n\nArguments:\n  bam              path to a coordinate-sorted bam file\n\nOptions:\n"
+      "  -o, --output=OUT.bai       where to write the index (default: <bam>.bai)\n  -D, --device=K             GPU to use (default: 0)\n"
+      "  -v, --verbose\n  -h, --help                 Show this help\n";
+  if (argc <= 2) { fputs(usage, stdout); return 0; }
+  const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"device", 'D', true}, {"verbose", 'v', false}}, usage);
+  if (a.pos.size() != 1) quit("expected 1 argument (bam)\n%s", usage);
+  const std::string bam = a.pos[0], out = a.get("output", (bam + ".bai").c_str());
+  if (CramFile::is_cram(bam)) quit("[strling] bamindex: %s is a CRAM; its index (.crai) is out of scope: this command writes the .bai of a BAM", bam.c_str());
+  if (!file_exists(bam)) quit("couldn't open bam");
+  set_device0(a.get("device", ""));
+  // the HIP runtime and the context come up on a thread beside the header walk, the page-locked buffers and the first chunk's read
+  strl_ctx *ctx = nullptr;
+  int ctx_rc = 0;
+  std::string ctx_err;
+  std::thread ctx_thread([&] { ctx_rc = strl_ctx_create(device_of(0), &ctx); if (ctx_rc) ctx_err = strl_last_error(); });
+  g_bg_init = &ctx_thread;
+  auto get_ctx = [&](std::string &why) -> strl_ctx * { if (ctx_thread.joinable()) ctx_thread.join(); if (ctx_rc) why = ctx_err; return ctx_rc ? nullptr : ctx; };
+  std::string why;
+  int status = 0;
+  const bool ok = build_bai(get_ctx, bam, out, a.flag("verbose"), true, why, status);
+  if (ctx_thread.joinable()) ctx_thread.join();
+  g_bg_init = nullptr;
+  if (!ok) { if (ctx) strl_ctx_destroy(ctx); quit("[strling] bamindex: %s (status %d)", why.c_str(), status); }
+  return end_process(ctx);
+}
+
 // call.nim:51-285
 static int call_main(int argc, char **argv) {
   const char *usage =
@@ -1810,11 +1927,12 @@ static int call_main(int argc, char **argv) {
       "  -q, --min-mapq=MIN_MAPQ    minimum mapping quality (does not apply to STR reads) (default: 40)\n"
       "  -l, --loci=LOCI            Annoated bed file specifying additional STR loci to genotype. Format is: chr start stop repeatunit [name]\n"
       "  -b, --bounds=BOUNDS        STRling -bounds.txt file (usually produced by strling merge) specifying additional STR loci to genotype.\n"
-      "  -o, --output-prefix=OUTPUT_PREFIX\n                             prefix for output files (default: strling)\n  -v, --verbose\n  -h, --help                 Show this help\n";
+      "  -o, --output-prefix=OUTPUT_PREFIX\n                             prefix for output files (default: strling)\n"
+      "      --make-index           when the bam has no .bai, build one on the GPU and write it beside the bam (default: exit)\n  -v, --verbose\n  -h, --help                 Show this help\n";
   if (argc <= 2) { fputs(usage, stdout); return 0; }
   const Args a = parse(argc, argv, 2, {{"fasta", 'f', true}, {"min-support", 'm', true}, {"min-clip", 'c', true}, {"min-clip-total", 't', true},
                                        {"min-mapq", 'q', true}, {"loci", 'l', true}, {"bounds", 'b', true}, {"output-prefix", 'o', true},
-                                       {"verbose", 'v', false}, {"device", 'D', true}}, usage);
+                                       {"verbose", 'v', false}, {"device", 'D', true}, {"make-index", 0, false}}, usage);
   if (a.pos.size() != 2) quit("expected 2 arguments (bam, bin)\n%s", usage);
   set_device0(a.get("device", ""));
   if (a.flag("loci") && !file_exists(a.get("loci", ""))) quit("couldn't open loci file");          // call.nim:81-87
@@ -1871,8 +1989,23 @@ static int call_main(int argc, char **argv) {
   if (!frag_on_device) fragment_length_distribution(bam, frag);                       // call.nim:92
   BamReader rd;
   std::string err;
+  // --make-index: a BAM without a .bai gets one from the device (build_bai) before it is opened with its index
+  if (a.flag("make-index") && !CramFile::is_cram(bam) && file_exists(bam) && !file_exists(bam + ".bai") &&
+      !(bam.size() > 4 && file_exists(bam.substr(0, bam.size() - 4) + ".bai"))) {
+    ctx_thread.join();
+    if (!ctx_rc) {
+      std::string why;
+      int status = 0;
+      if (verbose) fprintf(stderr, "[strling] no index next to %s: building %s.bai on the GPU (--make-index)\n", bam.c_str(), bam.c_str());
+      if (!build_bai([&](std::string &) { return ctx; }, bam, bam + ".bai", verbose, false, why, status)) {
+        bin_thread.join();
+        if (fr_pin_thread.joinable()) fr_pin_thread.join();
+        quit("[strling] call --make-index: %s (status %d)", why.c_str(), status);
+      }
+    }
+  }
   const bool opened = rd.open(bam, err) && rd.load_index(bam, err);                   // index=true, call.nim:101-102
-  ctx_thread.join();
+  if (ctx_thread.joinable()) ctx_thread.join();
   if (fr_pin_thread.joinable()) fr_pin_thread.join();
   if (frag_on_device && opened && !ctx_rc) {
     bool have = true;
@@ -2603,7 +2736,8 @@ int main(int argc, char **argv) {
       "strling version: 0.6.0 (MI355X-native hot path)\n\nCommands:\n  extract  :   extract informative STR reads from a BAM/CRAM. This is a required first step.\n"
       "  merge    :   merge putitive STR loci from multiple samples. Only required for joint calling.\n  call     :   call STRs\n"
       "  index    :   identify large STRs in the reference genome, to produce ref.fasta.str.\n"
-      "  outliers :   cohort STR outlier scores from the call outputs of many samples (scripts/strling-outliers.py).\n";      // strling.nim:19-22 (pull_region, a debugging writer, is out of scope)
+      "  outliers :   cohort STR outlier scores from the call outputs of many samples (scripts/strling-outliers.py).\n"
+      "  bamindex :   build the index (.bai) of a coordinate-sorted BAM on the GPU (what `samtools index` writes).\n";      // strling.nim:19-22 (pull_region, a debugging writer, is out of scope)
   if (argc < 2) { fputs(top, stdout); return 1; }
   const std::string cmd = argv[1];
   if (cmd == "extract") return extract_main(argc, argv);
@@ -2611,6 +2745,7 @@ int main(int argc, char **argv) {
   if (cmd == "index") return index_main(argc, argv);
   if (cmd == "call") return call_main(argc, argv);
   if (cmd == "outliers") return outliers_main(argc, argv);
+  if (cmd == "bamindex") return bamindex_main(argc, argv);
   if (cmd == "_dump") return dump_main(argc, argv);
   if (cmd == "_decode") return decode_main(argc, argv);
   if (cmd == "_region") return region_main(argc, argv);

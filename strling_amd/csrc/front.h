@@ -12,6 +12,10 @@ namespace strl {
 constexpr uint32_t FRONT_SEG = 16384;            // bytes of inflated data whose records one lane chains through
 constexpr uint32_t FRONT_CARRY_MAX = 1u << 20;   // room in front of a chunk's inflated bytes for the partial record the previous chunk ended in
 constexpr uint32_t FRONT_NONE = 0xffffffffu;
+#if defined(__HIPCC__)
+__device__ __forceinline__ uint32_t ld32u(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+__device__ __forceinline__ uint32_t ld16u(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+#endif
 constexpr uint32_t FRONT_ERR_INFLATE = 1, FRONT_ERR_RECORD = 2, FRONT_ERR_LSEQ = 4, FRONT_ERR_CARRY = 8, FRONT_ERR_CRC = 16;
 
 // device-resident summary of one chunk; the host reads it back after the record scan and again after the parse
@@ -155,5 +159,7 @@ int front_tread_names(strl_ctx *c, strl_front *F, const strl_tread *d_treads, co
                       uint8_t *d_out, uint64_t out_cap, uint64_t *d_tile_sums, hipStream_t st);
 size_t front_name_tiles(uint32_t cap);      // words of d_tile_sums for `cap` names
 void front_destroy(strl_front *F);
+int front_init_slots(strl_ctx *c, strl_front *F);
+int front_begin_scan(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset);   // the front end without strl_front_begin's per-read state (bamindex.hip)
 
 }  // namespace strl

@@ -29,9 +29,6 @@ size_t strl_inflate_work_bytes(uint32_t n_blocks);
 
 namespace strl {
 
-__device__ __forceinline__ uint32_t ld32u(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint32_t ld16u(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-
 // BAM record at q: block_size u32 | refID i32 | pos i32 | l_read_name u8 | mapq u8 | bin u16 | n_cigar_op u16 | flag u16 |
 // l_seq u32 | next_refID i32 | next_pos i32 | tlen i32 | read_name | cigar | seq | qual | tags   (SAM spec 4.2)
 struct RecHdr { uint32_t bs; int32_t l_seq; uint32_t l_qname, n_cigar; };
@@ -674,6 +671,44 @@ int front_copy_names(strl_ctx *c, strl_front *F, const uint64_t *d_ref, const ui
   hipLaunchKernelGGL(name_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, st, F->qarena.as<uint8_t>(), d_ref, d_dst_off, n, d_out);
   STRL_HIP(hipGetLastError());
   return STRL_OK;
+}
+
+// events and the page-locked chunk summaries of both slots (strl_front_begin, front_begin_scan)
+int front_init_slots(strl_ctx *c, strl_front *F) {
+  const unsigned host_waited = hipEventDisableTiming | (c->blocking_waits ? hipEventBlockingSync : 0u);   // ev_a, ev_b: what the feeding thread waits for
+  for (FrontSlot &S : F->slot) {
+    STRL_HIP(hipEventCreateWithFlags(&S.ev_a, host_waited));
+    STRL_HIP(hipEventCreateWithFlags(&S.ev_b, host_waited));
+    STRL_HIP(hipEventCreateWithFlags(&S.ev_h2d, hipEventDisableTiming));
+    STRL_HIP(hipEventCreateWithFlags(&S.ev_i, hipEventDisableTiming));
+    STRL_HIP(hipEventCreateWithFlags(&S.ev_carry, hipEventDisableTiming));
+    STRL_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_info), 3 * sizeof(FrontInfo), hipHostMallocDefault));
+  }
+  return STRL_OK;
+}
+
+// The front end up to the record table only (copy + inflate + CRC + record scan: front_copy / front_stage_a), for a consumer of
+// its own behind it (bamindex.hip): streams, events and chunk summaries -- none of the per-read, pair-pass or name state
+// strl_front_begin allocates for `strling extract`, and nothing of the scorer
+int front_begin_scan(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset) {
+  STRL_HIP(hipSetDevice(c->device));
+  STRL_HIP(hipStreamSynchronize(c->stream));
+  if (c->front) {
+    for (hipStream_t q : c->front->st_i) if (q) (void)hipStreamSynchronize(q);
+    if (c->front->st_a) (void)hipStreamSynchronize(c->front->st_a);
+    if (c->front->st_c) (void)hipStreamSynchronize(c->front->st_c);
+    front_destroy(c->front); c->front = nullptr;
+  }
+  c->x_open = false; c->x_front = false;
+  strl_front *F = new strl_front();
+  c->front = F;
+  F->n_ref = n_ref; F->first_off = first_record_offset;
+  int least = 0, greatest = 0;
+  STRL_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+  for (hipStream_t &q : F->st_i) STRL_HIP(hipStreamCreateWithPriority(&q, hipStreamNonBlocking, least));
+  STRL_HIP(hipStreamCreateWithPriority(&F->st_a, hipStreamNonBlocking, greatest));
+  STRL_HIP(hipStreamCreateWithFlags(&F->st_c, hipStreamNonBlocking));
+  return front_init_slots(c, F);
 }
 
 void front_destroy(strl_front *F) {

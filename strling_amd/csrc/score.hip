@@ -969,6 +969,7 @@ void strl_ctx_destroy(strl_ctx *c) {
   if (c->comm) { strl::comm_destroy(c->comm); c->comm = nullptr; }
   if (c->x_soft_seen_ev) (void)hipEventDestroy(c->x_soft_seen_ev);
   if (c->x_soft_seen) (void)hipHostFree(c->x_soft_seen);
+  if (c->bai) { strl::bai_destroy(c->bai); c->bai = nullptr; }
   if (c->front) { if (c->front->st_c) (void)hipStreamSynchronize(c->front->st_c); for (hipStream_t q : c->front->st_i) if (q) (void)hipStreamSynchronize(q); if (c->front->st_a) (void)hipStreamSynchronize(c->front->st_a); strl::front_destroy(c->front); c->front = nullptr; }
   strl::DevBuf *bufs[] = {&c->lut, &c->thr, &c->g_tid, &c->g_bins, &c->g_start, &c->g_pmax, &c->queue, &c->soft_queue, &c->counters,
                           &c->soft_tmp, &c->sb_whole, &c->sb_soft, &c->queue_r, &c->soft_dense, &c->sb_state_w, &c->sb_state_s, &c->st_tid, &c->st_pos, &c->st_end, &c->st_seqoff, &c->st_lseq, &c->st_clipl, &c->st_clipr,
@@ -2070,15 +2071,7 @@ int strl_front_begin(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset, u
   F->qref = pre_qref; F->fragw = pre_fragw; F->qarena = pre_qarena;        // (allocated above, beside the others; the context owns them from here)
   F->n_ref = n_ref; F->first_off = first_record_offset;
   F->st_i[0] = pre_st[0]; F->st_i[1] = pre_st[1]; F->st_a = pre_st[2]; F->st_c = pre_st[3];   // (made above, beside the allocations)
-  const unsigned host_waited = hipEventDisableTiming | (c->blocking_waits ? hipEventBlockingSync : 0u);   // ev_a, ev_b: what the feeding thread waits for
-  for (strl::FrontSlot &S : F->slot) {
-    STRL_HIP(hipEventCreateWithFlags(&S.ev_a, host_waited));
-    STRL_HIP(hipEventCreateWithFlags(&S.ev_b, host_waited));
-    STRL_HIP(hipEventCreateWithFlags(&S.ev_h2d, hipEventDisableTiming));
-    STRL_HIP(hipEventCreateWithFlags(&S.ev_i, hipEventDisableTiming));
-    STRL_HIP(hipEventCreateWithFlags(&S.ev_carry, hipEventDisableTiming));
-    STRL_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_info), 3 * sizeof(strl::FrontInfo), hipHostMallocDefault));
-  }
+  if ((rc = strl::front_init_slots(c, F))) return rc;
   if ((rc = F->tid_seen.reserve((size_t)n_ref + 16))) return rc;
   STRL_HIP(hipMemsetAsync(F->tid_seen.p, 0, (size_t)n_ref + 16, c->stream));
   if ((rc = F->qref.grow((size_t)small * 8, 0, c->stream)) || (rc = F->fragw.grow((size_t)small * 4, 0, c->stream)) || (rc = F->qarena.grow((size_t)small * 24, 0, c->stream)))
