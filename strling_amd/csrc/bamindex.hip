@@ -286,7 +286,6 @@ struct strl_bai {
 
 void bai_destroy(strl_bai *B) {
   if (!B) return;
-  for (DevBuf *b : {&B->d_winoff, &B->lin, &B->ref_beg, &B->ref_end, &B->ref_cnt, &B->state, &B->runs, &B->flag, &B->blk_cnt, &B->vt[0], &B->vt[1]}) b->release();
   for (uint8_t *p : B->h_vt) if (p) (void)hipHostFree(p);
   if (B->h_state) (void)hipHostFree(B->h_state);
   delete B;
@@ -483,12 +482,9 @@ extern "C" int strl_bamindex_finish(strl_ctx *c, uint64_t *bai_bytes, strl_bamin
       const size_t sb = radix_sort_scratch_bytes(n, bits);
       const uint32_t nblk = (n + 255u) / 256u;
       DevBuf k0, k1, v0, v1, sc, out;
-      auto drop = [&] { for (DevBuf *b : {&k0, &k1, &v0, &v1, &sc, &out}) b->release(); };
       if ((rc = k0.reserve((size_t)n * 8)) || (rc = k1.reserve((size_t)n * 8)) || (rc = v0.reserve((size_t)n * 4)) || (rc = v1.reserve((size_t)n * 4)) || (rc = sc.reserve(sb)) ||
-          (rc = out.reserve((size_t)n * sizeof(BaiChunk))) || (rc = B->flag.reserve((size_t)n + 64)) || (rc = B->blk_cnt.reserve((size_t)nblk * 4 + 64))) {
-        drop();
+          (rc = out.reserve((size_t)n * sizeof(BaiChunk))) || (rc = B->flag.reserve((size_t)n + 64)) || (rc = B->blk_cnt.reserve((size_t)nblk * 4 + 64)))
         return rc;
-      }
       BaiState *S = B->state.as<BaiState>();
       hipLaunchKernelGGL(bai_keys_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), n, S, B->par, k0.as<uint64_t>(), v0.as<uint32_t>());
       uint32_t *d_n = &S->n_heads;                         // (the device-side count the sort reads)
@@ -509,7 +505,6 @@ extern "C" int strl_bamindex_finish(strl_ctx *c, uint64_t *bai_bytes, strl_bamin
           if (!ch.empty()) e = hipMemcpy(ch.data(), out.p, ch.size() * sizeof(BaiChunk), hipMemcpyDeviceToHost);
         }
       }
-      drop();
       if (se) { set_error("radix_sort_pairs failed: %s", hipGetErrorString((hipError_t)se)); return STRL_ERR_HIP; }
       if (e != hipSuccess) { set_error("strl_bamindex_finish: %s", hipGetErrorString(e)); return STRL_ERR_HIP; }
     } else {

@@ -371,7 +371,6 @@ extern "C" int strl_inflate_blocks(strl_ctx *c, const uint8_t *comp, uint64_t co
   c->inflate_ms = ms;
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  d_comp.release(); d_meta.release(); d_out.release(); d_work.release();
   if (err) { set_error("device inflate: %s", (err & IW_ERR_DATA) ? "invalid DEFLATE data" : "inflated size differs from the block's ISIZE"); return STRL_ERR_FORMAT; }
   return STRL_OK;
 }

@@ -921,7 +921,6 @@ extern "C" int strl_bounds_bare(strl_ctx *c, const uint32_t *positions, const ui
   RawBounds r{};
   STRL_HIP(hipMemcpyAsync(&r, d_out, sizeof r, hipMemcpyDeviceToHost, c->stream));
   STRL_HIP(hipStreamSynchronize(c->stream));
-  buf.release();
   memset(out, 0, sizeof *out);
   *good = (int)r.valid;
   out->left = r.left; out->left_most = r.left_most; out->right = r.right; out->right_most = r.right_most; out->center_mass = r.center_mass;

@@ -98,7 +98,6 @@ static Rccl &rccl() {
 void comm_destroy(strl_comm *m) {
   if (!m) return;
   for (auto *s : m->sets) {
-    s->t_local.release(); s->t_all.release(); s->c_all.release();
     if (s->ready) (void)hipEventDestroy(s->ready);
     if (s->copied) (void)hipEventDestroy(s->copied);
     delete s;

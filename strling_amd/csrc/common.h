@@ -23,10 +23,20 @@ void set_error(const char *fmt, ...);
     }                                                                                               \
   } while (0)
 
-// growable device buffer
+// growable device buffer (context.hip).  It owns its allocation: freed when the buffer goes out of scope, handed on by a move
+// (which leaves the source empty), never copied.
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+    return *this;
+  }
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
   int reserve(size_t bytes);
   // like reserve, but the first keep_bytes survive a reallocation (copied on `st`, which is synchronised before the old
   // block is freed); grows geometrically
@@ -87,48 +97,58 @@ inline uint64_t strl_record_limit() {
 
 namespace strl { struct strl_front; struct strl_comm; void comm_destroy(strl_comm *m); struct strl_bai; void bai_destroy(strl_bai *b); }
 struct strl_ctx;
-int side_join(strl_ctx *c);   // main stream waits for the side streams' pending work (score.hip)
-int side_streams(strl_ctx *c);   // the side streams of the overlapped mode, made at its first use (score.hip)
-void rotate_tail(strl_ctx *c);  // make the least recently used set of pair-logic / clustering state the current one (score.hip)
+int side_join(strl_ctx *c);   // main stream waits for the side streams' pending work (context.hip)
+int side_streams(strl_ctx *c);   // the side streams of the overlapped mode, made at its first use (context.hip)
+void rotate_tail(strl_ctx *c);  // make the least recently used set of pair-logic / clustering state the current one (context.hip)
+void rotate_head(strl_ctx *c);  // the same for the sets of the scorer's output (context.hip)
 constexpr int N_SETS = 2;        // batches in flight on a context: buffer sets of the scorer's output and of the tail (3 measured no faster than 2)
 
-// Everything the pair logic and the clustering of ONE batch own (the "tail" of a step).  A context has N_SETS: the members of
-// strl_ctx with these names are the current set, `alt[]` the others (most recently used first).  The overlapped
+// Everything the pair logic and the clustering of ONE batch own (the "tail" of a step).  A context has N_SETS: strl_ctx derives
+// from TailSet, that base is the current set, `alt[]` the others (most recently used first).  The overlapped
 // strl_extract_device rotates through them, each with its own side stream, so the tails of consecutive batches -- chains of small dependent launches that
 // crawl while the main stream saturates the chip -- make progress side by side.
 struct TailSet {
+  // clustering scratch
   strl::DevBuf c_buf[16];
   ClusterRun cl_run;
-  strl::DevBuf p_key0, p_key1, p_val0, p_val1, p_emit, sort_scratch, pair_cnt, treads;
+  // device pair logic (pair.hip): join items / emission keys (ping-pong), emitted treads, counters
+  strl::DevBuf p_key0, p_key1, p_val0, p_val1, p_emit, sort_scratch, pair_cnt;
+  // the treads the last strl_extract_device call produced, in .bin order: treads[0, *n_treads_dev)
+  strl::DevBuf treads;
   uint32_t *n_treads_dev = nullptr;
   uint32_t tread_cap = 0, pair_item_cap = 0;
+  // the last pair pass' treads before ordering: p_emit[i] with emission key po_key[i] (and the sort's other buffers)
   uint64_t *po_key = nullptr, *po_key_alt = nullptr;
   uint32_t *po_val = nullptr, *po_val_alt = nullptr;
   int po_bits = 0;
   bool pair_ordered = false;
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ev_side_done = nullptr;
-  bool side_pending = false, pair_on_side = false;
-};
-
-struct strl_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
   // Side stream: an asynchronous strl_cluster_resident (results stay on the device) runs here, so that the clustering of
   // one batch -- 20 small, latency-bound launches -- overlaps the VALU-bound scorer of the next batch.  Whatever touches
   // the treads or the cluster state afterwards calls side_join() first.
   hipStream_t stream2 = nullptr;
-  hipEvent_t ev_main_done = nullptr, ev_side_done = nullptr;
+  hipEvent_t ev_side_done = nullptr;
   bool side_pending = false;
-  // strl_extract_device on device-resident input goes further: the pair logic of batch i (latency-bound: Bloom probes,
-  // sorts, gathers) runs on the side stream too, beside classify + scorer of batch i + 1 on the main stream.  What the
-  // pair logic reads of the scorer's output exists N_SETS times (whole[], soft-clip records, counters, Bloom bitmap); a call
-  // rotates the sets and waits (on the device) until the side stream is done with the set it is about to overwrite.
-  struct HeadSet { strl::DevBuf st_whole, st_soft, counters, bloom; uint32_t bloom_mask = 0; } head_alt[N_SETS - 1];   // most recently used first
+  bool pair_on_side = false;       // the last pair logic ran on the side stream (its treads are ordered there already)
+};
+
+// strl_extract_device on device-resident input goes further: the pair logic of batch i (latency-bound: Bloom probes,
+// sorts, gathers) runs on the side stream too, beside classify + scorer of batch i + 1 on the main stream.  What the
+// pair logic reads of the scorer's output exists N_SETS times (whole[], soft-clip records, counters, Bloom bitmap): strl_ctx derives
+// from HeadSet, that base is the current set, `head_alt[]` the others.  A call rotates the sets and waits (on the device) until
+// the side stream is done with the set it is about to overwrite.
+struct HeadSet {
+  strl::DevBuf st_whole, st_soft, counters, bloom;
+  uint32_t bloom_mask = 0;
+};
+
+struct strl_ctx : TailSet, HeadSet {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_main_done = nullptr;
+  HeadSet head_alt[N_SETS - 1];    // the other head sets (see HeadSet), most recently used first
   hipEvent_t ev_head_done = nullptr, ev_set_free[N_SETS] = {};
   bool set_used[N_SETS] = {};
   int set = 0;
-  bool pair_on_side = false;       // the last pair logic ran on the side stream (its treads are ordered there already)
   TailSet alt[N_SETS - 1];         // the other tail sets (see TailSet), most recently used first
   int cl_where = 0;                // the last clustering pass lives in: 0 = the current tail set, k = alt[k - 1]
   bool timing = false;
@@ -145,28 +165,13 @@ struct strl_ctx {
   // genome STR intervals, per tid sorted by start, with prefix max of stop
   int32_t n_tid = 0;
   uint64_t n_iv = 0;
-  strl::DevBuf g_tid, g_bins, g_start, g_pmax;
+  strl::DevBuf g_tid, g_bins, g_start;
   // scratch
-  strl::DevBuf queue, soft_queue, counters, soft_tmp, sb_whole, sb_soft, soft_dense, sb_state_w, sb_state_s, queue_r;
+  strl::DevBuf queue, soft_queue, sb_whole, sb_soft, soft_dense, sb_state_w, sb_state_s, queue_r;
   // staging for host-memory batches
-  strl::DevBuf st_tid, st_pos, st_end, st_seqoff, st_lseq, st_clipl, st_clipr, st_mapq, st_cig, st_seq4, st_whole, st_soft, st_text, st_meta;
+  strl::DevBuf st_tid, st_pos, st_end, st_seqoff, st_lseq, st_clipl, st_clipr, st_mapq, st_cig, st_seq4, st_text, st_meta;
   // reads the host twin scores (score.hip long_reads_pass): their list, their SEQ bytes / the words that come back
   strl::DevBuf long_list, long_seq;
-  // clustering scratch
-  strl::DevBuf c_buf[16];
-  ClusterRun cl_run;
-  // device pair logic (pair.hip): join items / emission keys (ping-pong), emitted treads, Bloom bitmap, counters
-  strl::DevBuf p_key0, p_key1, p_val0, p_val1, p_emit, sort_scratch, pair_cnt, bloom;
-  uint32_t bloom_mask = 0;
-  // the treads the last strl_extract_device call produced, in .bin order: treads[0, *n_treads_dev)
-  strl::DevBuf treads;
-  uint32_t *n_treads_dev = nullptr;
-  uint32_t tread_cap = 0, pair_item_cap = 0;
-  // the last pair pass' treads before ordering: p_emit[i] with emission key po_key[i] (and the sort's other buffers)
-  uint64_t *po_key = nullptr, *po_key_alt = nullptr;
-  uint32_t *po_val = nullptr, *po_val_alt = nullptr;
-  int po_bits = 0;
-  bool pair_ordered = false;
   uint64_t ex_n = 0, ex_soft_cap = 0;
   // chunked extract (strl_extract_begin / _add / _finish): per-read state of all chunks so far
   strl::DevBuf x_rows, x_qhash, x_whole, x_soft, x_cnt, g_aux;
@@ -193,7 +198,7 @@ struct strl_ctx {
   strl::strl_bai *bai = nullptr;       // BAI builder behind the front end's record scan (bamindex.hip), created by strl_bamindex_begin
   strl::strl_comm *comm = nullptr;     // multi-GPU exchange (comm.hip): RCCL communicator / local group of this context
   // staging of the pairing arrays for host-memory batches
-  strl::DevBuf st_mtid, st_mpos, st_flag, st_qhash;
+  strl::DevBuf st_mtid, st_qhash;
 };
 
 // pair.hip: enqueue the device pair logic behind a scoring pass of the same batch
@@ -201,3 +206,6 @@ int strl_pair_order(strl_ctx *c, hipStream_t on_stream = nullptr);   // nullptr 
 int strl_pair_device(strl_ctx *c, uint64_t n, const strl_pair_soa *pp, const uint32_t *whole, const strl_soft_rec *soft,
                      const uint32_t *d_n_soft, uint64_t soft_cap, int64_t n_tail, uint64_t item_cap, uint64_t tread_cap,
                      hipStream_t on_stream = nullptr);   // nullptr = the main stream
+// extract.hip: the parts of the chunked extract the device front end (front_abi.hip) drives itself
+int extract_begin_sized(strl_ctx *c, uint64_t n_reads_hint, uint64_t n_now);
+int extract_add_scored(strl_ctx *c, const strl_read_soa *d, uint64_t at);

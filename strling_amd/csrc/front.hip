@@ -715,14 +715,10 @@ void front_destroy(strl_front *F) {
   if (!F) return;
   if (F->big) {
     if (F->big->th.joinable()) F->big->th.join();
-    for (DevBuf *b : {&F->big->rows, &F->big->qhash, &F->big->whole, &F->big->qref, &F->big->fragw, &F->big->qarena}) b->release();
     delete F->big;
     F->big = nullptr;
   }
-  for (DevBuf &b : F->trash) b.release();
-  F->trash.clear();
   for (FrontSlot &S : F->slot) {
-    for (DevBuf *b : {&S.comp, &S.infl, &S.coff, &S.clen, &S.uoff, &S.isize, &S.crc, &S.status, &S.seg, &S.recoff, &S.seqoff, &S.qoff, &S.info, &S.base3, &S.carry_stage, &S.iwork}) b->release();
     if (S.ev_a) (void)hipEventDestroy(S.ev_a);
     if (S.ev_b) (void)hipEventDestroy(S.ev_b);
     if (S.ev_h2d) (void)hipEventDestroy(S.ev_h2d);
@@ -731,13 +727,9 @@ void front_destroy(strl_front *F) {
     if (S.h_info) (void)hipHostFree(S.h_info);
     if (S.h_uoff) (void)hipHostFree(S.h_uoff);
   }
-  for (DevBuf *b : {&F->qref, &F->qarena, &F->fragw, &F->tidflag, &F->tid_seen, &F->s_tid, &F->s_pos, &F->s_end, &F->s_seqoff, &F->s_lseq, &F->s_clipl, &F->s_clipr, &F->s_mapq,
-                    &F->s_cig, &F->s_seq4, &F->s_meta})
-    b->release();
   for (hipEvent_t e : F->tev) (void)hipEventDestroy(e);
   if (F->st_a) (void)hipStreamDestroy(F->st_a);
   for (hipStream_t q : F->st_i) if (q) (void)hipStreamDestroy(q);
-  for (DevBuf &b : F->carry_buf) b.release();
   if (F->st_c) (void)hipStreamDestroy(F->st_c);
   delete F;
 }

@@ -361,37 +361,28 @@ inline unsigned grid_for(uint64_t n) {
   return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
 }
 
-// a device buffer that frees itself
-struct Scoped {
-  DevBuf b;
-  ~Scoped() { b.release(); }
-  int reserve(size_t bytes) { return b.reserve(bytes ? bytes : 8); }
-  template <typename T> T *as() { return b.as<T>(); }
-};
-
 // host or device arrays: device views of the inputs (copied in when host), outputs written back when host
 struct Io {
   strl_ctx *c;
   int mem;
-  std::vector<Scoped *> owned;
-  ~Io() { for (Scoped *s : owned) delete s; }
+  std::vector<DevBuf> owned;
   template <typename T> int in(const T *h, size_t n, const T **d) {
     if (!h || mem == STRL_MEM_DEVICE) { *d = h; return STRL_OK; }
-    Scoped *s = new Scoped();
-    owned.push_back(s);
-    int rc = s->reserve(n * sizeof(T));
+    owned.emplace_back();
+    DevBuf &s = owned.back();
+    int rc = s.reserve(n * sizeof(T));
     if (rc) return rc;
-    STRL_HIP(hipMemcpyAsync(s->b.p, h, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    *d = s->as<T>();
+    STRL_HIP(hipMemcpyAsync(s.p, h, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    *d = s.as<T>();
     return STRL_OK;
   }
   template <typename T> int out(T *h, size_t n, T **d) {
     if (!h || mem == STRL_MEM_DEVICE) { *d = h; return STRL_OK; }
-    Scoped *s = new Scoped();
-    owned.push_back(s);
-    int rc = s->reserve(n * sizeof(T));
+    owned.emplace_back();
+    DevBuf &s = owned.back();
+    int rc = s.reserve(n * sizeof(T));
     if (rc) return rc;
-    *d = s->as<T>();
+    *d = s.as<T>();
     return STRL_OK;
   }
   template <typename T> int back(T *h, const T *d, size_t n) {
@@ -408,17 +399,17 @@ int bits_for(uint64_t n) {       // bits that hold 0 .. n - 1
 }
 
 // stable sort of (keys, vals)[0, n) by key bits [0, bits) (sort.hip), result back in (keys, vals)
-int sort_in_place(strl_ctx *c, uint64_t *&keys, uint32_t *&vals, uint64_t *&k_alt, uint32_t *&v_alt, uint64_t n, int bits, Scoped &scratch,
-                  Scoped &dn) {
+int sort_in_place(strl_ctx *c, uint64_t *&keys, uint32_t *&vals, uint64_t *&k_alt, uint32_t *&v_alt, uint64_t n, int bits, DevBuf &scratch,
+                  DevBuf &dn) {
   if (bits <= 0 || n <= 1) return STRL_OK;
   const size_t sb = radix_sort_scratch_bytes((uint32_t)n, bits);
   int rc;
   if ((rc = scratch.reserve(sb))) return rc;
   const uint32_t n32 = (uint32_t)n;
-  STRL_HIP(hipMemcpyAsync(dn.b.p, &n32, 4, hipMemcpyHostToDevice, c->stream));
+  STRL_HIP(hipMemcpyAsync(dn.p, &n32, 4, hipMemcpyHostToDevice, c->stream));
   uint64_t *ok = nullptr;
   uint32_t *ov = nullptr;
-  const int e = radix_sort_pairs(c->stream, dn.as<uint32_t>(), n32, keys, vals, k_alt, v_alt, scratch.b.p, sb, 0, bits, &ok, &ov);
+  const int e = radix_sort_pairs(c->stream, dn.as<uint32_t>(), n32, keys, vals, k_alt, v_alt, scratch.p, sb, 0, bits, &ok, &ov);
   if (e) { set_error("radix_sort_pairs failed: %s", hipGetErrorString((hipError_t)e)); return STRL_ERR_HIP; }
   if (ok != keys) { std::swap(keys, k_alt); std::swap(vals, v_alt); }
   // the host copy of n32 above must outlive the enqueued copy
@@ -522,7 +513,7 @@ extern "C" int strl_outliers_scores(strl_ctx *c, const double *x, const double *
       (rc = io.in(null_mu, n_null, &dnm)) || (rc = io.in(null_sd, n_null, &dns)))
     return rc;
   // z / p / p_adj of the control-only rows are computed but not returned: they only count in BH
-  Scoped zb, pb, qb, k0, k1, v0, v1, scratch, dn;
+  DevBuf zb, pb, qb, k0, k1, v0, v1, scratch, dn;
   if ((rc = zb.reserve(n * 8)) || (rc = pb.reserve(n * 8)) || (rc = qb.reserve(n * 8)) || (rc = k0.reserve(n * 8)) || (rc = k1.reserve(n * 8)) ||
       (rc = v0.reserve(n * 4)) || (rc = v1.reserve(n * 4)) || (rc = dn.reserve(256)))
     return rc;
@@ -560,7 +551,7 @@ extern "C" int strl_outliers_order(strl_ctx *c, const double *outlier, const dou
   uint32_t *dord;
   int rc;
   if ((rc = io.in(outlier, n, &dz)) || (rc = io.in(allele2, n, &da)) || (rc = io.out(order, n, &dord))) return rc;
-  Scoped k0, k1, v0, v1, scratch, dn;
+  DevBuf k0, k1, v0, v1, scratch, dn;
   if ((rc = k0.reserve(n * 8)) || (rc = k1.reserve(n * 8)) || (rc = v0.reserve(n * 4)) || (rc = v1.reserve(n * 4)) || (rc = dn.reserve(256)))
     return rc;
   uint64_t *keys = k0.as<uint64_t>(), *ka = k1.as<uint64_t>();

@@ -704,7 +704,6 @@ extern "C" int strl_pair_rule_device(strl_ctx *c, int op, strl_tread *A, const s
   STRL_HIP(hipMemcpyAsync(A, dA, sizeof *A, hipMemcpyDeviceToHost, c->stream));
   STRL_HIP(hipMemcpyAsync(result, dres, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   STRL_HIP(hipStreamSynchronize(c->stream));
-  buf.release();
   return STRL_OK;
 }
 

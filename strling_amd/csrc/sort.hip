@@ -273,6 +273,5 @@ extern "C" int strl_sort_pairs(strl_ctx *c, uint64_t *keys, uint32_t *vals, uint
   STRL_HIP(hipMemcpyAsync(keys, ok, n * 8, hipMemcpyDeviceToHost, c->stream));
   STRL_HIP(hipMemcpyAsync(vals, ov, n * 4, hipMemcpyDeviceToHost, c->stream));
   STRL_HIP(hipStreamSynchronize(c->stream));
-  k0.release(); k1.release(); v0.release(); v1.release(); sc.release(); dn.release();
   return STRL_OK;
 }
