@@ -721,6 +721,76 @@ int strl_bamindex_fetch(strl_ctx *ctx, uint8_t *out, uint64_t cap);
  * end's chunk buffers stay with the context */
 int strl_bamindex_end(strl_ctx *ctx);
 
+/* ---- `strling pull`: a region's primary records and their mates (extract_region.nim:7-20,46-68) ----
+ * Two batched device passes over strl_regions_fetch's inputs (the blocks of many region queries, found through the .bai), and
+ * their host twins over raw record bytes (pull_logic.cpp), which need no device.
+ *
+ * A row describes one record; `off` is where its block_size word lies in the bytes the same call returns. */
+typedef struct {
+  uint64_t off;
+  int32_t tid, pos, mtid, mpos; /* refID, pos, next_refID, next_pos */
+  uint32_t size;                /* 4 + block_size */
+  uint32_t hash;                /* Nim's murmur hash of the qname (hashes.nim), which only narrows the name compares */
+  uint16_t flag;
+  uint8_t l_name;               /* l_read_name: the qname's bytes + 1 */
+  uint8_t found;                /* mates: 1 = the request was answered (otherwise the whole row is 0); select: 1 */
+  uint32_t count;               /* select: kept records of the whole call with exactly this row's qname bytes (:50) */
+} strl_pull_row;
+/* A merged region [beg, end) of `tid` is cut on the 16 KiB windows of the linear index; a tile keeps the records of the region
+ * (refID == tid, pos < end, bam_endpos > beg, neither 0x100 nor 0x800: :46-47 behind htslib's iterator filter) whose pos lies
+ * in [own_beg, own_end).  The region's first tile has own_beg = INT32_MIN, so that it also takes the records that start before
+ * `beg` and reach in; every record is therefore kept by exactly one tile.  The tile's strl_region_req is the query
+ * (tid, max(beg, own_beg), own_end). */
+typedef struct {
+  int32_t tid, beg, end;
+  int32_t own_beg, own_end;
+} strl_pull_tile;
+/* One kept record whose qname count is not 2 asks for its mate (:57-59, get_mate :15-19): the first record in file order of
+ * next_refID that overlaps [beg, end) = [max(0, next_pos - 1), next_pos + 1), has neither 0x100 nor 0x800, differs from `flag`
+ * in 0x40 and has the qname names[name_off, name_off + name_len). */
+typedef struct {
+  uint32_t hash;
+  int32_t beg, end;
+  uint32_t name_off;
+  uint16_t flag;
+  uint8_t name_len;
+  uint8_t pad;
+} strl_pull_req;
+/* The select pass: inflate, CRC and walk as strl_regions_fetch (req[t] per tile), then one workgroup per tile goes through the
+ * tile's records in batches of 256 (no cap on the records of a tile) and writes a row per kept record; the qname counts are
+ * taken over all tiles (radix sort by hash, byte compare inside a run of equal hashes); the kept records' bytes are gathered.
+ * rows[tile_rows[t], tile_rows[t + 1]) are tile t's rows in file order (tile_rows has n_tiles + 1 entries); rows[i].off indexes
+ * `bytes` (every record starts at its source's offset modulo 16; *n_bytes = the bytes used).  status[t] = 0: done; 1: as
+ * strl_regions_fetch; 2: bytes that do not parse -- such a tile has no rows and is read on the host.
+ * STRL_ERR_CAPACITY: *n_rows / *n_bytes = what is needed (the blocks' ISIZE sum / 36 rows and twice the ISIZE sum always suffice).
+ * kernel_ms (may be NULL): HIP-event time of the kernels behind the walk. */
+int strl_pull_select(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                     const uint32_t *crc32, uint32_t n_blocks, const strl_region_req *req, const strl_pull_tile *tiles, uint32_t n_tiles,
+                     strl_pull_row *rows, uint64_t row_cap, uint64_t *n_rows, uint64_t *tile_rows, uint8_t *bytes, uint64_t bytes_cap,
+                     uint64_t *n_bytes, uint8_t *status, double *kernel_ms);
+/* The mate pass: the requests with a placed mate, grouped by the caller by (next_refID, 16 KiB window of `beg`): window w is
+ * fetched by req[w] (tid, the window's start, the largest `end` of its requests) and holds reqs[win_off[w], win_off[w + 1]).
+ * One workgroup per window enters its requests, 256 a round, in an LDS hash table keyed by the qname hash and walks the
+ * window's records once per round; a record that meets a request's rule folds its place in the stream into the request's
+ * answer with an integer atomicMin: the first match in file order.  rows[k] answers reqs[k] (found = 0: no mate, or its window
+ * has status != 0 and is searched on the host); the mates' bytes come back like strl_pull_select's. */
+int strl_pull_mates(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                    const uint32_t *crc32, uint32_t n_blocks, const strl_region_req *req, const uint32_t *win_off, uint32_t n_windows,
+                    const strl_pull_req *reqs, const uint8_t *names, uint64_t names_bytes, strl_pull_row *rows, uint8_t *bytes,
+                    uint64_t bytes_cap, uint64_t *n_bytes, uint8_t *status, double *kernel_ms);
+/* The host twins (no device): `bytes` = block_size-prefixed records back to back, as BamReader's raw region read returns them.
+ * strl_pull_select_host appends the tile's rows (off = base_off + the record's offset in `bytes`) behind rows[*n_rows];
+ * strl_pull_counts_host fills rows[i].count, rows[i].off indexing `bytes`; strl_pull_mates_host answers the requests that are
+ * not answered yet (found == 0) from the records of `bytes` in order -- use_interval = 0 leaves the overlap test out: the
+ * records behind the last placed one, for the requests with next_refID == -1 (:9-13); strl_pull_order gives the stable order by
+ * (tid, pos) as signed integers (:65-68).  STRL_ERR_FORMAT: bytes that are no records; STRL_ERR_CAPACITY: row_cap. */
+int strl_pull_select_host(const uint8_t *bytes, uint64_t n_bytes, const strl_pull_tile *tile, uint64_t base_off, strl_pull_row *rows,
+                          uint64_t row_cap, uint64_t *n_rows);
+int strl_pull_counts_host(const uint8_t *bytes, strl_pull_row *rows, uint64_t n);
+int strl_pull_mates_host(const uint8_t *bytes, uint64_t n_bytes, int use_interval, int32_t tid, const strl_pull_req *reqs, uint32_t n_req,
+                         const uint8_t *names, uint64_t base_off, strl_pull_row *rows);
+int strl_pull_order(const strl_pull_row *rows, uint64_t n, uint32_t *order);
+
 /* ---- fragment-length statistics (utils.nim:139-146) ---- */
 int strl_frag_median(const uint32_t frag[4096], double pct);
 

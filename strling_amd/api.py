@@ -84,6 +84,11 @@ TREAD_DTYPE = np.dtype([("tid", "<i4"), ("position", "<u4"), ("repeat", "S6"), (
                         ("mapping_quality", "u1"), ("repeat_count", "u1"), ("align_length", "u1"), ("qname_id", "<i8")],
                        align=True)
 REGION_REQ_DTYPE = np.dtype([("first_block", "<u4"), ("n_blocks", "<u4"), ("in_block", "<u4"), ("tid", "<i4"), ("beg", "<i4"), ("end", "<i4")])
+# `strling pull` (strl_pull_row / strl_pull_tile / strl_pull_req of include/strling_amd.h)
+PULL_ROW_DTYPE = np.dtype([("off", "<u8"), ("tid", "<i4"), ("pos", "<i4"), ("mtid", "<i4"), ("mpos", "<i4"), ("size", "<u4"), ("hash", "<u4"), ("flag", "<u2"),
+                           ("l_name", "u1"), ("found", "u1"), ("count", "<u4")])
+PULL_TILE_DTYPE = np.dtype([("tid", "<i4"), ("beg", "<i4"), ("end", "<i4"), ("own_beg", "<i4"), ("own_end", "<i4")])
+PULL_REQ_DTYPE = np.dtype([("hash", "<u4"), ("beg", "<i4"), ("end", "<i4"), ("name_off", "<u4"), ("flag", "<u2"), ("name_len", "u1"), ("pad", "u1")])
 BOUNDS_DTYPE = np.dtype([("tid", "<i4"), ("left", "<u4"), ("left_most", "<u4"), ("right", "<u4"), ("right_most", "<u4"),
                          ("center_mass", "<u4"), ("n_left", "<u2"), ("n_right", "<u2"), ("n_total", "<u2"),
                          ("repeat", "S7")], align=True)
@@ -128,7 +133,8 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_bin_write", "strl_bin_read", "strl_bounds_row", "strl_cluster_members", "strl_spanners", "strl_genotype",
            "strl_calls_finish", "strl_unplaced_order", "strl_call_row", "strl_canonical_repeat", "strl_assign_reads_loci", "strl_group_order",
            "strl_extract_device", "strl_treads_fetch", "strl_ctx_pair_times", "strl_sort_pairs", "strl_cluster_resident", "strl_ctx_cluster_times", "strl_pair_rows", "strl_extract_begin", "strl_extract_add", "strl_extract_finish", "strl_pair_rule", "strl_bounds_bare", "strl_ctx_treads_device", "strl_cluster_gathered", "strl_inflate_blocks", "strl_ctx_inflate_ms", "strl_regions_fetch", "strl_evidence_records", "strl_regions_evidence", "strl_front_begin", "strl_front_push", "strl_front_push_after", "strl_front_reserve", "strl_front_stage", "strl_front_enqueue_after", "strl_front_collect", "strl_ctxs_extract_gather", "strl_front_finish", "strl_front_fragwords", "strl_front_fragwords_async", "strl_event_wait", "strl_front_records", "strl_front_tids", "strl_front_qnames", "strl_front_treads_named", "strl_pinned_alloc", "strl_pinned_free", "strl_comm_unique_id", "strl_ctx_comm_init", "strl_ctxs_comm_init", "strl_ctx_comm_info", "strl_cluster_exchange", "strl_ctxs_cluster_exchange", "strl_exchange_treads", "strl_ctx_set_treads", "strl_cluster_collect", "strl_ctx_tail_stream", "strl_ctx_mem_info", "strl_bin_peek", "strl_front_trim_next", "strl_front_tail_bytes", "strl_ctx_blocking_waits", "strl_score_read_host", "strl_front_end",
-           "strl_bamindex_begin", "strl_bamindex_reserve", "strl_bamindex_push", "strl_bamindex_finish", "strl_bamindex_fetch", "strl_bamindex_end"]
+           "strl_bamindex_begin", "strl_bamindex_reserve", "strl_bamindex_push", "strl_bamindex_finish", "strl_bamindex_fetch", "strl_bamindex_end",
+           "strl_pull_select", "strl_pull_mates", "strl_pull_select_host", "strl_pull_counts_host", "strl_pull_mates_host", "strl_pull_order"]
 
 
 def lib_path():
@@ -218,6 +224,15 @@ def load(build_if_missing=True):
     L.strl_regions_evidence.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(C.c_double)]
+    L.strl_pull_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                   C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
+                                   C.POINTER(C.c_double)]
+    L.strl_pull_mates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                  C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_double)]
+    L.strl_pull_select_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.strl_pull_counts_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_pull_mates_host.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.strl_pull_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
     L.strl_front_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64]
     L.strl_front_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_int)]
     L.strl_front_finish.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
@@ -685,6 +700,53 @@ class Context:
                                                 _ptr(soff), sm.ctypes.data, _ptr(st), C.byref(ms))
         return self._evidence_call(n, call, sum(int(isz[r[0]:r[0] + r[1]].sum()) for r in regions) // 128 + 64 * n + 64)
 
+    def _pull_blocks(self, streams, sizes, regions, crcs):
+        comp = np.frombuffer(b"".join(streams) + b"\0" * 8, np.uint8)
+        clen = np.array([len(x) for x in streams], np.uint32)
+        coff = np.zeros(len(streams), np.uint64)
+        coff[1:] = np.cumsum(clen[:-1], dtype=np.uint64)
+        isz = np.asarray(sizes, np.uint32)
+        req = np.zeros(len(regions), REGION_REQ_DTYPE)
+        for k, r in enumerate(regions):
+            req[k] = tuple(r)
+        crc = None if crcs is None else np.asarray(crcs, np.uint32)
+        return comp, clen, coff, isz, req, crc
+
+    def pull_select(self, streams, sizes, regions, tiles, crcs=None):
+        """strl_pull_select: regions_fetch's `streams` / `sizes` / `regions` (one per tile) plus tiles = PULL_TILE_DTYPE records ->
+        (rows, tile_rows, record bytes, status per tile, kernel ms); rows[tile_rows[t]:tile_rows[t + 1]] are tile t's kept
+        records in file order, rows["off"] indexes the bytes, rows["count"] = kept records of the call with the same qname"""
+        comp, clen, coff, isz, req, crc = self._pull_blocks(streams, sizes, regions, crcs)
+        n = len(regions)
+        tl = np.ascontiguousarray(tiles, PULL_TILE_DTYPE).reshape(n)
+        tot = int(isz.sum())
+        rows = np.zeros(tot // 36 + n + 1, PULL_ROW_DTYPE)
+        out = np.zeros(2 * tot + 64, np.uint8)
+        tile_rows = np.zeros(n + 1, np.uint64)
+        st = np.zeros(max(1, n), np.uint8)
+        nr, nb, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+        _check(self.L.strl_pull_select(self.h, comp.ctypes.data, int(clen.sum()), _ptr(coff), _ptr(clen), _ptr(isz), None if crc is None else _ptr(crc), len(streams),
+                                       req.ctypes.data, tl.ctypes.data, n, rows.ctypes.data, rows.size, C.byref(nr), _ptr(tile_rows), out.ctypes.data, out.size,
+                                       C.byref(nb), _ptr(st), C.byref(ms)))
+        return rows[:nr.value].copy(), tile_rows, out[:nb.value].tobytes(), st[:n], ms.value
+
+    def pull_mates(self, streams, sizes, regions, win_off, reqs, names, crcs=None):
+        """strl_pull_mates: one region per window, window w holding reqs[win_off[w]:win_off[w + 1]] (PULL_REQ_DTYPE, names in
+        `names`) -> (rows, record bytes, status per window, kernel ms); rows[k] answers reqs[k] (found = 0: no mate)"""
+        comp, clen, coff, isz, req, crc = self._pull_blocks(streams, sizes, regions, crcs)
+        n = len(regions)
+        wo = np.ascontiguousarray(win_off, np.uint32)
+        rq = np.ascontiguousarray(reqs, PULL_REQ_DTYPE)
+        nm = np.frombuffer(bytes(names) + b"\0" * 8, np.uint8)
+        rows = np.zeros(max(1, rq.size), PULL_ROW_DTYPE)
+        out = np.zeros(2 * int(isz.sum()) + 64, np.uint8)
+        st = np.zeros(max(1, n), np.uint8)
+        nb, ms = C.c_uint64(0), C.c_double(0)
+        _check(self.L.strl_pull_mates(self.h, comp.ctypes.data, int(clen.sum()), _ptr(coff), _ptr(clen), _ptr(isz), None if crc is None else _ptr(crc), len(streams),
+                                      req.ctypes.data, _ptr(wo), n, rq.ctypes.data, nm.ctypes.data, len(names), rows.ctypes.data, out.ctypes.data, out.size,
+                                      C.byref(nb), _ptr(st), C.byref(ms)))
+        return rows[:rq.size].copy(), out[:nb.value].tobytes(), st[:n], ms.value
+
     def inflate_blocks(self, streams, sizes):
         """raw DEFLATE streams (list of bytes) with their inflated sizes -> list of inflated bytes (strl_inflate_blocks)"""
         comp = np.frombuffer(b"".join(streams) + b"\0" * 8, np.uint8)
@@ -1055,6 +1117,46 @@ def pair_rule(ctx, op, A, B, opts, B_position=0):
     res = C.c_int(0)
     _check(load().strl_pair_rule(ctx.h if ctx is not None else None, op, a.ctypes.data, b.ctypes.data, C.byref(o), int(B_position), C.byref(res)))
     return res.value, a[0]
+
+
+def pull_select_host(raw, tile, base_off=0):
+    """strl_pull_select_host: the rows a tile (PULL_TILE_DTYPE record) keeps of block_size-prefixed records `raw`, in order"""
+    L = load()
+    buf = np.frombuffer(bytes(raw) + b"\0" * 8, np.uint8)
+    tl = np.ascontiguousarray(tile, PULL_TILE_DTYPE).reshape(1)
+    rows = np.zeros(len(raw) // 36 + 1, PULL_ROW_DTYPE)
+    n = C.c_uint64(0)
+    _check(L.strl_pull_select_host(buf.ctypes.data, len(raw), tl.ctypes.data, base_off, rows.ctypes.data, rows.size, C.byref(n)))
+    return rows[:n.value].copy()
+
+
+def pull_counts_host(raw, rows):
+    """strl_pull_counts_host: rows with `count` = rows of the same qname bytes (rows["off"] index `raw`)"""
+    L = load()
+    buf = np.frombuffer(bytes(raw) + b"\0" * 8, np.uint8)
+    rows = np.ascontiguousarray(rows, PULL_ROW_DTYPE).copy()
+    _check(L.strl_pull_counts_host(buf.ctypes.data, rows.ctypes.data, rows.size))
+    return rows
+
+
+def pull_mates_host(raw, reqs, names, tid=-1, use_interval=True, base_off=0):
+    """strl_pull_mates_host: one row per request (PULL_REQ_DTYPE), found = 0 where no record of `raw` meets its rule"""
+    L = load()
+    buf = np.frombuffer(bytes(raw) + b"\0" * 8, np.uint8)
+    rq = np.ascontiguousarray(reqs, PULL_REQ_DTYPE)
+    nm = np.frombuffer(bytes(names) + b"\0" * 8, np.uint8)
+    rows = np.zeros(max(1, rq.size), PULL_ROW_DTYPE)
+    _check(L.strl_pull_mates_host(buf.ctypes.data, len(raw), int(bool(use_interval)), tid, rq.ctypes.data, rq.size, nm.ctypes.data, base_off, rows.ctypes.data))
+    return rows[:rq.size]
+
+
+def pull_order(rows):
+    """strl_pull_order: the stable order of the rows by (tid, pos) as signed integers"""
+    L = load()
+    rows = np.ascontiguousarray(rows, PULL_ROW_DTYPE)
+    order = np.zeros(rows.size, np.uint32)
+    _check(L.strl_pull_order(rows.ctypes.data, rows.size, order.ctypes.data))
+    return order
 
 
 def _noop():

@@ -123,21 +123,28 @@ bool BamReader::open(const std::string &path, std::string &err) {
   eof_ = false; next_block_ = 0; upos_ = 0; ubuf_.clear();
   char magic[4];
   int32_t l_text = 0, n_ref = 0;
-  if (!get(magic, 4, err) || memcmp(magic, "BAM\1", 4) != 0) { err = "not a BAM file"; return false; }
-  if (!get(&l_text, 4, err) || l_text < 0) return false;
+  hdr_raw_.clear();
+  auto getr = [&](void *dst, size_t n) {               // the header's bytes are kept as they are: `strling pull` copies them
+    if (!get(dst, n, err)) return false;
+    hdr_raw_.insert(hdr_raw_.end(), static_cast<uint8_t *>(dst), static_cast<uint8_t *>(dst) + n);
+    return true;
+  };
+  if (!getr(magic, 4) || memcmp(magic, "BAM\1", 4) != 0) { err = "not a BAM file"; return false; }
+  if (!getr(&l_text, 4) || l_text < 0) return false;
   text_.resize((size_t)l_text);
-  if (l_text && !get(&text_[0], (size_t)l_text, err)) return false;
+  if (l_text && !getr(&text_[0], (size_t)l_text)) return false;
   while (!text_.empty() && text_.back() == '\0') text_.pop_back();
-  if (!get(&n_ref, 4, err) || n_ref < 0) return false;
+  if (!getr(&n_ref, 4) || n_ref < 0) return false;
   targets_.clear();
   for (int32_t i = 0; i < n_ref; ++i) {
     int32_t l_name = 0, l_ref = 0;
-    if (!get(&l_name, 4, err) || l_name <= 0) { err = "bad reference name"; return false; }
+    if (!getr(&l_name, 4) || l_name <= 0) { err = "bad reference name"; return false; }
     std::string nm((size_t)l_name, '\0');
-    if (!get(&nm[0], (size_t)l_name, err) || !get(&l_ref, 4, err)) return false;
+    if (!getr(&nm[0], (size_t)l_name) || !getr(&l_ref, 4)) return false;
     nm.pop_back();
     targets_.push_back(BamTarget{nm, (uint32_t)l_ref});
   }
+  first_rec_ = tell();
   return true;
 }
 
@@ -155,6 +162,7 @@ bool BamReader::open_like(const BamReader &o, std::string &err) {
   path_ = o.path_;
   eof_ = false; next_block_ = 0; upos_ = 0; ubuf_.clear();
   text_ = o.text_; targets_ = o.targets_; lin_ = o.lin_; ref_beg_ = o.ref_beg_;
+  tail_beg_ = o.tail_beg_; first_rec_ = o.first_rec_; hdr_raw_ = o.hdr_raw_;
   return true;
 }
 
@@ -190,6 +198,7 @@ bool BamReader::load_index(const std::string &bam_path, std::string &err) {
   if (!ok) n_ref = 0;
   lin_.assign((size_t)std::max(n_ref, 0), {});
   ref_beg_.assign((size_t)std::max(n_ref, 0), 0);
+  tail_beg_ = 0;
   for (int32_t r = 0; ok && r < n_ref; ++r) {
     int32_t n_bin = 0;
     ok = rd(&n_bin, 4);
@@ -202,6 +211,7 @@ bool BamReader::load_index(const std::string &bam_path, std::string &err) {
         uint64_t be[2];
         ok = rd(be, 16);
         if (ok && bin != 37450 && (first == 0 || be[0] < first)) first = be[0];   // 37450: the metadata pseudo-bin
+        if (ok && bin != 37450 && be[1] > tail_beg_) tail_beg_ = be[1];
       }
     }
     int32_t n_intv = 0;
@@ -231,6 +241,46 @@ int64_t BamReader::read_region(RecordBatch &b, int32_t tid, int64_t beg, int64_t
   if (off == 0) off = ref_beg_[(size_t)tid];
   if (!seek(Pos{off >> 16, (uint32_t)(off & 0xffff)}, err)) return -1;
   return read_until(b, INT64_MAX, tid, (int32_t)std::min<int64_t>(end, INT32_MAX), err);
+}
+
+int64_t BamReader::read_region_raw(std::vector<uint8_t> &out, int32_t tid, int64_t beg, int64_t end, std::string &err) {
+  if (cram_) { err = "raw records of a CRAM"; return -1; }
+  if (tid < 0 || (size_t)tid >= ref_beg_.size() || ref_beg_[(size_t)tid] == 0 || end <= beg) return 0;
+  const std::vector<uint64_t> &lin = lin_[(size_t)tid];
+  uint64_t off = 0;                                    // as read_region
+  int64_t w = beg >> 14;
+  if (w >= (int64_t)lin.size()) w = (int64_t)lin.size() - 1;
+  for (; w >= 0 && off == 0; --w) off = lin[(size_t)w];
+  if (off == 0) off = ref_beg_[(size_t)tid];
+  if (!seek(Pos{off >> 16, (uint32_t)(off & 0xffff)}, err)) return -1;
+  return read_raw_until(out, INT64_MAX, tid, (int32_t)std::min<int64_t>(end, INT32_MAX), err);
+}
+
+bool BamReader::seek_tail(std::string &err) {
+  if (cram_) { err = "raw records of a CRAM"; return false; }
+  return seek(tail_beg_ ? Pos{tail_beg_ >> 16, (uint32_t)(tail_beg_ & 0xffff)} : first_rec_, err);
+}
+
+int64_t BamReader::read_raw_until(std::vector<uint8_t> &out, int64_t max_records, int32_t stop_tid, int32_t stop_pos, std::string &err) {
+  int64_t n = 0;
+  while (n < max_records) {
+    if (upos_ == ubuf_.size()) {
+      if (!fill(err)) return -1;
+      if (eof_) break;
+    }
+    int32_t bs = 0;
+    if (!get(&bs, 4, err)) return -1;
+    if (bs < 32) { err = "corrupt BAM record"; return -1; }
+    const size_t at = out.size();
+    out.resize(at + 4 + (size_t)bs);
+    memcpy(out.data() + at, &bs, 4);
+    if (!get(out.data() + at + 4, (size_t)bs, err)) return -1;
+    int32_t refID, pos;
+    memcpy(&refID, out.data() + at + 4, 4); memcpy(&pos, out.data() + at + 8, 4);
+    if (stop_tid != INT32_MIN && (refID != stop_tid || pos >= stop_pos)) { out.resize(at); break; }
+    ++n;
+  }
+  return n;
 }
 
 bool BamReader::region_span(int32_t tid, int64_t beg, int64_t end, uint64_t &c_beg, uint32_t &in_block, uint64_t &c_hint) const {

@@ -124,6 +124,16 @@ class BamReader {
   // it unless a record spans more than a window).  false: the region holds nothing / the index has no later window (BAM
   // files only; the caller then uses read_region).
   bool region_span(int32_t tid, int64_t beg, int64_t end, uint64_t &c_beg, uint32_t &in_block, uint64_t &c_hint) const;
+  // What `strling pull` copies (extract_region.nim:46,9,75; BAM files only).  read_region_raw: read_region's records as they
+  // lie in the file, block_size-prefixed and back to back, with their qualities and tags.  seek_tail + read_raw: the records
+  // behind the last placed one (htslib's query("*")), from the largest chunk end of any bin of the index on, max_records a
+  // call (0 at the end of the file).  header_bytes: magic, text and reference list, byte for byte.  index_windows: 16 KiB
+  // windows of the reference's linear index (no record overlaps a later one).  The reads return the records appended, -1 on error.
+  int64_t read_region_raw(std::vector<uint8_t> &out, int32_t tid, int64_t beg, int64_t end, std::string &err);
+  bool seek_tail(std::string &err);
+  int64_t read_raw(std::vector<uint8_t> &out, int64_t max_records, std::string &err) { return read_raw_until(out, max_records, INT32_MIN, 0, err); }
+  const std::vector<uint8_t> &header_bytes() const { return hdr_raw_; }
+  size_t index_windows(int32_t tid) const { return tid >= 0 && (size_t)tid < lin_.size() ? lin_[(size_t)tid].size() : 0; }
   bool is_cram() const { return (bool)cram_; }
   const std::string &path() const { return path_; }
   // BAM records in memory (block_size-prefixed, back to back: what read_until walks through the BGZF layer) appended to `b`.
@@ -136,6 +146,7 @@ class BamReader {
 
  private:
   bool fill(std::string &err);                       // inflate the next BGZF block into ubuf_
+  int64_t read_raw_until(std::vector<uint8_t> &out, int64_t max_records, int32_t stop_tid, int32_t stop_pos, std::string &err);
   bool get(void *dst, size_t n, std::string &err);   // copy n decompressed bytes, crossing blocks
   FILE *f_ = nullptr;
   std::string path_;
@@ -148,6 +159,9 @@ class BamReader {
   std::vector<BamTarget> targets_;
   std::vector<std::vector<uint64_t>> lin_;   // per reference: linear index (virtual offset per 16 KiB window)
   std::vector<uint64_t> ref_beg_;            // per reference: smallest chunk start of any bin (0 = no records)
+  uint64_t tail_beg_ = 0;                    // largest chunk end of any bin (0 = no placed records: the tail starts at first_rec_)
+  Pos first_rec_{0, 0};                      // behind the header
+  std::vector<uint8_t> hdr_raw_;
 };
 
 // Minimal fork-join pool: parallel_for(n, fn) runs fn(i) for every i in [0, n) on `threads` threads (the caller is one).

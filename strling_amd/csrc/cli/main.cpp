@@ -3,6 +3,7 @@
 //   strling merge   [-w -1] [-m 5] [-c 0] [-t 0] [-q 40] [-o PREFIX] [-v] BIN...  (src/strpkg/merge.nim:47-191)
 //   strling index   [-g STR.bed] [-p 0.8] FASTA                                  (src/strpkg/genome_strs.nim:61-135,175-205)
 //   strling call    [-m 5] [-c 0] [-t 0] [-q 40] [-l BED] [-b BOUNDS] [-o PREFIX] [-v] BAM BIN   (src/strpkg/call.nim:51-285)
+//   strling pull    [-o OUT.bam] [-L BED] [-v] BAM [REGION ...]                              (src/strpkg/extract_region.nim:22-80)
 // The BAM is decoded on the host (own multi-threaded BGZF/BAM reader), batches go through the C ABI into the HIP kernels
 // as they are decoded, the pair logic (Cache.add) runs on the device once the whole file has been scored, and the
 // .bin / -bounds.txt / -genotype.txt / -unplaced.txt writers are byte-compatible with the reference's.
@@ -1772,14 +1773,15 @@ static bool fragment_lengths_on_device(strl_ctx *ctx, const std::string &bam, ui
 }
 
 struct RegionPlan { bool ok = false; uint64_t c_beg = 0, c_end = 0; uint32_t in_block = 0; std::vector<uint32_t> hdr, bsize, isz, crc; };
-static void plan_region(const BamReader &rd, int fd, int32_t tid, int64_t beg, int64_t end, RegionPlan &P) {
+// `more` (1 = the plan `strling call` uses): that many times the inflated bytes and blocks, and blocks behind the hinted one
+static void plan_region(const BamReader &rd, int fd, int32_t tid, int64_t beg, int64_t end, RegionPlan &P, int more = 1) {
   uint64_t c_hint = 0;
   P.ok = false;
   if (!rd.region_span(tid, beg, end, P.c_beg, P.in_block, c_hint)) return;
   uint64_t o = P.c_beg, infl = 0;
   int beyond = 0;
   bool good = true;
-  while (beyond < 2 && infl < ((uint64_t)8 << 20) && P.bsize.size() < 4096) {   // (a window of 30x data is ~1 MB)
+  while (beyond < 2 * more && infl < ((uint64_t)8 << 20) * (uint64_t)more && P.bsize.size() < (size_t)4096 * (size_t)more) {   // (a window of 30x data is ~1 MB)
     uint8_t h[18], tr[8];
     if (pread(fd, h, 18, (off_t)o) != 18) break;                                  // end of the file
     const uint32_t xlen = h[10] | (h[11] << 8);
@@ -2710,6 +2712,403 @@ static int shares_main(int argc, char **argv) {
   return 0;
 }
 
+// ---- `strling pull` (extract_region.nim): a region's primary records and the mates that lie elsewhere, as a BAM --------------
+struct PullRegion { int32_t tid; int64_t beg, end; };
+// htslib's region forms (hts_parse_reg behind `ibam.query(opts.region)`, extract_region.nim:46): NAME, NAME:BEG, NAME:BEG-END,
+// 1-based and inclusive, commas allowed in the numbers; a string that is a reference's name as a whole is that reference
+static PullRegion parse_pull_region(const std::string &s, const std::vector<BamTarget> &targets) {
+  int tid = get_tid(s, targets);
+  if (tid >= 0) return PullRegion{tid, 0, INT32_MAX};
+  const size_t colon = s.rfind(':');
+  if (colon == std::string::npos || (tid = get_tid(s.substr(0, colon), targets)) < 0)
+    quit("[strling] pull: unknown reference in region %s", s.c_str());
+  std::string num;
+  for (char ch : s.substr(colon + 1)) if (ch != ',') num += ch;
+  const size_t dash = num.find('-');
+  const std::string b = num.substr(0, dash), e = dash == std::string::npos ? "" : num.substr(dash + 1);
+  auto digits = [](const std::string &x) { return !x.empty() && x.size() <= 10 && x.find_first_not_of("0123456789") == std::string::npos; };
+  if (!digits(b) || (!e.empty() && !digits(e))) quit("[strling] pull: cannot read the coordinates of region %s", s.c_str());
+  const int64_t beg = std::max<int64_t>(0, atoll(b.c_str()) - 1), end = e.empty() ? INT32_MAX : std::min<int64_t>(atoll(e.c_str()), INT32_MAX);
+  if (end <= beg) quit("[strling] pull: region %s is empty", s.c_str());
+  return PullRegion{tid, beg, end};
+}
+
+// the output (extract_region.nim:70-80): BGZF blocks of at most 0xFF00 input bytes, deflated on the pool, and the EOF block
+static bool write_bgzf(const std::string &path, const std::vector<uint8_t> &payload, ThreadPool &pool, std::string &why) {
+  const size_t BLK = 0xFF00, nb = (payload.size() + BLK - 1) / BLK;
+  std::vector<std::vector<uint8_t>> blocks(nb);
+  std::atomic<bool> bad{false};
+  pool.parallel_for(nb, [&](size_t k) {
+    const uint8_t *src = payload.data() + k * BLK;
+    const size_t len = std::min(BLK, payload.size() - k * BLK);
+    std::vector<uint8_t> &o = blocks[k];
+    o.resize(18 + compressBound((uLong)len) + 64 + 8);
+    z_stream zs;
+    memset(&zs, 0, sizeof zs);
+    if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { bad = true; return; }
+    zs.next_in = const_cast<uint8_t *>(src); zs.avail_in = (uInt)len;
+    zs.next_out = o.data() + 18; zs.avail_out = (uInt)(o.size() - 26);
+    const int rc = deflate(&zs, Z_FINISH);
+    const size_t clen = zs.total_out;
+    deflateEnd(&zs);
+    if (rc != Z_STREAM_END || 18 + clen + 8 > 65536) { bad = true; return; }
+    const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+    memcpy(o.data(), hdr, 16);
+    const uint16_t bsize = (uint16_t)(18 + clen + 8 - 1);
+    memcpy(o.data() + 16, &bsize, 2);
+    const uint32_t crc = (uint32_t)crc32(crc32(0, nullptr, 0), src, (uInt)len), isz = (uint32_t)len;
+    memcpy(o.data() + 18 + clen, &crc, 4); memcpy(o.data() + 18 + clen + 4, &isz, 4);
+    o.resize(18 + clen + 8);
+  });
+  if (bad.load()) { why = "deflate failed"; return false; }
+  static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  FILE *f = fopen(path.c_str(), "wb");
+  if (!f) { why = std::string("cannot write ") + path + ": " + strerror(errno); return false; }
+  bool ok = true;
+  for (auto &o : blocks) ok = ok && fwrite(o.data(), 1, o.size(), f) == o.size();
+  ok = ok && fwrite(eof, 1, 28, f) == 28;
+  ok = (fclose(f) == 0) && ok;
+  if (!ok) why = std::string("cannot write ") + path + ": " + strerror(errno);
+  return ok;
+}
+
+static int pull_main(int argc, char **argv) {
+  const char *usage =
+      "strling pull\n\nUsage:\n  strling pull [options] bam [region ...]\n\nArguments:\n  bam              path to a coordinate-sorted bam file with its .bai index\n"
+      "  region           NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive)\n\nOptions:\n"
+      "  -o, --output-bam=OUT.bam   path to output bam (default: extracted.bam)\n  -L, --regions=BED          regions as BED rows: chrom start end\n"
+      "  -f, --fasta=FASTA          accepted for the reference's command line; a bam needs none\n"
+      "  -v, --verbose\n  -h, --help                 Show this help\n";
+  if (argc <= 2) { fputs(usage, stdout); return 0; }
+  const Args a = parse(argc, argv, 2, {{"output-bam", 'o', true}, {"regions", 'L', true}, {"fasta", 'f', true}, {"verbose", 'v', false}}, usage);
+  if (a.pos.empty()) quit("expected a bam\n%s", usage);
+  const std::string bam = a.pos[0], out_path = a.get("output-bam", "extracted.bam");
+  const bool verbose = a.flag("verbose");
+  if (!file_exists(bam)) quit("could not open bam");                                                   // :41
+  if (CramFile::is_cram(bam))
+    quit("[strling] pull: %s is a CRAM; the CRAM reader of this build decodes the fields `extract` needs, not qualities and tags, so it cannot give back whole records: pull from a BAM",
+         bam.c_str());
+  const auto t0 = std::chrono::steady_clock::now();
+  BamReader rd;
+  std::string err;
+  if (!rd.open(bam, err)) quit("could not open bam");
+  if (!rd.load_index(bam, err)) quit("[strling] pull: %s", err.c_str());
+  // ---- the regions: sorted, overlapping or touching ones merged, so that no record is selected twice
+  std::vector<PullRegion> regions;
+  for (size_t k = 1; k < a.pos.size(); ++k) regions.push_back(parse_pull_region(a.pos[k], rd.targets()));
+  if (a.flag("regions")) {
+    for (const std::string &line : read_lines(a.get("regions", ""))) {
+      if (line.empty() || line[0] == '#' || !line.compare(0, 5, "track") || !line.compare(0, 7, "browser")) continue;
+      char chrom[1024];
+      long long s = 0, e = 0;
+      if (sscanf(line.c_str(), "%1023s %lld %lld", chrom, &s, &e) != 3 || s < 0) quit("[strling] pull: cannot read the BED row: %s", line.c_str());
+      const int tid = get_tid(chrom, rd.targets());
+      if (tid < 0) quit("[strling] pull: unknown reference in BED row: %s", line.c_str());
+      if (e > s) regions.push_back(PullRegion{tid, s, std::min<int64_t>(e, INT32_MAX)});
+    }
+  }
+  if (regions.empty()) quit("[strling] pull: no region given\n%s", usage);
+  std::sort(regions.begin(), regions.end(), [](const PullRegion &x, const PullRegion &y) { return x.tid != y.tid ? x.tid < y.tid : x.beg < y.beg; });
+  {
+    std::vector<PullRegion> merged;
+    for (const PullRegion &r : regions) {
+      if (!merged.empty() && merged.back().tid == r.tid && r.beg <= merged.back().end) merged.back().end = std::max(merged.back().end, r.end);
+      else merged.push_back(r);
+    }
+    regions.swap(merged);
+  }
+  // ---- tiles: a region cut on the 16 KiB windows of the linear index (no record overlaps a window behind the index's last)
+  std::vector<strl_pull_tile> tiles;
+  std::vector<strl_region_req> tile_req;
+  for (const PullRegion &r : regions) {
+    const int64_t nwin = (int64_t)rd.index_windows(r.tid), first = r.beg >> 14, last = std::min<int64_t>((r.end - 1) >> 14, nwin - 1);
+    for (int64_t w = first; w <= last; ++w) {
+      strl_pull_tile T{r.tid, (int32_t)r.beg, (int32_t)r.end, w == first ? INT32_MIN : (int32_t)(w << 14), w == last ? (int32_t)r.end : (int32_t)((w + 1) << 14)};
+      strl_region_req q{};
+      q.tid = r.tid; q.beg = (int32_t)std::max<int64_t>(r.beg, w << 14); q.end = T.own_end;
+      tiles.push_back(T); tile_req.push_back(q);
+    }
+  }
+  const char *mode = getenv("STRL_PULL");
+  bool use_device = !(mode && !strcmp(mode, "host")) && strl_device_count() > 0;
+  set_device0("");
+  strl_ctx *ctx = nullptr;
+  if (use_device && strl_ctx_create(device_of(0), &ctx) != STRL_OK) {
+    if (verbose) fprintf(stderr, "[strling] pull: no context on the device (%s), reading on the host\n", strl_last_error());
+    use_device = false; ctx = nullptr;
+  } else if (!use_device && verbose)
+    fprintf(stderr, "[strling] pull: reading on the host (%s)\n", mode && !strcmp(mode, "host") ? "STRL_PULL=host" : "no device");
+  ThreadPool pool(std::min(decode_threads(), 16));
+  const int fd = open(bam.c_str(), O_RDONLY);
+  if (fd < 0) quit("could not open bam");
+
+  struct Stats { uint64_t dev_tiles = 0, host_tiles = 0, retried = 0, dev_windows = 0, host_windows = 0, select_calls = 0, mate_calls = 0; double select_ms = 0, mates_ms = 0; } S;
+  std::vector<uint8_t> store;                       // the bytes of every record that goes out; the rows index it
+  std::vector<strl_pull_row> kept, mates;
+  std::vector<strl_pull_req> reqs;
+  std::vector<uint8_t> names;
+  std::vector<uint32_t> req_row;                    // the kept record that asks
+  auto keep_bytes = [&](strl_pull_row &r, const uint8_t *from) { const uint64_t at = store.size(); store.insert(store.end(), from + r.off, from + r.off + r.size); r.off = at; };
+  // The blocks of several region queries, read and laid out as the region entry points take them
+  struct Blocks {
+    std::vector<uint8_t> comp; std::vector<uint64_t> coff; std::vector<uint32_t> clen, isize, crc; uint64_t inflated = 0;
+    void clear() { comp.clear(); coff.clear(); clen.clear(); isize.clear(); crc.clear(); inflated = 0; }
+  };
+  auto add_blocks = [&](Blocks &B, const RegionPlan &P, strl_region_req &q) -> bool {
+    q.first_block = (uint32_t)B.clen.size(); q.n_blocks = (uint32_t)P.bsize.size(); q.in_block = P.in_block;
+    const size_t at = B.comp.size(), len = (size_t)(P.c_end - P.c_beg);
+    B.comp.resize(at + ((len + 15) & ~(size_t)15));
+    for (size_t got = 0; got < len;) {
+      const ssize_t n = pread(fd, B.comp.data() + at + got, len - got, (off_t)(P.c_beg + got));
+      if (n <= 0) return false;
+      got += (size_t)n;
+    }
+    uint64_t o = 0;
+    for (size_t k = 0; k < P.bsize.size(); ++k) {
+      B.coff.push_back(at + o + P.hdr[k]); B.clen.push_back(P.bsize[k] - P.hdr[k] - 8); B.isize.push_back(P.isz[k]); B.crc.push_back(P.crc[k]);
+      B.inflated += P.isz[k];
+      o += P.bsize[k];
+    }
+    return true;
+  };
+  const uint64_t batch_inflated = getenv("STRL_PULL_BATCH_MB") ? (uint64_t)atoll(getenv("STRL_PULL_BATCH_MB")) << 20 : (uint64_t)128 << 20;
+  bool nomem = false;
+
+  // ---- 1. the select pass (:46-50) -------------------------------------------------------------------------------------------
+  std::vector<std::vector<strl_pull_row>> per_tile(tiles.size());
+  bool one_device_call = false;
+  auto host_tile = [&](size_t t) {
+    std::vector<uint8_t> raw;
+    std::string e;
+    if (rd.read_region_raw(raw, tile_req[t].tid, tile_req[t].beg, tile_req[t].end, e) < 0) quit("[strling] error reading %s: %s", bam.c_str(), e.c_str());
+    std::vector<strl_pull_row> &rows = per_tile[t];
+    rows.resize(raw.size() / 36 + 1);
+    uint64_t n = 0;
+    CHECK(strl_pull_select_host(raw.data(), raw.size(), &tiles[t], 0, rows.data(), rows.size(), &n));
+    rows.resize((size_t)n);
+    for (strl_pull_row &r : rows) keep_bytes(r, raw.data());
+    ++S.host_tiles;
+  };
+  // the tiles `which` through the device; the ones it passes on come back in `failed`
+  auto device_tiles = [&](const std::vector<size_t> &which, int more, std::vector<size_t> &failed) {
+    for (size_t j = 0; j < which.size() && !nomem;) {
+      Blocks B;
+      std::vector<size_t> in;
+      std::vector<strl_region_req> rq;
+      std::vector<strl_pull_tile> tl;
+      while (j < which.size() && (B.inflated < batch_inflated || in.empty())) {
+        const size_t t = which[j++];
+        RegionPlan P;
+        plan_region(rd, fd, tiles[t].tid, tile_req[t].beg, tile_req[t].end, P, more);
+        strl_region_req q = tile_req[t];
+        if (!P.ok || !add_blocks(B, P, q)) { failed.push_back(t); continue; }
+        in.push_back(t); rq.push_back(q); tl.push_back(tiles[t]);
+      }
+      if (in.empty()) continue;
+      // rows and bytes sized from the blocks' ISIZE sum, which always suffices (a record is 36 bytes or more and is kept once)
+      std::vector<strl_pull_row> rows((size_t)(B.inflated / 36) + in.size() + 1);
+      std::vector<uint8_t> bytes((size_t)(2 * B.inflated) + 64);
+      std::vector<uint64_t> tile_rows(in.size() + 1);
+      std::vector<uint8_t> status(in.size(), 1);
+      uint64_t n_rows = 0, n_bytes = 0;
+      double ms = 0;
+      const int rc = strl_pull_select(ctx, B.comp.data(), B.comp.size(), B.coff.data(), B.clen.data(), B.isize.data(), B.crc.data(), (uint32_t)B.clen.size(), rq.data(), tl.data(),
+                                      (uint32_t)in.size(), rows.data(), rows.size(), &n_rows, tile_rows.data(), bytes.data(), bytes.size(), &n_bytes, status.data(), &ms);
+      ++S.select_calls;
+      if (rc == STRL_ERR_NOMEM) { nomem = true; return; }
+      if (rc == STRL_ERR_FORMAT || rc == STRL_ERR_CRC || rc == STRL_ERR_CAPACITY) {      // the host reader, zlib behind it, has the last word
+        for (size_t t : in) failed.push_back(t);
+        continue;
+      }
+      if (rc) quit("[strling] pull: %s (status %d)", strl_last_error(), rc);
+      S.select_ms += ms;
+      for (size_t k = 0; k < in.size(); ++k) {
+        if (status[k]) { failed.push_back(in[k]); continue; }
+        std::vector<strl_pull_row> &dst = per_tile[in[k]];
+        dst.assign(rows.begin() + (ptrdiff_t)tile_rows[k], rows.begin() + (ptrdiff_t)tile_rows[k + 1]);
+        for (strl_pull_row &r : dst) keep_bytes(r, bytes.data());
+        ++S.dev_tiles;
+      }
+    }
+  };
+  std::vector<size_t> all_tiles(tiles.size());
+  for (size_t t = 0; t < tiles.size(); ++t) all_tiles[t] = t;
+  if (use_device) {
+    std::vector<size_t> failed, failed2;
+    device_tiles(all_tiles, 1, failed);
+    // a tile whose blocks ended before its query did (a pile-up larger than the plan's run of blocks): once more with eight
+    // times the blocks, then the host reader
+    std::vector<size_t> again;
+    for (size_t t : failed) { uint64_t cb, ch; uint32_t ib; if (rd.region_span(tiles[t].tid, tile_req[t].beg, tile_req[t].end, cb, ib, ch)) again.push_back(t); else failed2.push_back(t); }
+    S.retried = again.size();
+    if (!nomem && !again.empty()) device_tiles(again, 8, failed2);
+    if (!nomem) for (size_t t : failed2) host_tile(t);
+    if (!nomem && verbose && !failed2.empty()) fprintf(stderr, "[strling] pull: %zu of %zu tiles read on the host (blocks the index cannot bound, or passed on by the device)\n", failed2.size(), tiles.size());
+    one_device_call = !nomem && S.select_calls == 1 && S.host_tiles == 0;
+  }
+  if (nomem) {                                      // STRL_ERR_NOMEM: the whole run on the host
+    if (verbose) fprintf(stderr, "[strling] pull: device memory exhausted, reading on the host\n");
+    use_device = false;
+    store.clear();
+    for (auto &v : per_tile) v.clear();
+    S = Stats{};
+  }
+  if (!use_device) for (size_t t : all_tiles) host_tile(t);
+  for (auto &v : per_tile) { kept.insert(kept.end(), v.begin(), v.end()); std::vector<strl_pull_row>().swap(v); }
+  if (!one_device_call) CHECK(strl_pull_counts_host(store.data(), kept.data(), kept.size()));   // (counts[] spans every tile: one device call has them, several do not)
+  fprintf(stderr, "extracted %zu alignments. now checking for mates\n", kept.size());              // :51
+
+  // ---- 2. the requests (:54-59) and the mate pass (:7-19) -------------------------------------------------------------------
+  const int32_t n_ref = (int32_t)rd.targets().size();
+  std::vector<uint32_t> placed, unplaced;           // requests by kind, in record order
+  for (size_t i = 0; i < kept.size(); ++i) {
+    const strl_pull_row &r = kept[i];
+    if (r.count == 2) continue;                     // got both mates (:57)
+    strl_pull_req q{};
+    q.hash = r.hash; q.flag = r.flag; q.name_len = (uint8_t)(r.l_name ? r.l_name - 1 : 0); q.name_off = (uint32_t)names.size();
+    names.insert(names.end(), store.begin() + (ptrdiff_t)(r.off + 36), store.begin() + (ptrdiff_t)(r.off + 36 + q.name_len));
+    q.beg = (int32_t)std::max<int64_t>(0, (int64_t)r.mpos - 1);                                      // :15
+    q.end = (int32_t)std::min<int64_t>((int64_t)r.mpos + 1, INT32_MAX);
+    const uint32_t k = (uint32_t)reqs.size();
+    if (r.mtid == -1) unplaced.push_back(k);
+    else if (r.mtid >= 0 && r.mtid < n_ref && q.end > q.beg) placed.push_back(k);                    // (else: an empty query, no mate)
+    reqs.push_back(q); req_row.push_back((uint32_t)i);
+  }
+  if (names.size() > 0xfffffff0ull) quit("[strling] pull: the names of the mate requests exceed 4 GiB");
+  mates.assign(reqs.size(), strl_pull_row{});
+  // placed mates, grouped by (next_refID, 16 KiB window): a window is fetched and walked once, however many requests point into it
+  auto win_key = [&](uint32_t k) { return ((uint64_t)(uint32_t)kept[req_row[k]].mtid << 32) | (uint32_t)(reqs[k].beg >> 14); };
+  std::stable_sort(placed.begin(), placed.end(), [&](uint32_t x, uint32_t y) { return win_key(x) < win_key(y); });
+  struct Window { int32_t tid; int32_t beg, end; uint32_t q0, q1; };
+  std::vector<Window> windows;
+  std::vector<strl_pull_req> wreqs(placed.size());
+  std::vector<strl_pull_row> wrows(placed.size(), strl_pull_row{});
+  for (uint32_t k = 0; k < placed.size(); ++k) {
+    wreqs[k] = reqs[placed[k]];
+    if (windows.empty() || win_key(placed[k]) != win_key(placed[windows.back().q0])) windows.push_back(Window{kept[req_row[placed[k]]].mtid, (reqs[placed[k]].beg >> 14) << 14, 0, k, k});
+    windows.back().q1 = k + 1;
+    windows.back().end = std::max(windows.back().end, reqs[placed[k]].end);
+  }
+  auto host_window = [&](const Window &W) {
+    std::vector<uint8_t> raw;
+    std::string e;
+    if (rd.read_region_raw(raw, W.tid, W.beg, W.end, e) < 0) quit("[strling] error reading %s: %s", bam.c_str(), e.c_str());
+    CHECK(strl_pull_mates_host(raw.data(), raw.size(), 1, W.tid, wreqs.data() + W.q0, W.q1 - W.q0, names.data(), 0, wrows.data() + W.q0));
+    for (uint32_t k = W.q0; k < W.q1; ++k) if (wrows[k].found) keep_bytes(wrows[k], raw.data());
+    ++S.host_windows;
+  };
+  auto device_windows = [&](const std::vector<size_t> &which, int more, std::vector<size_t> &failed) {
+    for (size_t j = 0; j < which.size() && !nomem;) {
+      Blocks B;
+      std::vector<size_t> in;
+      std::vector<strl_region_req> rq;
+      std::vector<uint32_t> win_off{0};
+      std::vector<strl_pull_req> rr;
+      while (j < which.size() && (B.inflated < batch_inflated || in.empty())) {
+        const size_t w = which[j++];
+        const Window &W = windows[w];
+        RegionPlan P;
+        plan_region(rd, fd, W.tid, W.beg, W.end, P, more);
+        strl_region_req q{};
+        q.tid = W.tid; q.beg = W.beg; q.end = W.end;
+        if (!P.ok || !add_blocks(B, P, q)) { failed.push_back(w); continue; }
+        in.push_back(w); rq.push_back(q);
+        rr.insert(rr.end(), wreqs.begin() + W.q0, wreqs.begin() + W.q1);
+        win_off.push_back((uint32_t)rr.size());
+      }
+      if (in.empty()) continue;
+      std::vector<strl_pull_row> rows(rr.size());
+      std::vector<uint8_t> bytes(rr.size() * 640 + 4096), status(in.size(), 1);
+      uint64_t n_bytes = 0;
+      double ms = 0;
+      int rc = 0;
+      for (int attempt = 0; attempt < 2; ++attempt) {
+        rc = strl_pull_mates(ctx, B.comp.data(), B.comp.size(), B.coff.data(), B.clen.data(), B.isize.data(), B.crc.data(), (uint32_t)B.clen.size(), rq.data(), win_off.data(),
+                             (uint32_t)in.size(), rr.data(), names.data(), names.size(), rows.data(), bytes.data(), bytes.size(), &n_bytes, status.data(), &ms);
+        if (rc != STRL_ERR_CAPACITY) break;
+        bytes.resize((size_t)n_bytes + 64);
+      }
+      ++S.mate_calls;
+      if (rc == STRL_ERR_NOMEM || rc == STRL_ERR_FORMAT || rc == STRL_ERR_CRC || rc == STRL_ERR_CAPACITY) {   // (so late, memory too: these windows on the host)
+        for (size_t w : in) failed.push_back(w);
+        continue;
+      }
+      if (rc) quit("[strling] pull: %s (status %d)", strl_last_error(), rc);
+      S.mates_ms += ms;
+      for (size_t k = 0; k < in.size(); ++k) {
+        if (status[k]) { failed.push_back(in[k]); continue; }
+        const Window &W = windows[in[k]];
+        for (uint32_t i = 0; i < W.q1 - W.q0; ++i) {
+          wrows[W.q0 + i] = rows[win_off[k] + i];
+          if (wrows[W.q0 + i].found) keep_bytes(wrows[W.q0 + i], bytes.data());
+        }
+        ++S.dev_windows;
+      }
+    }
+  };
+  std::vector<size_t> all_windows(windows.size());
+  for (size_t w = 0; w < windows.size(); ++w) all_windows[w] = w;
+  if (use_device) {
+    std::vector<size_t> failed, failed2, again;
+    device_windows(all_windows, 1, failed);
+    for (size_t w : failed) { uint64_t cb, ch; uint32_t ib; if (rd.region_span(windows[w].tid, windows[w].beg, windows[w].end, cb, ib, ch)) again.push_back(w); else failed2.push_back(w); }
+    if (!again.empty()) device_windows(again, 8, failed2);
+    for (size_t w : failed2) host_window(windows[w]);
+    if (verbose && !failed2.empty()) fprintf(stderr, "[strling] pull: %zu of %zu mate windows searched on the host\n", failed2.size(), windows.size());
+  } else
+    for (size_t w : all_windows) host_window(windows[w]);
+  for (uint32_t k = 0; k < placed.size(); ++k) mates[placed[k]] = wrows[k];
+  // unplaced mates (:9-13): the records behind the last placed one, visited once for all such requests
+  if (!unplaced.empty()) {
+    std::vector<strl_pull_req> ur(unplaced.size());
+    std::vector<strl_pull_row> urow(unplaced.size(), strl_pull_row{});
+    for (size_t k = 0; k < unplaced.size(); ++k) ur[k] = reqs[unplaced[k]];
+    std::string e;
+    if (!rd.seek_tail(e)) quit("[strling] error reading %s: %s", bam.c_str(), e.c_str());
+    std::vector<uint8_t> raw;
+    std::vector<uint8_t> was(unplaced.size(), 0);
+    size_t open_reqs = unplaced.size();
+    while (open_reqs) {
+      raw.clear();
+      const int64_t got = rd.read_raw(raw, 65536, e);
+      if (got < 0) quit("[strling] error reading %s: %s", bam.c_str(), e.c_str());
+      if (got == 0) break;
+      CHECK(strl_pull_mates_host(raw.data(), raw.size(), 0, -1, ur.data(), (uint32_t)ur.size(), names.data(), 0, urow.data()));
+      for (size_t k = 0; k < urow.size(); ++k) if (urow[k].found && !was[k]) { keep_bytes(urow[k], raw.data()); was[k] = 1; --open_reqs; }
+    }
+    for (size_t k = 0; k < unplaced.size(); ++k) mates[unplaced[k]] = urow[k];
+  }
+  close(fd);
+
+  // ---- 3. order (:63-68) and output (:70-80) --------------------------------------------------------------------------------
+  std::vector<strl_pull_row> all = kept;
+  for (size_t k = 0; k < mates.size(); ++k) {
+    if (mates[k].found) { all.push_back(mates[k]); continue; }
+    const strl_pull_req &q = reqs[k];
+    fprintf(stderr, "skipping pair. mate not found for %.*s\n", (int)q.name_len, reinterpret_cast<const char *>(names.data() + q.name_off));   // :20
+  }
+  std::vector<uint32_t> order(all.size());
+  CHECK(strl_pull_order(all.data(), all.size(), order.data()));
+  std::vector<uint8_t> payload(rd.header_bytes());
+  {
+    size_t total = payload.size();
+    for (const strl_pull_row &r : all) total += r.size;
+    payload.reserve(total);
+    for (uint32_t i : order) payload.insert(payload.end(), store.begin() + (ptrdiff_t)all[i].off, store.begin() + (ptrdiff_t)(all[i].off + all[i].size));
+  }
+  std::string why;
+  if (!write_bgzf(out_path, payload, pool, why)) quit("couldn't open output bam: %s", why.c_str());       // :72-73
+  if (verbose)
+    fprintf(stderr,
+            "[strling] pull: {\"regions\": %zu, \"tiles\": %zu, \"device_tiles\": %llu, \"host_tiles\": %llu, \"retried_tiles\": %llu, \"kept\": %zu, \"requests\": %zu, "
+            "\"windows\": %zu, \"device_windows\": %llu, \"host_windows\": %llu, \"unplaced_requests\": %zu, \"mates\": %zu, \"select_kernel_ms\": %.3f, "
+            "\"mates_kernel_ms\": %.3f, \"device_counts\": %s, \"seconds\": %.3f}\n",
+            regions.size(), tiles.size(), (unsigned long long)S.dev_tiles, (unsigned long long)S.host_tiles, (unsigned long long)S.retried, kept.size(), reqs.size(),
+            windows.size(), (unsigned long long)S.dev_windows, (unsigned long long)S.host_windows, unplaced.size(), all.size() - kept.size(), S.select_ms, S.mates_ms,
+            one_device_call ? "true" : "false", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  return ctx ? end_process(ctx) : 0;
+}
+
 // seconds since the kernel started this process (its start time in /proc/self/stat against the uptime clock; 10 ms ticks):
 // what -v reports of the time in front of main() -- the loader mapping the HIP runtime and this program's device code
 static double since_exec() {
@@ -2737,7 +3136,8 @@ int main(int argc, char **argv) {
       "  merge    :   merge putitive STR loci from multiple samples. Only required for joint calling.\n  call     :   call STRs\n"
       "  index    :   identify large STRs in the reference genome, to produce ref.fasta.str.\n"
       "  outliers :   cohort STR outlier scores from the call outputs of many samples (scripts/strling-outliers.py).\n"
-      "  bamindex :   build the index (.bai) of a coordinate-sorted BAM on the GPU (what `samtools index` writes).\n";      // strling.nim:19-22 (pull_region, a debugging writer, is out of scope)
+      "  bamindex :   build the index (.bai) of a coordinate-sorted BAM on the GPU (what `samtools index` writes).\n"
+      "  pull     :   write a region's reads and their mates to a small BAM, for debugging (the reference's pull_region).\n";      // strling.nim:18-24
   if (argc < 2) { fputs(top, stdout); return 1; }
   const std::string cmd = argv[1];
   if (cmd == "extract") return extract_main(argc, argv);
@@ -2746,6 +3146,7 @@ int main(int argc, char **argv) {
   if (cmd == "call") return call_main(argc, argv);
   if (cmd == "outliers") return outliers_main(argc, argv);
   if (cmd == "bamindex") return bamindex_main(argc, argv);
+  if (cmd == "pull") return pull_main(argc, argv);
   if (cmd == "_dump") return dump_main(argc, argv);
   if (cmd == "_decode") return decode_main(argc, argv);
   if (cmd == "_region") return region_main(argc, argv);
@@ -2758,7 +3159,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (cmd == "pull_region")
-    quit("[strling] `%s` is not part of this build (the MI355X path covers index, extract, merge and call; see DESIGN.md section 9)", cmd.c_str());
+    quit("[strling] `%s` is not part of this build (the MI355X path covers index, extract, merge and call; see DESIGN.md section 9); use `strling pull`", cmd.c_str());
   fputs(top, stdout);
   return 1;
 }
