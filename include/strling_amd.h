@@ -721,6 +721,31 @@ int strl_bamindex_fetch(strl_ctx *ctx, uint8_t *out, uint64_t cap);
  * end's chunk buffers stay with the context */
 int strl_bamindex_end(strl_ctx *ctx);
 
+/* ---- the .bai as a by-product of `strling extract`'s own pass (`strling extract --write-index`) ----
+ * strl_front_push already copies, inflates, CRC-checks, record-scans and parses every block; the index needs of a record only
+ * where it starts, refID, pos, end and flag, and the parse has just written those as dense columns.  A builder attached to the
+ * context reuses strl_bamindex_*'s resident tables (runs, linear index, per-reference words) and its finish step; the per-record
+ * step reads the columns instead of the records.  Nothing is added to the chunk loop that the host waits for: the base of a
+ * chunk's runs is a running total on the device, the run table is sized for every record of the chunks the host has not heard
+ * of yet (it looks at a copy of the device's counts a chunk late and grows the table ahead of need), and a refusal is noticed
+ * late -- the chunks behind it skip the index kernels -- and reported by _finish.  A failure of the index never changes what
+ * strl_extract_finish, strl_treads_fetch or strl_front_treads_named return.
+ *   strl_front_index_begin   after strl_front_begin, before the first chunk, on a context that gets the whole file from its first
+ *                            block (STRL_ERR_ARG on a share -- strl_front_trim_next -- and once a chunk has been handed over; a
+ *                            chunk that comes with a `prev` context ends the index).  l_ref: [n_ref of strl_front_begin] as
+ *                            strl_bamindex_begin; runs0: runs the table holds at first (40 B each), 0 = 2^20.
+ *   strl_front_index_blocks  block_off / end_off (as strl_bamindex_push, checked the same way) of the chunk handed over NEXT:
+ *                            call it before that chunk's strl_front_stage, strl_front_push or strl_front_enqueue_after; the
+ *                            offsets of up to four chunks may wait, in file order.  A chunk handed over without its offsets ends
+ *                            the index with a message and leaves the extraction alone.
+ *   strl_front_index_finish  after strl_front_finish, before or after strl_extract_finish: the refusals of strl_bamindex_* with
+ *                            the same codes and messages (record ordinal included), else sort, merge and serialization as
+ *                            strl_bamindex_finish.  The bytes come out through strl_bamindex_fetch; strl_bamindex_end or the
+ *                            next strl_front_begin frees the builder. */
+int strl_front_index_begin(strl_ctx *ctx, const int32_t *l_ref, uint64_t runs0);
+int strl_front_index_blocks(strl_ctx *ctx, const uint64_t *block_off, uint64_t end_off, uint32_t n_blocks);
+int strl_front_index_finish(strl_ctx *ctx, uint64_t *bai_bytes, strl_bamindex_info *info);
+
 /* ---- `strling pull`: a region's primary records and their mates (extract_region.nim:7-20,46-68) ----
  * Two batched device passes over strl_regions_fetch's inputs (the blocks of many region queries, found through the .bai), and
  * their host twins over raw record bytes (pull_logic.cpp), which need no device.

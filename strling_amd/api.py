@@ -134,6 +134,7 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_calls_finish", "strl_unplaced_order", "strl_call_row", "strl_canonical_repeat", "strl_assign_reads_loci", "strl_group_order",
            "strl_extract_device", "strl_treads_fetch", "strl_ctx_pair_times", "strl_sort_pairs", "strl_cluster_resident", "strl_ctx_cluster_times", "strl_pair_rows", "strl_extract_begin", "strl_extract_add", "strl_extract_finish", "strl_pair_rule", "strl_bounds_bare", "strl_ctx_treads_device", "strl_cluster_gathered", "strl_inflate_blocks", "strl_ctx_inflate_ms", "strl_regions_fetch", "strl_evidence_records", "strl_regions_evidence", "strl_front_begin", "strl_front_push", "strl_front_push_after", "strl_front_reserve", "strl_front_stage", "strl_front_enqueue_after", "strl_front_collect", "strl_ctxs_extract_gather", "strl_front_finish", "strl_front_fragwords", "strl_front_fragwords_async", "strl_event_wait", "strl_front_records", "strl_front_tids", "strl_front_qnames", "strl_front_treads_named", "strl_pinned_alloc", "strl_pinned_free", "strl_comm_unique_id", "strl_ctx_comm_init", "strl_ctxs_comm_init", "strl_ctx_comm_info", "strl_cluster_exchange", "strl_ctxs_cluster_exchange", "strl_exchange_treads", "strl_ctx_set_treads", "strl_cluster_collect", "strl_ctx_tail_stream", "strl_ctx_mem_info", "strl_bin_peek", "strl_front_trim_next", "strl_front_tail_bytes", "strl_ctx_blocking_waits", "strl_score_read_host", "strl_front_end",
            "strl_bamindex_begin", "strl_bamindex_reserve", "strl_bamindex_push", "strl_bamindex_finish", "strl_bamindex_fetch", "strl_bamindex_end",
+           "strl_front_index_begin", "strl_front_index_blocks", "strl_front_index_finish",
            "strl_pull_select", "strl_pull_mates", "strl_pull_select_host", "strl_pull_counts_host", "strl_pull_mates_host", "strl_pull_order"]
 
 
@@ -249,6 +250,9 @@ def load(build_if_missing=True):
     L.strl_bamindex_finish.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(BamindexInfo)]
     L.strl_bamindex_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.strl_bamindex_end.argtypes = [C.c_void_p]
+    L.strl_front_index_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_front_index_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+    L.strl_front_index_finish.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(BamindexInfo)]
     L.strl_pinned_alloc.argtypes = [C.c_uint64]
     L.strl_pinned_alloc.restype = C.c_void_p
     L.strl_pinned_free.argtypes = [C.c_void_p]
@@ -809,9 +813,10 @@ class Context:
             b0 += 1
         return dict(data=data, raw=raw, blocks=blocks, block_off=block_off, n_ref=n_ref, targets=targets, text=text, b0=b0, first_off=at - cum)
 
-    def _front_push_blocks(self, B, c0, c1, chunk_blocks, check_crc, trim=0):
+    def _front_push_blocks(self, B, c0, c1, chunk_blocks, check_crc, trim=0, index=False, no_offsets_at=None):
         """blocks [c0, c1) of the table through strl_front_push in chunks; trim = inflated bytes at the end of the LAST block that
-        are not this context's (strl_front_trim_next before the last chunk) -> the chunk summaries that came back"""
+        are not this context's (strl_front_trim_next before the last chunk) -> the chunk summaries that came back.
+        index: every chunk's file offsets go to strl_front_index_blocks first (but not those of push number no_offsets_at)"""
         done = (FrontChunk * 2)()
         nd = C.c_int(0)
         chunks, keep = [], []
@@ -827,6 +832,9 @@ class Context:
             keep.append((comp, coff, clen, isz, crc))           # pageable memory: the copy is staged by the runtime
             if trim and s0 + chunk_blocks >= c1:
                 _check(self.L.strl_front_trim_next(self.h, trim))
+            if index and (s0 - c0) // chunk_blocks != no_offsets_at:
+                boff = np.array(B["block_off"][s0:min(c1, s0 + chunk_blocks)], np.uint64)
+                _check(self.L.strl_front_index_blocks(self.h, _ptr(boff), hi + 8, len(cb)))
             _check(self.L.strl_front_push(self.h, comp.ctypes.data, comp.size, _ptr(coff), _ptr(clen), _ptr(isz), _ptr(crc) if check_crc else None, len(cb), done, C.byref(nd)))
             chunks += [_front_chunk(done[i]) for i in range(nd.value)]
             keep = keep[-3:]
@@ -868,6 +876,31 @@ class Context:
         _check(self.L.strl_front_begin(self.h, B["n_ref"], B["first_off"], n_reads_hint))
         chunks = self._front_push_blocks(B, B["b0"], len(B["blocks"]), chunk_blocks, check_crc)
         return self._front_results(B, chunks)
+
+    def extract_bam_device_indexed(self, path, chunk_blocks=16384, runs0=0, n_reads_hint=0, check_crc=True, no_offsets_at=None):
+        """extract_bam_device with the .bai built in the same pass (strl_front_index_begin / _blocks / _finish; `strling extract
+        --write-index`).  runs0: initial capacity of the run table.  -> (extract_bam_device's dict, bytes of the .bai or None,
+        dict(n_records, n_no_coor, n_runs, n_chunks) or None, None or (status, message) of the index's refusal)"""
+        B = self._bam_blocks(path)
+        l_ref = np.array([t[1] for t in B["targets"]], np.int32)
+        _check(self.L.strl_front_begin(self.h, B["n_ref"], B["first_off"], n_reads_hint))
+        try:
+            _check(self.L.strl_front_index_begin(self.h, _ptr(l_ref) if l_ref.size else None, runs0))
+            chunks = self._front_push_blocks(B, B["b0"], len(B["blocks"]), chunk_blocks, check_crc, index=True, no_offsets_at=no_offsets_at)
+            nbytes = C.c_uint64(0)
+            info = BamindexInfo()
+            rc = self.L.strl_front_index_finish(self.h, C.byref(nbytes), C.byref(info))
+            bai, inf, refused = None, None, None
+            if rc:
+                refused = (rc, self.L.strl_last_error().decode())
+            else:
+                out = np.zeros(max(1, nbytes.value), np.uint8)
+                _check(self.L.strl_bamindex_fetch(self.h, out.ctypes.data, out.size))
+                bai, inf = out[:nbytes.value].tobytes(), {k: int(getattr(info, k)) for k, _ in BamindexInfo._fields_}
+            res = self._front_results(B, chunks)
+        finally:
+            self.L.strl_bamindex_end(self.h)
+        return res, bai, inf, refused
 
     def bamindex(self, path, chunk_blocks=16384, check_crc=True):
         """the .bai of a coordinate-sorted BAM FILE built on the device (strl_bamindex_begin / _push / _finish / _fetch; what

@@ -13,8 +13,13 @@
 // At the end one stable radix sort (sort.hip) of the runs by (tid, bin), a second merge of runs that have become neighbours
 // (prev.end == cur.beg in the inflated stream), and the host packs the bytes from the sorted chunks.
 // rec_parse_kernel, the scorer and strl_front_begin's per-read state are not involved.
+//
+// The same builder also hangs off `strling extract`'s own pass (strl_front_index_*): behind rec_parse_kernel the
+// per-record step reads the dense columns the parse has just written instead of the records, the run base is a running total in
+// the device's state words, and the host learns of counts and refusals one chunk late, from a copy it never waits for.
 #include <string.h>
 #include <algorithm>
+#include <deque>
 #include "front.h"
 #include "sort.h"
 #include "device_util.h"
@@ -39,8 +44,15 @@ struct BaiState {         // device words of the builder; the host reads them ba
   uint64_t n_no_coor;
   uint32_t n_heads, pad;             // runs that start in the chunk just scanned / chunks after the merge
   BaiLast last[2];                   // [parity of the chunk]: read from one, written to the other
+  uint64_t run_base, run_total;      // (builder behind extract) runs in front of the chunk just scanned / runs so far: kept by the scan
+  uint32_t overflow, pad2;           // (builder behind extract) a run did not fit the table: never written, reported at the end
 };
 
+struct BaiCols {           // the parse kernel's dense columns of the chunk's records (front.hip rec_parse_kernel)
+  const int32_t *tid, *pos, *end;
+  const uint32_t *fragw;   // flag in the low 16 bits
+  uint32_t rec_end;        // buffer offset behind the chunk's last complete record
+};
 struct BaiPush {
   const uint8_t *U;
   const uint32_t *recoff;
@@ -58,7 +70,10 @@ struct BaiPush {
   uint8_t *flag;
   uint32_t *blk_cnt;
   BaiRun *runs;
-  uint64_t run_base;
+  uint64_t run_base;        // first slot of the chunk's runs, when the host knows it (run_acc == nullptr)
+  const uint64_t *run_acc;  // ... else &BaiState::run_base on the device
+  uint64_t run_cap;         // slots of runs[]
+  BaiCols C;
 };
 
 struct BaiRec { int32_t tid, pos, end; uint32_t flag, bs; };
@@ -79,6 +94,17 @@ __device__ __forceinline__ void bai_read(const uint8_t *U, uint32_t q, BaiRec &r
   }
   const int64_t e = (int64_t)r.pos + (rl ? rl : 1);
   r.end = e > 0x7fffffffll ? 0x7fffffff : (int32_t)e;
+}
+// the record's five numbers: from its bytes, or (COLS) from the parse's columns -- the byte length is the distance to the next
+// record (records lie back to back), end is bam_endpos as rec_parse_kernel computed it
+template <bool COLS> __device__ __forceinline__ void bai_fetch(const BaiPush &P, uint32_t i, BaiRec &r) {
+  if constexpr (COLS) {
+    r.tid = P.C.tid[i]; r.pos = P.C.pos[i]; r.end = P.C.end[i]; r.flag = P.C.fragw[i] & 0xffffu;
+    if (r.end <= r.pos) r.end = 0x7fffffff;     // (a reference span that left 31 bits: bai_read's clamp)
+    r.bs = (i + 1u < P.n ? P.recoff[i + 1u] : P.C.rec_end) - P.recoff[i] - 4u;
+  } else {
+    bai_read(P.U, P.recoff[i], r);
+  }
 }
 __device__ __forceinline__ uint32_t bai_reg2bin(int32_t beg, int32_t end) {      // SAM spec 5.3
   --end;
@@ -112,13 +138,14 @@ __device__ __forceinline__ uint64_t bai_voff(const int64_t *vrel, const uint64_t
   return (vfoff[lo] << 16) | (uint64_t)(q - vrel[lo]);
 }
 
-__global__ __launch_bounds__(256) void bai_record_kernel(BaiPush P) {
+// the per-record step; the rules (refusals, bin, windows, virtual offsets, run heads) are this one body for both sources
+template <bool COLS> __device__ __forceinline__ void bai_record_body(const BaiPush &P) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
   const bool act = i < P.n;
   BaiRec r{-1, -1, 0, 0, 0};
   uint32_t q = 0;
   int bad = -1;
-  if (act) { q = P.recoff[i]; bai_read(P.U, q, r); bad = bai_refusal(r, P.n_ref, P.win_off); }
+  if (act) { q = P.recoff[i]; bai_fetch<COLS>(P, i, r); bad = bai_refusal(r, P.n_ref, P.win_off); }
   const bool placed = act && r.tid >= 0 && bad < 0;
   const uint64_t key = act ? bai_key(r, P.n_ref, bad < 0) : BAI_KEY_NONE;
   const int32_t end_win = placed ? (r.end - 1) >> 14 : -1;
@@ -129,7 +156,7 @@ __global__ __launch_bounds__(256) void bai_record_kernel(BaiPush P) {
     if (i == 0) { const BaiLast &L = P.S->last[P.par]; ptid = L.tid; ppos = L.pos; pwin = L.end_win; pkey = L.key; }
     else {
       BaiRec p;
-      bai_read(P.U, P.recoff[i - 1], p);
+      bai_fetch<COLS>(P, i - 1u, p);
       const bool pok = bai_refusal(p, P.n_ref, P.win_off) < 0;
       ptid = p.tid; ppos = p.pos; pkey = bai_key(p, P.n_ref, pok);
       pwin = (p.tid >= 0 && pok) ? (p.end - 1) >> 14 : -1;
@@ -187,16 +214,19 @@ __global__ __launch_bounds__(256) void bai_record_kernel(BaiPush P) {
     P.S->last[P.par ^ 1u] = L;
   }
 }
+__global__ __launch_bounds__(256) void bai_record_kernel(BaiPush P) { bai_record_body<false>(P); }
+__global__ __launch_bounds__(256) void bai_record_cols_kernel(BaiPush P) { bai_record_body<true>(P); }
 
-// One block: cnt[0, n) -> exclusive sums in place, the total to *total
-__global__ __launch_bounds__(1024) void bai_scan_kernel(uint32_t *cnt, uint32_t n, uint32_t *total) {
+// One block: cnt[0, n) -> exclusive sums in place, the total to *total; acc (if given): acc[0] = the running total so far (the
+// base of this chunk's runs), acc[1] += total -- the host is not asked
+__global__ __launch_bounds__(1024) void bai_scan_kernel(uint32_t *cnt, uint32_t n, uint32_t *total, uint64_t *acc) {
   __shared__ uint32_t part[1024];
   const uint32_t t = threadIdx.x, per = (n + 1023u) / 1024u, a = min(n, t * per), b = min(n, a + per);
   uint32_t s = 0;
   for (uint32_t k = a; k < b; ++k) s += cnt[k];
   part[t] = s;
   __syncthreads();
-  if (t == 0) { uint32_t run = 0; for (int k = 0; k < 1024; ++k) { const uint32_t v = part[k]; part[k] = run; run += v; } *total = run; }
+  if (t == 0) { uint32_t run = 0; for (int k = 0; k < 1024; ++k) { const uint32_t v = part[k]; part[k] = run; run += v; } *total = run; if (acc) { acc[0] = acc[1]; acc[1] += run; } }
   __syncthreads();
   uint32_t run = part[t];
   for (uint32_t k = a; k < b; ++k) { const uint32_t v = cnt[k]; cnt[k] = run; run += v; }
@@ -214,20 +244,23 @@ __device__ __forceinline__ uint32_t bai_block_rank(bool f) {
   return r;
 }
 
-__global__ __launch_bounds__(256) void bai_emit_kernel(BaiPush P) {
+template <bool COLS> __device__ __forceinline__ void bai_emit_body(const BaiPush &P) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const bool head = i < P.n && P.flag[i];
   const uint32_t rank = bai_block_rank(head);
   if (!head) return;
-  const uint64_t slot = P.run_base + P.blk_cnt[blockIdx.x] + rank;
+  const uint64_t slot = (P.run_acc ? *P.run_acc : P.run_base) + P.blk_cnt[blockIdx.x] + rank;
+  if (slot >= P.run_cap) { P.S->overflow = 1u; return; }       // (the host sizes the table for every record of the chunk: not reached)
   const uint32_t q = P.recoff[i];
   BaiRec r;
-  bai_read(P.U, q, r);
+  bai_fetch<COLS>(P, i, r);
   const uint64_t beg_v = bai_voff(P.vrel, P.vfoff, P.vm, (int64_t)q), beg_abs = (uint64_t)(P.abs0 + (int64_t)q);
   BaiRun &R = P.runs[slot];
   R.key = bai_key(r, P.n_ref, bai_refusal(r, P.n_ref, P.win_off) < 0); R.beg_v = beg_v; R.beg_abs = beg_abs;
   if (slot) { BaiRun &B = P.runs[slot - 1]; B.end_v = beg_v; B.end_abs = beg_abs; }
 }
+__global__ __launch_bounds__(256) void bai_emit_kernel(BaiPush P) { bai_emit_body<false>(P); }
+__global__ __launch_bounds__(256) void bai_emit_cols_kernel(BaiPush P) { bai_emit_body<true>(P); }
 
 // finish: the open run ends behind the last record; sort keys of the runs
 __global__ void bai_keys_kernel(BaiRun *runs, uint32_t n, const BaiState *S, uint32_t par, uint64_t *keys, uint32_t *vals) {
@@ -282,12 +315,29 @@ struct strl_bai {
   uint32_t par = 0;
   bool finished = false;
   std::vector<uint8_t> bytes;                         // the serialized index
+  // ---- behind `strling extract`'s own pass (strl_front_index_*): nothing here is waited for inside the chunk loop
+  bool attached = false;
+  int fail_rc = 0;                                    // the index ended early (the extraction goes on): reported by strl_front_index_finish
+  std::string fail;
+  struct Offsets { std::vector<uint64_t> block_off; uint64_t end_off; };
+  std::deque<Offsets> want;                           // strl_front_index_blocks: file offsets of the chunks handed over next, in file order
+  uint64_t want_end = 0;                              // file offset behind the last block announced
+  bool have_table[2] = {false, false};                // [slot] the chunk in the slot came with its offsets
+  uint64_t run_cap = 0;                               // slots of runs
+  uint64_t known_runs = 0, known_at = 0;              // the device's running total as last seen, and the records indexed up to that look
+  BaiState *h_snap = nullptr;                         // pinned: a copy of the state words made behind a chunk, looked at a chunk later
+  hipEvent_t ev_snap = nullptr;
+  bool snap_flying = false, refusal_seen = false;
+  uint64_t snap_at = 0;
+  std::vector<DevBuf> trash;                          // outgrown tables (kernels in flight may still use them): freed with the builder
 };
 
 void bai_destroy(strl_bai *B) {
   if (!B) return;
   for (uint8_t *p : B->h_vt) if (p) (void)hipHostFree(p);
   if (B->h_state) (void)hipHostFree(B->h_state);
+  if (B->h_snap) (void)hipHostFree(B->h_snap);
+  if (B->ev_snap) (void)hipEventDestroy(B->ev_snap);
   delete B;
 }
 
@@ -331,7 +381,7 @@ static int bai_index_chunk(strl_ctx *c, strl_front *F, strl_bai *B, int si) {
     P.S = B->state.as<BaiState>(); P.par = B->par; P.flag = B->flag.as<uint8_t>(); P.blk_cnt = B->blk_cnt.as<uint32_t>();
     hipLaunchKernelGGL(bai_record_kernel, dim3(nblk), dim3(256), 0, st, P);
     STRL_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, P.blk_cnt, nblk, &P.S->n_heads);
+    hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, P.blk_cnt, nblk, &P.S->n_heads, (uint64_t *)nullptr);
     STRL_HIP(hipGetLastError());
     STRL_HIP(hipMemcpyAsync(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost, st));
     STRL_HIP(hipStreamSynchronize(st));                 // the number of runs that start in the chunk: the table grows by exactly that
@@ -340,7 +390,7 @@ static int bai_index_chunk(strl_ctx *c, strl_front *F, strl_bai *B, int si) {
     if (B->n_runs + heads > 0x7ffffff0ull) { set_error("more than 2^31 runs of equal (reference, bin): beyond one device sort"); return STRL_ERR_LIMIT; }
     if (heads) {
       if ((rc = B->runs.grow((size_t)(B->n_runs + heads) * sizeof(BaiRun), (size_t)B->n_runs * sizeof(BaiRun), st))) return rc;
-      P.runs = B->runs.as<BaiRun>(); P.run_base = B->n_runs;
+      P.runs = B->runs.as<BaiRun>(); P.run_base = B->n_runs; P.run_acc = nullptr; P.run_cap = B->runs.cap / sizeof(BaiRun);
       hipLaunchKernelGGL(bai_emit_kernel, dim3(nblk), dim3(256), 0, st, P);
       STRL_HIP(hipGetLastError());
       B->n_runs += heads;
@@ -360,10 +410,9 @@ static void put64(std::vector<uint8_t> &o, uint64_t v) { for (int k = 0; k < 8; 
 
 using namespace strl;
 
-extern "C" int strl_bamindex_begin(strl_ctx *c, int32_t n_ref, const int32_t *l_ref, uint64_t first_record_offset) {
-  if (!c || n_ref < 0 || (n_ref && !l_ref)) { set_error("strl_bamindex_begin: bad argument"); return STRL_ERR_ARG; }
+// the resident tables of a new builder (linear index, per-reference words, state words) on the context; replaces c->bai
+static int bai_setup(strl_ctx *c, int32_t n_ref, const int32_t *l_ref) {
   int rc;
-  if ((rc = front_begin_scan(c, n_ref, first_record_offset))) return rc;
   if (c->bai) { bai_destroy(c->bai); c->bai = nullptr; }
   strl_bai *B = new strl_bai();
   c->bai = B;
@@ -394,37 +443,21 @@ extern "C" int strl_bamindex_begin(strl_ctx *c, int32_t n_ref, const int32_t *l_
   return STRL_OK;
 }
 
-extern "C" int strl_bamindex_reserve(strl_ctx *c, uint32_t max_blocks, uint64_t max_comp_bytes) {
-  if (!c || !c->bai || !c->front || !max_blocks) { set_error("strl_bamindex_reserve: bad argument / no strl_bamindex_begin"); return STRL_ERR_ARG; }
-  STRL_HIP(hipSetDevice(c->device));
-  int rc;
-  const uint64_t rec_cap = (uint64_t)max_blocks * 65280u / 36 + 16;      // no record is shorter than 36 bytes (front_reserve's bound)
-  if ((rc = c->bai->flag.reserve((size_t)rec_cap + 64)) || (rc = c->bai->blk_cnt.reserve((size_t)(rec_cap / 256 + 2) * 4 + 64))) return rc;
-  return front_reserve(c, c->front, max_blocks, max_comp_bytes);
-}
-
-extern "C" int strl_bamindex_push(strl_ctx *c, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
-                                  const uint32_t *crc32, const uint64_t *block_off, uint64_t end_off, uint32_t n_blocks) {
-  if (!c || !c->bai || !c->front || c->bai->finished || (n_blocks && (!comp || !coff || !clen || !isize || !block_off))) {
-    set_error("strl_bamindex_push: bad argument / no strl_bamindex_begin");
-    return STRL_ERR_ARG;
-  }
-  if (!n_blocks) return STRL_OK;
-  STRL_HIP(hipSetDevice(c->device));
-  strl_front *F = c->front;
-  strl_bai *B = c->bai;
-  const int si = (int)(B->chunks & 1);
-  FrontSlot &S = F->slot[si];
-  int rc;
+// what a chunk's block offsets must be: ascending, behind `floor` (the end of what came before), 48 bits; ISIZE (where known) in [1, 65536]
+static int bai_check_blocks(const char *who, uint64_t floor, const uint64_t *block_off, uint64_t end_off, const uint32_t *isize, uint32_t n_blocks) {
   for (uint32_t i = 0; i < n_blocks; ++i)
-    if (block_off[i] >= (1ull << 48) || (i && block_off[i] <= block_off[i - 1]) || block_off[i] < B->end_off || isize[i] > 65536u || !isize[i]) {
-      set_error("strl_bamindex_push: block %u: file offsets must ascend and fit 48 bits, ISIZE must be in [1, 65536]", i);
+    if (block_off[i] >= (1ull << 48) || (i && block_off[i] <= block_off[i - 1]) || block_off[i] < floor || (isize && (isize[i] > 65536u || !isize[i]))) {
+      set_error("%s: block %u: file offsets must ascend and fit 48 bits, ISIZE must be in [1, 65536]", who, i);
       return STRL_ERR_ARG;
     }
-  if (end_off <= block_off[n_blocks - 1] || end_off >= (1ull << 48)) { set_error("strl_bamindex_push: end_off is not behind the last block"); return STRL_ERR_ARG; }
-  // the chunk two back has left the slot (its table in h_vt was copied in front of its kernels)
-  if (S.b_pending) { STRL_HIP(hipEventSynchronize(S.ev_b)); S.b_pending = false; }
-  // block table of the chunk, with the blocks a carried record may start in
+  if (end_off <= block_off[n_blocks - 1] || end_off >= (1ull << 48)) { set_error("%s: end_off is not behind the last block", who); return STRL_ERR_ARG; }
+  return STRL_OK;
+}
+
+// block table of the chunk that goes to slot si, in the slot's pinned source (the previous chunk of the slot has left it): where
+// each block's first inflated byte lies in the chunk's buffer and the block's file offset, the blocks of the previous chunks
+// that the carried record may start in first (`tail`), the end last
+static int bai_block_table(strl_bai *B, int si, const uint64_t *block_off, uint64_t end_off, const uint32_t *isize, uint32_t n_blocks) {
   const size_t m = B->tail.size() + n_blocks;
   if (B->h_vt_cap[si] < (m + 1) * 16) {
     if (B->h_vt[si]) { (void)hipHostFree(B->h_vt[si]); B->h_vt[si] = nullptr; }
@@ -450,6 +483,42 @@ extern "C" int strl_bamindex_push(strl_ctx *c, const uint8_t *comp, uint64_t com
   size_t drop = 0;                                                    // keep the blocks that hold the last FRONT_CARRY_MAX bytes
   while (drop + 1 < B->tail.size() && B->tail[drop + 1].abs <= at - (int64_t)FRONT_CARRY_MAX) ++drop;
   B->tail.erase(B->tail.begin(), B->tail.begin() + (ptrdiff_t)drop);
+  return STRL_OK;
+}
+
+extern "C" int strl_bamindex_begin(strl_ctx *c, int32_t n_ref, const int32_t *l_ref, uint64_t first_record_offset) {
+  if (!c || n_ref < 0 || (n_ref && !l_ref)) { set_error("strl_bamindex_begin: bad argument"); return STRL_ERR_ARG; }
+  int rc;
+  if ((rc = front_begin_scan(c, n_ref, first_record_offset))) return rc;
+  return bai_setup(c, n_ref, l_ref);
+}
+
+extern "C" int strl_bamindex_reserve(strl_ctx *c, uint32_t max_blocks, uint64_t max_comp_bytes) {
+  if (!c || !c->bai || !c->front || !max_blocks) { set_error("strl_bamindex_reserve: bad argument / no strl_bamindex_begin"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  int rc;
+  const uint64_t rec_cap = (uint64_t)max_blocks * 65280u / 36 + 16;      // no record is shorter than 36 bytes (front_reserve's bound)
+  if ((rc = c->bai->flag.reserve((size_t)rec_cap + 64)) || (rc = c->bai->blk_cnt.reserve((size_t)(rec_cap / 256 + 2) * 4 + 64))) return rc;
+  return front_reserve(c, c->front, max_blocks, max_comp_bytes);
+}
+
+extern "C" int strl_bamindex_push(strl_ctx *c, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                                  const uint32_t *crc32, const uint64_t *block_off, uint64_t end_off, uint32_t n_blocks) {
+  if (!c || !c->bai || !c->front || c->bai->finished || c->bai->attached || (n_blocks && (!comp || !coff || !clen || !isize || !block_off))) {
+    set_error("strl_bamindex_push: bad argument / no strl_bamindex_begin");
+    return STRL_ERR_ARG;
+  }
+  if (!n_blocks) return STRL_OK;
+  STRL_HIP(hipSetDevice(c->device));
+  strl_front *F = c->front;
+  strl_bai *B = c->bai;
+  const int si = (int)(B->chunks & 1);
+  FrontSlot &S = F->slot[si];
+  int rc;
+  if ((rc = bai_check_blocks("strl_bamindex_push", B->end_off, block_off, end_off, isize, n_blocks))) return rc;
+  // the chunk two back has left the slot (its table in h_vt was copied in front of its kernels)
+  if (S.b_pending) { STRL_HIP(hipEventSynchronize(S.ev_b)); S.b_pending = false; }
+  if ((rc = bai_block_table(B, si, block_off, end_off, isize, n_blocks))) return rc;
   const FrontChunkDesc d{comp, comp_bytes, coff, clen, isize, crc32, n_blocks};
   if ((rc = front_stage_a(c, F, si, d, B->chunks == 0))) return rc;
   ++B->chunks;
@@ -461,8 +530,94 @@ extern "C" int strl_bamindex_push(strl_ctx *c, const uint8_t *comp, uint64_t com
   return STRL_OK;
 }
 
+// the finish step of both builders: every chunk's runs are in the table and the stream has been waited for
+static int bai_sort_and_pack(strl_ctx *c, strl_bai *B) {
+  hipStream_t st = c->stream;
+  int rc;
+  // one stable sort of the runs by (tid, bin), the second merge, the chunks to the host
+  const uint32_t n = (uint32_t)B->n_runs;
+  std::vector<BaiChunk> ch;
+  if (n) {
+    int bits = 17;
+    while (bits < 48 && ((uint64_t)B->n_ref >> (bits - 16))) ++bits;
+    const size_t sb = radix_sort_scratch_bytes(n, bits);
+    const uint32_t nblk = (n + 255u) / 256u;
+    DevBuf k0, k1, v0, v1, sc, out;
+    if ((rc = k0.reserve((size_t)n * 8)) || (rc = k1.reserve((size_t)n * 8)) || (rc = v0.reserve((size_t)n * 4)) || (rc = v1.reserve((size_t)n * 4)) || (rc = sc.reserve(sb)) ||
+        (rc = out.reserve((size_t)n * sizeof(BaiChunk))) || (rc = B->flag.reserve((size_t)n + 64)) || (rc = B->blk_cnt.reserve((size_t)nblk * 4 + 64)))
+      return rc;
+    BaiState *S = B->state.as<BaiState>();
+    hipLaunchKernelGGL(bai_keys_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), n, S, B->par, k0.as<uint64_t>(), v0.as<uint32_t>());
+    uint32_t *d_n = &S->n_heads;                         // (the device-side count the sort reads)
+    hipError_t e = hipMemcpyAsync(d_n, &n, 4, hipMemcpyHostToDevice, st);
+    uint64_t *ok = nullptr;
+    uint32_t *ov = nullptr;
+    int se = 0;
+    if (e == hipSuccess) se = radix_sort_pairs(st, d_n, n, k0.as<uint64_t>(), v0.as<uint32_t>(), k1.as<uint64_t>(), v1.as<uint32_t>(), sc.p, sb, 0, bits, &ok, &ov);
+    if (e == hipSuccess && !se) {
+      hipLaunchKernelGGL(bai_merge_flag_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), ok, ov, n, B->flag.as<uint8_t>(), B->blk_cnt.as<uint32_t>());
+      hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, B->blk_cnt.as<uint32_t>(), nblk, d_n, (uint64_t *)nullptr);
+      hipLaunchKernelGGL(bai_merge_emit_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), ok, ov, n, B->flag.as<uint8_t>(), B->blk_cnt.as<uint32_t>(), d_n, out.as<BaiChunk>());
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (e == hipSuccess) {
+        ch.resize(B->h_state->n_heads);
+        if (!ch.empty()) e = hipMemcpy(ch.data(), out.p, ch.size() * sizeof(BaiChunk), hipMemcpyDeviceToHost);
+      }
+    }
+    if (se) { set_error("radix_sort_pairs failed: %s", hipGetErrorString((hipError_t)se)); return STRL_ERR_HIP; }
+    if (e != hipSuccess) { set_error("strl_bamindex_finish: %s", hipGetErrorString(e)); return STRL_ERR_HIP; }
+  } else {
+    STRL_HIP(hipMemcpy(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost));
+  }
+  const size_t nr = (size_t)B->n_ref, nw = (size_t)B->win_off[nr];
+  std::vector<uint64_t> lin(nw), rb(nr), re(nr), cnt(2 * nr);
+  if (nw) STRL_HIP(hipMemcpy(lin.data(), B->lin.p, nw * 8, hipMemcpyDeviceToHost));
+  if (nr) {
+    STRL_HIP(hipMemcpy(rb.data(), B->ref_beg.p, nr * 8, hipMemcpyDeviceToHost));
+    STRL_HIP(hipMemcpy(re.data(), B->ref_end.p, nr * 8, hipMemcpyDeviceToHost));
+    STRL_HIP(hipMemcpy(cnt.data(), B->ref_cnt.p, nr * 16, hipMemcpyDeviceToHost));
+  }
+  // the bytes (SAM spec 5.2): per reference the bins ascending with their chunks, the pseudo-bin last, the linear index up to
+  // the last window touched (empty windows 0), n_no_coor at the end
+  std::vector<uint8_t> &o = B->bytes;
+  o.clear();
+  o.reserve(8 + ch.size() * 24 + nw * 8 + nr * 64 + 8);
+  o.insert(o.end(), {'B', 'A', 'I', 1});
+  put32(o, (uint32_t)B->n_ref);
+  size_t at = 0;
+  uint64_t n_chunks = 0;
+  for (size_t t = 0; t < nr; ++t) {
+    size_t e = at, n_bin = 0;
+    while (e < ch.size() && (ch[e].key >> 16) == t) { if (e == at || ch[e].key != ch[e - 1].key) ++n_bin; ++e; }
+    const bool meta = cnt[2 * t] + cnt[2 * t + 1] != 0;
+    put32(o, (uint32_t)(n_bin + (meta ? 1 : 0)));
+    for (size_t a = at; a < e;) {
+      size_t b = a;
+      while (b < e && ch[b].key == ch[a].key) ++b;
+      put32(o, (uint32_t)(ch[a].key & 0xffffu));
+      put32(o, (uint32_t)(b - a));
+      for (size_t k = a; k < b; ++k) { put64(o, ch[k].beg_v); put64(o, ch[k].end_v); }
+      n_chunks += b - a;
+      a = b;
+    }
+    if (meta) { put32(o, BAI_META_BIN); put32(o, 2); put64(o, rb[t]); put64(o, re[t]); put64(o, cnt[2 * t]); put64(o, cnt[2 * t + 1]); }
+    const uint64_t w0 = B->win_off[t], w1 = B->win_off[t + 1];
+    uint64_t n_intv = 0;
+    for (uint64_t w = w1; w > w0; --w) if (lin[(size_t)w - 1] != ~0ull) { n_intv = w - w0; break; }
+    put32(o, (uint32_t)n_intv);
+    for (uint64_t w = 0; w < n_intv; ++w) { const uint64_t v = lin[(size_t)(w0 + w)]; put64(o, v == ~0ull ? 0 : v); }
+    at = e;
+  }
+  put64(o, B->h_state->n_no_coor);
+  B->n_chunks = n_chunks;
+  B->finished = true;
+  return STRL_OK;
+}
+
 extern "C" int strl_bamindex_finish(strl_ctx *c, uint64_t *bai_bytes, strl_bamindex_info *info) {
-  if (!c || !c->bai || !c->front) { set_error("strl_bamindex_finish without strl_bamindex_begin"); return STRL_ERR_ARG; }
+  if (!c || !c->bai || !c->front || c->bai->attached) { set_error("strl_bamindex_finish without strl_bamindex_begin"); return STRL_ERR_ARG; }
   STRL_HIP(hipSetDevice(c->device));
   strl_front *F = c->front;
   strl_bai *B = c->bai;
@@ -473,85 +628,165 @@ extern "C" int strl_bamindex_finish(strl_ctx *c, uint64_t *bai_bytes, strl_bamin
       if ((rc = bai_index_chunk(c, F, B, (int)(B->done & 1)))) return rc;
     STRL_HIP(hipStreamSynchronize(st));
     if (F->last_slot >= 0 && F->slot[F->last_slot].h_info[0].carry_len) { set_error("the BAM ends inside a record (truncated file)"); return STRL_ERR_FORMAT; }
-    // one stable sort of the runs by (tid, bin), the second merge, the chunks to the host
-    const uint32_t n = (uint32_t)B->n_runs;
-    std::vector<BaiChunk> ch;
-    if (n) {
-      int bits = 17;
-      while (bits < 48 && ((uint64_t)B->n_ref >> (bits - 16))) ++bits;
-      const size_t sb = radix_sort_scratch_bytes(n, bits);
-      const uint32_t nblk = (n + 255u) / 256u;
-      DevBuf k0, k1, v0, v1, sc, out;
-      if ((rc = k0.reserve((size_t)n * 8)) || (rc = k1.reserve((size_t)n * 8)) || (rc = v0.reserve((size_t)n * 4)) || (rc = v1.reserve((size_t)n * 4)) || (rc = sc.reserve(sb)) ||
-          (rc = out.reserve((size_t)n * sizeof(BaiChunk))) || (rc = B->flag.reserve((size_t)n + 64)) || (rc = B->blk_cnt.reserve((size_t)nblk * 4 + 64)))
-        return rc;
-      BaiState *S = B->state.as<BaiState>();
-      hipLaunchKernelGGL(bai_keys_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), n, S, B->par, k0.as<uint64_t>(), v0.as<uint32_t>());
-      uint32_t *d_n = &S->n_heads;                         // (the device-side count the sort reads)
-      hipError_t e = hipMemcpyAsync(d_n, &n, 4, hipMemcpyHostToDevice, st);
-      uint64_t *ok = nullptr;
-      uint32_t *ov = nullptr;
-      int se = 0;
-      if (e == hipSuccess) se = radix_sort_pairs(st, d_n, n, k0.as<uint64_t>(), v0.as<uint32_t>(), k1.as<uint64_t>(), v1.as<uint32_t>(), sc.p, sb, 0, bits, &ok, &ov);
-      if (e == hipSuccess && !se) {
-        hipLaunchKernelGGL(bai_merge_flag_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), ok, ov, n, B->flag.as<uint8_t>(), B->blk_cnt.as<uint32_t>());
-        hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, B->blk_cnt.as<uint32_t>(), nblk, d_n);
-        hipLaunchKernelGGL(bai_merge_emit_kernel, dim3(nblk), dim3(256), 0, st, B->runs.as<BaiRun>(), ok, ov, n, B->flag.as<uint8_t>(), B->blk_cnt.as<uint32_t>(), d_n, out.as<BaiChunk>());
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) {
-          ch.resize(B->h_state->n_heads);
-          if (!ch.empty()) e = hipMemcpy(ch.data(), out.p, ch.size() * sizeof(BaiChunk), hipMemcpyDeviceToHost);
-        }
-      }
-      if (se) { set_error("radix_sort_pairs failed: %s", hipGetErrorString((hipError_t)se)); return STRL_ERR_HIP; }
-      if (e != hipSuccess) { set_error("strl_bamindex_finish: %s", hipGetErrorString(e)); return STRL_ERR_HIP; }
-    } else {
-      STRL_HIP(hipMemcpy(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost));
-    }
-    const size_t nr = (size_t)B->n_ref, nw = (size_t)B->win_off[nr];
-    std::vector<uint64_t> lin(nw), rb(nr), re(nr), cnt(2 * nr);
-    if (nw) STRL_HIP(hipMemcpy(lin.data(), B->lin.p, nw * 8, hipMemcpyDeviceToHost));
-    if (nr) {
-      STRL_HIP(hipMemcpy(rb.data(), B->ref_beg.p, nr * 8, hipMemcpyDeviceToHost));
-      STRL_HIP(hipMemcpy(re.data(), B->ref_end.p, nr * 8, hipMemcpyDeviceToHost));
-      STRL_HIP(hipMemcpy(cnt.data(), B->ref_cnt.p, nr * 16, hipMemcpyDeviceToHost));
-    }
-    // the bytes (SAM spec 5.2): per reference the bins ascending with their chunks, the pseudo-bin last, the linear index up to
-    // the last window touched (empty windows 0), n_no_coor at the end
-    std::vector<uint8_t> &o = B->bytes;
-    o.clear();
-    o.reserve(8 + ch.size() * 24 + nw * 8 + nr * 64 + 8);
-    o.insert(o.end(), {'B', 'A', 'I', 1});
-    put32(o, (uint32_t)B->n_ref);
-    size_t at = 0;
-    uint64_t n_chunks = 0;
-    for (size_t t = 0; t < nr; ++t) {
-      size_t e = at, n_bin = 0;
-      while (e < ch.size() && (ch[e].key >> 16) == t) { if (e == at || ch[e].key != ch[e - 1].key) ++n_bin; ++e; }
-      const bool meta = cnt[2 * t] + cnt[2 * t + 1] != 0;
-      put32(o, (uint32_t)(n_bin + (meta ? 1 : 0)));
-      for (size_t a = at; a < e;) {
-        size_t b = a;
-        while (b < e && ch[b].key == ch[a].key) ++b;
-        put32(o, (uint32_t)(ch[a].key & 0xffffu));
-        put32(o, (uint32_t)(b - a));
-        for (size_t k = a; k < b; ++k) { put64(o, ch[k].beg_v); put64(o, ch[k].end_v); }
-        n_chunks += b - a;
-        a = b;
-      }
-      if (meta) { put32(o, BAI_META_BIN); put32(o, 2); put64(o, rb[t]); put64(o, re[t]); put64(o, cnt[2 * t]); put64(o, cnt[2 * t + 1]); }
-      const uint64_t w0 = B->win_off[t], w1 = B->win_off[t + 1];
-      uint64_t n_intv = 0;
-      for (uint64_t w = w1; w > w0; --w) if (lin[(size_t)w - 1] != ~0ull) { n_intv = w - w0; break; }
-      put32(o, (uint32_t)n_intv);
-      for (uint64_t w = 0; w < n_intv; ++w) { const uint64_t v = lin[(size_t)(w0 + w)]; put64(o, v == ~0ull ? 0 : v); }
-      at = e;
-    }
-    put64(o, B->h_state->n_no_coor);
-    B->n_chunks = n_chunks;
-    B->finished = true;
+    if ((rc = bai_sort_and_pack(c, B))) return rc;
+  }
+  if (bai_bytes) *bai_bytes = B->bytes.size();
+  if (info) { info->n_records = B->n_records; info->n_no_coor = B->h_state->n_no_coor; info->n_runs = B->n_runs; info->n_chunks = B->n_chunks; }
+  return STRL_OK;
+}
+
+// ---- the index as a by-product of `strling extract`'s own pass ----
+// The builder hangs off a context whose front end strl_front_begin started.  Per chunk the front end calls bai_front_chunk where
+// the chunk is handed over (the block table) and bai_front_index behind its parse (the kernels).  Neither waits for the device
+// and neither can fail the extraction: what goes wrong ends the index and is reported by strl_front_index_finish.
+static void bai_fail(strl_bai *B, int rc, const char *msg) {
+  if (B->fail.empty()) { B->fail_rc = rc; B->fail = msg; }
+}
+// room for `bytes` in a chunk-temporary table without freeing what kernels in flight may still read (a free waits for the device)
+static int bai_room(strl_bai *B, DevBuf &b, size_t bytes) {
+  if (b.p && b.cap >= bytes) return STRL_OK;
+  DevBuf nb;
+  const int rc = nb.reserve(bytes + bytes / 4 + 4096);
+  if (rc) return rc;
+  if (b.p) B->trash.push_back(std::move(b));
+  b = std::move(nb);
+  return STRL_OK;
+}
+
+extern "C" int strl_front_index_begin(strl_ctx *c, const int32_t *l_ref, uint64_t runs0) {
+  if (!c || !c->front || !c->x_open || !c->x_front) { set_error("strl_front_index_begin without strl_front_begin"); return STRL_ERR_ARG; }
+  strl_front *F = c->front;
+  if (F->n_ref && !l_ref) { set_error("strl_front_index_begin: bad argument"); return STRL_ERR_ARG; }
+  if (F->chunks || F->not_first || F->next_trim || F->slot[0].staged || F->slot[1].staged) {
+    set_error("strl_front_index_begin: the context must get the whole file from its first block (no chunk handed over yet, no share)");
+    return STRL_ERR_ARG;
+  }
+  STRL_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = bai_setup(c, (int32_t)F->n_ref, l_ref))) return rc;
+  strl_bai *B = c->bai;
+  B->attached = true;
+  B->run_cap = std::max<uint64_t>(runs0 ? runs0 : (1ull << 20), 16);
+  if ((rc = B->runs.reserve((size_t)B->run_cap * sizeof(BaiRun)))) return rc;
+  STRL_HIP(hipHostMalloc(reinterpret_cast<void **>(&B->h_snap), sizeof(BaiState), hipHostMallocDefault));
+  STRL_HIP(hipEventCreateWithFlags(&B->ev_snap, hipEventDisableTiming));
+  return STRL_OK;
+}
+
+extern "C" int strl_front_index_blocks(strl_ctx *c, const uint64_t *block_off, uint64_t end_off, uint32_t n_blocks) {
+  if (!c || !c->bai || !c->bai->attached || !c->front || c->bai->finished || !n_blocks || !block_off) {
+    set_error("strl_front_index_blocks: bad argument / no strl_front_index_begin");
+    return STRL_ERR_ARG;
+  }
+  strl_bai *B = c->bai;
+  int rc;
+  if (!B->fail.empty()) return STRL_OK;          // (the index has ended; strl_front_index_finish says why)
+  if ((rc = bai_check_blocks("strl_front_index_blocks", B->want_end, block_off, end_off, nullptr, n_blocks))) return rc;
+  if (B->want.size() >= 4) { set_error("strl_front_index_blocks: the offsets of four chunks are waiting for their chunks"); return STRL_ERR_ARG; }
+  B->want.push_back(strl_bai::Offsets{std::vector<uint64_t>(block_off, block_off + n_blocks), end_off});
+  B->want_end = end_off;
+  return STRL_OK;
+}
+
+// a chunk has been handed over to slot si (its record scan is queued; the slot's previous chunk has completed): its block table
+void strl::bai_front_chunk(strl_ctx *c, int si, const uint32_t *isize, uint32_t n_blocks, bool whole_file) {
+  strl_bai *B = c->bai;
+  if (!B || !B->attached || B->finished || !B->fail.empty()) return;
+  B->have_table[si] = false;
+  if (!whole_file) return bai_fail(B, STRL_ERR_ARG, "the context does not get the whole file (a share, or chunks in turn over several contexts): no index");
+  if (B->want.empty()) return bai_fail(B, STRL_ERR_ARG, "a chunk was handed over without its block offsets (strl_front_index_blocks)");
+  const strl_bai::Offsets W = std::move(B->want.front());
+  B->want.pop_front();
+  if (W.block_off.size() != n_blocks) return bai_fail(B, STRL_ERR_ARG, "strl_front_index_blocks named another number of blocks than the chunk handed over has");
+  for (uint32_t i = 0; i < n_blocks; ++i)
+    if (isize[i] > 65536u || !isize[i]) return bai_fail(B, STRL_ERR_ARG, "a block's ISIZE is outside [1, 65536]");
+  if (bai_block_table(B, si, W.block_off.data(), W.end_off, isize, n_blocks)) return bai_fail(B, STRL_ERR_HIP, strl_last_error());
+  B->have_table[si] = true;
+}
+
+// behind the parse of the chunk in slot si, on the context's stream: per-record step over the parse's columns, scan, emit, and a
+// copy of the state words that is looked at when a later chunk comes by.  The table holds every run the chunks not yet
+// accounted for can start (a chunk of n records starts at most n), so the emit kernel stays inside it whatever the counts are.
+void strl::bai_front_index(strl_ctx *c, strl_front *F, int si, const FrontInfo &I, const int32_t *tid, const int32_t *pos, const int32_t *end, const uint32_t *fragw) {
+  strl_bai *B = c->bai;
+  if (!B || !B->attached || B->finished || !B->fail.empty()) return;
+  hipStream_t st = c->stream;
+  if (B->snap_flying) {                          // a look, not a wait
+    if (hipEventQuery(B->ev_snap) != hipSuccess) (void)hipGetLastError();        // (not ready: not an error to find behind the next launch)
+    else B->snap_flying = false;
+  }
+  if (!B->snap_flying && B->snap_at > B->known_at) {
+    B->known_runs = B->h_snap->run_total; B->known_at = B->snap_at;
+    for (uint64_t eo : B->h_snap->err_ord) if (eo != ~0ull) B->refusal_seen = true;
+  }
+  if (B->refusal_seen) return;                   // (what it is: strl_front_index_finish, from the state words)
+  if (!B->have_table[si]) return bai_fail(B, STRL_ERR_ARG, "a chunk was handed over without its block offsets (strl_front_index_blocks)");
+  B->have_table[si] = false;
+  const uint32_t n = I.n_records;
+  if (!n) return;
+  FrontSlot &S = F->slot[si];
+  const uint32_t nblk = (n + 255u) / 256u, m = B->vm[si];
+  const uint64_t before = B->known_runs + (B->n_records - B->known_at), need = before + n;
+  auto hip_fail = [&](hipError_t e) { bai_fail(B, STRL_ERR_HIP, hipGetErrorString(e)); };
+  hipError_t e;
+  if (need > B->run_cap) {
+    const uint64_t cap = std::max<uint64_t>(need + need / 2, 2 * B->run_cap);
+    DevBuf nb;
+    if (nb.reserve((size_t)cap * sizeof(BaiRun))) return bai_fail(B, STRL_ERR_NOMEM, strl_last_error());
+    const uint64_t keep = std::min(before, B->run_cap);
+    if (keep && (e = hipMemcpyAsync(nb.p, B->runs.p, (size_t)keep * sizeof(BaiRun), hipMemcpyDeviceToDevice, st)) != hipSuccess) return hip_fail(e);
+    B->trash.push_back(std::move(B->runs));
+    B->runs = std::move(nb);
+    B->run_cap = cap;
+  }
+  const size_t rec_room = std::max<size_t>(n, S.recoff.cap / 4);        // (what the slot's record table holds: later chunks do not reallocate)
+  if (bai_room(B, B->flag, rec_room + 64) || bai_room(B, B->blk_cnt, (rec_room / 256 + 2) * 4 + 64) || bai_room(B, B->vt[si], (size_t)(m + 1) * 16))
+    return bai_fail(B, STRL_ERR_NOMEM, strl_last_error());
+  if ((e = hipMemcpyAsync(B->vt[si].p, B->h_vt[si], (size_t)(m + 1) * 16, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e);
+  BaiPush P{};
+  P.U = S.infl.as<uint8_t>(); P.recoff = S.recoff.as<uint32_t>(); P.n = n;
+  P.vrel = B->vt[si].as<int64_t>(); P.vfoff = B->vt[si].as<uint64_t>() + (m + 1); P.vm = m;
+  P.abs0 = B->abs0[si]; P.ord0 = B->n_records;
+  P.n_ref = B->n_ref; P.win_off = B->d_winoff.as<uint64_t>();
+  P.lin = B->lin.as<uint64_t>(); P.ref_beg = B->ref_beg.as<uint64_t>(); P.ref_end = B->ref_end.as<uint64_t>(); P.ref_cnt = B->ref_cnt.as<uint64_t>();
+  P.S = B->state.as<BaiState>(); P.par = B->par; P.flag = B->flag.as<uint8_t>(); P.blk_cnt = B->blk_cnt.as<uint32_t>();
+  P.runs = B->runs.as<BaiRun>(); P.run_base = 0; P.run_acc = &P.S->run_base; P.run_cap = B->run_cap;
+  P.C = BaiCols{tid, pos, end, fragw, I.carry_off};
+  // STRL_BAI_RECORDS=1 (measurements): the record-reading form of the per-record step, as `strling bamindex` runs it
+  static const bool from_records = getenv("STRL_BAI_RECORDS") != nullptr;
+  if (from_records) hipLaunchKernelGGL(bai_record_kernel, dim3(nblk), dim3(256), 0, st, P);
+  else hipLaunchKernelGGL(bai_record_cols_kernel, dim3(nblk), dim3(256), 0, st, P);
+  hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, P.blk_cnt, nblk, &P.S->n_heads, &P.S->run_base);
+  if (from_records) hipLaunchKernelGGL(bai_emit_kernel, dim3(nblk), dim3(256), 0, st, P);
+  else hipLaunchKernelGGL(bai_emit_cols_kernel, dim3(nblk), dim3(256), 0, st, P);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e);
+  B->n_records += n;
+  B->par ^= 1u;
+  if (!B->snap_flying) {
+    if ((e = hipMemcpyAsync(B->h_snap, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipEventRecord(B->ev_snap, st)) != hipSuccess) return hip_fail(e);
+    B->snap_flying = true;
+    B->snap_at = B->n_records;
+  }
+}
+
+extern "C" int strl_front_index_finish(strl_ctx *c, uint64_t *bai_bytes, strl_bamindex_info *info) {
+  if (!c || !c->bai || !c->bai->attached || !c->front) { set_error("strl_front_index_finish without strl_front_index_begin"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  strl_front *F = c->front;
+  strl_bai *B = c->bai;
+  int rc;
+  if (!B->finished) {
+    if (F->b_issued < F->chunks) { set_error("strl_front_index_finish before strl_front_finish"); return STRL_ERR_ARG; }
+    if (!B->fail.empty()) { set_error("%s", B->fail.c_str()); return B->fail_rc; }
+    STRL_HIP(hipStreamSynchronize(c->stream));
+    B->snap_flying = false;
+    STRL_HIP(hipMemcpy(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost));
+    if ((rc = bai_refuse(B, *B->h_state))) { bai_fail(B, rc, strl_last_error()); return rc; }
+    if (B->h_state->overflow) { bai_fail(B, STRL_ERR_CAPACITY, "the run table was outgrown (internal error)"); set_error("%s", B->fail.c_str()); return B->fail_rc; }
+    if (B->h_state->run_total > 0x7ffffff0ull) { set_error("more than 2^31 runs of equal (reference, bin): beyond one device sort"); bai_fail(B, STRL_ERR_LIMIT, strl_last_error()); return STRL_ERR_LIMIT; }
+    if (F->last_slot >= 0 && F->slot[F->last_slot].h_info[0].carry_len) { set_error("the BAM ends inside a record (truncated file)"); bai_fail(B, STRL_ERR_FORMAT, strl_last_error()); return STRL_ERR_FORMAT; }
+    B->n_runs = B->h_state->run_total;
+    if ((rc = bai_sort_and_pack(c, B))) return rc;
   }
   if (bai_bytes) *bai_bytes = B->bytes.size();
   if (info) { info->n_records = B->n_records; info->n_no_coor = B->h_state->n_no_coor; info->n_runs = B->n_runs; info->n_chunks = B->n_chunks; }

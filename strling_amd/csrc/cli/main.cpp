@@ -327,6 +327,7 @@ static void setup_genome(strl_ctx *ctx, const Args &a, const std::vector<BamTarg
 }
 
 static int extract_front(const Args &a, const std::string &bam, const std::string &bin, double p, uint8_t min_mapq, bool verbose);
+static bool g_index_done = false;      // extract --write-index: the index of the first pass has been written or refused; a repeated extraction leaves it alone
 constexpr int EXTRACT_AGAIN_ON_HOST = -77, EXTRACT_AGAIN_HOST_FRONT = -78, EXTRACT_AGAIN_BY_CHUNKS = -79;
 
 static int extract_main(int argc, char **argv) {
@@ -338,11 +339,24 @@ static int extract_main(int argc, char **argv) {
       "  -q, --min-mapq=MIN_MAPQ    minimum mapping quality (does not apply to STR reads) (default: 40)\n"
       "  --gpus=N                   spread the file over N GPUs (a contiguous share each: inflate, parse and scoring there; the pair logic on the first) (default: 1)\n"
       "  --device=K                 the GPU this process uses (the first of --gpus N) (default: 0; STRL_DEVICE)\n"
+      "  --write-index              also write the bam's index (.bai), built on the GPU in the same pass over the file (one GPU, BAM only)\n"
+      "  --index-out=OUT.bai        where --write-index writes it (default: <bam>.bai)\n"
       "  -v, --verbose\n  -h, --help                 Show this help\n";
   if (argc <= 2) { fputs(usage, stdout); return 0; }
   const Args a = parse(argc, argv, 2, {{"fasta", 'f', true}, {"genome-repeats", 'g', true}, {"proportion-repeat", 'p', true},
-                                       {"min-mapq", 'q', true}, {"verbose", 'v', false}, {"batch", 'B', true}, {"gpus", 'G', true}, {"device", 'D', true}}, usage);
+                                       {"min-mapq", 'q', true}, {"verbose", 'v', false}, {"batch", 'B', true}, {"gpus", 'G', true}, {"device", 'D', true},
+                                       {"write-index", 0, false}, {"index-out", 0, true}}, usage);
   if (a.pos.size() != 2) quit("expected 2 arguments (bam, bin)\n%s", usage);
+  if (a.flag("index-out") && !a.flag("write-index")) quit("--index-out needs --write-index\n%s", usage);
+  if (a.flag("write-index")) {       // what cannot build the index is refused before anything is read
+    const char *fe = getenv("STRL_FRONT"), *pe = getenv("STRL_PAIR");
+    if (atoi(a.get("gpus", "1").c_str()) > 1)
+      quit("[strling] extract: --write-index cannot be combined with --gpus N: the contexts' shares of the file are cut at record starts that an index names, so they "
+           "need the index beforehand (run `strling bamindex` first, or extract on one GPU)");
+    if (CramFile::is_cram(a.pos[0])) quit("[strling] extract: --write-index: %s is a CRAM; its index (.crai) is out of scope: this flag writes the .bai of a BAM", a.pos[0].c_str());
+    if ((fe && strcmp(fe, "host") == 0) || (pe && strcmp(pe, "host") == 0))
+      quit("[strling] extract: --write-index needs the device front end, which is what builds the index: not with STRL_FRONT=host / STRL_PAIR=host");
+  }
   set_device0(a.get("device", ""));
   const std::string bam = a.pos[0], bin = a.pos[1];
   const double p = atof(a.get("proportion-repeat", "0.8").c_str());
@@ -661,6 +675,16 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   }
   const size_t chunk_blocks = env_blocks && atoi(env_blocks) > 0 ? (size_t)atoi(env_blocks) : auto_blocks;
   const size_t chunk_bytes = std::max<size_t>((size_t)1 << 20, chunk_blocks * 20000);       // compressed bytes one chunk may span
+  // --write-index: the .bai as a by-product of this pass (strl_front_index_*).  Whatever goes wrong with it is one line on stderr
+  // and no index; the extraction goes on as without the flag.
+  const std::string index_out = a.get("index-out", (bam + ".bai").c_str());
+  std::atomic<bool> idx_on{a.flag("write-index") && !g_index_done && G == 1};      // (read by the thread that stages the chunks ahead)
+  auto idx_give_up = [&](const std::string &why) {
+    if (!idx_on) return;
+    fprintf(stderr, "[strling] index not written: %s\n", why.c_str());
+    idx_on = false; g_index_done = true;
+  };
+  std::vector<uint64_t> boff_ring[3];           // file offsets of the blocks of the chunk in ring[c % 3]
   std::vector<strl_ctx *> ctxs((size_t)G, nullptr);
   std::vector<int> ctx_rc((size_t)G, 0);
   std::vector<std::string> ctx_err((size_t)G);
@@ -853,6 +877,11 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   };
   { const int br = bring_up_finish(); if (br) return br; }
   strl_ctx *ctx = ctxs[0];
+  if (idx_on) {
+    std::vector<int32_t> l_ref;
+    for (const BamTarget &t : feed.targets()) l_ref.push_back((int32_t)std::min<uint64_t>(t.length, 0x7fffffffu));
+    if (strl_front_index_begin(ctx, l_ref.data(), 0)) idx_give_up(strl_last_error());
+  }
   if (verbose) {
     std::string devs;
     for (int g = 0; g < G; ++g) devs += (g ? " " : "") + std::to_string(device_of(g));
@@ -895,6 +924,7 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   // a file the device front end refuses (STRL_ERR_FORMAT) goes to the host reader instead of ending the run
   auto give_up_front = [&]() -> int {
     fprintf(stderr, "[strling] %s: repeating the extraction with the host reader\n", strl_last_error());
+    idx_give_up("the device front end gave the file up, and it is what builds the index");
     if (ahead.joinable()) ahead.join();
     if (frag_thread.joinable()) frag_thread.join();
     for (size_t k = 0; k < pin.size(); ++k) { strl_pinned_free(pin[k]); strl_pinned_free(pin_meta[k]); }
@@ -906,6 +936,7 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   // read on the device
   auto over_limit = [&]() -> int {
     fprintf(stderr, "[strling] %s: repeating the extraction with the host pair logic\n", strl_last_error());
+    idx_give_up("the pass over the file was given up before its end");
     if (ahead.joinable()) ahead.join();
     if (frag_thread.joinable()) frag_thread.join();
     for (size_t k = 0; k < pin.size(); ++k) { strl_pinned_free(pin[k]); strl_pinned_free(pin_meta[k]); }
@@ -955,6 +986,7 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   struct Staged {
     int64_t nb = 0;
     size_t lo = 0, hi = 0, slot = 0;
+    uint64_t ci = 0;
     int g = 0;
     std::string err;
     bool short_read = false;
@@ -969,7 +1001,13 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
     if (S.nb <= 0) return;
     const auto tb = now();
     S.g = (int)(ci % (uint64_t)G);
+    S.ci = ci;
     S.lo = blks.front().c_off; S.hi = blks.back().c_off + blks.back().clen;
+    if (idx_on) {        // a block starts at its gzip header; CRC-32 and ISIZE close the last one
+      std::vector<uint64_t> &bo = boff_ring[ci % 3];
+      bo.resize((size_t)S.nb);
+      for (size_t k = 0; k < (size_t)S.nb; ++k) bo[k] = blks[k].c_off - blks[k].hdr;
+    }
     S.slot = RING * (size_t)S.g + (size_t)(staged[(size_t)S.g]++ % RING);
     uint8_t *dst = pin[S.slot];
     const size_t lo = S.lo, hi = S.hi, piece = (size_t)4 << 20, pieces = (hi - lo + piece - 1) / piece;
@@ -983,6 +1021,7 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
     t_walk += secs(ta, tb); t_copy += secs(tb, now());
   };
   auto queue_copy = [&](const Staged &S) -> int {     // the chunk's copy to the device, ahead of its turn
+    if (idx_on && strl_front_index_blocks(ctxs[(size_t)S.g], boff_ring[S.ci % 3].data(), S.hi + 8, (uint32_t)S.nb)) idx_give_up(strl_last_error());
     uint64_t *ncoff = reinterpret_cast<uint64_t *>(pin_meta[S.slot]);
     uint32_t *nclen = reinterpret_cast<uint32_t *>(ncoff + chunk_blocks), *nisz = nclen + chunk_blocks, *ncrc = nisz + chunk_blocks;
     return strl_front_stage(ctxs[(size_t)S.g], pin[S.slot], S.hi - S.lo, ncoff, nclen, nisz, ncrc, (uint32_t)S.nb);
@@ -1206,6 +1245,32 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   }
   account();
   }   // (chunk by chunk)
+  if (idx_on) {
+    // every chunk has been through: the runs are sorted and merged and the bytes written now, so that an extraction that is
+    // repeated with the host pair logic below still leaves its index
+    const auto ti0 = now();
+    uint64_t nbytes = 0;
+    strl_bamindex_info info;
+    std::vector<uint8_t> bytes;
+    int irc = strl_front_index_finish(ctx, &nbytes, &info);
+    if (!irc) { bytes.resize((size_t)nbytes + 1); irc = strl_bamindex_fetch(ctx, bytes.data(), bytes.size()); }
+    if (irc) idx_give_up(strl_last_error());
+    else {
+      const std::string tmp = index_out + ".tmp." + std::to_string((long long)getpid());
+      FILE *f = fopen(tmp.c_str(), "wb");
+      const bool wrote = f && fwrite(bytes.data(), 1, (size_t)nbytes, f) == (size_t)nbytes;
+      const bool closed = f && fclose(f) == 0;
+      if (!wrote || !closed || rename(tmp.c_str(), index_out.c_str()) != 0) {
+        const std::string why = "cannot write " + (f ? index_out : tmp) + ": " + strerror(errno);
+        if (f) (void)unlink(tmp.c_str());
+        idx_give_up(why);
+      } else if (verbose)
+        fprintf(stderr, "[strling] index: %llu records (%llu without a reference), %llu runs resident on the device, %llu chunks, %llu bytes -> %s (sort, merge and write %.3f s)\n",
+                (unsigned long long)info.n_records, (unsigned long long)info.n_no_coor, (unsigned long long)info.n_runs, (unsigned long long)info.n_chunks,
+                (unsigned long long)nbytes, index_out.c_str(), secs(ti0, now()));
+    }
+    idx_on = false; g_index_done = true;
+  }
   const auto tf2 = now();
   if (G > 1) {
     std::vector<uint64_t> recs(summary.size());

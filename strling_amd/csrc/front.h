@@ -161,5 +161,11 @@ size_t front_name_tiles(uint32_t cap);      // words of d_tile_sums for `cap` na
 void front_destroy(strl_front *F);
 int front_init_slots(strl_ctx *c, strl_front *F);
 int front_begin_scan(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset);   // the front end without strl_front_begin's per-read state (bamindex.hip)
+// bamindex.hip: the index builder behind strl_front_begin's own pass (strl_front_index_*); no-ops without one.  Neither waits
+// for the device, neither can fail the extraction.
+//   bai_front_chunk   a chunk has been handed over to slot si: its block table (whole_file: no other context took the chunk before)
+//   bai_front_index   behind the parse of the chunk in slot si, on the context's stream: the index kernels over the parse's columns
+void bai_front_chunk(strl_ctx *c, int si, const uint32_t *isize, uint32_t n_blocks, bool whole_file);
+void bai_front_index(strl_ctx *c, strl_front *F, int si, const FrontInfo &I, const int32_t *tid, const int32_t *pos, const int32_t *end, const uint32_t *fragw);
 
 }  // namespace strl

@@ -90,6 +90,7 @@ static int front_stage_b(strl_ctx *c, strl::strl_front *F, int si) {
   // same stream, so the parse queues behind it.)
   if ((rc = front_parse(c, F, si, (uint32_t)n, o, c->stream))) return rc;
   F->qarena_used += I.qname_bytes;
+  if (c->bai) bai_front_index(c, F, si, I, o.tid, o.pos, o.end, o.fragw);       // extract --write-index: the columns just written are its input
   if (n) {
     strl_read_soa d{};
     d.n = n; d.tid = o.tid; d.pos = o.pos; d.end = o.end; d.seq_off = o.seq_off; d.l_seq = o.l_seq; d.clip_l = o.clip_l; d.clip_r = o.clip_r;
@@ -177,6 +178,7 @@ int strl_front_begin(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset, u
     if (c->front->st_a) (void)hipStreamSynchronize(c->front->st_a);
     strl::front_destroy(c->front); c->front = nullptr;
   }
+  if (c->bai) { strl::bai_destroy(c->bai); c->bai = nullptr; }       // (a builder of the previous pass: everything it had in flight has completed)
   strl::strl_front *F = new strl::strl_front();
   c->front = F;
   c->x_front = true;
@@ -310,6 +312,7 @@ int strl_front_enqueue_after(strl_ctx *c, strl_ctx *prev, const uint8_t *comp, u
     if ((rc = front_fill_done(c, F->slot[si], done))) return rc;
     if (n_done) *n_done = 1;
   }
+  if (c->bai) strl::bai_front_chunk(c, si, isize, n_blocks, !prev && !F->not_first && !F->slot[si].staged_trim);
   ++F->chunks;
   F->comp_total += comp_bytes;
   F->infl_total += F->slot[si].infl_bytes;
