@@ -703,8 +703,22 @@ void strl_pinned_free(void *p);
  *                         samtools' file is not claimed (a chunk that ends at the end of a block may name it either way).
  * Refused, never indexed wrongly: STRL_ERR_FORMAT a file that is not coordinate sorted (the message names the record), a record
  * that reaches more than 1 Mbase past its reference's l_ref or has a refID outside the header, a malformed record, invalid DEFLATE data, a file
- * that ends inside a record; STRL_ERR_LIMIT a position or end >= 2^29 (a .bai cannot hold it; CSI is not written);
- * STRL_ERR_CRC; STRL_ERR_NOMEM. */
+ * that ends inside a record; STRL_ERR_LIMIT a position or end >= 2^29 (a .bai cannot hold it; strl_bamindex_begin_csi can);
+ * STRL_ERR_CRC; STRL_ERR_NOMEM.
+ *
+ * CSI (CSIv1): the same builder with the binning scheme as a parameter -- windows of 2^min_shift bases and `depth` levels of bins
+ * below bin 0; a .bai is the scheme (14, 5).  strl_bamindex_begin_csi instead of strl_bamindex_begin, everything else as above:
+ *   min_shift             in [8, 24]
+ *   depth                 in [0, 8]; < 0: samtools' rule, the smallest depth with 2^(min_shift + 3 depth) >= max(l_ref) + 256.
+ *                         Anything else is STRL_ERR_ARG with a message (window tables and bin numbers stay small).
+ *   strl_bamindex_fetch   then gives the UNCOMPRESSED CSI payload: magic CSI\1, min_shift, depth, l_aux = 0, n_ref; per reference
+ *                         n_bin and per bin { bin u32, loffset u64, n_chunk i32, (beg, end) u64 x n_chunk }, bins ascending, the
+ *                         pseudo-bin (8^(depth + 1) - 1) / 7 + 1 last with loffset 0; n_no_coor u64.  loffset = the scheme's linear
+ *                         index at the bin's first window, empty windows filled from the next filled one (0 behind the last).
+ *                         A .csi FILE is that payload in BGZF blocks: this library links nothing but the HIP runtime, so the
+ *                         BGZF wrapping is the caller's job (the CLI's write_bgzf, bamio.write_csi).
+ * STRL_ERR_LIMIT then is an end > min(2^(min_shift + 3 depth), 2^31 - 2): BAM positions are 32-bit and an end that left them is
+ * clamped to 2^31 - 1, which is refused, not indexed. */
 typedef struct {
   uint64_t n_records;  /* records of the file */
   uint64_t n_no_coor;  /* those without a reference (the index's last word) */
@@ -712,6 +726,7 @@ typedef struct {
   uint64_t n_chunks;   /* chunks written to the bins (runs merged again behind the sort) */
 } strl_bamindex_info;
 int strl_bamindex_begin(strl_ctx *ctx, int32_t n_ref, const int32_t *l_ref, uint64_t first_record_offset);
+int strl_bamindex_begin_csi(strl_ctx *ctx, int32_t n_ref, const int32_t *l_ref, uint64_t first_record_offset, int32_t min_shift, int32_t depth);
 int strl_bamindex_reserve(strl_ctx *ctx, uint32_t max_blocks, uint64_t max_comp_bytes);
 int strl_bamindex_push(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
                        const uint32_t *crc32, const uint64_t *block_off, uint64_t end_off, uint32_t n_blocks);
@@ -741,8 +756,11 @@ int strl_bamindex_end(strl_ctx *ctx);
  *   strl_front_index_finish  after strl_front_finish, before or after strl_extract_finish: the refusals of strl_bamindex_* with
  *                            the same codes and messages (record ordinal included), else sort, merge and serialization as
  *                            strl_bamindex_finish.  The bytes come out through strl_bamindex_fetch; strl_bamindex_end or the
- *                            next strl_front_begin frees the builder. */
+ *                            next strl_front_begin frees the builder.
+ *   strl_front_index_begin_csi  strl_front_index_begin with a CSI scheme (min_shift, depth as strl_bamindex_begin_csi): _finish and
+ *                            _fetch then give the uncompressed CSI payload. */
 int strl_front_index_begin(strl_ctx *ctx, const int32_t *l_ref, uint64_t runs0);
+int strl_front_index_begin_csi(strl_ctx *ctx, const int32_t *l_ref, uint64_t runs0, int32_t min_shift, int32_t depth);
 int strl_front_index_blocks(strl_ctx *ctx, const uint64_t *block_off, uint64_t end_off, uint32_t n_blocks);
 int strl_front_index_finish(strl_ctx *ctx, uint64_t *bai_bytes, strl_bamindex_info *info);
 

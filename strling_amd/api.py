@@ -134,7 +134,7 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_calls_finish", "strl_unplaced_order", "strl_call_row", "strl_canonical_repeat", "strl_assign_reads_loci", "strl_group_order",
            "strl_extract_device", "strl_treads_fetch", "strl_ctx_pair_times", "strl_sort_pairs", "strl_cluster_resident", "strl_ctx_cluster_times", "strl_pair_rows", "strl_extract_begin", "strl_extract_add", "strl_extract_finish", "strl_pair_rule", "strl_bounds_bare", "strl_ctx_treads_device", "strl_cluster_gathered", "strl_inflate_blocks", "strl_ctx_inflate_ms", "strl_regions_fetch", "strl_evidence_records", "strl_regions_evidence", "strl_front_begin", "strl_front_push", "strl_front_push_after", "strl_front_reserve", "strl_front_stage", "strl_front_enqueue_after", "strl_front_collect", "strl_ctxs_extract_gather", "strl_front_finish", "strl_front_fragwords", "strl_front_fragwords_async", "strl_event_wait", "strl_front_records", "strl_front_tids", "strl_front_qnames", "strl_front_treads_named", "strl_pinned_alloc", "strl_pinned_free", "strl_comm_unique_id", "strl_ctx_comm_init", "strl_ctxs_comm_init", "strl_ctx_comm_info", "strl_cluster_exchange", "strl_ctxs_cluster_exchange", "strl_exchange_treads", "strl_ctx_set_treads", "strl_cluster_collect", "strl_ctx_tail_stream", "strl_ctx_mem_info", "strl_bin_peek", "strl_front_trim_next", "strl_front_tail_bytes", "strl_ctx_blocking_waits", "strl_score_read_host", "strl_front_end",
            "strl_bamindex_begin", "strl_bamindex_reserve", "strl_bamindex_push", "strl_bamindex_finish", "strl_bamindex_fetch", "strl_bamindex_end",
-           "strl_front_index_begin", "strl_front_index_blocks", "strl_front_index_finish",
+           "strl_front_index_begin", "strl_front_index_blocks", "strl_front_index_finish", "strl_bamindex_begin_csi", "strl_front_index_begin_csi",
            "strl_pull_select", "strl_pull_mates", "strl_pull_select_host", "strl_pull_counts_host", "strl_pull_mates_host", "strl_pull_order"]
 
 
@@ -251,6 +251,8 @@ def load(build_if_missing=True):
     L.strl_bamindex_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.strl_bamindex_end.argtypes = [C.c_void_p]
     L.strl_front_index_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_bamindex_begin_csi.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32]
+    L.strl_front_index_begin_csi.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32]
     L.strl_front_index_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
     L.strl_front_index_finish.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(BamindexInfo)]
     L.strl_pinned_alloc.argtypes = [C.c_uint64]
@@ -877,15 +879,19 @@ class Context:
         chunks = self._front_push_blocks(B, B["b0"], len(B["blocks"]), chunk_blocks, check_crc)
         return self._front_results(B, chunks)
 
-    def extract_bam_device_indexed(self, path, chunk_blocks=16384, runs0=0, n_reads_hint=0, check_crc=True, no_offsets_at=None):
+    def extract_bam_device_indexed(self, path, chunk_blocks=16384, runs0=0, n_reads_hint=0, check_crc=True, no_offsets_at=None, csi=None):
         """extract_bam_device with the .bai built in the same pass (strl_front_index_begin / _blocks / _finish; `strling extract
-        --write-index`).  runs0: initial capacity of the run table.  -> (extract_bam_device's dict, bytes of the .bai or None,
+        --write-index`).  runs0: initial capacity of the run table.  csi = (min_shift, depth): the uncompressed CSI payload instead
+        (strl_front_index_begin_csi; depth None or < 0 = samtools' rule).  -> (extract_bam_device's dict, bytes of the .bai or None,
         dict(n_records, n_no_coor, n_runs, n_chunks) or None, None or (status, message) of the index's refusal)"""
         B = self._bam_blocks(path)
         l_ref = np.array([t[1] for t in B["targets"]], np.int32)
         _check(self.L.strl_front_begin(self.h, B["n_ref"], B["first_off"], n_reads_hint))
         try:
-            _check(self.L.strl_front_index_begin(self.h, _ptr(l_ref) if l_ref.size else None, runs0))
+            if csi is None:
+                _check(self.L.strl_front_index_begin(self.h, _ptr(l_ref) if l_ref.size else None, runs0))
+            else:
+                _check(self.L.strl_front_index_begin_csi(self.h, _ptr(l_ref) if l_ref.size else None, runs0, int(csi[0]), -1 if csi[1] is None else int(csi[1])))
             chunks = self._front_push_blocks(B, B["b0"], len(B["blocks"]), chunk_blocks, check_crc, index=True, no_offsets_at=no_offsets_at)
             nbytes = C.c_uint64(0)
             info = BamindexInfo()
@@ -902,12 +908,17 @@ class Context:
             self.L.strl_bamindex_end(self.h)
         return res, bai, inf, refused
 
-    def bamindex(self, path, chunk_blocks=16384, check_crc=True):
+    def bamindex(self, path, chunk_blocks=16384, check_crc=True, csi=None):
         """the .bai of a coordinate-sorted BAM FILE built on the device (strl_bamindex_begin / _push / _finish / _fetch; what
-        `samtools index` writes).  -> (bytes of the .bai, dict(n_records, n_no_coor, n_runs, n_chunks))"""
+        `samtools index` writes).  csi = (min_shift, depth): the CSI index instead (strl_bamindex_begin_csi; depth None or < 0 =
+        samtools' rule), as its UNCOMPRESSED payload -- a .csi file is that in BGZF blocks (bamio.bgzf_bytes).
+        -> (bytes of the .bai / of the CSI payload, dict(n_records, n_no_coor, n_runs, n_chunks))"""
         B = self._bam_blocks(path)
         l_ref = np.array([t[1] for t in B["targets"]], np.int32)
-        _check(self.L.strl_bamindex_begin(self.h, B["n_ref"], _ptr(l_ref) if l_ref.size else None, B["first_off"]))
+        if csi is None:
+            _check(self.L.strl_bamindex_begin(self.h, B["n_ref"], _ptr(l_ref) if l_ref.size else None, B["first_off"]))
+        else:
+            _check(self.L.strl_bamindex_begin_csi(self.h, B["n_ref"], _ptr(l_ref) if l_ref.size else None, B["first_off"], int(csi[0]), -1 if csi[1] is None else int(csi[1])))
         try:
             data, blocks, keep = B["data"], B["blocks"], []
             for s0 in range(B["b0"], len(blocks), chunk_blocks):

@@ -2,8 +2,10 @@
 
 Writes spec-conformant BGZF-compressed BAM (SAM spec sections 4.1-4.2) from a records.RecordBatch so that the
 `strling` CLI's own BGZF/BAM reader can be exercised end to end, plus the matching .bai (SAM spec 5.2: binning
-index + 16 KiB linear index) that `strling call` needs for its region reads.
+index + 16 KiB linear index) that `strling call` needs for its region reads, or the CSI index (CSIv1: the binning scheme (min_shift, depth) as a parameter,
+a loffset per bin instead of the linear index, the payload in BGZF blocks) that a contig longer than 2^29 bases needs.
 """
+import bisect
 import struct
 import zlib
 
@@ -25,7 +27,8 @@ def sam_header(targets, sort_order="coordinate"):
 
 
 def write_bam(path, rec, header_text=None, level=1, block=0xFF00, index=True, repeat=1):
-    """repeat > 1 (benchmarks only): the header gets its own BGZF blocks and the record blocks are written `repeat` times;
+    """index: True = <path>.bai, "csi" = <path>.csi (min_shift 14, samtools' depth rule), False = none.
+    repeat > 1 (benchmarks only): the header gets its own BGZF blocks and the record blocks are written `repeat` times;
     such a file is not coordinate sorted and gets no index."""
     targets = rec.targets
     text = (header_text if header_text is not None else sam_header(targets)).encode()
@@ -68,7 +71,11 @@ def write_bam(path, rec, header_text=None, level=1, block=0xFF00, index=True, re
             f.write(_bgzf_block(bytes(out[o:o + block]), level))
         block_off.append(f.tell())
         f.write(_EOF)
-    if index:
+    if isinstance(index, str):
+        if index != "csi":
+            raise ValueError(f"index={index!r}: True, False or \"csi\"")
+        write_csi(path + ".csi", rec, rec_off, block_off, block)
+    elif index:
         write_bai(path + ".bai", rec, rec_off, block_off, block)
     return text.decode()
 
@@ -202,6 +209,98 @@ def write_bai(path, rec, rec_off, block_off, block):
     out += struct.pack("<Q", no_coor)                        # n_no_coor, as samtools writes it
     with open(path, "wb") as f:
         f.write(out)
+
+
+def csi_reg2bin(beg, end, min_shift, depth):
+    """CSIv1 specification; (14, 5) is _reg2bin"""
+    end -= 1
+    s, t = min_shift, ((1 << 3 * depth) - 1) // 7
+    for l in range(depth, 0, -1):
+        if beg >> s == end >> s:
+            return t + (beg >> s)
+        s += 3
+        t -= 1 << 3 * (l - 1)
+    return 0
+
+
+def csi_depth(min_shift, max_len):
+    """samtools' rule: the smallest depth >= 0 whose scheme reaches max_len + 256"""
+    d = 0
+    while (1 << (min_shift + 3 * d)) < max_len + 256:
+        d += 1
+    return d
+
+
+def csi_bin_first_window(b, depth):
+    """the first window (of 2^min_shift bases) bin b covers"""
+    l = 0
+    while l < depth and b >= ((1 << 3 * (l + 1)) - 1) // 7:
+        l += 1
+    return (b - ((1 << 3 * l) - 1) // 7) << 3 * (depth - l)
+
+
+def bgzf_bytes(payload, block=0xFF00, level=6, eof=True):
+    """payload in BGZF blocks of `block` input bytes, the EOF block behind them"""
+    return b"".join(_bgzf_block(bytes(payload[o:o + block]), level) for o in range(0, len(payload), block)) + (_EOF if eof else b"")
+
+
+def csi_payload(rec, rec_off, block_off, block, min_shift=14, depth=None):
+    """the uncompressed bytes of the CSI index of the records (write_bai's arguments and chunk policy: consecutive records of a
+    bin that touch in the inflated stream are one chunk).  loffset of a bin = the scheme's linear index at the bin's first
+    window, an empty window taking the next filled window's value (htslib's update_loff), 0 behind the last filled window."""
+    def voff(u):
+        k = u // block
+        return (block_off[k] << 16) | (u - k * block)
+    n_ref = len(rec.targets)
+    if depth is None:
+        depth = csi_depth(min_shift, max([l for _, l in rec.targets], default=0))
+    bins = [dict() for _ in range(n_ref)]
+    lin = [dict() for _ in range(n_ref)]
+    meta = [None] * n_ref
+    no_coor = 0
+    for i in range(rec.n):
+        t = int(rec.tid[i])
+        if t < 0:
+            no_coor += 1
+            continue
+        if meta[t] is None:
+            meta[t] = [voff(rec_off[i]), 0, 0, 0]
+        meta[t][1] = voff(rec_off[i + 1])
+        meta[t][3 if int(rec.flag[i]) & 4 else 2] += 1
+        beg = int(rec.pos[i])
+        end = beg + _ref_len(rec, i)
+        if end > 1 << (min_shift + 3 * depth):
+            raise ValueError(f"record {i} reaches past what the scheme ({min_shift}, {depth}) addresses")
+        v0, v1 = voff(rec_off[i]), voff(rec_off[i + 1])
+        ch = bins[t].setdefault(csi_reg2bin(beg, end, min_shift, depth), [])
+        if ch and ch[-1][1] == v0:
+            ch[-1][1] = v1
+        else:
+            ch.append([v0, v1])
+        for w in range(beg >> min_shift, ((end - 1) >> min_shift) + 1):
+            lin[t].setdefault(w, v0)
+    out = bytearray(b"CSI\1" + struct.pack("<iiii", min_shift, depth, 0, n_ref))
+    for t in range(n_ref):
+        filled = sorted(lin[t])
+
+        def loff(w):
+            k = bisect.bisect_left(filled, w)
+            return lin[t][filled[k]] if k < len(filled) else 0
+        out += struct.pack("<i", len(bins[t]) + (meta[t] is not None))
+        for b, chunks in sorted(bins[t].items()):
+            out += struct.pack("<IQi", b, loff(csi_bin_first_window(b, depth)), len(chunks))
+            for v0, v1 in chunks:
+                out += struct.pack("<QQ", v0, v1)
+        if meta[t] is not None:
+            out += struct.pack("<IQiQQQQ", ((1 << 3 * (depth + 1)) - 1) // 7 + 1, 0, 2, *meta[t])
+    out += struct.pack("<Q", no_coor)
+    return bytes(out)
+
+
+def write_csi(path, rec, rec_off, block_off, block, min_shift=14, depth=None, bgzf_block=0xFF00):
+    """the .csi of the records (csi_payload) in BGZF blocks of bgzf_block bytes and the EOF block, as samtools writes it"""
+    with open(path, "wb") as f:
+        f.write(bgzf_bytes(csi_payload(rec, rec_off, block_off, block, min_shift, depth), bgzf_block))
 
 
 def write_genome_bed(path, genome, targets, unit="AC"):

@@ -30,10 +30,14 @@ constexpr uint32_t BAI_ERR_KINDS = 5;
 constexpr uint32_t BAI_E_UNSORTED = 0, BAI_E_RANGE = 1, BAI_E_TID = 2, BAI_E_LREF = 3, BAI_E_NEGPOS = 4;
 constexpr uint64_t BAI_KEY_NONE = ~0ull;
 constexpr int32_t BAI_MAX_POS = 1 << 29;       // what the five-level binning scheme of a .bai addresses
-constexpr uint32_t BAI_META_BIN = 37450;
-constexpr int64_t BAI_LREF_SLACK = 64;         // windows of the linear index kept behind l_ref (1 Mbase)
+constexpr int64_t BAI_LREF_SLACK = 1 << 20;    // bases of the linear index kept behind l_ref: max(1, 2^20 >> min_shift) windows (64 of a .bai)
+constexpr int32_t CSI_MIN_SHIFT_LO = 8, CSI_MIN_SHIFT_HI = 24, CSI_DEPTH_HI = 8;      // schemes strl_*_begin_csi accepts
+constexpr int32_t CSI_MAX_END = 0x7ffffffe;    // bai_read clamps an end to 2^31 - 1: an end of that value may be a clamped one and is refused
 
-struct BaiRun { uint64_t key, beg_v, end_v, beg_abs, end_abs; };   // key = tid << 16 | bin; virtual offsets; offsets in the inflated stream
+// The binning scheme (CSIv1): windows of 2^min_shift bases, `depth` levels of bins below bin 0.  A .bai is (14, 5).  A bin number is
+// below 2^(3 depth + 1), so the bin field of a run's key has key_shift = 3 depth + 1 bits (16 for a .bai).
+struct BaiScheme { int32_t min_shift, depth, key_shift, max_end; };   // max_end: the largest end of a record the scheme (and a BAM position) holds
+struct BaiRun { uint64_t key, beg_v, end_v, beg_abs, end_abs; };   // key = tid << key_shift | bin; virtual offsets; offsets in the inflated stream
 struct BaiChunk { uint64_t key, beg_v, end_v; };
 struct BaiLast {          // the last record so far
   uint64_t key, end_v, end_abs;
@@ -74,6 +78,7 @@ struct BaiPush {
   const uint64_t *run_acc;  // ... else &BaiState::run_base on the device
   uint64_t run_cap;         // slots of runs[]
   BaiCols C;
+  BaiScheme sch;            // read by the kernels only where the scheme is not a .bai's (template parameter BAI)
 };
 
 struct BaiRec { int32_t tid, pos, end; uint32_t flag, bs; };
@@ -115,18 +120,38 @@ __device__ __forceinline__ uint32_t bai_reg2bin(int32_t beg, int32_t end) {     
   if (beg >> 26 == end >> 26) return 1u + (uint32_t)(beg >> 26);
   return 0u;
 }
-// a record the index can hold: a reference of the header, 0 <= pos, end <= 2^29, its last window one of the reference's
-// (l_ref and BAI_LREF_SLACK windows behind it: aligners do leave reads that hang over the end of a contig).  else the kind of refusal
-__device__ __forceinline__ int bai_refusal(const BaiRec &r, int32_t n_ref, const uint64_t *win_off) {
-  if (r.tid < -1 || r.tid >= n_ref) return (int)BAI_E_TID;
+// the CSI specification's reg2bin for (min_shift, depth); every lane makes all `depth` trips (at most 8), shifts in 64 bits
+// (min_shift + 3 (depth - 1) reaches 45).  depth 0: no trip, bin 0
+__device__ __forceinline__ uint32_t csi_reg2bin(int32_t beg, int32_t end, int32_t min_shift, int32_t depth) {
+  const uint64_t b = (uint64_t)(uint32_t)beg, e = (uint64_t)(uint32_t)(end - 1);
+  uint32_t t = (uint32_t)(((1ull << (3 * depth)) - 1ull) / 7ull), bin = 0;
+  int32_t s = min_shift;
+  bool found = false;
+  for (int32_t l = depth; l > 0; --l) {
+    const bool hit = !found && (b >> s) == (e >> s);
+    bin = hit ? t + (uint32_t)(b >> s) : bin;
+    found = found || hit;
+    s += 3;
+    t -= 1u << (3 * (l - 1));
+  }
+  return bin;
+}
+template <bool BAI> __device__ __forceinline__ int32_t bai_shift(const BaiPush &P) { return BAI ? 14 : P.sch.min_shift; }
+// a record the index can hold: a reference of the header, 0 <= pos, end <= what the scheme addresses (2^29 for a .bai), its last
+// window one of the reference's (l_ref and 1 Mbase behind it: aligners do leave reads that hang over the end of a contig).  else the kind of refusal
+template <bool BAI> __device__ __forceinline__ int bai_refusal(const BaiRec &r, const BaiPush &P) {
+  if (r.tid < -1 || r.tid >= P.n_ref) return (int)BAI_E_TID;
   if (r.tid < 0) return -1;
   if (r.pos < 0) return (int)BAI_E_NEGPOS;
-  if (r.pos >= BAI_MAX_POS || r.end > BAI_MAX_POS) return (int)BAI_E_RANGE;
-  if ((uint64_t)((r.end - 1) >> 14) >= win_off[r.tid + 1] - win_off[r.tid]) return (int)BAI_E_LREF;
+  const int32_t max_end = BAI ? BAI_MAX_POS : P.sch.max_end;
+  if (r.pos >= max_end || r.end > max_end) return (int)BAI_E_RANGE;
+  if ((uint64_t)((r.end - 1) >> bai_shift<BAI>(P)) >= P.win_off[r.tid + 1] - P.win_off[r.tid]) return (int)BAI_E_LREF;
   return -1;
 }
-__device__ __forceinline__ uint64_t bai_key(const BaiRec &r, int32_t n_ref, bool indexable) {
-  return (r.tid < 0 || !indexable) ? (uint64_t)(uint32_t)n_ref << 16 : ((uint64_t)(uint32_t)r.tid << 16) | bai_reg2bin(r.pos, r.end);
+template <bool BAI> __device__ __forceinline__ uint64_t bai_key(const BaiRec &r, const BaiPush &P, bool indexable) {
+  const int32_t ks = BAI ? 16 : P.sch.key_shift;
+  if (r.tid < 0 || !indexable) return (uint64_t)(uint32_t)P.n_ref << ks;
+  return ((uint64_t)(uint32_t)r.tid << ks) | (BAI ? bai_reg2bin(r.pos, r.end) : csi_reg2bin(r.pos, r.end, P.sch.min_shift, P.sch.depth));
 }
 // virtual offset of the byte at buffer offset q: the last block that starts at or in front of it (vrel[0] <= q <= vrel[m])
 __device__ __forceinline__ uint64_t bai_voff(const int64_t *vrel, const uint64_t *vfoff, uint32_t m, int64_t q) {
@@ -139,16 +164,17 @@ __device__ __forceinline__ uint64_t bai_voff(const int64_t *vrel, const uint64_t
 }
 
 // the per-record step; the rules (refusals, bin, windows, virtual offsets, run heads) are this one body for both sources
-template <bool COLS> __device__ __forceinline__ void bai_record_body(const BaiPush &P) {
+template <bool COLS, bool BAI> __device__ __forceinline__ void bai_record_body(const BaiPush &P) {
+  const int32_t m = bai_shift<BAI>(P);
   const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
   const bool act = i < P.n;
   BaiRec r{-1, -1, 0, 0, 0};
   uint32_t q = 0;
   int bad = -1;
-  if (act) { q = P.recoff[i]; bai_fetch<COLS>(P, i, r); bad = bai_refusal(r, P.n_ref, P.win_off); }
+  if (act) { q = P.recoff[i]; bai_fetch<COLS>(P, i, r); bad = bai_refusal<BAI>(r, P); }
   const bool placed = act && r.tid >= 0 && bad < 0;
-  const uint64_t key = act ? bai_key(r, P.n_ref, bad < 0) : BAI_KEY_NONE;
-  const int32_t end_win = placed ? (r.end - 1) >> 14 : -1;
+  const uint64_t key = act ? bai_key<BAI>(r, P, bad < 0) : BAI_KEY_NONE;
+  const int32_t end_win = placed ? (r.end - 1) >> m : -1;
   // the record in front: the lane below, or (first lane of a wave) read again / the previous chunk's last
   int32_t ptid = __shfl_up(r.tid, 1), ppos = __shfl_up(r.pos, 1), pwin = __shfl_up(end_win, 1);
   uint64_t pkey = __shfl_up(key, 1);
@@ -157,9 +183,9 @@ template <bool COLS> __device__ __forceinline__ void bai_record_body(const BaiPu
     else {
       BaiRec p;
       bai_fetch<COLS>(P, i - 1u, p);
-      const bool pok = bai_refusal(p, P.n_ref, P.win_off) < 0;
-      ptid = p.tid; ppos = p.pos; pkey = bai_key(p, P.n_ref, pok);
-      pwin = (p.tid >= 0 && pok) ? (p.end - 1) >> 14 : -1;
+      const bool pok = bai_refusal<BAI>(p, P) < 0;
+      ptid = p.tid; ppos = p.pos; pkey = bai_key<BAI>(p, P, pok);
+      pwin = (p.tid >= 0 && pok) ? (p.end - 1) >> m : -1;
     }
   }
   uint64_t beg_v = 0, end_v = 0;
@@ -176,7 +202,7 @@ template <bool COLS> __device__ __forceinline__ void bai_record_body(const BaiPu
   // linear index: the windows no record in front of this one has reached (in a sorted stream the lane below covers all
   // but the window a record is the first to enter; an N skip of hundreds of kilobases enters many)
   if (placed) {
-    const int32_t w0 = r.pos >> 14, from = (ptid == r.tid && pwin >= w0) ? pwin + 1 : w0;
+    const int32_t w0 = r.pos >> m, from = (ptid == r.tid && pwin >= w0) ? pwin + 1 : w0;
     uint64_t *lin = P.lin + P.win_off[r.tid];
     for (int32_t w = from; w <= end_win; ++w) atomicMin(reinterpret_cast<unsigned long long *>(&lin[w]), (unsigned long long)beg_v);
   }
@@ -214,8 +240,9 @@ template <bool COLS> __device__ __forceinline__ void bai_record_body(const BaiPu
     P.S->last[P.par ^ 1u] = L;
   }
 }
-__global__ __launch_bounds__(256) void bai_record_kernel(BaiPush P) { bai_record_body<false>(P); }
-__global__ __launch_bounds__(256) void bai_record_cols_kernel(BaiPush P) { bai_record_body<true>(P); }
+// <BAI>: the scheme is a .bai's (14, 5), compiled in -- the code of that path is what it was before schemes; else read from P.sch
+template <bool BAI> __global__ __launch_bounds__(256) void bai_record_kernel(BaiPush P) { bai_record_body<false, BAI>(P); }
+template <bool BAI> __global__ __launch_bounds__(256) void bai_record_cols_kernel(BaiPush P) { bai_record_body<true, BAI>(P); }
 
 // One block: cnt[0, n) -> exclusive sums in place, the total to *total; acc (if given): acc[0] = the running total so far (the
 // base of this chunk's runs), acc[1] += total -- the host is not asked
@@ -244,7 +271,7 @@ __device__ __forceinline__ uint32_t bai_block_rank(bool f) {
   return r;
 }
 
-template <bool COLS> __device__ __forceinline__ void bai_emit_body(const BaiPush &P) {
+template <bool COLS, bool BAI> __device__ __forceinline__ void bai_emit_body(const BaiPush &P) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const bool head = i < P.n && P.flag[i];
   const uint32_t rank = bai_block_rank(head);
@@ -256,11 +283,11 @@ template <bool COLS> __device__ __forceinline__ void bai_emit_body(const BaiPush
   bai_fetch<COLS>(P, i, r);
   const uint64_t beg_v = bai_voff(P.vrel, P.vfoff, P.vm, (int64_t)q), beg_abs = (uint64_t)(P.abs0 + (int64_t)q);
   BaiRun &R = P.runs[slot];
-  R.key = bai_key(r, P.n_ref, bai_refusal(r, P.n_ref, P.win_off) < 0); R.beg_v = beg_v; R.beg_abs = beg_abs;
+  R.key = bai_key<BAI>(r, P, bai_refusal<BAI>(r, P) < 0); R.beg_v = beg_v; R.beg_abs = beg_abs;
   if (slot) { BaiRun &B = P.runs[slot - 1]; B.end_v = beg_v; B.end_abs = beg_abs; }
 }
-__global__ __launch_bounds__(256) void bai_emit_kernel(BaiPush P) { bai_emit_body<false>(P); }
-__global__ __launch_bounds__(256) void bai_emit_cols_kernel(BaiPush P) { bai_emit_body<true>(P); }
+template <bool BAI> __global__ __launch_bounds__(256) void bai_emit_kernel(BaiPush P) { bai_emit_body<false, BAI>(P); }
+template <bool BAI> __global__ __launch_bounds__(256) void bai_emit_cols_kernel(BaiPush P) { bai_emit_body<true, BAI>(P); }
 
 // finish: the open run ends behind the last record; sort keys of the runs
 __global__ void bai_keys_kernel(BaiRun *runs, uint32_t n, const BaiState *S, uint32_t par, uint64_t *keys, uint32_t *vals) {
@@ -298,6 +325,10 @@ __global__ void bai_fill_kernel(uint64_t *p, size_t n, uint64_t v) {
 struct BaiBlock { int64_t abs; uint64_t foff; };       // a pushed block: offset of its first byte in the inflated stream, file offset
 struct strl_bai {
   int32_t n_ref = 0;
+  BaiScheme sch{14, 5, 16, BAI_MAX_POS};
+  bool auto_depth = false;                            // the depth follows from the header's longest reference (samtools' rule)
+  bool csi = false;                                   // the bytes are a CSI payload (uncompressed), not a .bai -- whatever the scheme
+  bool bai_scheme() const { return sch.min_shift == 14 && sch.depth == 5; }      // the kernels with the scheme compiled in
   std::vector<int32_t> l_ref;
   std::vector<uint64_t> win_off;                      // [n_ref + 1]
   DevBuf d_winoff, lin, ref_beg, ref_end, ref_cnt, state, runs, flag, blk_cnt;
@@ -349,9 +380,17 @@ static int bai_refuse(const strl_bai *B, const BaiState &S) {
   const unsigned long long at = (unsigned long long)S.err_ord[kind];
   switch (kind) {
     case BAI_E_UNSORTED: set_error("the BAM is not coordinate sorted: record %llu comes behind a record of a later position (or behind an unplaced one); sort it first", at); return STRL_ERR_FORMAT;
-    case BAI_E_RANGE: set_error("record %llu lies at or reaches past position 2^29 = 536870912, which a .bai cannot address (a CSI index can; writing CSI is not supported)", at); return STRL_ERR_LIMIT;
+    case BAI_E_RANGE:
+      if (!B->csi) set_error("record %llu lies at or reaches past position 2^29 = 536870912, which a .bai cannot address; a CSI index can: `strling bamindex --csi` (strl_bamindex_begin_csi)", at);
+      else if (B->sch.max_end == CSI_MAX_END) set_error("record %llu reaches position 2^31 - 1 = 2147483647 or past it, which a BAM position cannot hold; not indexed", at);
+      else if (B->auto_depth)
+        set_error("record %llu lies at or reaches past position 2^%d = %lld, which the CSI scheme (min_shift %d, depth %d: chosen for the longest reference of the header) cannot "
+                  "address: the record lies past the end of its reference", at, B->sch.min_shift + 3 * B->sch.depth, (long long)B->sch.max_end, B->sch.min_shift, B->sch.depth);
+      else set_error("record %llu lies at or reaches past position 2^%d = %lld, which the CSI scheme (min_shift %d, depth %d) cannot address; a greater depth can", at,
+                     B->sch.min_shift + 3 * B->sch.depth, (long long)B->sch.max_end, B->sch.min_shift, B->sch.depth);
+      return STRL_ERR_LIMIT;
     case BAI_E_TID: set_error("malformed BAM record %llu: its refID is not one of the header's %d references", at, B->n_ref); return STRL_ERR_FORMAT;
-    case BAI_E_LREF: set_error("record %llu reaches more than %lld bases past the end of its reference as the header gives it (l_ref); not indexed", at, (long long)(BAI_LREF_SLACK << 14)); return STRL_ERR_FORMAT;
+    case BAI_E_LREF: set_error("record %llu reaches more than %lld bases past the end of its reference as the header gives it (l_ref); not indexed", at, (long long)std::max<int64_t>(BAI_LREF_SLACK, 1ll << B->sch.min_shift)); return STRL_ERR_FORMAT;
     default: set_error("record %llu has a reference but a negative position; not indexed", at); return STRL_ERR_FORMAT;
   }
 }
@@ -379,7 +418,9 @@ static int bai_index_chunk(strl_ctx *c, strl_front *F, strl_bai *B, int si) {
     P.n_ref = B->n_ref; P.win_off = B->d_winoff.as<uint64_t>();
     P.lin = B->lin.as<uint64_t>(); P.ref_beg = B->ref_beg.as<uint64_t>(); P.ref_end = B->ref_end.as<uint64_t>(); P.ref_cnt = B->ref_cnt.as<uint64_t>();
     P.S = B->state.as<BaiState>(); P.par = B->par; P.flag = B->flag.as<uint8_t>(); P.blk_cnt = B->blk_cnt.as<uint32_t>();
-    hipLaunchKernelGGL(bai_record_kernel, dim3(nblk), dim3(256), 0, st, P);
+    P.sch = B->sch;
+    const bool bai = B->bai_scheme();
+    hipLaunchKernelGGL(bai ? bai_record_kernel<true> : bai_record_kernel<false>, dim3(nblk), dim3(256), 0, st, P);
     STRL_HIP(hipGetLastError());
     hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, P.blk_cnt, nblk, &P.S->n_heads, (uint64_t *)nullptr);
     STRL_HIP(hipGetLastError());
@@ -391,7 +432,7 @@ static int bai_index_chunk(strl_ctx *c, strl_front *F, strl_bai *B, int si) {
     if (heads) {
       if ((rc = B->runs.grow((size_t)(B->n_runs + heads) * sizeof(BaiRun), (size_t)B->n_runs * sizeof(BaiRun), st))) return rc;
       P.runs = B->runs.as<BaiRun>(); P.run_base = B->n_runs; P.run_acc = nullptr; P.run_cap = B->runs.cap / sizeof(BaiRun);
-      hipLaunchKernelGGL(bai_emit_kernel, dim3(nblk), dim3(256), 0, st, P);
+      hipLaunchKernelGGL(bai ? bai_emit_kernel<true> : bai_emit_kernel<false>, dim3(nblk), dim3(256), 0, st, P);
       STRL_HIP(hipGetLastError());
       B->n_runs += heads;
     }
@@ -410,18 +451,42 @@ static void put64(std::vector<uint8_t> &o, uint64_t v) { for (int k = 0; k < 8; 
 
 using namespace strl;
 
-// the resident tables of a new builder (linear index, per-reference words, state words) on the context; replaces c->bai
-static int bai_setup(strl_ctx *c, int32_t n_ref, const int32_t *l_ref) {
+// the schemes the builder takes: window tables and bin numbers stay small (depth < 0: the rule, see bai_setup)
+static int csi_check(int32_t m, int32_t d) {
+  if (m >= CSI_MIN_SHIFT_LO && m <= CSI_MIN_SHIFT_HI && d <= CSI_DEPTH_HI) return STRL_OK;
+  set_error("CSI scheme: min_shift must be in [%d, %d] and depth at most %d (got min_shift %d, depth %d)", CSI_MIN_SHIFT_LO, CSI_MIN_SHIFT_HI, CSI_DEPTH_HI, m, d);
+  return STRL_ERR_ARG;
+}
+// the resident tables of a new builder (linear index, per-reference words, state words) on the context; replaces c->bai.
+// csi: null = a .bai; else {min_shift, depth}, depth < 0 = samtools' rule (the smallest depth whose scheme reaches max(l_ref) + 256)
+static int bai_setup(strl_ctx *c, int32_t n_ref, const int32_t *l_ref, const int32_t *csi) {
   int rc;
+  BaiScheme sch{14, 5, 16, BAI_MAX_POS};
+  if (csi) {
+    int32_t m = csi[0], d = csi[1];
+    if ((rc = csi_check(m, d))) return rc;
+    if (d < 0) {
+      int64_t max_len = 0;
+      for (int32_t t = 0; t < n_ref; ++t) max_len = std::max<int64_t>(max_len, l_ref[t]);
+      max_len += 256;
+      for (d = 0; d < CSI_DEPTH_HI && (1ll << (m + 3 * d)) < max_len; ++d) {}
+    }
+    sch = BaiScheme{m, d, 3 * d + 1, (int32_t)std::min<int64_t>(1ll << (m + 3 * d), CSI_MAX_END)};
+  }
   if (c->bai) { bai_destroy(c->bai); c->bai = nullptr; }
   strl_bai *B = new strl_bai();
   c->bai = B;
   B->n_ref = n_ref;
+  B->sch = sch;
+  B->csi = csi != nullptr;
+  B->auto_depth = csi && csi[1] < 0;
   B->l_ref.assign(l_ref, l_ref + n_ref);
   B->win_off.assign((size_t)n_ref + 1, 0);
+  // windows of 2^min_shift bases up to l_ref and 1 Mbase behind it, never more than the scheme addresses ((14, 5): 64 behind l_ref, at most 2^15)
+  const int64_t win = 1ll << sch.min_shift, slack = std::max<int64_t>(1, BAI_LREF_SLACK >> sch.min_shift);
   for (int32_t t = 0; t < n_ref; ++t) {
-    const int64_t len = std::min<int64_t>(std::max<int64_t>(l_ref[t], 0), BAI_MAX_POS);
-    B->win_off[(size_t)t + 1] = B->win_off[(size_t)t] + (uint64_t)std::min<int64_t>(((len + 16383) >> 14) + BAI_LREF_SLACK, BAI_MAX_POS >> 14);
+    const int64_t len = std::min<int64_t>(std::max<int64_t>(l_ref[t], 0), sch.max_end);
+    B->win_off[(size_t)t + 1] = B->win_off[(size_t)t] + (uint64_t)std::min<int64_t>(((len + win - 1) >> sch.min_shift) + slack, ((int64_t)sch.max_end + win - 1) >> sch.min_shift);
   }
   const size_t nw = (size_t)B->win_off[(size_t)n_ref], nr = (size_t)n_ref;
   if ((rc = B->d_winoff.reserve((nr + 1) * 8)) || (rc = B->lin.reserve(nw * 8 + 16)) || (rc = B->ref_beg.reserve(nr * 8 + 16)) ||
@@ -490,7 +555,15 @@ extern "C" int strl_bamindex_begin(strl_ctx *c, int32_t n_ref, const int32_t *l_
   if (!c || n_ref < 0 || (n_ref && !l_ref)) { set_error("strl_bamindex_begin: bad argument"); return STRL_ERR_ARG; }
   int rc;
   if ((rc = front_begin_scan(c, n_ref, first_record_offset))) return rc;
-  return bai_setup(c, n_ref, l_ref);
+  return bai_setup(c, n_ref, l_ref, nullptr);
+}
+
+extern "C" int strl_bamindex_begin_csi(strl_ctx *c, int32_t n_ref, const int32_t *l_ref, uint64_t first_record_offset, int32_t min_shift, int32_t depth) {
+  if (!c || n_ref < 0 || (n_ref && !l_ref)) { set_error("strl_bamindex_begin_csi: bad argument"); return STRL_ERR_ARG; }
+  int rc;
+  if ((rc = csi_check(min_shift, depth)) || (rc = front_begin_scan(c, n_ref, first_record_offset))) return rc;
+  const int32_t csi[2] = {min_shift, depth};
+  return bai_setup(c, n_ref, l_ref, csi);
 }
 
 extern "C" int strl_bamindex_reserve(strl_ctx *c, uint32_t max_blocks, uint64_t max_comp_bytes) {
@@ -538,8 +611,9 @@ static int bai_sort_and_pack(strl_ctx *c, strl_bai *B) {
   const uint32_t n = (uint32_t)B->n_runs;
   std::vector<BaiChunk> ch;
   if (n) {
-    int bits = 17;
-    while (bits < 48 && ((uint64_t)B->n_ref >> (bits - 16))) ++bits;
+    const int ks = B->sch.key_shift;                      // bits of the bin field (16 for a .bai); the reference field up to n_ref, the key of the unplaced
+    int bits = ks + 1;
+    while (bits < ks + 32 && ((uint64_t)B->n_ref >> (bits - ks))) ++bits;
     const size_t sb = radix_sort_scratch_bytes(n, bits);
     const uint32_t nblk = (n + 255u) / 256u;
     DevBuf k0, k1, v0, v1, sc, out;
@@ -579,35 +653,54 @@ static int bai_sort_and_pack(strl_ctx *c, strl_bai *B) {
     STRL_HIP(hipMemcpy(re.data(), B->ref_end.p, nr * 8, hipMemcpyDeviceToHost));
     STRL_HIP(hipMemcpy(cnt.data(), B->ref_cnt.p, nr * 16, hipMemcpyDeviceToHost));
   }
-  // the bytes (SAM spec 5.2): per reference the bins ascending with their chunks, the pseudo-bin last, the linear index up to
-  // the last window touched (empty windows 0), n_no_coor at the end
+  // the bytes: per reference the bins ascending with their chunks, the pseudo-bin last, n_no_coor at the end.  .bai (SAM spec
+  // 5.2): the linear index up to the last window touched behind the bins (empty windows 0).  CSI (CSIv1): no linear index, every
+  // bin carries loffset = the linear index at the bin's first window, after empty windows have taken the next filled window's
+  // value from the end towards the start (htslib's update_loff); 0 behind the last window touched.  Done here, on the host's
+  // copy of lin[]: one pass over words that are copied anyway, and a gather per bin beside the bytes being written.
+  const int ks = B->sch.key_shift, m = B->sch.min_shift, d = B->sch.depth;
+  const uint64_t bin_mask = (1ull << ks) - 1ull;
+  const uint32_t meta_bin = (uint32_t)(((1ull << (3 * (d + 1))) - 1ull) / 7ull + 1ull);      // 37450 for depth 5
   std::vector<uint8_t> &o = B->bytes;
   o.clear();
-  o.reserve(8 + ch.size() * 24 + nw * 8 + nr * 64 + 8);
-  o.insert(o.end(), {'B', 'A', 'I', 1});
+  o.reserve(16 + ch.size() * 36 + (B->csi ? 0 : nw * 8) + nr * 64 + 8);
+  if (B->csi) { o.insert(o.end(), {'C', 'S', 'I', 1}); put32(o, (uint32_t)m); put32(o, (uint32_t)d); put32(o, 0); }
+  else o.insert(o.end(), {'B', 'A', 'I', 1});
   put32(o, (uint32_t)B->n_ref);
   size_t at = 0;
   uint64_t n_chunks = 0;
   for (size_t t = 0; t < nr; ++t) {
     size_t e = at, n_bin = 0;
-    while (e < ch.size() && (ch[e].key >> 16) == t) { if (e == at || ch[e].key != ch[e - 1].key) ++n_bin; ++e; }
+    while (e < ch.size() && (ch[e].key >> ks) == t) { if (e == at || ch[e].key != ch[e - 1].key) ++n_bin; ++e; }
     const bool meta = cnt[2 * t] + cnt[2 * t + 1] != 0;
+    const uint64_t w0 = B->win_off[t], w1 = B->win_off[t + 1];
+    uint64_t n_intv = 0;
+    for (uint64_t w = w1; w > w0; --w) if (lin[(size_t)w - 1] != ~0ull) { n_intv = w - w0; break; }
+    if (B->csi)
+      for (uint64_t w = n_intv; w > 1; --w) if (lin[(size_t)(w0 + w - 2)] == ~0ull) lin[(size_t)(w0 + w - 2)] = lin[(size_t)(w0 + w - 1)];
     put32(o, (uint32_t)(n_bin + (meta ? 1 : 0)));
     for (size_t a = at; a < e;) {
       size_t b = a;
       while (b < e && ch[b].key == ch[a].key) ++b;
-      put32(o, (uint32_t)(ch[a].key & 0xffffu));
+      const uint32_t bin = (uint32_t)(ch[a].key & bin_mask);
+      put32(o, bin);
+      if (B->csi) {
+        // the bin's level: the first bin of level l is (8^l - 1) / 7; its bins cover 2^(m + 3 (d - l)) bases = 8^(d - l) windows each
+        int l = 0;
+        while (l < d && bin >= (uint32_t)(((1ull << (3 * (l + 1))) - 1ull) / 7ull)) ++l;
+        const uint64_t w = (uint64_t)(bin - (uint32_t)(((1ull << (3 * l)) - 1ull) / 7ull)) << (3 * (d - l));
+        put64(o, w < n_intv ? lin[(size_t)(w0 + w)] : 0);
+      }
       put32(o, (uint32_t)(b - a));
       for (size_t k = a; k < b; ++k) { put64(o, ch[k].beg_v); put64(o, ch[k].end_v); }
       n_chunks += b - a;
       a = b;
     }
-    if (meta) { put32(o, BAI_META_BIN); put32(o, 2); put64(o, rb[t]); put64(o, re[t]); put64(o, cnt[2 * t]); put64(o, cnt[2 * t + 1]); }
-    const uint64_t w0 = B->win_off[t], w1 = B->win_off[t + 1];
-    uint64_t n_intv = 0;
-    for (uint64_t w = w1; w > w0; --w) if (lin[(size_t)w - 1] != ~0ull) { n_intv = w - w0; break; }
-    put32(o, (uint32_t)n_intv);
-    for (uint64_t w = 0; w < n_intv; ++w) { const uint64_t v = lin[(size_t)(w0 + w)]; put64(o, v == ~0ull ? 0 : v); }
+    if (meta) { put32(o, meta_bin); if (B->csi) put64(o, 0); put32(o, 2); put64(o, rb[t]); put64(o, re[t]); put64(o, cnt[2 * t]); put64(o, cnt[2 * t + 1]); }
+    if (!B->csi) {
+      put32(o, (uint32_t)n_intv);
+      for (uint64_t w = 0; w < n_intv; ++w) { const uint64_t v = lin[(size_t)(w0 + w)]; put64(o, v == ~0ull ? 0 : v); }
+    }
     at = e;
   }
   put64(o, B->h_state->n_no_coor);
@@ -653,7 +746,7 @@ static int bai_room(strl_bai *B, DevBuf &b, size_t bytes) {
   return STRL_OK;
 }
 
-extern "C" int strl_front_index_begin(strl_ctx *c, const int32_t *l_ref, uint64_t runs0) {
+static int front_index_begin(strl_ctx *c, const int32_t *l_ref, uint64_t runs0, const int32_t *csi) {
   if (!c || !c->front || !c->x_open || !c->x_front) { set_error("strl_front_index_begin without strl_front_begin"); return STRL_ERR_ARG; }
   strl_front *F = c->front;
   if (F->n_ref && !l_ref) { set_error("strl_front_index_begin: bad argument"); return STRL_ERR_ARG; }
@@ -663,7 +756,7 @@ extern "C" int strl_front_index_begin(strl_ctx *c, const int32_t *l_ref, uint64_
   }
   STRL_HIP(hipSetDevice(c->device));
   int rc;
-  if ((rc = bai_setup(c, (int32_t)F->n_ref, l_ref))) return rc;
+  if ((rc = bai_setup(c, (int32_t)F->n_ref, l_ref, csi))) return rc;
   strl_bai *B = c->bai;
   B->attached = true;
   B->run_cap = std::max<uint64_t>(runs0 ? runs0 : (1ull << 20), 16);
@@ -671,6 +764,11 @@ extern "C" int strl_front_index_begin(strl_ctx *c, const int32_t *l_ref, uint64_
   STRL_HIP(hipHostMalloc(reinterpret_cast<void **>(&B->h_snap), sizeof(BaiState), hipHostMallocDefault));
   STRL_HIP(hipEventCreateWithFlags(&B->ev_snap, hipEventDisableTiming));
   return STRL_OK;
+}
+extern "C" int strl_front_index_begin(strl_ctx *c, const int32_t *l_ref, uint64_t runs0) { return front_index_begin(c, l_ref, runs0, nullptr); }
+extern "C" int strl_front_index_begin_csi(strl_ctx *c, const int32_t *l_ref, uint64_t runs0, int32_t min_shift, int32_t depth) {
+  const int32_t csi[2] = {min_shift, depth};
+  return front_index_begin(c, l_ref, runs0, csi);
 }
 
 extern "C" int strl_front_index_blocks(strl_ctx *c, const uint64_t *block_off, uint64_t end_off, uint32_t n_blocks) {
@@ -752,13 +850,15 @@ void strl::bai_front_index(strl_ctx *c, strl_front *F, int si, const FrontInfo &
   P.S = B->state.as<BaiState>(); P.par = B->par; P.flag = B->flag.as<uint8_t>(); P.blk_cnt = B->blk_cnt.as<uint32_t>();
   P.runs = B->runs.as<BaiRun>(); P.run_base = 0; P.run_acc = &P.S->run_base; P.run_cap = B->run_cap;
   P.C = BaiCols{tid, pos, end, fragw, I.carry_off};
+  P.sch = B->sch;
+  const bool bai = B->bai_scheme();
   // STRL_BAI_RECORDS=1 (measurements): the record-reading form of the per-record step, as `strling bamindex` runs it
   static const bool from_records = getenv("STRL_BAI_RECORDS") != nullptr;
-  if (from_records) hipLaunchKernelGGL(bai_record_kernel, dim3(nblk), dim3(256), 0, st, P);
-  else hipLaunchKernelGGL(bai_record_cols_kernel, dim3(nblk), dim3(256), 0, st, P);
+  if (from_records) hipLaunchKernelGGL(bai ? bai_record_kernel<true> : bai_record_kernel<false>, dim3(nblk), dim3(256), 0, st, P);
+  else hipLaunchKernelGGL(bai ? bai_record_cols_kernel<true> : bai_record_cols_kernel<false>, dim3(nblk), dim3(256), 0, st, P);
   hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, P.blk_cnt, nblk, &P.S->n_heads, &P.S->run_base);
-  if (from_records) hipLaunchKernelGGL(bai_emit_kernel, dim3(nblk), dim3(256), 0, st, P);
-  else hipLaunchKernelGGL(bai_emit_cols_kernel, dim3(nblk), dim3(256), 0, st, P);
+  if (from_records) hipLaunchKernelGGL(bai ? bai_emit_kernel<true> : bai_emit_kernel<false>, dim3(nblk), dim3(256), 0, st, P);
+  else hipLaunchKernelGGL(bai ? bai_emit_cols_kernel<true> : bai_emit_cols_kernel<false>, dim3(nblk), dim3(256), 0, st, P);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e);
   B->n_records += n;
   B->par ^= 1u;

@@ -176,54 +176,155 @@ bool BamReader::seek(Pos p, std::string &err) {
   return true;
 }
 
-// BAI (SAM spec 5.2): magic, n_ref, per reference { n_bin, { bin, n_chunk, { beg, end } }, n_intv, ioffset[] }
+// ---- the index beside a BAM ------------------------------------------------------------------------------------------------
+namespace {
+bool slurp(FILE *f, std::vector<uint8_t> &out) {
+  if (fseeko(f, 0, SEEK_END) != 0) return false;
+  const off_t n = ftello(f);
+  if (n < 0 || fseeko(f, 0, SEEK_SET) != 0) return false;
+  out.resize((size_t)n);
+  return n == 0 || fread(out.data(), 1, (size_t)n, f) == (size_t)n;
+}
+// every BGZF block of `raw` inflated into `out` (the EOF block or none at the end; anything else: false)
+bool bgzf_inflate_all(const std::vector<uint8_t> &raw, std::vector<uint8_t> &out) {
+  out.clear();
+  size_t o = 0;
+  while (o < raw.size()) {
+    if (raw.size() - o < 18) return false;
+    const uint8_t *h = raw.data() + o;
+    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return false;
+    const uint32_t xlen = h[10] | (h[11] << 8);
+    if (raw.size() - o < 12 + (size_t)xlen) return false;
+    uint32_t bsize = 0;
+    for (uint32_t x = 0; x + 4 <= xlen;) {
+      const uint8_t *e = h + 12 + x;
+      const uint32_t sl = e[2] | (e[3] << 8);
+      if (x + 4 + sl > xlen) return false;
+      if (e[0] == 'B' && e[1] == 'C' && sl == 2) bsize = (e[4] | (e[5] << 8)) + 1u;
+      x += 4 + sl;
+    }
+    if (!bsize || bsize < 12 + xlen + 8 || raw.size() - o < bsize) return false;
+    const uint32_t clen = bsize - 12 - xlen - 8;
+    const uint8_t *t = h + bsize - 4;
+    const uint32_t isz = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
+    if (isz > 65536u) return false;
+    if (isz) {
+      const size_t at = out.size();
+      out.resize(at + isz);
+      if (!inflate_block(h + 12 + xlen, clen, out.data() + at, isz)) return false;
+    }
+    o += bsize;
+  }
+  return true;
+}
+struct Cursor {         // the parsers' discipline: a count the bytes left cannot hold is a corrupt index, not an allocation
+  const uint8_t *p;
+  size_t n, at = 0;
+  size_t left() const { return n - at; }
+  bool rd(void *dst, size_t k) { if (k > left()) return false; memcpy(dst, p + at, k); at += k; return true; }
+};
+}  // namespace
+
+int64_t BamIndexFile::bin_start(uint32_t bin) const {
+  int l = 0;                                               // the first bin of level l is (8^l - 1) / 7; a bin of it covers 2^(min_shift + 3 (depth - l)) bases
+  while (l < depth && bin >= (uint32_t)(((1ull << (3 * (l + 1))) - 1ull) / 7ull)) ++l;
+  return (int64_t)((uint64_t)(bin - (uint32_t)(((1ull << (3 * l)) - 1ull) / 7ull)) << (min_shift + 3 * (depth - l)));
+}
+
+int BamIndexFile::load(const std::string &bam_path, std::string &err) {
+  *this = BamIndexFile();
+  const std::string stem = bam_path.size() > 4 ? bam_path.substr(0, bam_path.size() - 4) : std::string();
+  FILE *f = fopen((bam_path + ".bai").c_str(), "rb");
+  if (!f && !stem.empty()) f = fopen((stem + ".bai").c_str(), "rb");
+  if (!f) {
+    f = fopen((bam_path + ".csi").c_str(), "rb");
+    if (!f && !stem.empty()) f = fopen((stem + ".csi").c_str(), "rb");
+    csi = f != nullptr;
+  }
+  if (!f) { err = "no .bai index next to " + bam_path + " (nor a .csi)"; return MISSING; }
+  std::vector<uint8_t> raw, infl;
+  bool ok = slurp(f, raw);
+  fclose(f);
+  if (ok && csi) { ok = bgzf_inflate_all(raw, infl); raw.swap(infl); }
+  Cursor c{raw.data(), raw.size()};
+  char magic[4];
+  int32_t n_ref = 0, l_aux = 0;
+  ok = ok && c.rd(magic, 4) && memcmp(magic, csi ? "CSI\1" : "BAI\1", 4) == 0;
+  if (ok && csi) {       // the schemes the builder accepts (strl_bamindex_begin_csi): what keeps bin numbers and window tables small
+    ok = c.rd(&min_shift, 4) && c.rd(&depth, 4) && c.rd(&l_aux, 4) && min_shift >= 8 && min_shift <= 24 && depth >= 0 && depth <= 8 && l_aux >= 0 && (size_t)l_aux <= c.left();
+    if (ok) c.at += (size_t)l_aux;
+  }
+  // (a reference takes 4 bytes at least in a .csi, 8 in a .bai; a bin 8 and 16; a chunk 16; an interval 8)
+  ok = ok && c.rd(&n_ref, 4) && n_ref >= 0 && (uint64_t)n_ref * (csi ? 4 : 8) <= c.left();
+  if (ok) refs.resize((size_t)n_ref);
+  const uint32_t mb = meta_bin();
+  for (int32_t r = 0; ok && r < n_ref; ++r) {
+    Ref &R = refs[(size_t)r];
+    int32_t n_bin = 0;
+    ok = c.rd(&n_bin, 4) && n_bin >= 0 && (uint64_t)n_bin * (csi ? 16 : 8) <= c.left();
+    if (ok) R.bins.reserve((size_t)n_bin);
+    for (int32_t k = 0; ok && k < n_bin; ++k) {
+      Bin b{0, 0, chunks.size(), 0};
+      int32_t n_chunk = 0;
+      ok = c.rd(&b.bin, 4) && (!csi || c.rd(&b.loffset, 8)) && c.rd(&n_chunk, 4) && n_chunk >= 0 && (uint64_t)n_chunk * 16 <= c.left();
+      if (!ok) break;
+      if (b.bin == mb) {                 // the metadata pseudo-bin: (first, end) and (n_mapped, n_unmapped); another shape carries no counts
+        uint64_t v[4];
+        if (n_chunk == 2) { c.rd(v, 32); R.meta = true; R.span[0] = v[0]; R.span[1] = v[1]; R.n_mapped = v[2]; R.n_unmapped = v[3]; }
+        else { c.at += (size_t)n_chunk * 16; R.meta_bad = true; }
+        continue;
+      }
+      b.n_chunk = (size_t)n_chunk;
+      chunks.resize(b.chunk0 + b.n_chunk);
+      if (n_chunk) c.rd(chunks.data() + b.chunk0, (size_t)n_chunk * 16);
+      R.bins.push_back(b);
+    }
+    if (ok && !csi) {
+      int32_t n_intv = 0;
+      ok = c.rd(&n_intv, 4) && n_intv >= 0 && (uint64_t)n_intv * 8 <= c.left();
+      if (ok) { R.lin.resize((size_t)n_intv); if (n_intv) c.rd(R.lin.data(), (size_t)n_intv * 8); }
+    }
+  }
+  if (ok && c.left() >= 8) { c.rd(&n_no_coor, 8); have_no_coor = true; }
+  if (!ok) { const bool was_csi = csi; *this = BamIndexFile(); err = was_csi ? "corrupt .csi index" : "corrupt .bai index"; return CORRUPT; }
+  return OK;
+}
+
+// lin_: a table of 16 KiB windows, whatever the index.  A .bai brings it.  From a .csi it is rebuilt as a lower bound: every bin with
+// a loffset is an anchor (p = the first base the bin covers, loffset) that holds from the first window that starts at or behind
+// p, and a window's value is the largest anchor at or in front of it (DESIGN section 20 has the argument)
 bool BamReader::load_index(const std::string &bam_path, std::string &err) {
   if (cram_) {
     if (!cram_->load_index(err)) return false;
     lin_.assign(1, {});                // has_index()
     return true;
   }
-  FILE *f = fopen((bam_path + ".bai").c_str(), "rb");
-  if (!f && bam_path.size() > 4) f = fopen((bam_path.substr(0, bam_path.size() - 4) + ".bai").c_str(), "rb");
-  if (!f) { err = "no .bai index next to " + bam_path; return false; }
-  auto rd = [&](void *p, size_t n) { return fread(p, 1, n, f) == n; };
-  fseeko(f, 0, SEEK_END);
-  const uint64_t f_size = (uint64_t)std::max<off_t>(ftello(f), 0);
-  fseeko(f, 0, SEEK_SET);
-  auto left = [&]() -> uint64_t { const off_t at = ftello(f); return at < 0 || (uint64_t)at > f_size ? 0 : f_size - (uint64_t)at; };
-  char magic[4];
-  int32_t n_ref = 0;
-  // (counts the file cannot hold -- a reference takes 8 bytes at least, an interval 8 -- are a corrupt index, not allocations)
-  bool ok = rd(magic, 4) && memcmp(magic, "BAI\1", 4) == 0 && rd(&n_ref, 4) && n_ref >= 0 && (uint64_t)n_ref * 8 <= left();
-  if (!ok) n_ref = 0;
-  lin_.assign((size_t)std::max(n_ref, 0), {});
-  ref_beg_.assign((size_t)std::max(n_ref, 0), 0);
+  BamIndexFile X;
+  if (X.load(bam_path, err) != BamIndexFile::OK) { lin_.clear(); return false; }
+  const size_t n_ref = X.refs.size();
+  lin_.assign(n_ref, {});
+  ref_beg_.assign(n_ref, 0);
   tail_beg_ = 0;
-  for (int32_t r = 0; ok && r < n_ref; ++r) {
-    int32_t n_bin = 0;
-    ok = rd(&n_bin, 4);
+  for (size_t r = 0; r < n_ref; ++r) {
+    BamIndexFile::Ref &R = X.refs[r];
     uint64_t first = 0;
-    for (int32_t k = 0; ok && k < n_bin; ++k) {
-      uint32_t bin = 0;
-      int32_t n_chunk = 0;
-      ok = rd(&bin, 4) && rd(&n_chunk, 4) && n_chunk >= 0;
-      for (int32_t c = 0; ok && c < n_chunk; ++c) {
-        uint64_t be[2];
-        ok = rd(be, 16);
-        if (ok && bin != 37450 && (first == 0 || be[0] < first)) first = be[0];   // 37450: the metadata pseudo-bin
-        if (ok && bin != 37450 && be[1] > tail_beg_) tail_beg_ = be[1];
+    for (const BamIndexFile::Bin &b : R.bins)
+      for (size_t k = b.chunk0; k < b.chunk0 + b.n_chunk; ++k) {
+        if (first == 0 || X.chunks[k].first < first) first = X.chunks[k].first;
+        if (X.chunks[k].second > tail_beg_) tail_beg_ = X.chunks[k].second;
       }
+    ref_beg_[r] = first;
+    if (!X.csi) { lin_[r].swap(R.lin); continue; }
+    const uint64_t l_ref = r < targets_.size() ? targets_[r].length : 0;
+    std::vector<uint64_t> &lin = lin_[r];
+    lin.assign((size_t)((l_ref + 16383) >> 14) + 64, 0);         // (and 1 Mbase behind l_ref, as the builder keeps)
+    for (const BamIndexFile::Bin &b : R.bins) {
+      if (!b.loffset) continue;
+      const uint64_t w = ((uint64_t)X.bin_start(b.bin) + 16383) >> 14;
+      if (w < lin.size() && b.loffset > lin[(size_t)w]) lin[(size_t)w] = b.loffset;
     }
-    int32_t n_intv = 0;
-    ok = ok && rd(&n_intv, 4) && n_intv >= 0 && (uint64_t)n_intv * 8 <= left();
-    if (ok) {
-      lin_[(size_t)r].resize((size_t)n_intv);
-      ok = n_intv == 0 || rd(lin_[(size_t)r].data(), (size_t)n_intv * 8);
-      ref_beg_[(size_t)r] = first;
-    }
+    for (size_t w = 1; w < lin.size(); ++w) if (lin[w] < lin[w - 1]) lin[w] = lin[w - 1];
   }
-  fclose(f);
-  if (!ok) { lin_.clear(); err = "corrupt .bai index"; return false; }
   if (lin_.empty()) lin_.push_back({});   // has_index() for a BAM without references
   return true;
 }

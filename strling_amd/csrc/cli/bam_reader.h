@@ -96,6 +96,32 @@ struct RecordBatch {
   strl_records view();  // pads seq4 with the 32 bytes of slack the kernels may read
 };
 
+// The index beside a BAM, parsed once for everything that reads one (BamReader::load_index, BgzfFeed::split_points,
+// BgzfFeed::indexed_records): a .bai (SAM spec 5.2) or a .csi (CSIv1: BGZF around magic, min_shift, depth, l_aux, n_ref and per
+// bin a loffset instead of the per-reference linear index).  Looked for as <bam>.bai, <stem>.bai, <bam>.csi, <stem>.csi: a
+// .bai that exists wins, so nothing changes for a file that has one.
+struct BamIndexFile {
+  struct Bin { uint32_t bin; uint64_t loffset; size_t chunk0, n_chunk; };      // chunks[chunk0, chunk0 + n_chunk); loffset 0 in a .bai
+  struct Ref {
+    std::vector<Bin> bins;              // without the pseudo-bin
+    bool meta = false, meta_bad = false;   // the pseudo-bin was there (meta_bad: not as two chunks, so without counts): ...
+    uint64_t span[2] = {0, 0}, n_mapped = 0, n_unmapped = 0;
+    std::vector<uint64_t> lin;          // .bai only: the linear index
+  };
+  bool csi = false;
+  int32_t min_shift = 14, depth = 5;    // a .bai is the scheme (14, 5)
+  std::vector<Ref> refs;
+  std::vector<std::pair<uint64_t, uint64_t>> chunks;
+  bool have_no_coor = false;            // the trailing count is optional in both formats
+  uint64_t n_no_coor = 0;
+  uint32_t meta_bin() const { return (uint32_t)(((1ull << (3 * (depth + 1))) - 1ull) / 7ull + 1ull); }
+  // the first base a bin covers
+  int64_t bin_start(uint32_t bin) const;
+  enum { OK = 0, MISSING = 1, CORRUPT = 2 };
+  // err: "no .bai index next to <bam> (nor a .csi)", "corrupt .bai index", "corrupt .csi index"
+  int load(const std::string &bam_path, std::string &err);
+};
+
 class BamReader {
  public:
   ~BamReader();
@@ -111,7 +137,8 @@ class BamReader {
   int64_t read(RecordBatch &b, int64_t max_records, std::string &err) { return read_until(b, max_records, INT32_MIN, 0, err); }
   // Same, but stops (without appending) at the first record that is not on stop_tid or starts at/after stop_pos.
   int64_t read_until(RecordBatch &b, int64_t max_records, int32_t stop_tid, int32_t stop_pos, std::string &err);
-  // Region read through the .bai linear index (hts-nim `b.query(tid, beg, end)`, collect.nim:141): appends every record
+  // Region read through the index's 16 KiB linear index (a .bai's own; from a .csi a conservative one rebuilt from the bins'
+  // loffsets: never behind the true start of a window) (hts-nim `b.query(tid, beg, end)`, collect.nim:141): appends every record
   // of `tid` from the first one that can overlap [beg, end) up to the first one starting at or after `end`, in file
   // order.  Records ending before `beg` may be included; consumers apply the overlap filter (strl_spanners does).
   bool load_index(const std::string &bam_path, std::string &err);

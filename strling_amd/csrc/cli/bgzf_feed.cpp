@@ -126,43 +126,20 @@ bool BgzfFeed::open_share(const BgzfFeed &whole, uint64_t start_coff, uint32_t f
   return true;
 }
 
-// BAI (SAM spec 5.2): every ioffset of the linear indices and every chunk start of the bins is the virtual offset of a record
+// every chunk start of the bins, every ioffset of a .bai's linear indices and every loffset of a .csi's bins is the virtual
+// offset of a record (BamIndexFile, bam_reader.h)
 std::vector<uint64_t> BgzfFeed::split_points(const std::string &path) {
   std::vector<uint64_t> v;
-  FILE *f = fopen((path + ".bai").c_str(), "rb");
-  if (!f && path.size() > 4) f = fopen((path.substr(0, path.size() - 4) + ".bai").c_str(), "rb");
-  if (!f) return v;
-  auto rd = [&](void *p, size_t n) { return fread(p, 1, n, f) == n; };
-  fseeko(f, 0, SEEK_END);
-  const uint64_t f_size = (uint64_t)std::max<off_t>(ftello(f), 0);
-  fseeko(f, 0, SEEK_SET);
-  auto left = [&]() -> uint64_t { const off_t at = ftello(f); return at < 0 || (uint64_t)at > f_size ? 0 : f_size - (uint64_t)at; };
-  char magic[4];
-  int32_t n_ref = 0;
-  bool ok = rd(magic, 4) && memcmp(magic, "BAI\1", 4) == 0 && rd(&n_ref, 4) && n_ref >= 0;
-  std::vector<uint64_t> buf;
-  for (int32_t r = 0; ok && r < n_ref; ++r) {
-    int32_t n_bin = 0;
-    ok = rd(&n_bin, 4) && n_bin >= 0;
-    for (int32_t k = 0; ok && k < n_bin; ++k) {
-      uint32_t bin = 0;
-      int32_t n_chunk = 0;
-      ok = rd(&bin, 4) && rd(&n_chunk, 4) && n_chunk >= 0 && (uint64_t)n_chunk * 16 <= left();      // (a count the file cannot hold: not an allocation)
-      if (!ok) break;
-      buf.resize((size_t)n_chunk * 2);
-      ok = n_chunk == 0 || rd(buf.data(), (size_t)n_chunk * 16);
-      if (ok && bin != 37450) for (int32_t c = 0; c < n_chunk; ++c) v.push_back(buf[(size_t)c * 2]);   // 37450: the metadata pseudo-bin
+  BamIndexFile X;
+  std::string err;
+  if (X.load(path, err) != BamIndexFile::OK) return v;
+  for (const BamIndexFile::Ref &R : X.refs) {
+    for (const BamIndexFile::Bin &b : R.bins) {
+      for (size_t k = b.chunk0; k < b.chunk0 + b.n_chunk; ++k) v.push_back(X.chunks[k].first);
+      if (b.loffset) v.push_back(b.loffset);
     }
-    int32_t n_intv = 0;
-    ok = ok && rd(&n_intv, 4) && n_intv >= 0 && (uint64_t)n_intv * 8 <= left();
-    if (ok && n_intv) {
-      buf.resize((size_t)n_intv);
-      ok = rd(buf.data(), (size_t)n_intv * 8);
-      if (ok) for (uint64_t x : buf) if (x) v.push_back(x);
-    }
+    for (uint64_t x : R.lin) if (x) v.push_back(x);
   }
-  fclose(f);
-  if (!ok) { v.clear(); return v; }
   std::sort(v.begin(), v.end());
   v.erase(std::unique(v.begin(), v.end()), v.end());
   return v;
@@ -170,44 +147,15 @@ std::vector<uint64_t> BgzfFeed::split_points(const std::string &path) {
 
 bool BgzfFeed::indexed_records(const std::string &path, uint64_t &n) {
   n = 0;
-  FILE *f = fopen((path + ".bai").c_str(), "rb");
-  if (!f && path.size() > 4) f = fopen((path.substr(0, path.size() - 4) + ".bai").c_str(), "rb");
-  if (!f) return false;
-  auto rd = [&](void *p, size_t k) { return fread(p, 1, k, f) == k; };
-  fseeko(f, 0, SEEK_END);
-  const uint64_t f_size = (uint64_t)std::max<off_t>(ftello(f), 0);
-  fseeko(f, 0, SEEK_SET);
-  auto left = [&]() -> uint64_t { const off_t at = ftello(f); return at < 0 || (uint64_t)at > f_size ? 0 : f_size - (uint64_t)at; };
-  char magic[4];
-  int32_t n_ref = 0;
-  bool ok = rd(magic, 4) && memcmp(magic, "BAI\1", 4) == 0 && rd(&n_ref, 4) && n_ref >= 0;
+  BamIndexFile X;
+  std::string err;
+  if (X.load(path, err) != BamIndexFile::OK || !X.have_no_coor) return false;      // (n_no_coor is optional in the format; samtools writes it -- without it the count is not known)
   uint64_t total = 0;
-  std::vector<uint64_t> buf;
-  for (int32_t r = 0; ok && r < n_ref; ++r) {
-    int32_t n_bin = 0;
-    ok = rd(&n_bin, 4) && n_bin >= 0;
-    bool meta = false;
-    for (int32_t k = 0; ok && k < n_bin; ++k) {
-      uint32_t bin = 0;
-      int32_t n_chunk = 0;
-      ok = rd(&bin, 4) && rd(&n_chunk, 4) && n_chunk >= 0 && (uint64_t)n_chunk * 16 <= left();      // (a count the file cannot hold: not an allocation)
-      if (!ok) break;
-      buf.resize((size_t)n_chunk * 2);
-      ok = n_chunk == 0 || rd(buf.data(), (size_t)n_chunk * 16);
-      if (ok && bin == 37450) {
-        if (n_chunk != 2) ok = false;
-        else { total += buf[2] + buf[3]; meta = true; }      // chunk 1 = (n_mapped, n_unmapped)
-      }
-    }
-    if (ok && n_bin > 0 && !meta) ok = false;                 // a reference with records and no counts: an index written without them
-    int32_t n_intv = 0;
-    ok = ok && rd(&n_intv, 4) && n_intv >= 0 && (uint64_t)n_intv * 8 <= left() && fseeko(f, (off_t)n_intv * 8, SEEK_CUR) == 0;
+  for (const BamIndexFile::Ref &R : X.refs) {
+    if (R.meta_bad || (!R.bins.empty() && !R.meta)) return false;          // a reference with records and no counts: an index written without them
+    total += R.n_mapped + R.n_unmapped;
   }
-  uint64_t no_coor = 0;
-  ok = ok && rd(&no_coor, 8);                                 // (optional in the format; samtools writes it -- without it the count is not known)
-  fclose(f);
-  if (!ok) return false;
-  n = total + no_coor;
+  n = total + X.n_no_coor;
   return true;
 }
 

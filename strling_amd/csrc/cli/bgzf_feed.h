@@ -27,10 +27,10 @@ class BgzfFeed {
   // in its first block's inflated bytes.  Both ends are record starts taken from the .bai (split_points).
   bool open_share(const BgzfFeed &whole, uint64_t start_coff, uint32_t first_off, uint64_t end_coff, uint32_t end_uoff, std::string &err);
   void close();
-  // Virtual offsets (coffset << 16 | uoffset) of record starts named by the .bai next to `path` (linear index + bin chunk
-  // starts), ascending and distinct; empty when there is no usable index.
+  // Virtual offsets (coffset << 16 | uoffset) of record starts named by the index next to `path` (BamIndexFile: a .bai's linear
+  // index + bin chunk starts, a .csi's bin chunk starts + loffsets), ascending and distinct; empty when there is no usable index.
   static std::vector<uint64_t> split_points(const std::string &path);
-  // the number of records of an indexed BAM from the index's metadata pseudo-bins (bin 37450 of every reference: mapped /
+  // the number of records of an indexed BAM from the index's metadata pseudo-bins (bin 37450 of every reference of a .bai, the scheme's of a .csi: mapped /
   // placed-unmapped records) and the count of unplaced records behind the last reference -- what `samtools idxstats` adds up.
   // false: no index, or one written without them
   static bool indexed_records(const std::string &path, uint64_t &n);

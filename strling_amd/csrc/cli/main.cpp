@@ -327,6 +327,38 @@ static void setup_genome(strl_ctx *ctx, const Args &a, const std::vector<BamTarg
 }
 
 static int extract_front(const Args &a, const std::string &bam, const std::string &bin, double p, uint8_t min_mapq, bool verbose);
+static bool write_bgzf(const std::string &path, const std::vector<uint8_t> &payload, ThreadPool &pool, std::string &why);
+// --csi [-m N] of `bamindex` and `extract --write-index`: min_shift of the CSI scheme, -1 without --csi; usage errors end the process
+static int csi_min_shift(const Args &a, const char *usage) {
+  if (!a.flag("csi")) {
+    if (a.flag("min-shift")) quit("-m / --min-shift needs --csi\n%s", usage);
+    return -1;
+  }
+  const std::string v = a.get("min-shift", "14");
+  const int m = atoi(v.c_str());
+  if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || m < 8 || m > 24) quit("--min-shift must be in [8, 24]\n%s", usage);
+  return m;
+}
+// the bytes of an index to `out` through a temporary name (a failed run leaves no half index); bgzf: in BGZF blocks with the EOF
+// block, as samtools writes a .csi.  false: why
+static bool write_index_file(const std::string &out, const std::vector<uint8_t> &bytes, bool bgzf, std::string &why, ThreadPool *pool = nullptr) {
+  const std::string tmp = out + ".tmp." + std::to_string((long long)getpid());
+  bool ok;
+  if (bgzf) {
+    ThreadPool own(pool ? 1 : 4);
+    ok = write_bgzf(tmp, bytes, pool ? *pool : own, why);
+    if (!ok && why.compare(0, 12, "cannot write") != 0) why = "cannot write " + tmp + ": " + why;
+  } else {
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) { why = "cannot write " + tmp + ": " + strerror(errno); return false; }
+    const bool wrote = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    ok = (fclose(f) == 0) && wrote;
+    if (!ok) why = "cannot write " + out + ": " + strerror(errno);
+  }
+  if (ok && rename(tmp.c_str(), out.c_str()) != 0) { ok = false; why = "cannot write " + out + ": " + strerror(errno); }
+  if (!ok) (void)unlink(tmp.c_str());
+  return ok;
+}
 static bool g_index_done = false;      // extract --write-index: the index of the first pass has been written or refused; a repeated extraction leaves it alone
 constexpr int EXTRACT_AGAIN_ON_HOST = -77, EXTRACT_AGAIN_HOST_FRONT = -78, EXTRACT_AGAIN_BY_CHUNKS = -79;
 
@@ -340,14 +372,18 @@ static int extract_main(int argc, char **argv) {
       "  --gpus=N                   spread the file over N GPUs (a contiguous share each: inflate, parse and scoring there; the pair logic on the first) (default: 1)\n"
       "  --device=K                 the GPU this process uses (the first of --gpus N) (default: 0; STRL_DEVICE)\n"
       "  --write-index              also write the bam's index (.bai), built on the GPU in the same pass over the file (one GPU, BAM only)\n"
-      "  --index-out=OUT.bai        where --write-index writes it (default: <bam>.bai)\n"
+      "  --index-out=OUT.bai        where --write-index writes it (default: <bam>.bai; with --csi <bam>.csi)\n"
+      "  --csi                      with --write-index: a CSI index (.csi), which also holds contigs longer than 2^29 bases\n"
+      "  -m, --min-shift=N          with --csi: bases per window of the smallest bins = 2^N, N in [8, 24] (default: 14)\n"
       "  -v, --verbose\n  -h, --help                 Show this help\n";
   if (argc <= 2) { fputs(usage, stdout); return 0; }
   const Args a = parse(argc, argv, 2, {{"fasta", 'f', true}, {"genome-repeats", 'g', true}, {"proportion-repeat", 'p', true},
                                        {"min-mapq", 'q', true}, {"verbose", 'v', false}, {"batch", 'B', true}, {"gpus", 'G', true}, {"device", 'D', true},
-                                       {"write-index", 0, false}, {"index-out", 0, true}}, usage);
+                                       {"write-index", 0, false}, {"index-out", 0, true}, {"csi", 0, false}, {"min-shift", 'm', true}}, usage);
   if (a.pos.size() != 2) quit("expected 2 arguments (bam, bin)\n%s", usage);
   if (a.flag("index-out") && !a.flag("write-index")) quit("--index-out needs --write-index\n%s", usage);
+  if (a.flag("csi") && !a.flag("write-index")) quit("--csi needs --write-index\n%s", usage);
+  (void)csi_min_shift(a, usage);
   if (a.flag("write-index")) {       // what cannot build the index is refused before anything is read
     const char *fe = getenv("STRL_FRONT"), *pe = getenv("STRL_PAIR");
     if (atoi(a.get("gpus", "1").c_str()) > 1)
@@ -677,7 +713,8 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   const size_t chunk_bytes = std::max<size_t>((size_t)1 << 20, chunk_blocks * 20000);       // compressed bytes one chunk may span
   // --write-index: the .bai as a by-product of this pass (strl_front_index_*).  Whatever goes wrong with it is one line on stderr
   // and no index; the extraction goes on as without the flag.
-  const std::string index_out = a.get("index-out", (bam + ".bai").c_str());
+  const int idx_min_shift = a.flag("csi") ? atoi(a.get("min-shift", "14").c_str()) : -1;       // (checked by extract_main)
+  const std::string index_out = a.get("index-out", (bam + (idx_min_shift >= 0 ? ".csi" : ".bai")).c_str());
   std::atomic<bool> idx_on{a.flag("write-index") && !g_index_done && G == 1};      // (read by the thread that stages the chunks ahead)
   auto idx_give_up = [&](const std::string &why) {
     if (!idx_on) return;
@@ -880,7 +917,7 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   if (idx_on) {
     std::vector<int32_t> l_ref;
     for (const BamTarget &t : feed.targets()) l_ref.push_back((int32_t)std::min<uint64_t>(t.length, 0x7fffffffu));
-    if (strl_front_index_begin(ctx, l_ref.data(), 0)) idx_give_up(strl_last_error());
+    if (idx_min_shift >= 0 ? strl_front_index_begin_csi(ctx, l_ref.data(), 0, idx_min_shift, -1) : strl_front_index_begin(ctx, l_ref.data(), 0)) idx_give_up(strl_last_error());
   }
   if (verbose) {
     std::string devs;
@@ -1254,17 +1291,12 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
     std::vector<uint8_t> bytes;
     int irc = strl_front_index_finish(ctx, &nbytes, &info);
     if (!irc) { bytes.resize((size_t)nbytes + 1); irc = strl_bamindex_fetch(ctx, bytes.data(), bytes.size()); }
+    std::string why;
     if (irc) idx_give_up(strl_last_error());
     else {
-      const std::string tmp = index_out + ".tmp." + std::to_string((long long)getpid());
-      FILE *f = fopen(tmp.c_str(), "wb");
-      const bool wrote = f && fwrite(bytes.data(), 1, (size_t)nbytes, f) == (size_t)nbytes;
-      const bool closed = f && fclose(f) == 0;
-      if (!wrote || !closed || rename(tmp.c_str(), index_out.c_str()) != 0) {
-        const std::string why = "cannot write " + (f ? index_out : tmp) + ": " + strerror(errno);
-        if (f) (void)unlink(tmp.c_str());
-        idx_give_up(why);
-      } else if (verbose)
+      bytes.resize((size_t)nbytes);
+      if (!write_index_file(index_out, bytes, idx_min_shift >= 0, why)) idx_give_up(why);
+      else if (verbose)
         fprintf(stderr, "[strling] index: %llu records (%llu without a reference), %llu runs resident on the device, %llu chunks, %llu bytes -> %s (sort, merge and write %.3f s)\n",
                 (unsigned long long)info.n_records, (unsigned long long)info.n_no_coor, (unsigned long long)info.n_runs, (unsigned long long)info.n_chunks,
                 (unsigned long long)nbytes, index_out.c_str(), secs(ti0, now()));
@@ -1871,9 +1903,10 @@ static void plan_region(const BamReader &rd, int fd, int32_t tid, int64_t beg, i
 // front end: BgzfFeed walks the block headers, the compressed bytes go into page-locked buffers, chunk ci + 1 is read beside the
 // push of chunk ci.  get_ctx is asked for the context only once the file is open, the buffers are there and the first chunk is
 // read: a caller brings the context up on a thread beside that.  last_use: the process ends behind this (nothing is freed).
+// csi_min_shift >= 0: the CSI index with that min_shift and samtools' depth rule instead, its payload in BGZF blocks.
 // false: `why` says what the file was refused for (status = the library's, STRL_ERR_IO for the output)
 static bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::string &out, bool verbose, bool last_use, std::string &why,
-                      int &status) {
+                      int &status, int csi_min_shift = -1) {
   const auto t0 = std::chrono::steady_clock::now();
   status = STRL_ERR_IO;
   BgzfFeed feed;
@@ -1919,7 +1952,8 @@ static bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, c
   if (!(ctx = get_ctx(why))) { status = STRL_ERR_NO_DEVICE; release(); return false; }
   std::vector<int32_t> l_ref;
   for (const BamTarget &t : feed.targets()) l_ref.push_back((int32_t)std::min<uint64_t>(t.length, 0x7fffffffu));
-  int rc = strl_bamindex_begin(ctx, (int32_t)l_ref.size(), l_ref.data(), feed.first_record_offset());
+  int rc = csi_min_shift >= 0 ? strl_bamindex_begin_csi(ctx, (int32_t)l_ref.size(), l_ref.data(), feed.first_record_offset(), csi_min_shift, -1)
+                              : strl_bamindex_begin(ctx, (int32_t)l_ref.size(), l_ref.data(), feed.first_record_offset());
   if (!rc) rc = strl_bamindex_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes);
   if (rc) return fail(rc);
   for (uint64_t ci = 0;; ++ci) {
@@ -1940,12 +1974,7 @@ static bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, c
   if (!last_use) (void)strl_bamindex_end(ctx);
   // (the page-locked buffers are left to the end of the process: unlocking them stalls the device -- as `call` leaves its own)
   status = STRL_ERR_IO;
-  const std::string tmp = out + ".tmp." + std::to_string((long long)getpid());
-  FILE *f = fopen(tmp.c_str(), "wb");
-  if (!f) { why = "cannot write " + tmp + ": " + strerror(errno); return false; }
-  const bool wrote = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
-  const bool closed = fclose(f) == 0;
-  if (!wrote || !closed || rename(tmp.c_str(), out.c_str()) != 0) { why = "cannot write " + out + ": " + strerror(errno); (void)unlink(tmp.c_str()); return false; }
+  if (!write_index_file(out, bytes, csi_min_shift >= 0, why, &pool)) return false;
   if (verbose)
     fprintf(stderr, "[strling] bamindex: %llu records (%llu without a reference), %llu runs resident on the device, %llu chunks, %llu bytes -> %s in %.3f s\n",
             (unsigned long long)info.n_records, (unsigned long long)info.n_no_coor, (unsigned long long)info.n_runs, (unsigned long long)info.n_chunks,
@@ -1958,12 +1987,16 @@ static bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, c
 static int bamindex_main(int argc, char **argv) {
   const char *usage =
       "strling bamindex\n\nUsage:\n  strling bamindex [options] bam\n\nArguments:\n  bam              path to a coordinate-sorted bam file\n\nOptions:\n"
-      "  -o, --output=OUT.bai       where to write the index (default: <bam>.bai)\n  -D, --device=K             GPU to use (default: 0)\n"
+      "  -o, --output=OUT.bai       where to write the index (default: <bam>.bai; with --csi <bam>.csi)\n"
+      "      --csi                  write a CSI index (.csi) instead, which also holds contigs longer than 2^29 bases\n"
+      "  -m, --min-shift=N          with --csi: bases per window of the smallest bins = 2^N, N in [8, 24] (default: 14)\n"
+      "  -D, --device=K             GPU to use (default: 0)\n"
       "  -v, --verbose\n  -h, --help                 Show this help\n";
   if (argc <= 2) { fputs(usage, stdout); return 0; }
-  const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"device", 'D', true}, {"verbose", 'v', false}}, usage);
+  const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"device", 'D', true}, {"verbose", 'v', false}, {"csi", 0, false}, {"min-shift", 'm', true}}, usage);
   if (a.pos.size() != 1) quit("expected 1 argument (bam)\n%s", usage);
-  const std::string bam = a.pos[0], out = a.get("output", (bam + ".bai").c_str());
+  const int min_shift = csi_min_shift(a, usage);
+  const std::string bam = a.pos[0], out = a.get("output", (bam + (min_shift >= 0 ? ".csi" : ".bai")).c_str());
   if (CramFile::is_cram(bam)) quit("[strling] bamindex: %s is a CRAM; its index (.crai) is out of scope: this command writes the .bai of a BAM", bam.c_str());
   if (!file_exists(bam)) quit("couldn't open bam");
   set_device0(a.get("device", ""));
@@ -1976,7 +2009,7 @@ static int bamindex_main(int argc, char **argv) {
   auto get_ctx = [&](std::string &why) -> strl_ctx * { if (ctx_thread.joinable()) ctx_thread.join(); if (ctx_rc) why = ctx_err; return ctx_rc ? nullptr : ctx; };
   std::string why;
   int status = 0;
-  const bool ok = build_bai(get_ctx, bam, out, a.flag("verbose"), true, why, status);
+  const bool ok = build_bai(get_ctx, bam, out, a.flag("verbose"), true, why, status, min_shift);
   if (ctx_thread.joinable()) ctx_thread.join();
   g_bg_init = nullptr;
   if (!ok) { if (ctx) strl_ctx_destroy(ctx); quit("[strling] bamindex: %s (status %d)", why.c_str(), status); }
@@ -1995,7 +2028,8 @@ static int call_main(int argc, char **argv) {
       "  -l, --loci=LOCI            Annoated bed file specifying additional STR loci to genotype. Format is: chr start stop repeatunit [name]\n"
       "  -b, --bounds=BOUNDS        STRling -bounds.txt file (usually produced by strling merge) specifying additional STR loci to genotype.\n"
       "  -o, --output-prefix=OUTPUT_PREFIX\n                             prefix for output files (default: strling)\n"
-      "      --make-index           when the bam has no .bai, build one on the GPU and write it beside the bam (default: exit)\n  -v, --verbose\n  -h, --help                 Show this help\n";
+      "      --make-index           when the bam has no index, build one on the GPU and write it beside the bam: a .bai, or a .csi\n"
+      "                             when a reference is longer than 2^29 bases (default: exit)\n  -v, --verbose\n  -h, --help                 Show this help\n";
   if (argc <= 2) { fputs(usage, stdout); return 0; }
   const Args a = parse(argc, argv, 2, {{"fasta", 'f', true}, {"min-support", 'm', true}, {"min-clip", 'c', true}, {"min-clip-total", 't', true},
                                        {"min-mapq", 'q', true}, {"loci", 'l', true}, {"bounds", 'b', true}, {"output-prefix", 'o', true},
@@ -2056,15 +2090,23 @@ static int call_main(int argc, char **argv) {
   if (!frag_on_device) fragment_length_distribution(bam, frag);                       // call.nim:92
   BamReader rd;
   std::string err;
-  // --make-index: a BAM without a .bai gets one from the device (build_bai) before it is opened with its index
-  if (a.flag("make-index") && !CramFile::is_cram(bam) && file_exists(bam) && !file_exists(bam + ".bai") &&
-      !(bam.size() > 4 && file_exists(bam.substr(0, bam.size() - 4) + ".bai"))) {
+  // --make-index: a BAM without an index gets one from the device (build_bai) before it is opened with its index: a .bai, or --
+  // the header names a reference a .bai cannot address -- a .csi with the default scheme
+  if (a.flag("make-index") && !CramFile::is_cram(bam) && file_exists(bam) && !file_exists(bam + ".bai") && !file_exists(bam + ".csi") &&
+      !(bam.size() > 4 && (file_exists(bam.substr(0, bam.size() - 4) + ".bai") || file_exists(bam.substr(0, bam.size() - 4) + ".csi")))) {
     ctx_thread.join();
     if (!ctx_rc) {
       std::string why;
       int status = 0;
-      if (verbose) fprintf(stderr, "[strling] no index next to %s: building %s.bai on the GPU (--make-index)\n", bam.c_str(), bam.c_str());
-      if (!build_bai([&](std::string &) { return ctx; }, bam, bam + ".bai", verbose, false, why, status)) {
+      bool long_ref = false;
+      {
+        BamReader hdr;
+        std::string herr;
+        if (hdr.open(bam, herr)) for (const BamTarget &t : hdr.targets()) long_ref = long_ref || t.length > (1u << 29);
+      }
+      const std::string idx = bam + (long_ref ? ".csi" : ".bai");
+      if (verbose) fprintf(stderr, "[strling] no index next to %s: building %s on the GPU (--make-index)\n", bam.c_str(), idx.c_str());
+      if (!build_bai([&](std::string &) { return ctx; }, bam, idx, verbose, false, why, status, long_ref ? 14 : -1)) {
         bin_thread.join();
         if (fr_pin_thread.joinable()) fr_pin_thread.join();
         quit("[strling] call --make-index: %s (status %d)", why.c_str(), status);
@@ -2839,7 +2881,7 @@ static bool write_bgzf(const std::string &path, const std::vector<uint8_t> &payl
 
 static int pull_main(int argc, char **argv) {
   const char *usage =
-      "strling pull\n\nUsage:\n  strling pull [options] bam [region ...]\n\nArguments:\n  bam              path to a coordinate-sorted bam file with its .bai index\n"
+      "strling pull\n\nUsage:\n  strling pull [options] bam [region ...]\n\nArguments:\n  bam              path to a coordinate-sorted bam file with its .bai or .csi index\n"
       "  region           NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive)\n\nOptions:\n"
       "  -o, --output-bam=OUT.bam   path to output bam (default: extracted.bam)\n  -L, --regions=BED          regions as BED rows: chrom start end\n"
       "  -f, --fasta=FASTA          accepted for the reference's command line; a bam needs none\n"
@@ -3201,7 +3243,7 @@ int main(int argc, char **argv) {
       "  merge    :   merge putitive STR loci from multiple samples. Only required for joint calling.\n  call     :   call STRs\n"
       "  index    :   identify large STRs in the reference genome, to produce ref.fasta.str.\n"
       "  outliers :   cohort STR outlier scores from the call outputs of many samples (scripts/strling-outliers.py).\n"
-      "  bamindex :   build the index (.bai) of a coordinate-sorted BAM on the GPU (what `samtools index` writes).\n"
+      "  bamindex :   build the index (.bai, or .csi with --csi) of a coordinate-sorted BAM on the GPU (what `samtools index` writes).\n"
       "  pull     :   write a region's reads and their mates to a small BAM, for debugging (the reference's pull_region).\n";      // strling.nim:18-24
   if (argc < 2) { fputs(top, stdout); return 1; }
   const std::string cmd = argv[1];

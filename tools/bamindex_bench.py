@@ -1,6 +1,6 @@
 """`strling bamindex` on a coordinate-sorted BAM: wall clock beside `strling extract` of another build on the same file, one JSON line.
 
-    python tools/bamindex_bench.py [--pairs N] [--parent DIR] [--repeats K] [--trace OUTDIR] [--dir D]
+    python tools/bamindex_bench.py [--pairs N] [--parent DIR] [--repeats K] [--trace OUTDIR] [--dir D] [--csi]
 
 The input is the whole-genome BAM `bench.py --full` caches (tools/e2e_bench.py: 2^28 pairs, 57 GB) when its side-car is in the
 work directory; else a file of --pairs pairs from the same writer (bamio.write_bam_slabs, zlib level 6, binned qualities, aux
@@ -9,6 +9,8 @@ tags), whose size the line states.  One after the other on one box:
   * `strling extract` of the build in --parent (a checkout of the parent commit with `python -m strling_amd.build` run inside it;
     default: this build) on the same file, K runs -- the yardstick: the index pass inflates, checks and scans the same bytes and
     does strictly less behind the scan.  The ratio is reported, no margin asserted;
+  * --csi: `strling bamindex --csi -v -o <scratch>.csi BAM` as well, in turn with the two above (the same kernels with the binning
+    scheme as an argument, the payload deflated into BGZF blocks: expected within run-to-run noise of the .bai; no threshold);
   * the device-built index against the writer's own .bai, as structures (every virtual offset turned into an offset of the
     inflated stream): bins and chunk lists, linear index, the pseudo-bin's numbers, n_no_coor;
   * --trace: two more `bamindex` runs under `rocprofv3 --kernel-trace --stats` (runs of their own), as shipped and with
@@ -92,6 +94,7 @@ def main():
     ap.add_argument("--trace", default="", help="directory for the kernel table of one more run under rocprofv3 --kernel-trace --stats")
     ap.add_argument("--dir", default=None, help="where the input lives (default: e2e_bench's work directory)")
     ap.add_argument("--no-compare", action="store_true", help="skip the structural comparison with the writer's .bai")
+    ap.add_argument("--csi", action="store_true", help="also time `bamindex --csi` on the same file, in turn with the .bai")
     a = ap.parse_args()
     full = 2 ** 28
     d = a.dir or e2e_bench.work_dir(full * 2 * 115)
@@ -104,7 +107,8 @@ def main():
     out_bai, out_bin = os.path.join(scratch, "dev.bai"), os.path.join(scratch, "x.bin")
     res = {"tool": "bamindex_bench", "input": inp.get("input"), "reads": inp["reads"], "bam_MB": inp["bam_MB"], "whole_genome_cache": n_pairs == full,
            "yardstick": "the parent commit's `strling extract`" if a.parent else "THIS build's `strling extract` (no --parent given)"}
-    idx, ext = [], []
+    idx, ext, csi = [], [], []
+    out_csi = os.path.join(scratch, "dev.csi")
     for k in range(a.repeats):          # alternating, one process at a time
         r, w = _timed([cli, "bamindex", "-v", "-o", out_bai, bam])
         if r.returncode != 0:
@@ -112,6 +116,13 @@ def main():
             sys.exit(r.returncode)
         idx.append(round(w, 3))
         res["bamindex_says"] = r.stderr.strip().splitlines()[-1]
+        if a.csi:
+            r, w = _timed([cli, "bamindex", "--csi", "-v", "-o", out_csi, bam])
+            if r.returncode != 0:
+                sys.stderr.write(r.stderr[-4000:])
+                sys.exit(r.returncode)
+            csi.append(round(w, 3))
+            res["bamindex_csi_says"] = r.stderr.strip().splitlines()[-1]
         r, w = _timed([parent_cli, "extract", "-g", bed, bam, out_bin])
         if r.returncode != 0:
             sys.stderr.write(r.stderr[-4000:])
@@ -120,6 +131,9 @@ def main():
     res["bamindex_wall_s"], res["extract_wall_s"] = idx, ext
     res["ratio_bamindex_to_extract_best"] = round(min(idx) / min(ext), 3)
     res["bai_bytes"] = os.path.getsize(out_bai)
+    if a.csi:
+        res["bamindex_csi_wall_s"], res["csi_file_bytes"] = csi, os.path.getsize(out_csi)
+        res["ratio_csi_to_bai_best"] = round(min(csi) / min(idx), 3)
     if not a.no_compare:
         t = time.time()
         at = _block_starts(bam)

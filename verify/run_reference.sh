@@ -29,5 +29,19 @@ if command -v samtools > /dev/null 2>&1; then
 else
   echo "SKIP  cram   (samtools not on PATH: the CRAM reader stays checked against strling_amd/cramio.py's files only)"
 fi
+# ---- CSI: the index `strling bamindex --csi` writes against `samtools index -c` of the same file, and samtools' .csi read by strling.
+# verify/run_reference.sh /path/to/strling_amd/lib/strling (needs a GPU for bamindex, samtools and python3 on PATH); skipped otherwise.
+if command -v samtools > /dev/null 2>&1 && "$S" bamindex 2> /dev/null | grep -q -- --csi; then
+  cp "$D/widths.bam" "$T/csi_ours.bam" && cp "$D/widths.bam" "$T/csi_theirs.bam"
+  "$S" bamindex --csi "$T/csi_ours.bam" > "$T/csi.log" 2>&1 && samtools index -c "$T/csi_theirs.bam"
+  if python3 "$(dirname "$0")/compare_csi.py" "$T/csi_ours.bam.csi" "$T/csi_theirs.bam.csi" > "$T/csi.cmp" 2>&1; then echo "PASS  csi   (bins, chunks modulo compress_binning, loffsets = samtools index -c)"
+  else echo "FAIL  csi   (see $T/csi.cmp)"; fail=1; fi
+  "$S" _region "$T/csi_ours.bam" 0 0 100000 > "$T/csi_ours.region" 2>&1; "$S" _region "$T/csi_theirs.bam" 0 0 100000 > "$T/csi_theirs.region" 2>&1
+  check csi_read "$T/csi_theirs.region" "$T/csi_ours.region" "a .csi that samtools wrote reads like ours"
+  samtools view "$T/csi_ours.bam" "$(samtools view -H "$T/csi_ours.bam" | awk '/^@SQ/ { sub("SN:", "", $2); print $2; exit }')" > "$T/csi_htslib.sam" 2> "$T/csi_htslib.log" \
+    && echo "PASS  csi_htslib   (htslib reads the .csi strling wrote)" || { echo "FAIL  csi_htslib   (see $T/csi_htslib.log)"; fail=1; }
+else
+  echo "SKIP  csi    (needs samtools and a strling with bamindex --csi: the CSI writer and reader stay checked against the specification, bamio.write_csi and the .bai only)"
+fi
 if [ $fail = 0 ]; then echo "all assumptions confirmed"; else echo "outputs kept in $T (the .tsv beside an expected .bin lists its treads)"; fi
 exit $fail
