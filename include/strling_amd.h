@@ -360,7 +360,7 @@ typedef struct {
   float ms_sort, ms_sweep, ms_bounds;
 } strl_cluster_stats;
 
-#define STRL_MODE_MERGE 0 /* merge.nim:172-187: tid<0 dropped on load, has_per_sample_reads gate, qname_id = sample */
+#define STRL_MODE_MERGE 0 /* merge.nim:172-187: tid<0 dropped on load, has_per_sample_reads gate, qname_id = sample in [0, 2^32) */
 #define STRL_MODE_CALL 1  /* call.nim:223-235: unplaced groups reported, no per-sample gate */
 /* Group treads by (tid, repeat), stable-sort by position (call.nim:118-130 / merge.nim:121-135),
  * cluster every group and derive the gated Bounds.  Output order = the reference's order (Nim Table

@@ -203,6 +203,7 @@ def load(build_if_missing=True):
     L.strl_cluster_resident.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_uint32, C.c_int32, C.c_uint16, C.c_uint16, C.c_uint16,
                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                         C.POINTER(ClusterStats)]
+    L.strl_ctx_set_treads.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.strl_ctx_tail_stream.argtypes = [C.c_void_p]
     L.strl_ctx_tail_stream.restype = C.c_void_p
     L.strl_cluster_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
@@ -581,6 +582,12 @@ class Context:
         _check(self.L.strl_cluster(self.h, _ptr(t), t.size, mode, window, min_support, min_clip, min_clip_total, max_clip_dist,
                                    out.ctypes.data, cap, C.byref(no), unpl.ctypes.data, unpl.size, C.byref(nu), C.byref(st)))
         return out[:no.value].copy(), unpl[:nu.value].copy(), st
+
+    def set_treads(self, treads):
+        """make a host array of treads the context's resident treads, as extract_device would have left them
+        (strl_ctx_set_treads): what cluster_resident clusters next"""
+        t = np.ascontiguousarray(treads, TREAD_DTYPE)
+        _check(self.L.strl_ctx_set_treads(self.h, _ptr(t), t.size))
 
     def cluster_resident(self, n_tid, window, min_support=5, min_clip=0, min_clip_total=0, max_clip_dist=200, pos_bits=0, fetch=True,
                          cap=None):

@@ -44,7 +44,7 @@ struct RawBounds {  // one candidate row per (candidate cluster, half)
 
 // device-side counters of one clustering pass
 constexpr int CC_N = 0, CC_NGROUPS = 1, CC_NCAND = 2, CC_NCLUSTERS = 3, CC_BIG = 4, CC_ERR = 5, CC_NSEEN = 6, CC_WORDS = 16;   // CC_NSEEN: *d_n as the pass saw it
-constexpr uint32_t CERR_UNIT = 1u, CERR_TID = 2u, CERR_POS = 4u, CERR_CAND = 8u, CERR_BIG = 16u;
+constexpr uint32_t CERR_UNIT = 1u, CERR_TID = 2u, CERR_POS = 4u, CERR_CAND = 8u, CERR_BIG = 16u, CERR_SAMPLE = 32u;
 
 struct ClusterParams {
   const uint32_t *d_n;      // number of treads (device)
@@ -334,6 +334,7 @@ struct KeyParams {
   const uint64_t *first_key;    // ... the emission key of an unordered tread (treads straight from the pair logic), or nullptr
   uint32_t *cnt;
   int composite, pos_bits, fold;
+  int merge;        // merge mode: qname_id is the sample index the per-sample gate counts, kept in 32 bits
   int32_t n_tid;    // tids must be < n_tid
 };
 __global__ __launch_bounds__(256) void tread_keys_kernel(KeyParams K) {
@@ -360,6 +361,7 @@ __global__ __launch_bounds__(256) void tread_keys_kernel(KeyParams K) {
     ++len;
   }
   if (t.tid < -1 || t.tid >= K.n_tid) err |= CERR_TID;
+  if (K.merge && ((uint64_t)t.qname_id >> 32)) err |= CERR_SAMPLE;   // two samples must not meet in the low 32 bits
   const uint64_t gkey = ((uint64_t)(uint32_t)(t.tid + 1) << 15) | ((uint64_t)len << 12) | code;
   K.pos_in[i] = t.position;
   K.split_in[i] = t.split;
@@ -634,7 +636,7 @@ static int cluster_device_pass(strl_ctx *c, const strl_tread *treads, const uint
   K.d_n = d_n; K.n_max = n_max; K.treads = treads; K.key = B[B_KEY0].as<uint64_t>(); K.val = B[B_VAL0].as<uint32_t>();
   K.pos_in = d_posin; K.sample_in = d_samplein; K.split_in = d_splitin; K.gkey_in = R.composite ? nullptr : B[B_GKEY].as<uint64_t>();
   K.first_in = B[B_FIRST].as<uint64_t>(); K.first_key = R.first_key;
-  K.cnt = cnt; K.composite = R.composite ? 1 : 0; K.pos_bits = R.pos_bits; K.fold = R.fold ? 1 : 0; K.n_tid = R.n_tid;
+  K.cnt = cnt; K.composite = R.composite ? 1 : 0; K.pos_bits = R.pos_bits; K.fold = R.fold ? 1 : 0; K.merge = R.mode == STRL_MODE_MERGE ? 1 : 0; K.n_tid = R.n_tid;
   hipLaunchKernelGGL(tread_keys_kernel, dim3(nb), dim3(TB), 0, st, K);
   uint64_t *sk = nullptr;
   uint32_t *sv = nullptr;
@@ -754,6 +756,7 @@ static int cluster_collect(strl_ctx *c, const std::vector<std::pair<uint64_t, ui
   if (err & CERR_UNIT) { set_error("a tread's repeat unit is not a NUL-padded ACGT string"); return STRL_ERR_ARG; }
   if (err & CERR_TID) { set_error("a tread's tid is outside [-1, %d)", R.n_tid); return STRL_ERR_ARG; }
   if (err & CERR_POS) { set_error("a tread's position needs more than %d bits", R.pos_bits); return STRL_ERR_ARG; }
+  if (err & CERR_SAMPLE) { set_error("merge mode: a tread's qname_id (its sample index) is outside [0, 2^32)"); return STRL_ERR_ARG; }
   if (err & (CERR_CAND | CERR_BIG)) { set_error("clustering scratch exhausted (internal capacity)"); return STRL_ERR_CAPACITY; }
   R.n = n_dev;
   const uint32_t n1 = std::max<uint32_t>(R.n_max, 1);
