@@ -1,9 +1,11 @@
 // bgzf_feed.h -- the host side of the device BAM front end (strl_front_*): a thread walks the BGZF block headers ahead of the
 // consumer (one 26-byte pread per block: the trailer of a block and the header of the next sit side by side), and the consumer
-// reads whole runs of blocks -- compressed -- straight into page-locked buffers for the GPU (pread on several threads).  The file
-// is NOT mapped: a 57 GB mapping cost 2 s of page-table population in front of a cold run and 0.9 s to release at exit
-// (profiles/r04/e2e_full_mmap.json).  No inflate, no record ever touched on the host (extract.nim:275-329 does both
-// through htslib on one thread).
+// reads whole runs of blocks -- compressed -- straight into page-locked buffers for the GPU (cli/chunk_feed.h, on several threads).
+// The file IS mapped, read-only, and copy_at copies out of the mapping (1.5 x pread's rate); what made the first mapping cost 2 s
+// in front of a cold run and 0.9 s at exit (profiles/r04/e2e_full_mmap.json) -- populating and tearing down 57 GB of page tables
+// -- is avoided by faulting pages in only as they are copied and dropping their translations behind the copy (done_with).
+// STRL_FEED=pread keeps pread.  No inflate, no record ever touched on the host (extract.nim:275-329 does both through htslib on
+// one thread).
 #pragma once
 #include <stdint.h>
 #include <condition_variable>

@@ -29,10 +29,14 @@
 #include "../../../include/strling_amd.h"
 #include "bam_reader.h"
 #include "bgzf_feed.h"
+#include "chunk_feed.h"
 #include "cram_reader.h"
 #include "cram_codecs.h"
 
 using namespace strl;
+using Tick = std::chrono::steady_clock::time_point;
+static Tick tick() { return std::chrono::steady_clock::now(); }
+static double span(Tick x, Tick y) { return std::chrono::duration<double>(y - x).count(); }
 
 static std::thread *g_bg_init = nullptr;   // device bring-up running beside the first host pass; exit() waits for it
 static std::function<void()> g_bg_abort;   // ... after telling it to stop waiting for what the quitting thread will never publish
@@ -168,40 +172,30 @@ static int decode_threads() {
   return n;
 }
 
+// the median the pair logic and the clustering take, with the reference's -v lines (extract.nim:285, call.nim:100)
+static int frag_median_of(uint32_t frag[4096], bool verbose) {
+  const int median = strl_frag_median(frag, 0.5);
+  if (verbose) {
+    fprintf(stderr, "Calculated median fragment length:%d\n", median);
+    fprintf(stderr, "10th, 90th percentile of fragment length:%d %d\n", strl_frag_median(frag, 0.1), strl_frag_median(frag, 0.9));
+  }
+  return median;
+}
 static void fragment_length_distribution(const std::string &bam, uint32_t frag[4096]) {
-  const int64_t n_reads = 2000000, skip_reads = 100000;
-  memset(frag, 0, 4096 * sizeof(uint32_t));
   BamStream rd;
   std::string err;
   if (!rd.open(bam, decode_threads(), err)) quit_open(bam, err);
   RecordBatch b;
-  std::vector<int32_t> skipped;
-  int64_t i = -1, counted = 0;
-  bool done = false;
-  while (!done) {
+  FragLengths fl;
+  int64_t i = 0;
+  while (!fl.done()) {
     b.clear();
     const int64_t got = rd.read(b, 1 << 16, err);
     if (got < 0) quit("[strling] error reading %s: %s", bam.c_str(), err.c_str());
     if (got == 0) break;
-    for (int64_t k = 0; k < got; ++k) {
-      ++i;
-      const uint16_t f = b.flag[(size_t)k];
-      if (!(f & 0x2)) continue;
-      if (f & (0x800 | 0x100)) continue;
-      const int32_t is = b.isize[(size_t)k];
-      if (is < 0 || is > 4095) continue;
-      if (i < skip_reads) { skipped.push_back(is); continue; }
-      skipped.clear();
-      frag[is]++;
-      if (++counted > n_reads) { done = true; break; }
-    }
+    for (int64_t k = 0; k < got && !fl.done(); ++k) fl.add(b.flag[(size_t)k], (uint32_t)b.isize[(size_t)k], i++);
   }
-  uint64_t sum = 0;
-  for (int k = 0; k < 4096; ++k) sum += frag[k];
-  if ((uint32_t)sum == 0) {
-    fprintf(stderr, "using first reads in fragment_length_distribution calculation as there were not enough\n");
-    for (int32_t is : skipped) frag[is]++;
-  }
+  fl.finish(frag);
 }
 
 
@@ -432,11 +426,7 @@ static int extract_main(int argc, char **argv) {
   g_bg_init = &ctx_thread;
   uint32_t frag[4096];
   fragment_length_distribution(bam, frag);                                        // extract.nim:281
-  const int frag_median = strl_frag_median(frag, 0.5);
-  if (verbose) {
-    fprintf(stderr, "Calculated median fragment length:%d\n", frag_median);
-    fprintf(stderr, "10th, 90th percentile of fragment length:%d %d\n", strl_frag_median(frag, 0.1), strl_frag_median(frag, 0.9));
-  }
+  const int frag_median = frag_median_of(frag, verbose);
   BamStream rd;
   std::string err;
   if (!rd.open(bam, decode_threads(), err)) quit_open(bam, err);
@@ -470,13 +460,11 @@ static int extract_main(int argc, char **argv) {
   int64_t n_tail = 0;        // length of the trailing run of unplaced records: the "*" region extract.nim:326 visits again
   int64_t tail_primary = 0;  // primary records among them
   double t_read = 0, t_soa = 0, t_score = 0, t_pair = 0;   // -v: where the wall time of the loop goes
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   bool over_limit = false;   // more records than one device pass takes: the file goes to the streaming host Cache (STRL_ERR_LIMIT)
   auto run_batch = [&](RecordBatch &b) {
     const size_t n = b.size();
     if (!n || over_limit) return;
-    const auto ta = now();
+    const auto ta = tick();
     strl_records rec = b.view();
     end.resize(n); so.resize(n); ls.resize(n); cl.resize(n); cr.resize(n); cig.resize(n);
     if (!host_pair) { rows.resize(n); qh.resize(n); }
@@ -503,14 +491,14 @@ static int extract_main(int argc, char **argv) {
     soa.n = n; soa.tid = rec.tid; soa.pos = rec.pos; soa.end = end.data(); soa.seq_off = so.data(); soa.l_seq = ls.data();
     soa.clip_l = cl.data(); soa.clip_r = cr.data(); soa.mapq = rec.mapq; soa.cig = cig.data(); soa.seq4 = rec.seq4;
     soa.seq4_bytes = b.seq4.size(); soa.max_l_seq = mx; soa.mem = STRL_MEM_HOST;
-    const auto tb = now();
+    const auto tb = tick();
     if (host_pair) {
       whole.resize(n); soft.resize(2 * n + 2);
       uint64_t ns = 0;
       CHECK(strl_score_reads(ctx, &soa, whole.data(), soft.data(), 2 * n, &ns, nullptr));
-      const auto tc = now();
+      const auto tc = tick();
       CHECK(strl_pairer_add(pairer, &rec, whole.data(), soft.data(), ns));
-      t_score += secs(tb, tc); t_pair += secs(tc, now());
+      t_score += span(tb, tc); t_pair += span(tc, tick());
     } else {
       const strl_pair_soa pp{rows.data(), qh.data()};
       const int rc_add = strl_extract_add(ctx, &soa, &pp);
@@ -527,13 +515,13 @@ static int extract_main(int argc, char **argv) {
         else { n_tail = 0; tail_primary = 0; }
       }
       n_seen += n;
-      t_score += secs(tb, now());
+      t_score += span(tb, tick());
     }
-    t_soa += secs(ta, tb);
+    t_soa += span(ta, tb);
   };
 
   fprintf(stderr, "[strling] collecting str-like reads\n");
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = tick();
   // the decoder runs one batch ahead of scoring + pairing (two slots)
   struct Slot { RecordBatch b; int64_t got = 0; std::string err; };
   Slot slots[2];
@@ -562,12 +550,12 @@ static int extract_main(int argc, char **argv) {
   RecordBatch tail;
   int64_t nreads = 0, last_tid = -1;
   for (int r = 0;; r ^= 1) {
-    const auto tr0 = now();
+    const auto tr0 = tick();
     {
       std::unique_lock<std::mutex> lk(mu);
       cv.wait(lk, [&] { return filled > 0; });
     }
-    t_read += secs(tr0, now());
+    t_read += span(tr0, tick());
     RecordBatch &b = slots[r].b;
     const int64_t got = slots[r].got;
     if (got < 0) { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv.notify_all(); producer.join(); quit("[strling] error reading %s: %s", bam.c_str(), slots[r].err.c_str()); }
@@ -598,7 +586,7 @@ static int extract_main(int argc, char **argv) {
     }
     cv.notify_all();
     if (verbose) {
-      const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      const double s = span(t0, tick());
       fprintf(stderr, "%lld %.1f reads/sec\n", (long long)nreads, (double)nreads / std::max(s, 1e-9));
     }
   }
@@ -618,7 +606,7 @@ static int extract_main(int argc, char **argv) {
     CHECK(strl_pairer_result(pairer, &treads, &nt, &qoff, &qn, &pending));
   } else {
     nreads += tail_primary;   // the "*" region is counted a second time by the reference's progress counter (extract.nim:326-329)
-    const auto tp0 = now();
+    const auto tp0 = tick();
     int rc = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
       CHECK(strl_extract_finish(ctx, n_tail, attempt ? std::min<uint64_t>(3 * n_seen + 16, 0x7ffffff0ull) : 0, attempt ? std::min<uint64_t>(8 * n_seen + 16, 0x7ffffff0ull) : 0));
@@ -634,7 +622,7 @@ static int extract_main(int argc, char **argv) {
     if (rc) quit("[strling] %s (status %d)", strl_last_error(), rc);
     dev_treads.resize((size_t)nt + 1);
     CHECK(strl_treads_fetch(ctx, dev_treads.data(), nt, &nt, nullptr));
-    t_pair += secs(tp0, now());
+    t_pair += span(tp0, tick());
     dev_qoff.assign(1, 0);
     for (uint64_t i = 0; i < nt; ++i) {
       strl_tread &t = dev_treads[(size_t)i];
@@ -655,12 +643,38 @@ static int extract_main(int argc, char **argv) {
   if (verbose) {
     fprintf(stderr, "[strling] %lld reads, %llu STR reads, %llu reads still waiting for a mate\n", (long long)nreads, (unsigned long long)nt, (unsigned long long)pending);
     fprintf(stderr, "[strling] seconds: total %.3f  waiting for the decoder %.3f  soa %.3f  device scoring (incl. copies) %.3f  pair logic %.3f\n",
-            secs(t0, now()), t_read, t_soa, t_score, t_pair);
+            span(t0, tick()), t_read, t_soa, t_score, t_pair);
   }
   if (pairer) strl_pairer_destroy(pairer);
   strl_ctx_destroy(ctx);
   return 0;
 }
+
+static int end_process(strl_ctx *ctx);
+
+// N page-locked chunk buffers and their N block tables (chunk_feed.h), allocated on a thread per buffer: the time is the kernel's,
+// faulting and locking the pages.  Nothing is freed unless release() is called: `call` and `bamindex` leave theirs to the end of
+// the process on purpose.
+struct PinnedRing {
+  std::vector<uint8_t *> data, meta;
+  void alloc(size_t n, size_t chunk_blocks, size_t chunk_bytes) {
+    data.assign(n, nullptr); meta.assign(n, nullptr);
+    auto one = [&](size_t k) {
+      data[k] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_data_bytes(chunk_bytes)));
+      meta[k] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_table_bytes(chunk_blocks)));
+    };
+    std::vector<std::thread> each;
+    for (size_t k = 1; k < n; ++k) each.emplace_back(one, k);
+    one(0);
+    for (auto &t : each) t.join();
+  }
+  bool ok() const { return !data.empty() && !std::count(data.begin(), data.end(), nullptr) && !std::count(meta.begin(), meta.end(), nullptr); }
+  void release_except(const void *a, const void *b) {      // (freeing twice is harmless: the pointers are nulled)
+    for (auto *v : {&data, &meta})
+      for (uint8_t *&q : *v) if (q && q != a && q != b) { strl_pinned_free(q); q = nullptr; }
+  }
+  void release() { release_except(nullptr, nullptr); }
+};
 
 // `strling extract` with the BAM front end on the device: this thread walks BGZF headers and copies compressed bytes into
 // page-locked buffers; inflate, record scan, parse, scorer, pair logic all run on the GPU (extract.nim:275-348).
@@ -683,9 +697,321 @@ static std::vector<uint64_t> share_cuts(const BgzfFeed &feed, const std::string 
   return cut;
 }
 
-static int extract_front(const Args &a, const std::string &bam, const std::string &bin, double p, uint8_t min_mapq, bool verbose) {
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double>(y - x).count(); };
+// four per context: [4 g + (its chunk count % 4)] -- while chunk k is handed over, chunk k+2 is read from the file, chunk k+1's
+// copy to the device has just been queued and chunk k's may still be going; the buffer chunk k+2 takes is chunk k-2's, whose
+// record scan this thread has waited for.
+constexpr size_t EXTRACT_RING = 4;
+constexpr uint64_t EXTRACT_EARLY_N = 2400000;      // records whose flag / isize words are copied out early (fragment lengths)
+
+// Bring-up, one thread per context, side by side (round 6; before: one after the other, 0.1 - 0.2 s each, then options, genome
+// table and per-read state of every context in turn on the main thread -- more than a second of fixed cost at 8 contexts):
+//   create the context (the first HIP call of the process starts the runtime: one thread does that alone, the others wait
+//   for it and then run side by side) -> options -> [the genome table's host half is ready] -> genome table -> [the file's
+//   header is walked, the shares are cut] -> per-read state + front-end buffers of THIS context.
+// The main thread walks the header and parses the BED meanwhile and only waits where it needs a context.
+// STRL_SERIAL_CTX=1: the contexts one after the other, as before.
+struct BringUp {
+  const int G;
+  const strl_opts &opts;
+  const size_t chunk_blocks, chunk_bytes;
+  std::vector<strl_ctx *> &ctxs;
+  PinnedRing &pins;
+  uint32_t *&fw_early;
+  std::mutex mu;
+  std::condition_variable cv;
+  bool runtime_up = false, genome_ready = false, plan_ready = false, give_up = false;
+  std::vector<uint8_t> created, done;
+  std::vector<int> ctx_rc; std::vector<std::string> ctx_err;
+  strl_genome_str gs{};
+  int32_t n_ref = 0;
+  std::vector<uint64_t> first_off, hint;
+  std::vector<double> t_create, t_state;
+  double t_pin = 0, t_ctx = 0, t_begin = 0;
+  std::vector<std::thread> threads;
+  std::thread pin_thread, reaper;
+
+  BringUp(int G_, const strl_opts &o, size_t blocks, size_t bytes, std::vector<strl_ctx *> &c, PinnedRing &r, uint32_t *&fw)
+      : G(G_), opts(o), chunk_blocks(blocks), chunk_bytes(bytes), ctxs(c), pins(r), fw_early(fw), created((size_t)G_, 0), done((size_t)G_, 0),
+        ctx_rc((size_t)G_, 0), ctx_err((size_t)G_), first_off((size_t)G_, 0), hint((size_t)G_, 0), t_create((size_t)G_, 0.0), t_state((size_t)G_, 0.0) {}
+
+  template <typename P> bool wait_for(P pred) {             // -> false: the main thread gave up (an error exit is under way)
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return pred() || give_up; });
+    return !give_up;
+  }
+  template <typename F> void publish(F set) { { std::lock_guard<std::mutex> lk(mu); set(); } cv.notify_all(); }
+  void wait_created(int g) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return created[(size_t)g] != 0; }); }
+  int front_state(int g) {                                  // per-read state + front-end buffers of context g
+    const auto c1 = tick();
+    int rc = strl_front_begin(ctxs[(size_t)g], n_ref, first_off[(size_t)g], hint[(size_t)g]);
+    if (!rc) rc = strl_front_reserve(ctxs[(size_t)g], (uint32_t)chunk_blocks, chunk_bytes);
+    t_state[(size_t)g] = span(c1, tick());
+    return rc;
+  }
+  void one(int g) {
+    static const bool serial_ctx = getenv("STRL_SERIAL_CTX") != nullptr;
+    auto finish = [&](int rc) {
+      if (rc) { ctx_rc[(size_t)g] = rc; ctx_err[(size_t)g] = strl_last_error(); }
+      publish([&] { created[(size_t)g] = 1; done[(size_t)g] = 1; runtime_up = true; });
+    };
+    if (g > 0 && !wait_for([&] { return serial_ctx ? created[(size_t)g - 1] != 0 : runtime_up; })) return finish(0);
+    const auto c0 = tick();
+    if (g == 0) {
+      (void)strl_device_count();               // the runtime starts here, on one thread
+      publish([&] { runtime_up = true; });
+    }
+    int rc = strl_ctx_create(device_of(g), &ctxs[(size_t)g]);
+    t_create[(size_t)g] = span(c0, tick());
+    if (rc) return finish(rc);
+    strl_ctx *c = ctxs[(size_t)g];
+    if ((rc = strl_ctx_set_opts(c, &opts))) return finish(rc);
+    if (G > 1 && (rc = strl_ctx_blocking_waits(c, 1))) return finish(rc);       // N feeding threads: waits sleep instead of spinning
+    publish([&] { created[(size_t)g] = 1; });                                    // (usable: created, options set)
+    if (!wait_for([&] { return genome_ready; })) return finish(0);
+    if ((rc = strl_ctx_set_genome(c, &gs))) return finish(rc);
+    if (!wait_for([&] { return plan_ready; })) return finish(0);
+    if (getenv("STRL_STATE_ON_MAIN")) return finish(0);                          // (diagnosis)
+    finish(front_state(g));
+  }
+  // the HIP runtime, the contexts and the page-locked buffers come up on threads beside the header walk
+  void start() {
+    pin_thread = std::thread([this] {
+      const auto c0 = tick();
+      std::thread early([this] { fw_early = static_cast<uint32_t *>(strl_pinned_alloc(EXTRACT_EARLY_N * 4)); });     // (allocating page-locked memory inside the loop stalls the device)
+      pins.alloc(EXTRACT_RING * (size_t)G, chunk_blocks, chunk_bytes);
+      early.join();
+      t_pin = span(c0, tick());
+    });
+    for (int g = 0; g < G; ++g) threads.emplace_back([this, g] { one(g); });
+    // (an error exit -- quit() -- first tells the bring-up threads to give up where they wait, then waits for ONE background
+    // thread: this one, which collects them all and the buffers' allocation, so that no thread is inside the HIP runtime when
+    // the exit handlers run)
+    reaper = std::thread([this] { for (auto &t : threads) t.join(); pin_thread.join(); });
+    g_bg_init = &reaper;
+    g_bg_abort = [this] { publish([&] { give_up = true; }); };
+  }
+  // waits for everything; -> 0, or STRL_ERR_NOMEM (said on stderr: the caller repeats the extraction on the host); other failures end the process
+  int finish() {
+    const auto tb0 = tick();
+    reaper.join();
+    g_bg_init = nullptr; g_bg_abort = nullptr;
+    if (getenv("STRL_STATE_ON_MAIN"))
+      for (int g = 0; g < G && !ctx_rc[(size_t)g]; ++g)
+        if (int rc = front_state(g)) { ctx_rc[(size_t)g] = rc; ctx_err[(size_t)g] = strl_last_error(); }
+    t_begin = span(tb0, tick());
+    for (double v : t_create) t_ctx = std::max(t_ctx, v);
+    for (int g = 0; g < G; ++g)
+      if (ctx_rc[(size_t)g] == STRL_ERR_NOMEM) {
+        fprintf(stderr, "[strling] %s: repeating the extraction with the host pair logic\n", ctx_err[(size_t)g].c_str());
+        return STRL_ERR_NOMEM;
+      }
+    for (int g = 0; g < G; ++g) if (ctx_rc[(size_t)g]) quit("[strling] %s (status %d)", ctx_err[(size_t)g].c_str(), ctx_rc[(size_t)g]);
+    if (!pins.ok()) quit("[strling] could not allocate page-locked memory");
+    return 0;
+  }
+};
+
+// What the chunks' summaries add up to.  Summaries arrive per context in the order of ITS chunks; the file order is what counts.
+struct ChunkTally {
+  std::vector<std::vector<strl_front_chunk>> by_ctx;     // per context, in the order they arrived (a feeding thread only touches its own)
+  std::vector<uint32_t> owner;                           // by chunk of the file: its context
+  std::vector<size_t> taken;                             // per context: summaries accounted
+  std::vector<strl_front_chunk> summary;                 // by chunk of the file: the leading run whose summaries are in
+  int64_t nreads = 0, n_tail = 0, tail_primary = 0; uint64_t n_seen = 0, slow_segments = 0;
+  explicit ChunkTally(int G) : by_ctx((size_t)G), taken((size_t)G, 0) {}
+  void account(bool verbose, Tick t0) {
+    while (summary.size() < owner.size()) {
+      const size_t g = owner[summary.size()];
+      if (taken[g] >= by_ctx[g].size()) break;
+      const strl_front_chunk d = by_ctx[g][taken[g]++];
+      summary.push_back(d);
+      nreads += (int64_t)d.n_primary;
+      n_seen += d.n_records;
+      slow_segments += d.scan_slow_segments;
+      if (d.last_placed >= 0) { n_tail = (int64_t)d.n_records - 1 - d.last_placed; tail_primary = (int64_t)d.tail_primary; }
+      else { n_tail += (int64_t)d.n_records; tail_primary += (int64_t)d.n_primary; }
+      if (verbose) fprintf(stderr, "%lld %.1f reads/sec\n", (long long)nreads, (double)nreads / std::max(span(t0, tick()), 1e-9));
+    }
+  }
+};
+
+// One pass of extract's pipeline over one feed -- the whole file with its chunks going over the contexts in turn, or one context's
+// share of it (one such pass per share, side by side on threads of their own).
+// Two chunks ahead: while chunk k is handed to the device (strl_front_collect returns when chunk k-1 has been inflated and
+// scanned), a thread walks the headers of chunk k+2 and reads its bytes, and chunk k+1 -- read during the previous turn --
+// has its copy to the device queued first thing.  (Reading only after the push had returned put the read AND the copy
+// between "chunk k-1 done" and "chunk k+1 may start": 0.40 s of 3.03 s with the inflate stream idle on the 57 GB file;
+// reading one ahead and queueing the copy when the read was done still left it 0.3 s late in all: a 323 MB chunk takes
+// 5 ms to read and 6.5 ms to copy, an inflate 12.)
+struct FeedPass {
+  BgzfFeed &feed;
+  ThreadPool &pool;
+  const PinnedRing &pins;
+  const size_t chunk_blocks, chunk_bytes;
+  const std::vector<strl_ctx *> &ctxs;
+  ChunkTally &tally;
+  int share = -1;                    // >= 0: every chunk goes to this context, `last` and the feed's tail_trim apply; -1: chunk ci to context ci % G
+  bool feed_only = false;            // measurement: the host side alone, no device stage
+  std::function<void(strl_ctx *, const ChunkTables &, const StagedChunk &)> on_queue;     // as a chunk's copy is queued (--write-index)
+  std::function<void()> on_turn;     // behind every chunk's collect
+  // how it left: rc of a front-end call (err = its text), a malformed file, a short read; none: the end of the file
+  int rc = 0;
+  bool bad_file = false, short_read = false;
+  std::string err;
+  double t_walk = 0, t_copy = 0, t_wait = 0, t_stage_wait = 0; uint64_t bytes = 0, chunks = 0;
+
+  void run() {
+    ChunkAhead ring(feed, pool, pins.data.data(), pins.meta.data(), chunk_blocks, chunk_bytes, share >= 0);
+    ring.first_blocks = 2048;
+    loop(ring);
+    ring.join();
+    t_walk = ring.t_walk; t_copy = ring.t_copy; bytes = ring.bytes; chunks = ring.chunks;
+  }
+
+  void loop(ChunkAhead &ring) {
+    const uint64_t G = ctxs.size();
+    std::vector<uint64_t> staged((size_t)G, 0);
+    auto ctx_of = [&](uint64_t ci) { return share >= 0 ? (size_t)share : (size_t)(ci % G); };
+    auto slot_of = [&](uint64_t ci) { const size_t g = ctx_of(ci); return EXTRACT_RING * g + (size_t)(staged[g]++ % EXTRACT_RING); };
+    auto fail = [&](int r) { rc = r; err = strl_last_error(); };
+    auto queue_copy = [&](uint64_t ci) -> int {     // the chunk's copy to the device, ahead of its turn
+      const StagedChunk &S = ring.at(ci);
+      if (S.nb <= 0 || S.short_read) return 0;
+      strl_ctx *cx = ctxs[ctx_of(ci)];
+      const ChunkTables t = ring.tables(S);
+      if (on_queue) on_queue(cx, t, S);
+      const int r = S.last && feed.tail_trim() ? strl_front_trim_next(cx, feed.tail_trim()) : 0;
+      return r ? r : strl_front_stage(cx, ring.data(S), S.bytes(), t.coff, t.clen, t.isz, t.crc, (uint32_t)S.nb);
+    };
+    int r = 0;
+    ring.stage(0, slot_of(0));
+    if (!feed_only && (r = queue_copy(0))) return fail(r);
+    if (ring.at(0).nb > 0) ring.stage(1, slot_of(1));
+    for (uint64_t ci = 0;; ++ci) {
+      const StagedChunk cur = ring.at(ci);
+      if (cur.nb < 0) { bad_file = true; err = cur.err; return; }
+      if (cur.nb == 0) return;
+      if (cur.short_read) { short_read = true; err = "short read"; return; }
+      if (ring.at(ci + 1).nb > 0) ring.stage_ahead(ci + 2, slot_of(ci + 2));
+      else ring.clear(ci + 2);
+      if (!feed_only) {
+        if ((r = queue_copy(ci + 1))) return fail(r);
+        const auto tc = tick();
+        const size_t g = ctx_of(ci);
+        const ChunkTables t = ring.tables(cur);
+        strl_front_chunk done[2];
+        int n_done = 0;
+        if (share < 0) tally.owner.push_back((uint32_t)g);
+        // (ordered behind the previous chunk of the file, which may sit on another context)
+        if ((r = strl_front_enqueue_after(ctxs[g], ci ? ctxs[ctx_of(ci - 1)] : nullptr, ring.data(cur), cur.bytes(), t.coff, t.clen, t.isz, t.crc, (uint32_t)cur.nb, done, &n_done))) return fail(r);
+        tally.by_ctx[g].insert(tally.by_ctx[g].end(), done, done + n_done);
+        if ((r = strl_front_collect(ctxs[g]))) return fail(r);
+        if (on_turn) on_turn();
+        t_wait += span(tc, tick());
+      }
+      const auto td0 = tick();
+      ring.join();
+      t_stage_wait += span(td0, tick());
+    }
+  }
+};
+
+// the summaries still in context g's pipeline; -> the library's status
+static int finish_front(strl_ctx *cx, std::vector<strl_front_chunk> &sums) {
+  strl_front_chunk done[2];
+  int n_done = 0;
+  const int rc = strl_front_finish(cx, done, &n_done);
+  if (!rc) sums.insert(sums.end(), done, done + n_done);
+  return rc;
+}
+
+struct ExtractFront {
+  // what was asked for
+  const Args &a;
+  const std::string &bam, &bin;
+  const double p; const uint8_t min_mapq; const bool verbose;
+  // the plan
+  int G = 1;
+  bool use_shares = false; size_t chunk_blocks = 0, chunk_bytes = 0;
+  std::vector<uint64_t> cut;
+  uint64_t reads_hint = 0;
+  int32_t n_ref = 0;
+  strl_opts opts;                              // the fragment-length median is only needed by the pair logic: set before strl_extract_finish
+  // --write-index: the .bai as a by-product of this pass (strl_front_index_*).  Whatever goes wrong with it is one line on stderr
+  // and no index; the extraction goes on as without the flag.
+  int idx_min_shift = -1;
+  std::string index_out;
+  std::atomic<bool> idx_on{false};             // (read by the thread that stages the chunks ahead)
+  // what abandon() gives back
+  std::vector<strl_ctx *> ctxs;
+  PinnedRing pins;
+  BgzfFeed feed;
+  struct Share {
+    BgzfFeed fd;
+    int rc = 0;
+    bool fallback = false;        // a malformed block: the chunk-by-chunk run says so
+    std::string err;
+    uint32_t tail = 0;
+    double t_walk = 0, t_copy = 0, t_wait = 0, t_all = 0; uint64_t bytes = 0, chunks = 0;
+  };
+  std::vector<Share> shares;
+  std::thread frag_thread;
+  // fragment lengths from the flag / isize words the parse kept of every record
+  uint32_t *fw_early = nullptr;                // page-locked room for the words of the first records
+  FragLengths fl;
+  uint32_t frag[4096];
+  ChunkTally tally{1};
+  // -v: where the time went
+  Tick t_start, t0, tf;
+  struct { double t_begin = 0, t_ctx = 0, t_pin = 0, t_state = 0; } bring_times;
+  double t_open = 0, t_genome = 0, t_walk = 0, t_copy = 0, t_push = 0, t_stage_wait = 0, t_drain = 0, t_frag = 0, t_frag_copy = 0, t_setopts = 0;
+
+  ExtractFront(const Args &a_, const std::string &bam_, const std::string &bin_, double p_, uint8_t q_, bool v_)
+      : a(a_), bam(bam_), bin(bin_), p(p_), min_mapq(q_), verbose(v_), opts{0, p_, q_} {}
+
+  // The one way out of a pass that is to be repeated another way: nothing of this one is left behind.
+  int abandon(int code) {
+    if (frag_thread.joinable()) frag_thread.join();
+    for (Share &Z : shares) Z.fd.close();
+    pins.release();
+    for (strl_ctx *&c : ctxs) if (c) { strl_ctx_destroy(c); c = nullptr; }
+    return code;
+  }
+  void idx_give_up(const std::string &why) {
+    if (!idx_on) return;
+    fprintf(stderr, "[strling] index not written: %s\n", why.c_str());
+    idx_on = false; g_index_done = true;
+  }
+  // A front-end call failed.  A file the device front end refuses (STRL_ERR_FORMAT) goes to the host reader instead of ending the
+  // run; more records than one device pass takes (2^31 - 16; the reference has no cap, extract.nim:308), or more than the device's
+  // memory holds the per-read state of (STRL_ERR_NOMEM: ~130 B per read): the streaming host Cache, which keeps nothing per read
+  // on the device.
+  int front_failed(int rc, const std::string &err) {
+    if (rc == STRL_ERR_FORMAT) {
+      fprintf(stderr, "[strling] %s: repeating the extraction with the host reader\n", err.c_str());
+      idx_give_up("the device front end gave the file up, and it is what builds the index");
+      return abandon(EXTRACT_AGAIN_HOST_FRONT);
+    }
+    if (rc == STRL_ERR_LIMIT || rc == STRL_ERR_NOMEM) {
+      fprintf(stderr, "[strling] %s: repeating the extraction with the host pair logic\n", err.c_str());
+      idx_give_up("the pass over the file was given up before its end");
+      return abandon(EXTRACT_AGAIN_ON_HOST);
+    }
+    if (rc == STRL_ERR_CRC) quit("[strling] error reading %s: %s", bam.c_str(), err.c_str());
+    quit("[strling] %s (status %d)", err.c_str(), rc);
+  }
+#define FRONT_CHECK(call) do { if (const int rc__ = (call)) return front_failed(rc__, strl_last_error()); } while (0)
+
+  void plan_chunks();
+  int bring_up();
+  int feed_shares();
+  int feed_by_chunks(ThreadPool &copy_pool);
+  void write_index();
+  void fragment_lengths();
+  int run();
+};
+
+void ExtractFront::plan_chunks() {
   static const char *env_blocks = getenv("STRL_CHUNK_BLOCKS");     // tests: tiny chunks put records across chunk borders
   // Chunk = one inflate launch: 8192 blocks (~0.5 GB inflated) keep a 1 GB file's pipeline fine-grained (fill, drain and the
   // page-locked buffers all grow with the chunk); a whole-genome BAM takes 16384.  Consecutive chunks' inflates overlap (two
@@ -693,150 +1019,49 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   // 8192 / 16384 / 24576 / 32768 blocks: 0.40 / 0.36 / 0.37 / 0.37) -- but three page-locked buffers of 24576 blocks took
   // 0.39 - 0.44 s to allocate, longer than the device context beside them (0.30 s at 16384; profiles/r04/extract_chunk_sweep.txt)
   size_t auto_blocks = 8192;
-  {
-    struct stat st;
-    if (stat(bam.c_str(), &st) == 0) auto_blocks = std::min<size_t>(16384, std::max<size_t>(8192, (size_t)st.st_size / 16384 / 12));
-  }
-  const int G = std::max(1, atoi(a.get("gpus", "1").c_str()));
-  // --gpus N: every context takes one contiguous share of the file (below) unless STRL_SHARES=0 / there is no usable .bai
+  struct stat st;
+  const bool have_size = stat(bam.c_str(), &st) == 0;
+  if (have_size) auto_blocks = std::min<size_t>(16384, std::max<size_t>(8192, (size_t)st.st_size / 16384 / 12));
+  G = std::max(1, atoi(a.get("gpus", "1").c_str()));
+  // --gpus N: every context takes one contiguous share of the file unless STRL_SHARES=0 / there is no usable .bai
   const char *env_shares = getenv("STRL_SHARES");        // (read per call: extract_main sets it to 0 for the chunk-by-chunk repeat)
-  bool use_shares = G > 1 && !(env_shares && strcmp(env_shares, "0") == 0);
-  if (use_shares) {
-    struct stat st;
+  use_shares = G > 1 && !(env_shares && strcmp(env_shares, "0") == 0);
+  if (use_shares && have_size) {
     // (a share's ring is four page-locked buffers of a chunk each, and page-locking goes through the driver at ~20 GB/s whatever
     // the number of threads (profiles/r06/feed_probe_shm.log): 8 shares x 4 x 16384 blocks were 10 GB = half a second and more of
     // every start; 4096 blocks -- a 2.5 ms inflate launch of 4096 workgroups -- keep 8 rings at 2.6 GB)
     const size_t cap = G >= 4 ? 4096 : 8192;
-    if (stat(bam.c_str(), &st) == 0) auto_blocks = std::min<size_t>(cap, std::max<size_t>(2048, (size_t)st.st_size / (size_t)G / 16384 / 12));
+    auto_blocks = std::min<size_t>(cap, std::max<size_t>(2048, (size_t)st.st_size / (size_t)G / 16384 / 12));
   }
-  const size_t chunk_blocks = env_blocks && atoi(env_blocks) > 0 ? (size_t)atoi(env_blocks) : auto_blocks;
-  const size_t chunk_bytes = std::max<size_t>((size_t)1 << 20, chunk_blocks * 20000);       // compressed bytes one chunk may span
-  // --write-index: the .bai as a by-product of this pass (strl_front_index_*).  Whatever goes wrong with it is one line on stderr
-  // and no index; the extraction goes on as without the flag.
-  const int idx_min_shift = a.flag("csi") ? atoi(a.get("min-shift", "14").c_str()) : -1;       // (checked by extract_main)
-  const std::string index_out = a.get("index-out", (bam + (idx_min_shift >= 0 ? ".csi" : ".bai")).c_str());
-  std::atomic<bool> idx_on{a.flag("write-index") && !g_index_done && G == 1};      // (read by the thread that stages the chunks ahead)
-  auto idx_give_up = [&](const std::string &why) {
-    if (!idx_on) return;
-    fprintf(stderr, "[strling] index not written: %s\n", why.c_str());
-    idx_on = false; g_index_done = true;
-  };
-  std::vector<uint64_t> boff_ring[3];           // file offsets of the blocks of the chunk in ring[c % 3]
-  std::vector<strl_ctx *> ctxs((size_t)G, nullptr);
-  std::vector<int> ctx_rc((size_t)G, 0);
-  std::vector<std::string> ctx_err((size_t)G);
-  // four per context: [4 g + (its chunk count % 4)] -- while chunk k is handed over, chunk k+2 is read from the file, chunk k+1's
-  // copy to the device has just been queued and chunk k's may still be going; the buffer chunk k+2 takes is chunk k-2's, whose
-  // record scan this thread has waited for.  Block tables: coff u64 | clen | isize | crc u32
-  const size_t RING = 4;
-  std::vector<uint8_t *> pin(RING * G, nullptr), pin_meta(RING * G, nullptr);
-  const auto t_start = now();
-  double t_ctx = 0, t_pin = 0;
-  uint32_t *fw_early = nullptr;          // flag / isize words of the first records (fragment lengths)
-  const uint64_t early_n = 2400000;
-  // Bring-up, one thread per context, side by side (round 6; before: one after the other, 0.1 - 0.2 s each, then options, genome
-  // table and per-read state of every context in turn on the main thread -- more than a second of fixed cost at 8 contexts):
-  //   create the context (the first HIP call of the process starts the runtime: one thread does that alone, the others wait
-  //   for it and then run side by side) -> options -> [the genome table's host half is ready] -> genome table -> [the file's
-  //   header is walked, the shares are cut] -> per-read state + front-end buffers of THIS context.
-  // The main thread walks the header and parses the BED meanwhile and only waits where it needs a context.
-  // STRL_SERIAL_CTX=1: the contexts one after the other, as before.
-  strl_opts opts{0, p, min_mapq};              // the fragment-length median is only needed by the pair logic: set before strl_extract_finish
-  struct BringUp {
-    std::mutex mu;
-    std::condition_variable cv;
-    bool runtime_up = false, genome_ready = false, plan_ready = false, pin_done = false, give_up = false;
-    std::vector<uint8_t> created, done;
-    strl_genome_str gs{};
-    int32_t n_ref = 0;
-    std::vector<uint64_t> first_off, hint;
-    std::vector<double> t_create, t_state;
-  } bu;
-  bu.created.assign((size_t)G, 0); bu.done.assign((size_t)G, 0);
-  bu.first_off.assign((size_t)G, 0); bu.hint.assign((size_t)G, 0);
-  bu.t_create.assign((size_t)G, 0.0); bu.t_state.assign((size_t)G, 0.0);
-  // the HIP runtime, the contexts and the page-locked buffers come up on threads beside the header walk
-  std::thread pin_thread([&] {
-    const auto c0 = now();
-    std::vector<std::thread> each;            // (the time is the kernel's, faulting and locking the pages: a thread per buffer)
-    for (size_t k = 1; k < pin.size(); ++k) each.emplace_back([&, k] { pin[k] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_bytes + 64)); });
-    pin[0] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_bytes + 64));
-    for (auto &q : pin_meta) q = static_cast<uint8_t *>(strl_pinned_alloc(chunk_blocks * 20 + 64));
-    fw_early = static_cast<uint32_t *>(strl_pinned_alloc(early_n * 4));     // (allocating page-locked memory inside the loop stalls the device)
-    for (auto &t : each) t.join();
-    t_pin = secs(c0, now());
-    { std::lock_guard<std::mutex> lk(bu.mu); bu.pin_done = true; }
-    bu.cv.notify_all();
-  });
-  static const bool serial_ctx = getenv("STRL_SERIAL_CTX") != nullptr;
-  auto bring_up = [&](int g) {
-    auto wait_for = [&](auto pred) {             // -> false: the main thread gave up (an error exit is under way)
-      std::unique_lock<std::mutex> lk(bu.mu);
-      bu.cv.wait(lk, [&] { return pred() || bu.give_up; });
-      return !bu.give_up;
-    };
-    auto finish = [&](int rc) {
-      if (rc) { ctx_rc[(size_t)g] = rc; ctx_err[(size_t)g] = strl_last_error(); }
-      { std::lock_guard<std::mutex> lk(bu.mu); bu.created[(size_t)g] = 1; bu.done[(size_t)g] = 1; bu.runtime_up = true; }
-      bu.cv.notify_all();
-    };
-    if (g > 0 && !wait_for([&] { return serial_ctx ? bu.created[(size_t)g - 1] != 0 : bu.runtime_up; })) return finish(0);
-    const auto c0 = now();
-    if (g == 0) {
-      (void)strl_device_count();               // the runtime starts here, on one thread
-      { std::lock_guard<std::mutex> lk(bu.mu); bu.runtime_up = true; }
-      bu.cv.notify_all();
-    }
-    int rc = strl_ctx_create(device_of(g), &ctxs[(size_t)g]);
-    bu.t_create[(size_t)g] = secs(c0, now());
-    if (rc) return finish(rc);
-    strl_ctx *c = ctxs[(size_t)g];
-    if ((rc = strl_ctx_set_opts(c, &opts))) return finish(rc);
-    if (G > 1 && (rc = strl_ctx_blocking_waits(c, 1))) return finish(rc);       // N feeding threads: waits sleep instead of spinning
-    { std::lock_guard<std::mutex> lk(bu.mu); bu.created[(size_t)g] = 1; }       // (usable: created, options set)
-    bu.cv.notify_all();
-    if (!wait_for([&] { return bu.genome_ready; })) return finish(0);
-    if ((rc = strl_ctx_set_genome(c, &bu.gs))) return finish(rc);
-    if (!wait_for([&] { return bu.plan_ready; })) return finish(0);
-    static const bool state_on_main = getenv("STRL_STATE_ON_MAIN") != nullptr;      // (diagnosis)
-    if (state_on_main) return finish(0);
-    const auto c1 = now();
-    rc = strl_front_begin(c, bu.n_ref, bu.first_off[(size_t)g], bu.hint[(size_t)g]);
-    if (!rc) rc = strl_front_reserve(c, (uint32_t)chunk_blocks, chunk_bytes);
-    bu.t_state[(size_t)g] = secs(c1, now());
-    finish(rc);
-  };
-  std::vector<std::thread> bring_threads;
-  for (int g = 0; g < G; ++g) bring_threads.emplace_back(bring_up, g);
-  // (an error exit -- quit() -- first tells the bring-up threads to give up where they wait, then waits for ONE background
-  // thread: this one, which collects them all, so that no thread is inside the HIP runtime when the exit handlers run)
-  std::thread reaper([&] { for (auto &t : bring_threads) t.join(); });
-  g_bg_init = &reaper;
-  g_bg_abort = [&bu] { { std::lock_guard<std::mutex> lk(bu.mu); bu.give_up = true; } bu.cv.notify_all(); };
-  BgzfFeed feed;
+  chunk_blocks = env_blocks && atoi(env_blocks) > 0 ? (size_t)atoi(env_blocks) : auto_blocks;
+  chunk_bytes = std::max<size_t>((size_t)1 << 20, chunk_blocks * 20000);       // compressed bytes one chunk may span
+  idx_min_shift = a.flag("csi") ? atoi(a.get("min-shift", "14").c_str()) : -1;       // (checked by extract_main)
+  index_out = a.get("index-out", (bam + (idx_min_shift >= 0 ? ".csi" : ".bai")).c_str());
+  idx_on = a.flag("write-index") && !g_index_done && G == 1;
+  ctxs.assign((size_t)G, nullptr);
+  tally = ChunkTally(G);
+}
+
+// Contexts, page-locked buffers, the file's header, the genome table, the shares' cuts -> 0, or the EXTRACT_AGAIN_* the pass was abandoned with
+int ExtractFront::bring_up() {
+  BringUp bu(G, opts, chunk_blocks, chunk_bytes, ctxs, pins, fw_early);
+  bu.start();
   std::string err;
-  const bool opened = feed.open(bam, err);
-  if (!opened) quit("couldn't open bam");
-  const double t_open = secs(t_start, now());
+  if (!feed.open(bam, err)) quit("couldn't open bam");
+  t_open = span(t_start, tick());
   // the genome table's host half (the BED read and flattened per tid; built from the FASTA on the first context when there is none)
-  const auto tg0 = now();
-  auto wait_created = [&](int g) {
-    std::unique_lock<std::mutex> lk(bu.mu);
-    bu.cv.wait(lk, [&] { return bu.created[(size_t)g] != 0; });
-  };
+  const auto tg0 = tick();
   const Genome genome = genome_host_half(a, feed.targets(), [&]() -> strl_ctx * {
-    wait_created(0);
-    if (ctx_rc[0]) quit("[strling] %s (status %d)", ctx_err[0].c_str(), ctx_rc[0]);
+    bu.wait_created(0);
+    if (bu.ctx_rc[0]) quit("[strling] %s (status %d)", bu.ctx_err[0].c_str(), bu.ctx_rc[0]);
     return ctxs[0];
   });
-  {
-    std::lock_guard<std::mutex> lk(bu.mu);
-    bu.gs = strl_genome_str{(int32_t)feed.targets().size(), genome.has.data(), genome.off.data(), genome.st.data(), genome.en.data()};
+  n_ref = (int32_t)feed.targets().size();
+  bu.publish([&] {
+    bu.gs = strl_genome_str{n_ref, genome.has.data(), genome.off.data(), genome.st.data(), genome.en.data()};
     bu.genome_ready = true;
-  }
-  bu.cv.notify_all();
-  const double t_genome = secs(tg0, now());
-  const int32_t n_ref = (int32_t)feed.targets().size();
+  });
+  t_genome = span(tg0, tick());
   // Reads the per-read state is sized for at the start (it grows geometrically beyond): a record of 150 bases with qualities
   // and a few tags takes 90 - 110 bytes of a level-6 BAM, 60 - 70 without qualities.  (The first sizing was file bytes / 48:
   // 124 GB of device memory and seconds of set-up for a 57 GB file of 5.4e8 reads.)
@@ -847,14 +1072,13 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
   uint64_t indexed = 0;
   // (a count of more records than the file has bytes is not believed: the state would be allocated for it)
   const bool have_count = !env_hint && !getenv("STRL_NO_INDEX_COUNT") && BgzfFeed::indexed_records(bam, indexed) && indexed > 0 && indexed <= feed.file_bytes();
-  const uint64_t reads_hint = env_hint     ? strtoull(env_hint, nullptr, 10)
-                              : have_count ? (G > 1 ? (indexed + indexed / 20) / (uint64_t)G + 65536 : indexed + indexed / 256 + 65536)
-                                           : feed.file_bytes() / 88 / (size_t)G;
+  reads_hint = env_hint     ? strtoull(env_hint, nullptr, 10)
+               : have_count ? (G > 1 ? (indexed + indexed / 20) / (uint64_t)G + 65536 : indexed + indexed / 256 + 65536)
+                            : feed.file_bytes() / 88 / (size_t)G;
   if (verbose && have_count) fprintf(stderr, "[strling] %llu records by the index's counts\n", (unsigned long long)indexed);
   // Shares of the file, one per context: [cut[g], cut[g + 1]) in virtual offsets, every cut a record start the .bai names
   // (the one nearest to g / G of the bytes behind the header).  extract.nim:308-329 is one loop over the file in file order;
   // the shares are gathered in that order afterwards (strl_ctxs_extract_gather), so nothing downstream can tell.
-  std::vector<uint64_t> cut;
   if (use_shares) {
     cut = share_cuts(feed, bam, G);
     if (cut.size() < 2) {
@@ -862,9 +1086,7 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
       if (verbose) fprintf(stderr, "[strling] no .bai record starts to cut the file at: its chunks go over the contexts in turn\n");
     }
   }
-  const int n_shares = use_shares ? (int)cut.size() : 0;
-  {
-    std::lock_guard<std::mutex> lk(bu.mu);
+  bu.publish([&] {
     bu.n_ref = n_ref;
     for (int g = 0; g < G; ++g) {
       // (shares: the first context is sized for the whole file -- the other shares' per-read state is appended to its own in the end)
@@ -872,446 +1094,196 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
       bu.hint[(size_t)g] = use_shares && g == 0 ? reads_hint * (uint64_t)G : reads_hint;
     }
     bu.plan_ready = true;
-  }
-  bu.cv.notify_all();
-  // everything below needs the contexts' buffers; the threads that feed a share only wait for THEIR context (below), the
-  // one-context loop for the one there is
-  auto wait_done = [&](int g) {
-    std::unique_lock<std::mutex> lk(bu.mu);
-    bu.cv.wait(lk, [&] { return bu.done[(size_t)g] != 0; });
-  };
-  bool brought_up = false;
-  double t_begin = 0;
-  auto bring_up_finish = [&]() -> int {        // -> 0, or EXTRACT_AGAIN_ON_HOST
-    if (brought_up) return 0;
-    brought_up = true;
-    const auto tb0 = now();
-    for (int g = 0; g < G; ++g) wait_done(g);
-    if (reaper.joinable()) reaper.join();
-    pin_thread.join();
-    g_bg_init = nullptr; g_bg_abort = nullptr;
-    if (getenv("STRL_STATE_ON_MAIN"))
-      for (int g = 0; g < G && !ctx_rc[(size_t)g]; ++g) {
-        const auto c1 = now();
-        int rc = strl_front_begin(ctxs[(size_t)g], bu.n_ref, bu.first_off[(size_t)g], bu.hint[(size_t)g]);
-        if (!rc) rc = strl_front_reserve(ctxs[(size_t)g], (uint32_t)chunk_blocks, chunk_bytes);
-        if (rc) { ctx_rc[(size_t)g] = rc; ctx_err[(size_t)g] = strl_last_error(); }
-        bu.t_state[(size_t)g] = secs(c1, now());
-      }
-    t_begin = secs(tb0, now());
-    for (double v : bu.t_create) t_ctx = std::max(t_ctx, v);
-    bool nomem = false;
-    for (int g = 0; g < G; ++g) if (ctx_rc[(size_t)g] == STRL_ERR_NOMEM) nomem = true;
-    if (nomem) {
-      for (int g = 0; g < G; ++g) if (ctx_rc[(size_t)g] == STRL_ERR_NOMEM) { fprintf(stderr, "[strling] %s: repeating the extraction with the host pair logic\n", ctx_err[(size_t)g].c_str()); break; }
-      for (size_t k = 0; k < pin.size(); ++k) { strl_pinned_free(pin[k]); strl_pinned_free(pin_meta[k]); }
-      for (strl_ctx *cc : ctxs) if (cc) strl_ctx_destroy(cc);
-      return EXTRACT_AGAIN_ON_HOST;
-    }
-    for (int g = 0; g < G; ++g) if (ctx_rc[(size_t)g]) quit("[strling] %s (status %d)", ctx_err[(size_t)g].c_str(), ctx_rc[(size_t)g]);
-    for (size_t k = 0; k < pin.size(); ++k) if (!pin[k] || !pin_meta[k]) quit("[strling] could not allocate page-locked memory");
-    return 0;
-  };
-  { const int br = bring_up_finish(); if (br) return br; }
-  strl_ctx *ctx = ctxs[0];
+  });
+  if (bu.finish()) return abandon(EXTRACT_AGAIN_ON_HOST);
   if (idx_on) {
     std::vector<int32_t> l_ref;
     for (const BamTarget &t : feed.targets()) l_ref.push_back((int32_t)std::min<uint64_t>(t.length, 0x7fffffffu));
-    if (idx_min_shift >= 0 ? strl_front_index_begin_csi(ctx, l_ref.data(), 0, idx_min_shift, -1) : strl_front_index_begin(ctx, l_ref.data(), 0)) idx_give_up(strl_last_error());
+    if (idx_min_shift >= 0 ? strl_front_index_begin_csi(ctxs[0], l_ref.data(), 0, idx_min_shift, -1) : strl_front_index_begin(ctxs[0], l_ref.data(), 0)) idx_give_up(strl_last_error());
   }
   if (verbose) {
     std::string devs;
     for (int g = 0; g < G; ++g) devs += (g ? " " : "") + std::to_string(device_of(g));
     fprintf(stderr, "[strling] %d context(s) on device(s) %s of %d\n", G, devs.c_str(), std::max(1, strl_device_count()));
   }
+  bring_times.t_begin = bu.t_begin; bring_times.t_ctx = bu.t_ctx; bring_times.t_pin = bu.t_pin;
+  for (double v : bu.t_state) bring_times.t_state = std::max(bring_times.t_state, v);
+  return 0;
+}
 
+// One feeding thread per share, each with its own header walker, its own ring of page-locked buffers, its own copy threads and
+// its own context: FeedPass N times side by side.  Nothing is carried from a share to the next; what makes that exact is checked
+// when the shares are done (a share must end exactly where the next begins).
+int ExtractFront::feed_shares() {
+  const int n_shares = (int)cut.size();
+  feed.halt();
+  shares = std::vector<Share>((size_t)n_shares);
+  for (int g = 0; g < n_shares; ++g) {
+    const uint64_t end = g + 1 < n_shares ? cut[(size_t)g + 1] : 0;
+    std::string err;
+    if (!shares[(size_t)g].fd.open_share(feed, cut[(size_t)g] >> 16, (uint32_t)(cut[(size_t)g] & 0xffff), end >> 16, (uint32_t)(end & 0xffff), err)) {
+      // an offset of the index that is no block of THIS file (a stale .bai): like every later check, the way out is the
+      // chunk-by-chunk run, which needs no index -- `--gpus 1` reads the file fine
+      fprintf(stderr, "[strling] share %d of %d: %s; repeating the extraction chunk by chunk\n", g, n_shares, err.c_str());
+      return abandon(EXTRACT_AGAIN_BY_CHUNKS);
+    }
+  }
+  static const bool feed_only = getenv("STRL_FEED_ONLY") != nullptr;     // measurement: the host side alone, no device stage
+  const int per_share = std::max(2, std::min(12, decode_threads() / n_shares));
+  auto feeder = [&](int g) {
+    Share &Z = shares[(size_t)g];
+    const auto z0 = tick();
+    ThreadPool pool(per_share);
+    FeedPass P{Z.fd, pool, pins, chunk_blocks, chunk_bytes, ctxs, tally};
+    P.share = g; P.feed_only = feed_only;
+    P.run();
+    Z.rc = P.short_read ? STRL_ERR_ARG : P.rc;
+    Z.fallback = P.bad_file; Z.err = P.err;
+    Z.t_walk = P.t_walk; Z.t_copy = P.t_copy; Z.t_wait = P.t_wait; Z.bytes = P.bytes; Z.chunks = P.chunks;
+    if (!feed_only && !Z.rc && !Z.fallback && ((Z.rc = finish_front(ctxs[(size_t)g], tally.by_ctx[(size_t)g])) || (Z.rc = strl_front_tail_bytes(ctxs[(size_t)g], &Z.tail))))
+      Z.err = strl_last_error();
+    Z.t_all = span(z0, tick());
+  };
+  std::vector<std::thread> feeders;
+  for (int g = 1; g < n_shares; ++g) feeders.emplace_back(feeder, g);
+  feeder(0);
+  for (auto &t : feeders) t.join();
+  tf = tick();
+  if (feed_only) {
+    uint64_t bytes = 0;
+    for (const Share &Z : shares) bytes += Z.bytes;
+    const double dt = span(t0, tick());
+    fprintf(stderr, "[strling] feed only: %d shares, %d copy threads each (+ walker, + read-ahead), %.3f s, %.2f GB of BAM, %.2f GB/s\n", n_shares, per_share, dt, (double)bytes / 1e9, (double)bytes / 1e9 / dt);
+    for (int g = 0; g < n_shares; ++g)
+      fprintf(stderr, "[strling]   share %d: %.2f GB in %llu chunks, %.3f s (block headers %.3f, reading compressed bytes %.3f)\n", g, (double)shares[(size_t)g].bytes / 1e9,
+              (unsigned long long)shares[(size_t)g].chunks, shares[(size_t)g].t_all, shares[(size_t)g].t_walk, shares[(size_t)g].t_copy);
+    fprintf(stderr, "[strling] feed only: waited %.3f s for the bring-up threads (slowest context %.3f, page-locked buffers %.3f); main() entered %.2f s after exec, now %.2f s after exec\n", bring_times.t_begin,
+            bring_times.t_ctx, bring_times.t_pin, g_main_at, since_exec());
+    fflush(stderr);
+    _exit(0);
+  }
+  bool again = false, nomem = false;
+  for (int g = 0; g < n_shares; ++g) {
+    const Share &Z = shares[(size_t)g];
+    if (Z.rc == STRL_ERR_NOMEM) nomem = true;
+    if (Z.rc == STRL_ERR_FORMAT || Z.rc == STRL_ERR_LIMIT || Z.rc == STRL_ERR_NOMEM || Z.fallback || (g + 1 < n_shares && Z.tail)) again = true;
+    else if (Z.rc == STRL_ERR_CRC) quit("[strling] error reading %s: %s", bam.c_str(), Z.err.c_str());
+    else if (Z.rc) quit("[strling] %s (status %d)", Z.err.c_str(), Z.rc);
+  }
+  if (again) {
+    // a share that did not end on the next one's first record (a stale index), a block or record the device front end
+    // refuses, too many records for one pass: the chunk-by-chunk run sorts out which, with its own ways out
+    for (int g = 0; g < n_shares; ++g)
+      if (shares[(size_t)g].rc || shares[(size_t)g].fallback || (g + 1 < n_shares && shares[(size_t)g].tail))
+        fprintf(stderr, "[strling] share %d of %d: %s; repeating the extraction chunk by chunk\n", g, n_shares,
+                shares[(size_t)g].rc || shares[(size_t)g].fallback ? shares[(size_t)g].err.c_str() : "the .bai's record start is not where the share's records end");
+    return abandon(nomem ? EXTRACT_AGAIN_ON_HOST : EXTRACT_AGAIN_BY_CHUNKS);      // (out of device memory: the chunk-by-chunk run would need as much)
+  }
+  for (int g = 0; g < n_shares; ++g) tally.owner.insert(tally.owner.end(), tally.by_ctx[(size_t)g].size(), (uint32_t)g);
+  tally.account(verbose, t0);
+  for (const Share &Z : shares) { t_walk += Z.t_walk; t_copy += Z.t_copy; t_push += Z.t_wait; }
+  if (verbose)
+    for (int g = 0; g < n_shares; ++g)
+      fprintf(stderr, "[strling] share %d: %.2f GB of BAM from offset %llu, %zu chunks, %.3f s (block headers %.3f, reading compressed bytes %.3f, enqueueing + waiting for the device %.3f)\n", g,
+              (double)shares[(size_t)g].bytes / 1e9, (unsigned long long)(cut[(size_t)g] >> 16), tally.by_ctx[(size_t)g].size(), shares[(size_t)g].t_all, shares[(size_t)g].t_walk,
+              shares[(size_t)g].t_copy, shares[(size_t)g].t_wait);
+  return 0;
+}
+
+// The whole file through FeedPass, its chunks over the contexts in turn.  With one context the fragment lengths start beside it:
+// they need the first ~2.1 M records only, so as soon as those are parsed their words are copied out (behind the parse, no wait)
+// and a thread makes the histogram beside the rest of the file.
+int ExtractFront::feed_by_chunks(ThreadPool &copy_pool) {
+  FeedPass P{feed, copy_pool, pins, chunk_blocks, chunk_bytes, ctxs, tally};
+  P.on_queue = [&](strl_ctx *cx, const ChunkTables &t, const StagedChunk &S) {
+    if (idx_on && strl_front_index_blocks(cx, t.boff, S.end_off(), (uint32_t)S.nb)) idx_give_up(strl_last_error());
+  };
+  P.on_turn = [&] {
+    tally.account(verbose, t0);
+    if (G != 1 || frag_thread.joinable() || !fw_early) return;
+    uint64_t parsed = 0;
+    CHECK(strl_front_records(ctxs[0], &parsed));
+    if (parsed < EXTRACT_EARLY_N) return;
+    void *ev = nullptr;
+    CHECK(strl_front_fragwords_async(ctxs[0], 0, EXTRACT_EARLY_N, fw_early, &ev));
+    frag_thread = std::thread([this, ev] { if (strl_event_wait(ev) == STRL_OK) fl.add_words(fw_early, 0, EXTRACT_EARLY_N); });
+  };
+  P.run();
+  t_walk = P.t_walk; t_copy = P.t_copy; t_push = P.t_wait; t_stage_wait = P.t_stage_wait;
+  if (P.bad_file || P.short_read) quit("[strling] error reading %s: %s", bam.c_str(), P.err.c_str());
+  if (P.rc) return front_failed(P.rc, P.err);
+  if (frag_thread.joinable()) frag_thread.join();
+  tf = tick();
+  for (int g = 0; g < G; ++g) FRONT_CHECK(finish_front(ctxs[(size_t)g], tally.by_ctx[(size_t)g]));
+  tally.account(verbose, t0);
+  return 0;
+}
+
+// every chunk has been through: the runs are sorted and merged and the bytes written now, so that an extraction that is
+// repeated with the host pair logic below still leaves its index
+void ExtractFront::write_index() {
+  if (!idx_on) return;
+  const auto ti0 = tick();
+  uint64_t nbytes = 0;
+  strl_bamindex_info info;
+  std::vector<uint8_t> bytes;
+  int irc = strl_front_index_finish(ctxs[0], &nbytes, &info);
+  if (!irc) { bytes.resize((size_t)nbytes + 1); irc = strl_bamindex_fetch(ctxs[0], bytes.data(), bytes.size()); }
+  std::string why;
+  if (irc) idx_give_up(strl_last_error());
+  else {
+    bytes.resize((size_t)nbytes);
+    if (!write_index_file(index_out, bytes, idx_min_shift >= 0, why)) idx_give_up(why);
+    else if (verbose)
+      fprintf(stderr, "[strling] index: %llu records (%llu without a reference), %llu runs resident on the device, %llu chunks, %llu bytes -> %s (sort, merge and write %.3f s)\n",
+              (unsigned long long)info.n_records, (unsigned long long)info.n_no_coor, (unsigned long long)info.n_runs, (unsigned long long)info.n_chunks,
+              (unsigned long long)nbytes, index_out.c_str(), span(ti0, tick()));
+  }
+  idx_on = false; g_index_done = true;
+}
+
+// the rest of the fragment-length pass, if the early part did not finish it (few proper pairs, small files); the median goes to the pair logic
+void ExtractFront::fragment_lengths() {
+  const auto tq = tick();
+  uint32_t *fw = reinterpret_cast<uint32_t *>(pins.data[0]);          // (page-locked: the copy needs no staging)
+  const uint64_t fw_cap = chunk_bytes / 4;
+  while (!fl.done() && fl.next < tally.n_seen) {
+    const uint64_t first = fl.next, m = std::min<uint64_t>({tally.n_seen - first, fw_cap, (uint64_t)8000000});
+    const auto tw0 = tick();
+    CHECK(strl_front_fragwords(ctxs[0], first, m, fw));
+    t_frag_copy += span(tw0, tick());
+    fl.add_words(fw, first, m);
+  }
+  fl.finish(frag);
+  const int frag_median = frag_median_of(frag, verbose);
+  opts.median_fragment_length = frag_median;
+  const auto ts0 = tick();
+  CHECK(strl_ctx_set_opts(ctxs[0], &opts));
+  t_setopts = span(ts0, tick());
+  t_frag = span(tq, tick());
+}
+
+int ExtractFront::run() {
+  t_start = tick();
+  plan_chunks();
+  if (const int rc = bring_up()) return rc;
+  strl_ctx *ctx = ctxs[0];
   fprintf(stderr, "[strling] collecting str-like reads\n");
-  const auto t0 = now();
+  t0 = tf = tick();
   // threads that read the compressed bytes into the page-locked buffers: 12 keep one device fed (0.8 - 1.1 s per 57 GB beside a
   // 3 s loop); several devices take what the CPU quota gives
   ThreadPool copy_pool(std::min(decode_threads(), G > 1 ? 48 : 12));
-  std::vector<BgzfFeed::Block> blks;
-  int64_t nreads = 0, n_tail = 0, tail_primary = 0;
-  uint64_t n_seen = 0, slow_segments = 0;
-  double t_walk = 0, t_copy = 0, t_push = 0, t_stage_wait = 0;
-  // summaries arrive per context in the order of ITS chunks; the file order is what counts
-  std::vector<strl_front_chunk> summary;                 // by chunk of the file
-  std::vector<uint32_t> chunk_owner;
-  std::vector<std::vector<uint64_t>> waiting((size_t)G);  // per context: its chunks without a summary yet
-  std::vector<size_t> waiting_at((size_t)G, 0);
-  uint64_t accounted = 0;
-  auto got = [&](int g, const strl_front_chunk *done, int n_done) {
-    for (int k = 0; k < n_done; ++k) summary[(size_t)waiting[(size_t)g][waiting_at[(size_t)g]++]] = done[k];
-  };
-  std::vector<uint8_t> have;
-  auto account = [&] {           // the leading run of chunks whose summaries are in, in file order
-    while (accounted < summary.size() && have[(size_t)accounted]) {
-      const strl_front_chunk &d = summary[(size_t)accounted++];
-      nreads += (int64_t)d.n_primary;
-      n_seen += d.n_records;
-      slow_segments += d.scan_slow_segments;
-      if (d.last_placed >= 0) { n_tail = (int64_t)d.n_records - 1 - d.last_placed; tail_primary = (int64_t)d.tail_primary; }
-      else { n_tail += (int64_t)d.n_records; tail_primary += (int64_t)d.n_primary; }
-      if (verbose) fprintf(stderr, "%lld %.1f reads/sec\n", (long long)nreads, (double)nreads / std::max(secs(t0, now()), 1e-9));
-    }
-  };
-  auto mark = [&](int g, size_t before) { for (size_t k = before; k < waiting_at[(size_t)g]; ++k) have[(size_t)waiting[(size_t)g][k]] = 1; };
-  std::vector<uint64_t> pushes((size_t)G, 0);
-  std::thread frag_thread, ahead;          // ahead: reads the next chunk's bytes (below)
-  // a file the device front end refuses (STRL_ERR_FORMAT) goes to the host reader instead of ending the run
-  auto give_up_front = [&]() -> int {
-    fprintf(stderr, "[strling] %s: repeating the extraction with the host reader\n", strl_last_error());
-    idx_give_up("the device front end gave the file up, and it is what builds the index");
-    if (ahead.joinable()) ahead.join();
-    if (frag_thread.joinable()) frag_thread.join();
-    for (size_t k = 0; k < pin.size(); ++k) { strl_pinned_free(pin[k]); strl_pinned_free(pin_meta[k]); }
-    for (strl_ctx *c : ctxs) strl_ctx_destroy(c);
-    return EXTRACT_AGAIN_HOST_FRONT;
-  };
-  // more records than one device pass takes (2^31 - 16; the reference has no cap, extract.nim:308), or more than the device's
-  // memory holds the per-read state of (STRL_ERR_NOMEM: ~130 B per read): the streaming host Cache, which keeps nothing per
-  // read on the device
-  auto over_limit = [&]() -> int {
-    fprintf(stderr, "[strling] %s: repeating the extraction with the host pair logic\n", strl_last_error());
-    idx_give_up("the pass over the file was given up before its end");
-    if (ahead.joinable()) ahead.join();
-    if (frag_thread.joinable()) frag_thread.join();
-    for (size_t k = 0; k < pin.size(); ++k) { strl_pinned_free(pin[k]); strl_pinned_free(pin_meta[k]); }
-    for (strl_ctx *c : ctxs) strl_ctx_destroy(c);
-    return EXTRACT_AGAIN_ON_HOST;
-  };
-#define FRONT_CHECK(call)                                                                    \
-  do {                                                                                       \
-    const int rc__ = (call);                                                                 \
-    if (rc__ == STRL_ERR_FORMAT) return give_up_front();                                     \
-    if (rc__ == STRL_ERR_LIMIT || rc__ == STRL_ERR_NOMEM) return over_limit();              \
-    if (rc__ == STRL_ERR_CRC) quit("[strling] error reading %s: %s", bam.c_str(), strl_last_error());   \
-    if (rc__ != STRL_OK) quit("[strling] %s (status %d)", strl_last_error(), rc__);          \
-  } while (0)
-  // fragment_length_distribution (utils.nim:86-111, extract.nim:281) from the flag / isize words the parse kept of every record.
-  // It needs the first ~2.1 M records only: as soon as they are parsed their words are copied out (behind the parse, no wait)
-  // and a thread makes the histogram beside the rest of the file.
-  struct FragState {
-    uint32_t frag[4096];
-    std::vector<int32_t> skipped;
-    int64_t counted = 0;
-    uint64_t next = 0;         // first record not looked at yet
-    bool done = false;
-  } fs;
-  memset(fs.frag, 0, sizeof fs.frag);
-  auto frag_feed = [&fs](const uint32_t *fw, uint64_t first, uint64_t n) {
-    const int64_t n_reads = 2000000, skip_reads = 100000;
-    for (uint64_t k = 0; k < n && !fs.done; ++k) {
-      const int64_t i = (int64_t)(first + k);
-      const uint32_t f = fw[k] & 0xffffu, is = fw[k] >> 16;
-      if (!(f & 0x2)) continue;
-      if (f & (0x800 | 0x100)) continue;
-      if (is > 4095u) continue;
-      if (i < skip_reads) { fs.skipped.push_back((int32_t)is); continue; }
-      fs.skipped.clear();
-      fs.frag[is]++;
-      if (++fs.counted > n_reads) fs.done = true;
-    }
-    fs.next = first + n;
-  };
-  // Two chunks ahead: while chunk k is handed to the device (strl_front_collect returns when chunk k-1 has been inflated and
-  // scanned), a thread walks the headers of chunk k+2 and reads its bytes, and chunk k+1 -- read during the previous turn --
-  // has its copy to the device queued first thing.  (Reading only after the push had returned put the read AND the copy
-  // between "chunk k-1 done" and "chunk k+1 may start": 0.40 s of 3.03 s with the inflate stream idle on the 57 GB file;
-  // reading one ahead and queueing the copy when the read was done still left it 0.3 s late in all: a 323 MB chunk takes
-  // 5 ms to read and 6.5 ms to copy, an inflate 12.)
-  struct Staged {
-    int64_t nb = 0;
-    size_t lo = 0, hi = 0, slot = 0;
-    uint64_t ci = 0;
-    int g = 0;
-    std::string err;
-    bool short_read = false;
-  };
-  Staged ring[3];                 // chunk c in ring[c % 3]: handed over | copy queued | being read
-  std::vector<uint64_t> staged((size_t)G, 0);
-  auto stage = [&](uint64_t ci, Staged &S) {
-    const auto ta = now();
-    S = Staged{};
-    // a short first chunk gets the device going while the second is being copied
-    S.nb = feed.next(blks, ci == 0 ? std::min<size_t>(chunk_blocks, 2048) : chunk_blocks, chunk_bytes, S.err);
-    if (S.nb <= 0) return;
-    const auto tb = now();
-    S.g = (int)(ci % (uint64_t)G);
-    S.ci = ci;
-    S.lo = blks.front().c_off; S.hi = blks.back().c_off + blks.back().clen;
-    if (idx_on) {        // a block starts at its gzip header; CRC-32 and ISIZE close the last one
-      std::vector<uint64_t> &bo = boff_ring[ci % 3];
-      bo.resize((size_t)S.nb);
-      for (size_t k = 0; k < (size_t)S.nb; ++k) bo[k] = blks[k].c_off - blks[k].hdr;
-    }
-    S.slot = RING * (size_t)S.g + (size_t)(staged[(size_t)S.g]++ % RING);
-    uint8_t *dst = pin[S.slot];
-    const size_t lo = S.lo, hi = S.hi, piece = (size_t)4 << 20, pieces = (hi - lo + piece - 1) / piece;
-    std::atomic<int> short_reads{0};
-    copy_pool.parallel_for(pieces, [&](size_t k) { if (!feed.copy_at(dst + k * piece, lo + k * piece, std::min(piece, hi - lo - k * piece))) ++short_reads; });
-    feed.done_with(lo, hi - lo);        // (once per chunk, by this thread: per 4 MB piece it was a round of TLB shoot-downs per piece on every copying CPU)
-    S.short_read = short_reads.load() != 0;
-    uint64_t *coff = reinterpret_cast<uint64_t *>(pin_meta[S.slot]);
-    uint32_t *clen = reinterpret_cast<uint32_t *>(coff + chunk_blocks), *isz = clen + chunk_blocks, *crc = isz + chunk_blocks;
-    for (size_t k = 0; k < (size_t)S.nb; ++k) { coff[k] = blks[k].c_off - lo; clen[k] = blks[k].clen; isz[k] = blks[k].isize; crc[k] = blks[k].crc; }
-    t_walk += secs(ta, tb); t_copy += secs(tb, now());
-  };
-  auto queue_copy = [&](const Staged &S) -> int {     // the chunk's copy to the device, ahead of its turn
-    if (idx_on && strl_front_index_blocks(ctxs[(size_t)S.g], boff_ring[S.ci % 3].data(), S.hi + 8, (uint32_t)S.nb)) idx_give_up(strl_last_error());
-    uint64_t *ncoff = reinterpret_cast<uint64_t *>(pin_meta[S.slot]);
-    uint32_t *nclen = reinterpret_cast<uint32_t *>(ncoff + chunk_blocks), *nisz = nclen + chunk_blocks, *ncrc = nisz + chunk_blocks;
-    return strl_front_stage(ctxs[(size_t)S.g], pin[S.slot], S.hi - S.lo, ncoff, nclen, nisz, ncrc, (uint32_t)S.nb);
-  };
-  auto tf = now();
-  if (use_shares) {
-    // One feeding thread per share, each with its own header walker, its own ring of page-locked buffers, its own copy
-    // threads and its own context: the pipeline of the one-GPU loop below, N times side by side.  Nothing is carried from a
-    // share to the next; what makes that exact is checked when the shares are done (a share must end exactly where the
-    // next begins).
-    feed.halt();
-    struct Share {
-      BgzfFeed fd;
-      std::vector<strl_front_chunk> sums;
-      int rc = 0;
-      bool fallback = false;
-      std::string err;
-      uint32_t tail = 0;
-      double t_walk = 0, t_copy = 0, t_wait = 0, t_all = 0;
-      uint64_t bytes = 0, chunks = 0;
-    };
-    std::vector<Share> shares((size_t)n_shares);
-    for (int g = 0; g < n_shares; ++g) {
-      const uint64_t end = g + 1 < n_shares ? cut[(size_t)g + 1] : 0;
-      if (!shares[(size_t)g].fd.open_share(feed, cut[(size_t)g] >> 16, (uint32_t)(cut[(size_t)g] & 0xffff), end >> 16, (uint32_t)(end & 0xffff), err)) {
-        // an offset of the index that is no block of THIS file (a stale .bai): like every later check, the way out is the
-        // chunk-by-chunk run, which needs no index -- `--gpus 1` reads the file fine
-        fprintf(stderr, "[strling] share %d of %d: %s; repeating the extraction chunk by chunk\n", g, n_shares, err.c_str());
-        for (Share &Z : shares) Z.fd.close();
-        for (size_t k = 0; k < pin.size(); ++k) { strl_pinned_free(pin[k]); strl_pinned_free(pin_meta[k]); }
-        for (strl_ctx *c : ctxs) strl_ctx_destroy(c);
-        return EXTRACT_AGAIN_BY_CHUNKS;
-      }
-    }
-    static const bool feed_only = getenv("STRL_FEED_ONLY") != nullptr;     // measurement: the host side alone, no device stage
-    const int per_share = std::max(2, std::min(12, decode_threads() / n_shares));
-    auto feeder = [&](int g) {
-      Share &Z = shares[(size_t)g];
-      strl_ctx *cx = ctxs[(size_t)g];
-      const auto z0 = now();
-      ThreadPool pool(per_share);
-      std::vector<BgzfFeed::Block> bl;
-      struct St { int64_t nb = 0; size_t lo = 0, hi = 0, slot = 0; bool last = false, short_read = false; std::string err; };
-      St ring[3];
-      uint64_t staged = 0;
-      auto stage = [&](uint64_t ci, St &S) {
-        const auto ta = now();
-        S = St{};
-        S.nb = Z.fd.next(bl, ci == 0 ? std::min<size_t>(chunk_blocks, 2048) : chunk_blocks, chunk_bytes, S.err, &S.last);
-        if (S.nb <= 0) return;
-        const auto tb = now();
-        S.lo = bl.front().c_off; S.hi = bl.back().c_off + bl.back().clen;
-        S.slot = RING * (size_t)g + (size_t)(staged++ % RING);
-        uint8_t *dst = pin[S.slot];
-        const size_t lo = S.lo, hi = S.hi, piece = (size_t)4 << 20, pieces = (hi - lo + piece - 1) / piece;
-        std::atomic<int> short_reads{0};
-        pool.parallel_for(pieces, [&](size_t k) { if (!Z.fd.copy_at(dst + k * piece, lo + k * piece, std::min(piece, hi - lo - k * piece))) ++short_reads; });
-        Z.fd.done_with(lo, hi - lo);
-        S.short_read = short_reads.load() != 0;
-        uint64_t *coff = reinterpret_cast<uint64_t *>(pin_meta[S.slot]);
-        uint32_t *clen = reinterpret_cast<uint32_t *>(coff + chunk_blocks), *isz = clen + chunk_blocks, *crc = isz + chunk_blocks;
-        for (size_t k = 0; k < (size_t)S.nb; ++k) { coff[k] = bl[k].c_off - lo; clen[k] = bl[k].clen; isz[k] = bl[k].isize; crc[k] = bl[k].crc; }
-        Z.t_walk += secs(ta, tb); Z.t_copy += secs(tb, now());
-        Z.bytes += hi - lo; ++Z.chunks;
-      };
-      auto fail = [&](int rc) { Z.rc = rc; Z.err = strl_last_error(); };
-      auto tables = [&](const St &S, uint64_t *&coff, uint32_t *&clen, uint32_t *&isz, uint32_t *&crc) {
-        coff = reinterpret_cast<uint64_t *>(pin_meta[S.slot]);
-        clen = reinterpret_cast<uint32_t *>(coff + chunk_blocks); isz = clen + chunk_blocks; crc = isz + chunk_blocks;
-      };
-      auto queue_copy = [&](const St &S) -> int {     // the chunk's copy to the device, ahead of its turn
-        uint64_t *coff; uint32_t *clen, *isz, *crc;
-        tables(S, coff, clen, isz, crc);
-        int rc = S.last && Z.fd.tail_trim() ? strl_front_trim_next(cx, Z.fd.tail_trim()) : 0;
-        return rc ? rc : strl_front_stage(cx, pin[S.slot], S.hi - S.lo, coff, clen, isz, crc, (uint32_t)S.nb);
-      };
-      std::thread ahead;
-      int rc = 0;
-      stage(0, ring[0]);
-      if (!feed_only && ring[0].nb > 0 && !ring[0].short_read && (rc = queue_copy(ring[0]))) { fail(rc); return; }
-      if (ring[0].nb > 0) stage(1, ring[1]);
-      for (uint64_t ci = 0;; ++ci) {
-        const St cur = ring[ci % 3];
-        St &nxt = ring[(ci + 1) % 3];
-        if (cur.nb < 0) { Z.fallback = true; Z.err = cur.err; break; }     // (a damaged file says so again in the chunk-by-chunk run)
-        if (cur.nb == 0) break;
-        if (cur.short_read) { Z.rc = STRL_ERR_ARG; Z.err = "short read"; break; }
-        if (nxt.nb > 0) ahead = std::thread([&, ci] { stage(ci + 2, ring[(ci + 2) % 3]); });
-        else ring[(ci + 2) % 3] = St{};
-        if (!feed_only) {
-          if (nxt.nb > 0 && !nxt.short_read && (rc = queue_copy(nxt))) { fail(rc); break; }
-          uint64_t *coff; uint32_t *clen, *isz, *crc;
-          tables(cur, coff, clen, isz, crc);
-          strl_front_chunk done[2];
-          int n_done = 0;
-          const auto tc = now();
-          if ((rc = strl_front_enqueue_after(cx, nullptr, pin[cur.slot], cur.hi - cur.lo, coff, clen, isz, crc, (uint32_t)cur.nb, done, &n_done))) { fail(rc); break; }
-          for (int k = 0; k < n_done; ++k) Z.sums.push_back(done[k]);
-          if ((rc = strl_front_collect(cx))) { fail(rc); break; }
-          Z.t_wait += secs(tc, now());
-        }
-        if (ahead.joinable()) ahead.join();
-      }
-      if (ahead.joinable()) ahead.join();
-      if (!feed_only && !Z.rc && !Z.fallback) {
-        strl_front_chunk done[2];
-        int n_done = 0;
-        if ((rc = strl_front_finish(cx, done, &n_done))) fail(rc);
-        else {
-          for (int k = 0; k < n_done; ++k) Z.sums.push_back(done[k]);
-          if ((rc = strl_front_tail_bytes(cx, &Z.tail))) fail(rc);
-        }
-      }
-      Z.t_all = secs(z0, now());
-    };
-    std::vector<std::thread> feeders;
-    for (int g = 1; g < n_shares; ++g) feeders.emplace_back(feeder, g);
-    feeder(0);
-    for (auto &t : feeders) t.join();
-    tf = now();
-    if (feed_only) {
-      uint64_t bytes = 0;
-      for (const Share &Z : shares) bytes += Z.bytes;
-      const double dt = secs(t0, now());
-      fprintf(stderr, "[strling] feed only: %d shares, %d copy threads each (+ walker, + read-ahead), %.3f s, %.2f GB of BAM, %.2f GB/s\n", n_shares, per_share, dt, (double)bytes / 1e9, (double)bytes / 1e9 / dt);
-      for (int g = 0; g < n_shares; ++g)
-        fprintf(stderr, "[strling]   share %d: %.2f GB in %llu chunks, %.3f s (block headers %.3f, reading compressed bytes %.3f)\n", g, (double)shares[(size_t)g].bytes / 1e9,
-                (unsigned long long)shares[(size_t)g].chunks, shares[(size_t)g].t_all, shares[(size_t)g].t_walk, shares[(size_t)g].t_copy);
-      fprintf(stderr, "[strling] feed only: waited %.3f s for the bring-up threads (slowest context %.3f, page-locked buffers %.3f); main() entered %.2f s after exec, now %.2f s after exec\n", t_begin, t_ctx,
-              t_pin, g_main_at, since_exec());
-      fflush(stderr);
-      _exit(0);
-    }
-    bool again = false, nomem = false;
-    for (int g = 0; g < n_shares; ++g) {
-      const Share &Z = shares[(size_t)g];
-      if (Z.rc == STRL_ERR_NOMEM) nomem = true;
-      if (Z.rc == STRL_ERR_FORMAT || Z.rc == STRL_ERR_LIMIT || Z.rc == STRL_ERR_NOMEM || Z.fallback || (g + 1 < n_shares && Z.tail)) again = true;
-      else if (Z.rc == STRL_ERR_CRC) quit("[strling] error reading %s: %s", bam.c_str(), Z.err.c_str());
-      else if (Z.rc) quit("[strling] %s (status %d)", Z.err.c_str(), Z.rc);
-    }
-    if (again) {
-      // a share that did not end on the next one's first record (a stale index), a block or record the device front end
-      // refuses, too many records for one pass: the chunk-by-chunk run sorts out which, with its own ways out
-      for (int g = 0; g < n_shares; ++g)
-        if (shares[(size_t)g].rc || shares[(size_t)g].fallback || (g + 1 < n_shares && shares[(size_t)g].tail))
-          fprintf(stderr, "[strling] share %d of %d: %s; repeating the extraction chunk by chunk\n", g, n_shares,
-                  shares[(size_t)g].rc || shares[(size_t)g].fallback ? shares[(size_t)g].err.c_str() : "the .bai's record start is not where the share's records end");
-      for (Share &Z : shares) Z.fd.close();
-      for (size_t k = 0; k < pin.size(); ++k) { strl_pinned_free(pin[k]); strl_pinned_free(pin_meta[k]); }
-      for (strl_ctx *c : ctxs) strl_ctx_destroy(c);
-      return nomem ? EXTRACT_AGAIN_ON_HOST : EXTRACT_AGAIN_BY_CHUNKS;      // (out of device memory: the chunk-by-chunk run would need as much)
-    }
-    for (int g = 0; g < n_shares; ++g)
-      for (const strl_front_chunk &d : shares[(size_t)g].sums) { summary.push_back(d); have.push_back(1); chunk_owner.push_back((uint32_t)g); }
-    account();
-    for (int g = 0; g < n_shares; ++g) { t_walk += shares[(size_t)g].t_walk; t_copy += shares[(size_t)g].t_copy; t_push += shares[(size_t)g].t_wait; }
-    if (verbose)
-      for (int g = 0; g < n_shares; ++g)
-        fprintf(stderr, "[strling] share %d: %.2f GB of BAM from offset %llu, %zu chunks, %.3f s (block headers %.3f, reading compressed bytes %.3f, enqueueing + waiting for the device %.3f)\n", g,
-                (double)shares[(size_t)g].bytes / 1e9, (unsigned long long)(cut[(size_t)g] >> 16), shares[(size_t)g].sums.size(), shares[(size_t)g].t_all, shares[(size_t)g].t_walk,
-                shares[(size_t)g].t_copy, shares[(size_t)g].t_wait);
-  } else {
-  stage(0, ring[0]);
-  if (ring[0].nb > 0 && !ring[0].short_read) FRONT_CHECK(queue_copy(ring[0]));
-  if (ring[0].nb > 0) stage(1, ring[1]);
-  for (uint64_t ci = 0;; ++ci) {
-    const Staged cur = ring[ci % 3];
-    Staged &nxt = ring[(ci + 1) % 3];
-    const int64_t nb = cur.nb;
-    if (nb < 0) quit("[strling] error reading %s: %s", bam.c_str(), cur.err.c_str());
-    if (nb == 0) break;
-    if (cur.short_read) quit("[strling] error reading %s: short read", bam.c_str());
-    const int g = cur.g;
-    const size_t lo = cur.lo, hi = cur.hi;
-    uint8_t *dst = pin[cur.slot];
-    uint64_t *coff = reinterpret_cast<uint64_t *>(pin_meta[cur.slot]);
-    uint32_t *clen = reinterpret_cast<uint32_t *>(coff + chunk_blocks), *isz = clen + chunk_blocks, *crc = isz + chunk_blocks;
-    if (nxt.nb > 0) ahead = std::thread([&, ci] { stage(ci + 2, ring[(ci + 2) % 3]); });
-    else ring[(ci + 2) % 3] = Staged{};
-    if (nxt.nb > 0 && !nxt.short_read) FRONT_CHECK(queue_copy(nxt));
-    const auto tc = now();
-    strl_front_chunk done[2];
-    int n_done = 0;
-    summary.push_back(strl_front_chunk{});
-    have.push_back(0);
-    chunk_owner.push_back((uint32_t)g);
-    waiting[(size_t)g].push_back(ci);
-    const size_t before = waiting_at[(size_t)g];
-    FRONT_CHECK(strl_front_enqueue_after(ctxs[(size_t)g], ci ? ctxs[(size_t)((ci - 1) % (uint64_t)G)] : nullptr, dst, hi - lo, coff, clen, isz, crc, (uint32_t)nb, done, &n_done));
-    ++pushes[(size_t)g];
-    got(g, done, n_done);
-    mark(g, before);
-    FRONT_CHECK(strl_front_collect(ctxs[(size_t)g]));
-    account();
-    if (G == 1 && !frag_thread.joinable()) {
-      uint64_t parsed = 0;
-      CHECK(strl_front_records(ctx, &parsed));
-      if (parsed >= early_n) {
-        void *ev = nullptr;
-        if (fw_early) {
-          CHECK(strl_front_fragwords_async(ctx, 0, early_n, fw_early, &ev));
-          frag_thread = std::thread([&, ev] { if (strl_event_wait(ev) == STRL_OK) frag_feed(fw_early, 0, early_n); });
-        }
-      }
-    }
-    const auto td0 = now();
-    if (ahead.joinable()) ahead.join();
-    t_stage_wait += secs(td0, now());
-    t_push += secs(tc, now());
-  }
-  if (frag_thread.joinable()) frag_thread.join();
-  tf = now();
-  for (int g = 0; g < G; ++g) {
-    strl_front_chunk done[2];
-    int n_done = 0;
-    const size_t before = waiting_at[(size_t)g];
-    FRONT_CHECK(strl_front_finish(ctxs[(size_t)g], done, &n_done));
-    got(g, done, n_done);
-    mark(g, before);
-  }
-  account();
-  }   // (chunk by chunk)
-  if (idx_on) {
-    // every chunk has been through: the runs are sorted and merged and the bytes written now, so that an extraction that is
-    // repeated with the host pair logic below still leaves its index
-    const auto ti0 = now();
-    uint64_t nbytes = 0;
-    strl_bamindex_info info;
-    std::vector<uint8_t> bytes;
-    int irc = strl_front_index_finish(ctx, &nbytes, &info);
-    if (!irc) { bytes.resize((size_t)nbytes + 1); irc = strl_bamindex_fetch(ctx, bytes.data(), bytes.size()); }
-    std::string why;
-    if (irc) idx_give_up(strl_last_error());
-    else {
-      bytes.resize((size_t)nbytes);
-      if (!write_index_file(index_out, bytes, idx_min_shift >= 0, why)) idx_give_up(why);
-      else if (verbose)
-        fprintf(stderr, "[strling] index: %llu records (%llu without a reference), %llu runs resident on the device, %llu chunks, %llu bytes -> %s (sort, merge and write %.3f s)\n",
-                (unsigned long long)info.n_records, (unsigned long long)info.n_no_coor, (unsigned long long)info.n_runs, (unsigned long long)info.n_chunks,
-                (unsigned long long)nbytes, index_out.c_str(), secs(ti0, now()));
-    }
-    idx_on = false; g_index_done = true;
-  }
-  const auto tf2 = now();
+  if (const int rc = use_shares ? feed_shares() : feed_by_chunks(copy_pool)) return rc;
+  write_index();
+  const auto tf2 = tick();
   if (G > 1) {
-    std::vector<uint64_t> recs(summary.size());
-    for (size_t k = 0; k < summary.size(); ++k) recs[k] = summary[k].n_records;
-    FRONT_CHECK(strl_ctxs_extract_gather(ctxs.data(), G, chunk_owner.data(), recs.data(), recs.size()));
-    if (verbose) fprintf(stderr, "[strling] %zu chunks over %d contexts on %d device(s)%s; per-read state gathered on the first in %.3f s\n", summary.size(), G, std::min(G, std::max(1, strl_device_count())),
-                         use_shares ? ", a contiguous share of the file each" : " in turn", secs(tf2, now()));
+    std::vector<uint64_t> recs(tally.summary.size());
+    for (size_t k = 0; k < recs.size(); ++k) recs[k] = tally.summary[k].n_records;
+    FRONT_CHECK(strl_ctxs_extract_gather(ctxs.data(), G, tally.owner.data(), recs.data(), recs.size()));
+    if (verbose) fprintf(stderr, "[strling] %zu chunks over %d contexts on %d device(s)%s; per-read state gathered on the first in %.3f s\n", recs.size(), G, std::min(G, std::max(1, strl_device_count())),
+                         use_shares ? ", a contiguous share of the file each" : " in turn", span(tf2, tick()));
   }
-  const double t_drain = secs(tf, now());
+  t_drain = span(tf, tick());
   {   // extract.nim:310-313: one line per large contig that has reads (here: once the whole file has been through)
     std::vector<uint8_t> seen((size_t)n_ref + 1, 0);
     CHECK(strl_front_tids(ctx, seen.data(), n_ref));
@@ -1319,66 +1291,35 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
       if (seen[(size_t)t] && feed.targets()[(size_t)t].length > 2000000u) fprintf(stderr, "[strling] extracting chromosome:%s\n", feed.targets()[(size_t)t].name.c_str());
   }
   fprintf(stderr, "[strling] extracting unmapped reads\n");
-  nreads += tail_primary;   // the "*" region is counted a second time by the reference's progress counter (extract.nim:326-329)
-  // the rest of the fragment-length pass, if the early part did not finish it (few proper pairs, small files)
-  const auto tq = now();
-  double t_frag_copy = 0;
-  {
-    uint32_t *fw = reinterpret_cast<uint32_t *>(pin[0]);          // (page-locked: the copy needs no staging)
-    const uint64_t fw_cap = chunk_bytes / 4;
-    while (!fs.done && fs.next < n_seen) {
-      const uint64_t first = fs.next, m = std::min<uint64_t>({n_seen - first, fw_cap, (uint64_t)8000000});
-      const auto tw0 = now();
-      CHECK(strl_front_fragwords(ctx, first, m, fw));
-      t_frag_copy += secs(tw0, now());
-      frag_feed(fw, first, m);
-    }
-    uint64_t sum = 0;
-    for (int k = 0; k < 4096; ++k) sum += fs.frag[k];
-    if ((uint32_t)sum == 0) {
-      fprintf(stderr, "using first reads in fragment_length_distribution calculation as there were not enough\n");
-      for (int32_t is : fs.skipped) fs.frag[is]++;
-    }
-  }
-  uint32_t *frag = fs.frag;
-  const int frag_median = strl_frag_median(frag, 0.5);
-  if (verbose) {
-    fprintf(stderr, "Calculated median fragment length:%d\n", frag_median);
-    fprintf(stderr, "10th, 90th percentile of fragment length:%d %d\n", strl_frag_median(frag, 0.1), strl_frag_median(frag, 0.9));
-  }
-  opts.median_fragment_length = frag_median;
-  const auto ts0 = now();
-  CHECK(strl_ctx_set_opts(ctx, &opts));
-  const double t_setopts = secs(ts0, now());
-  const double t_frag = secs(tq, now());
-  const auto tp0 = now();
+  const int64_t nreads = tally.nreads + tally.tail_primary;   // the "*" region is counted a second time by the reference's progress counter (extract.nim:326-329)
+  const uint64_t n_seen = tally.n_seen;
+  fragment_lengths();
+  // pair logic over the whole file
+  const auto tp0 = tick();
   uint64_t nt = 0;
   int rc = 0;
-  double t_finish = 0;
   auto cap_of = [](uint64_t v) { return std::min<uint64_t>(v, 0x7ffffff0ull); };
   for (int attempt = 0; attempt < 2; ++attempt) {
-    rc = strl_extract_finish(ctx, n_tail, attempt ? cap_of(3 * n_seen + 16) : 0, attempt ? cap_of(8 * n_seen + 16) : 0);
+    rc = strl_extract_finish(ctx, tally.n_tail, attempt ? cap_of(3 * n_seen + 16) : 0, attempt ? cap_of(8 * n_seen + 16) : 0);
     if (rc == STRL_ERR_NOMEM) break;
     CHECK(rc);
     rc = strl_treads_fetch(ctx, nullptr, 0, &nt, nullptr);
     if (rc != STRL_ERR_CAPACITY) break;
   }
-  t_finish = secs(tp0, now());
+  const double t_finish = span(tp0, tick());
   if (rc == STRL_ERR_FORMAT || rc == STRL_ERR_NOMEM) {
     fprintf(stderr, "[strling] %s: repeating the extraction with the host pair logic\n", strl_last_error());
-    for (size_t k = 0; k < pin.size(); ++k) { strl_pinned_free(pin[k]); strl_pinned_free(pin_meta[k]); }
-    for (strl_ctx *c : ctxs) strl_ctx_destroy(c);
-    return EXTRACT_AGAIN_ON_HOST;
+    return abandon(EXTRACT_AGAIN_ON_HOST);
   }
   if (rc) quit("[strling] %s (status %d)", strl_last_error(), rc);
   // treads + names through the page-locked chunk buffers (free now): no staging copies; vectors when they are too small
   std::vector<strl_tread> tv;
   std::vector<uint64_t> qv;
   std::string nv;
-  strl_tread *treads_p = reinterpret_cast<strl_tread *>(pin[0]);
-  uint64_t *qoff_p = reinterpret_cast<uint64_t *>(pin[1]);
+  strl_tread *treads_p = reinterpret_cast<strl_tread *>(pins.data[0]);
+  uint64_t *qoff_p = reinterpret_cast<uint64_t *>(pins.data[1]);
   const uint64_t names_room = chunk_bytes > (nt + 1) * 8 + 4096 ? chunk_bytes - (nt + 1) * 8 - 64 : 0;
-  char *names_p = reinterpret_cast<char *>(pin[1]) + (nt + 1) * 8 + 64;
+  char *names_p = reinterpret_cast<char *>(pins.data[1]) + (nt + 1) * 8 + 64;
   // (names: the room behind the offsets serves unless the names average more than 24 bytes -- then the call reports what it
   // needs and is repeated with vectors; sizing for the 255-byte maximum made a whole genome's 8e6 treads zero-fill 2 GB)
   if ((nt + 1) * sizeof(strl_tread) > chunk_bytes || names_room < nt * 24) {
@@ -1398,66 +1339,50 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
     const uint64_t per = 1 << 17;
     copy_pool.parallel_for((size_t)((nt + per - 1) / per), [&](size_t q) { for (uint64_t i = q * per, e = std::min(nt, i + per); i < e; ++i) treads_p[i].qname_id = (int64_t)i; });
   }
-  const double t_pair = secs(tp0, now());
+  const double t_pair = span(tp0, tick());
   fprintf(stderr, "[strling] writing binary file:%s\n", bin.c_str());
-  const auto tw0 = now();
+  const auto tw0 = tick();
   // The rings the .bin is not written out of go back meanwhile: un-registering page-locked memory the DMA engines have used
   // is ~0.1 s per GB (profiles/r06/exit_where.log) whoever does it -- this thread beside the writer's, or the kernel behind
   // the process' last line, on the caller's clock.  (STRL_NO_EARLY_UNPIN=1: left to the exit.)
   std::thread early_unpin;
-  if (!getenv("STRL_NO_EARLY_UNPIN"))
-    early_unpin = std::thread([&] {
-      for (size_t k = 0; k < pin.size(); ++k) {
-        if (pin[k] && (void *)pin[k] != (void *)treads_p && (void *)pin[k] != (void *)qoff_p) { strl_pinned_free(pin[k]); pin[k] = nullptr; }
-        if (pin_meta[k]) { strl_pinned_free(pin_meta[k]); pin_meta[k] = nullptr; }
-      }
-    });
+  if (!getenv("STRL_NO_EARLY_UNPIN")) early_unpin = std::thread([&] { pins.release_except(treads_p, qoff_p); });
   const int bin_rc = strl_bin_write(bin.c_str(), (float)p, min_mapq, frag, feed.header_text().data(), (int32_t)feed.header_text().size(), treads_p, nt, qoff_p, names_p);
   if (early_unpin.joinable()) early_unpin.join();
   CHECK(bin_rc);
-  const double t_write = secs(tw0, now());
+  const double t_write = span(tw0, tick());
   fprintf(stderr, "[strling] finished extraction\n");
   if (verbose) {
     fprintf(stderr, "[strling] %lld reads, %llu STR reads, 0 reads still waiting for a mate\n", (long long)nreads, (unsigned long long)nt);
     fprintf(stderr, "[strling] seconds: total %.3f  (beside the device: block headers %.3f, reading compressed bytes %.3f)  enqueueing + waiting for the device %.3f  waiting for the next chunk's bytes %.3f  "
                     "draining the device %.3f  fragment lengths %.3f (copy %.3f, set_opts %.3f)  pair logic + names %.3f (pair logic over all reads + .bin order %.3f)  (device front end; %llu scan segments walked twice)\n",
-            secs(t0, now()), t_walk, t_copy, t_push - t_stage_wait, t_stage_wait, t_drain, t_frag, t_frag_copy, t_setopts, t_pair, t_finish, (unsigned long long)slow_segments);
-  }
-  if (verbose) {
+            span(t0, tick()), t_walk, t_copy, t_push, t_stage_wait, t_drain, t_frag, t_frag_copy, t_setopts, t_pair, t_finish, (unsigned long long)tally.slow_segments);
     uint64_t mf = 0, mt = 0;
     if (strl_ctx_mem_info(ctx, &mf, &mt) == STRL_OK)
       fprintf(stderr, "[strling] device memory in use at the end (all chunks' per-read state resident): %.2f GB of %.1f GB\n", (double)(mt - mf) / 1e9, (double)mt / 1e9);
-  }
-  if (verbose)
-  {
-    double t_state = 0;
-    for (double v : bu.t_state) t_state = std::max(t_state, v);
     fprintf(stderr, "[strling] seconds before the loop: header walk %.3f, genome table (host half) %.3f, then waiting for the bring-up threads %.3f -- beside all that, a thread "
                     "per context: slowest context + its options %.3f, slowest per-read state for %llu reads + front-end buffers %.3f; page-locked buffers %.3f; writing the .bin %.3f; whole run %.3f\n",
-            t_open, t_genome, t_begin, t_ctx, (unsigned long long)reads_hint, t_state, t_pin, t_write, secs(t_start, now()));
+            t_open, t_genome, bring_times.t_begin, bring_times.t_ctx, (unsigned long long)reads_hint, bring_times.t_state, bring_times.t_pin, t_write, span(t_start, tick()));
     fprintf(stderr, "[strling] process: main() entered %.2f s after exec, now %.2f s after exec (what the caller's clock adds behind this line is the kernel "
                     "reclaiming the process' device and page-locked memory)\n", g_main_at, since_exec());
   }
-  // the process ends here: the driver reclaims device and page-locked memory faster than freeing them piece by piece would
-  // (STRL_TEARDOWN=1 frees them explicitly)
+  // (the process ends in end_process; STRL_TEARDOWN=1 frees the page-locked buffers, the contexts and the feed by hand first)
   if (getenv("STRL_TEARDOWN")) {
-    const auto td0 = now();
-    for (size_t k = 0; k < pin.size(); ++k) { strl_pinned_free(pin[k]); strl_pinned_free(pin_meta[k]); }
-    const auto td1 = now();
-    for (strl_ctx *c : ctxs) strl_ctx_destroy(c);
-    const auto td2 = now();
+    const auto td0 = tick();
+    pins.release();
+    const auto td1 = tick();
+    for (strl_ctx *&c : ctxs) { strl_ctx_destroy(c); c = nullptr; }
+    const auto td2 = tick();
     feed.close();
     if (verbose) fprintf(stderr, "[strling] teardown by hand: page-locked buffers %.3f s, contexts (device memory, streams) %.3f s, the feed (mapping, threads) %.3f s; now %.2f s after exec\n",
-                         secs(td0, td1), secs(td1, td2), secs(td2, now()), since_exec());
-    return 0;
+                         span(td0, td1), span(td1, td2), span(td2, tick()), since_exec());
   }
-  // ... and so does the runtime's own shutdown (~0.15 s with gigabytes of device memory mapped).  Under a profiler the normal
-  // exit path is kept: its tool library writes its files from an exit handler.
-  const char *pre = getenv("LD_PRELOAD");
-  if ((pre && strstr(pre, "rocprof")) || getenv("ROCP_TOOL_LIBRARIES") || getenv("ROCPROFILER_LIBRARY_CTOR")) return 0;
-  fflush(stdout);
-  fflush(stderr);
-  _exit(0);
+  return end_process(ctxs[0]);
+}
+#undef FRONT_CHECK
+
+static int extract_front(const Args &a, const std::string &bam, const std::string &bin, double p, uint8_t min_mapq, bool verbose) {
+  return ExtractFront(a, bam, bin, p, min_mapq, verbose).run();
 }
 
 // The end of a `strling` process whose outputs are closed: the driver reclaims device and page-locked memory faster than the
@@ -1769,10 +1694,7 @@ static int merge_main(int argc, char **argv) {
 // and sample side by side: ~0.3 s each; the context alone is 0.11 s).  pin / pin_meta: three page-locked chunk buffers of
 // chunk_blocks blocks each (allocated beside the context).  false: the caller takes the host's pass (the verdict on a file the
 // front end refuses is the host reader's).
-static bool fragment_lengths_on_device(strl_ctx *ctx, const std::string &bam, uint32_t frag[4096], uint8_t *const pin[3], uint8_t *const pin_meta[3], size_t chunk_blocks,
-                                       size_t chunk_bytes, std::string &why) {
-  const int64_t n_reads = 2000000, skip_reads = 100000;
-  memset(frag, 0, 4096 * sizeof(uint32_t));
+static bool fragment_lengths_on_device(strl_ctx *ctx, const std::string &bam, uint32_t frag[4096], const PinnedRing &pins, size_t chunk_blocks, size_t chunk_bytes, std::string &why) {
   const bool tm = getenv("STRL_FRAG_TIMING") != nullptr;
   const auto tm0 = std::chrono::steady_clock::now();
   auto lap = [&](const char *what) { if (tm) fprintf(stderr, "[fragment lengths] %s at %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count()); };
@@ -1785,28 +1707,14 @@ static bool fragment_lengths_on_device(strl_ctx *ctx, const std::string &bam, ui
   if (strl_ctx_set_opts(ctx, &o) || strl_front_begin(ctx, (int32_t)feed.targets().size(), feed.first_record_offset(), 3u << 20) ||
       strl_front_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes))
     return fail("front end");
-  std::vector<int32_t> skipped;
-  int64_t counted = 0;
-  uint64_t next = 0;
-  bool done = false;
+  FragLengths fl;
   std::vector<uint32_t> fw;
-  auto take = [&](uint64_t upto) -> bool {                    // the words of records [next, upto)
-    while (next < upto && !done) {
-      const uint64_t m = std::min<uint64_t>(upto - next, 1u << 20);
+  auto take = [&](uint64_t upto) -> bool {                    // the words of records [fl.next, upto)
+    while (fl.next < upto && !fl.done()) {
+      const uint64_t m = std::min<uint64_t>(upto - fl.next, 1u << 20);
       fw.resize((size_t)m);
-      if (strl_front_fragwords(ctx, next, m, fw.data())) return false;
-      for (uint64_t k = 0; k < m && !done; ++k) {
-        const int64_t i = (int64_t)(next + k);
-        const uint32_t f = fw[(size_t)k] & 0xffffu, is = fw[(size_t)k] >> 16;
-        if (!(f & 0x2)) continue;
-        if (f & (0x800 | 0x100)) continue;
-        if (is > 4095u) continue;
-        if (i < skip_reads) { skipped.push_back((int32_t)is); continue; }
-        skipped.clear();
-        frag[is]++;
-        if (++counted > n_reads) done = true;
-      }
-      next += m;
+      if (strl_front_fragwords(ctx, fl.next, m, fw.data())) return false;
+      fl.add_words(fw.data(), fl.next, m);
     }
     return true;
   };
@@ -1814,44 +1722,23 @@ static bool fragment_lengths_on_device(strl_ctx *ctx, const std::string &bam, ui
   ThreadPool pool(std::min(decode_threads(), 12));
   // chunk ci + 1 is read (header walk, copy out of the file's mapping) by a thread beside the push of chunk ci and the wait for
   // chunk ci - 1's parse: one after the other the seven chunks of a sample took 12 ms each, 3 of them the device's
-  struct St { int64_t nb = 0; size_t lo = 0, hi = 0; bool short_read = false; std::string err; };
-  St ring[3];
-  std::vector<BgzfFeed::Block> bl;
-  auto stage = [&](uint64_t ci, St &S) {
-    S = St{};
-    S.nb = feed.next(bl, chunk_blocks, chunk_bytes, S.err);
-    if (S.nb <= 0) return;
-    uint8_t *dst = pin[ci % 3];
-    S.lo = bl.front().c_off; S.hi = bl.back().c_off + bl.back().clen;
-    const size_t lo = S.lo, hi = S.hi, piece = (size_t)4 << 20, pieces = (hi - lo + piece - 1) / piece;
-    std::atomic<int> short_reads{0};
-    pool.parallel_for(pieces, [&](size_t k) { if (!feed.copy_at(dst + k * piece, lo + k * piece, std::min(piece, hi - lo - k * piece))) ++short_reads; });
-    feed.done_with(lo, hi - lo);
-    S.short_read = short_reads.load() != 0;
-    uint64_t *coff = reinterpret_cast<uint64_t *>(pin_meta[ci % 3]);
-    uint32_t *clen = reinterpret_cast<uint32_t *>(coff + chunk_blocks), *isz = clen + chunk_blocks, *crc = isz + chunk_blocks;
-    for (size_t k = 0; k < (size_t)S.nb; ++k) { coff[k] = bl[k].c_off - lo; clen[k] = bl[k].clen; isz[k] = bl[k].isize; crc[k] = bl[k].crc; }
-  };
-  stage(0, ring[0]);
-  std::thread ahead;
-  bool file_ended = false;
-  for (uint64_t ci = 0; !done; ++ci) {
-    const St cur = ring[ci % 3];
+  ChunkAhead ring(feed, pool, pins.data.data(), pins.meta.data(), chunk_blocks, chunk_bytes);
+  ring.stage(0, 0);
+  for (uint64_t ci = 0; !fl.done(); ++ci) {
+    const StagedChunk cur = ring.at(ci);
     if (cur.nb < 0 || cur.short_read) { why = cur.nb < 0 ? cur.err : "short read"; (void)strl_front_end(ctx); return false; }
-    if (cur.nb == 0) { file_ended = true; break; }
-    ahead = std::thread([&, ci] { stage(ci + 1, ring[(ci + 1) % 3]); });
-    uint64_t *coff = reinterpret_cast<uint64_t *>(pin_meta[ci % 3]);
-    uint32_t *clen = reinterpret_cast<uint32_t *>(coff + chunk_blocks), *isz = clen + chunk_blocks, *crc = isz + chunk_blocks;
+    if (cur.nb == 0) break;
+    ring.stage_ahead(ci + 1, (ci + 1) % 3);
+    const ChunkTables t = ring.tables(cur);
     strl_front_chunk dn[2];
     int n_dn = 0;
     uint64_t parsed = 0;
-    const bool ok = !strl_front_push(ctx, pin[ci % 3], cur.hi - cur.lo, coff, clen, isz, crc, (uint32_t)cur.nb, dn, &n_dn) && !strl_front_records(ctx, &parsed) && take(parsed);
-    ahead.join();
+    const bool ok = !strl_front_push(ctx, ring.data(cur), cur.bytes(), t.coff, t.clen, t.isz, t.crc, (uint32_t)cur.nb, dn, &n_dn) && !strl_front_records(ctx, &parsed) && take(parsed);
+    ring.join();
     if (!ok) return fail("front end");
     lap("chunk pushed, words of the parsed records taken");
   }
-  (void)file_ended;
-  if (!done) {                                              // the file ended first: what is still in the pipeline
+  if (!fl.done()) {                                         // the file ended first: what is still in the pipeline
     strl_front_chunk dn[2];
     int n_dn = 0;
     uint64_t parsed = 0;
@@ -1860,12 +1747,7 @@ static bool fragment_lengths_on_device(strl_ctx *ctx, const std::string &bam, ui
   lap("sample complete");
   if (strl_front_end(ctx)) { why = strl_last_error(); return false; }
   lap("front end given up");
-  uint64_t sum = 0;
-  for (int k = 0; k < 4096; ++k) sum += frag[k];
-  if ((uint32_t)sum == 0) {
-    fprintf(stderr, "using first reads in fragment_length_distribution calculation as there were not enough\n");
-    for (int32_t is : skipped) frag[is]++;
-  }
+  fl.finish(frag);
   return true;
 }
 
@@ -1916,39 +1798,15 @@ static bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, c
   const size_t auto_blocks = std::min<size_t>(16384, std::max<size_t>(2048, feed.file_bytes() / 16384 / 12));
   const size_t chunk_blocks = env_blocks && atoi(env_blocks) > 0 ? (size_t)atoi(env_blocks) : auto_blocks;
   const size_t chunk_bytes = std::max<size_t>((size_t)1 << 20, chunk_blocks * 20000);
-  uint8_t *pin[3] = {nullptr, nullptr, nullptr}, *pin_meta[3] = {nullptr, nullptr, nullptr};   // tables: coff, block offset u64 | clen | isize | crc u32
-  auto release = [&] { for (int k = 0; k < 3; ++k) { if (pin[k]) strl_pinned_free(pin[k]); if (pin_meta[k]) strl_pinned_free(pin_meta[k]); } };
-  {
-    std::vector<std::thread> each;            // (the time is the kernel's, faulting and locking the pages: a thread per buffer)
-    for (int k = 0; k < 3; ++k) each.emplace_back([&, k] { pin[k] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_bytes + 64)); pin_meta[k] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_blocks * 28 + 64)); });
-    for (auto &t : each) t.join();
-  }
-  for (int k = 0; k < 3; ++k)
-    if (!pin[k] || !pin_meta[k]) { why = "page-locked memory for the chunks"; release(); return false; }
+  PinnedRing pins;
+  auto release = [&] { pins.release(); };
+  pins.alloc(3, chunk_blocks, chunk_bytes);
+  if (!pins.ok()) { why = "page-locked memory for the chunks"; release(); return false; }
   strl_ctx *ctx = nullptr;
   auto fail = [&](int rc) { why = strl_last_error(); status = rc; (void)strl_bamindex_end(ctx); release(); return false; };
   ThreadPool pool(std::min(decode_threads(), 12));
-  struct St { int64_t nb = 0; size_t lo = 0, hi = 0, end_off = 0; bool short_read = false; std::string err; };
-  St ring[3];
-  std::vector<BgzfFeed::Block> bl;
-  struct Tab { uint64_t *coff, *boff; uint32_t *clen, *isz, *crc; };
-  auto tab = [&](uint64_t ci) { Tab t; t.coff = reinterpret_cast<uint64_t *>(pin_meta[ci % 3]); t.boff = t.coff + chunk_blocks;
-                                t.clen = reinterpret_cast<uint32_t *>(t.boff + chunk_blocks); t.isz = t.clen + chunk_blocks; t.crc = t.isz + chunk_blocks; return t; };
-  auto stage = [&](uint64_t ci, St &S) {
-    S = St{};
-    S.nb = feed.next(bl, chunk_blocks, chunk_bytes, S.err);
-    if (S.nb <= 0) return;
-    uint8_t *dst = pin[ci % 3];
-    S.lo = bl.front().c_off; S.hi = bl.back().c_off + bl.back().clen; S.end_off = S.hi + 8;      // (CRC-32 and ISIZE close a block)
-    const size_t lo = S.lo, hi = S.hi, piece = (size_t)4 << 20, pieces = (hi - lo + piece - 1) / piece;
-    std::atomic<int> short_reads{0};
-    pool.parallel_for(pieces, [&](size_t k) { if (!feed.copy_at(dst + k * piece, lo + k * piece, std::min(piece, hi - lo - k * piece))) ++short_reads; });
-    feed.done_with(lo, hi - lo);
-    S.short_read = short_reads.load() != 0;
-    const Tab t = tab(ci);
-    for (size_t k = 0; k < (size_t)S.nb; ++k) { t.coff[k] = bl[k].c_off - lo; t.boff[k] = bl[k].c_off - bl[k].hdr; t.clen[k] = bl[k].clen; t.isz[k] = bl[k].isize; t.crc[k] = bl[k].crc; }
-  };
-  stage(0, ring[0]);
+  ChunkAhead ring(feed, pool, pins.data.data(), pins.meta.data(), chunk_blocks, chunk_bytes);
+  ring.stage(0, 0);
   if (!(ctx = get_ctx(why))) { status = STRL_ERR_NO_DEVICE; release(); return false; }
   std::vector<int32_t> l_ref;
   for (const BamTarget &t : feed.targets()) l_ref.push_back((int32_t)std::min<uint64_t>(t.length, 0x7fffffffu));
@@ -1957,13 +1815,13 @@ static bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, c
   if (!rc) rc = strl_bamindex_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes);
   if (rc) return fail(rc);
   for (uint64_t ci = 0;; ++ci) {
-    const St cur = ring[ci % 3];
+    const StagedChunk cur = ring.at(ci);
     if (cur.nb < 0 || cur.short_read) { why = cur.nb < 0 ? cur.err : "short read"; status = STRL_ERR_FORMAT; (void)strl_bamindex_end(ctx); release(); return false; }
     if (cur.nb == 0) break;
-    std::thread ahead([&, ci] { stage(ci + 1, ring[(ci + 1) % 3]); });
-    const Tab t = tab(ci);
-    rc = strl_bamindex_push(ctx, pin[ci % 3], cur.hi - cur.lo, t.coff, t.clen, t.isz, t.crc, t.boff, cur.end_off, (uint32_t)cur.nb);
-    ahead.join();
+    ring.stage_ahead(ci + 1, (ci + 1) % 3);
+    const ChunkTables t = ring.tables(cur);
+    rc = strl_bamindex_push(ctx, ring.data(cur), cur.bytes(), t.coff, t.clen, t.isz, t.crc, t.boff, cur.end_off(), (uint32_t)cur.nb);
+    ring.join();
     if (rc) return fail(rc);
   }
   uint64_t nbytes = 0;
@@ -2081,12 +1939,9 @@ static int call_main(int argc, char **argv) {
   const char *frag_env = getenv("STRL_CALL_FRAG");
   bool frag_on_device = !CramFile::is_cram(bam) && !(frag_env && !strcmp(frag_env, "host"));
   const size_t fr_blocks = 4096, fr_bytes = fr_blocks * 20000;
-  uint8_t *fr_pin[3] = {nullptr, nullptr, nullptr}, *fr_meta[3] = {nullptr, nullptr, nullptr};
+  PinnedRing fr_pins;
   std::thread fr_pin_thread;
-  if (frag_on_device)
-    fr_pin_thread = std::thread([&] {
-      for (int k = 0; k < 3; ++k) { fr_pin[k] = static_cast<uint8_t *>(strl_pinned_alloc(fr_bytes + 64)); fr_meta[k] = static_cast<uint8_t *>(strl_pinned_alloc(fr_blocks * 20 + 64)); }
-    });
+  if (frag_on_device) fr_pin_thread = std::thread([&] { fr_pins.alloc(3, fr_blocks, fr_bytes); });
   if (!frag_on_device) fragment_length_distribution(bam, frag);                       // call.nim:92
   BamReader rd;
   std::string err;
@@ -2117,20 +1972,14 @@ static int call_main(int argc, char **argv) {
   if (ctx_thread.joinable()) ctx_thread.join();
   if (fr_pin_thread.joinable()) fr_pin_thread.join();
   if (frag_on_device && opened && !ctx_rc) {
-    bool have = true;
-    for (int k = 0; k < 3; ++k) have = have && fr_pin[k] && fr_meta[k];
     std::string why = "page-locked memory";
-    if (!have || !fragment_lengths_on_device(ctx, bam, frag, fr_pin, fr_meta, fr_blocks, fr_bytes, why)) {
+    if (!fr_pins.ok() || !fragment_lengths_on_device(ctx, bam, frag, fr_pins, fr_blocks, fr_bytes, why)) {
       if (verbose) fprintf(stderr, "[strling] fragment lengths on the host (%s)\n", why.c_str());
       fragment_length_distribution(bam, frag);
     }
   } else if (frag_on_device) fragment_length_distribution(bam, frag);                 // (errors of the open / the context are reported below)
   // (the three page-locked buffers are left to the end of the process: unlocking them here would stall the device in front of the clustering)
-  const int frag_median = strl_frag_median(frag, 0.5);
-  if (verbose) {
-    fprintf(stderr, "Calculated median fragment length:%d\n", frag_median);
-    fprintf(stderr, "10th, 90th percentile of fragment length:%d %d\n", strl_frag_median(frag, 0.1), strl_frag_median(frag, 0.9));
-  }
+  const int frag_median = frag_median_of(frag, verbose);
   t_up_bam = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call0).count();
   bin_thread.join();
   g_bg_init = nullptr;

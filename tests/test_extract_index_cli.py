@@ -92,6 +92,10 @@ def test_write_index_equals_bamindex_and_leaves_the_bin_alone(sample):
     line = [l for l in r.stderr.splitlines() if l.startswith("[strling] index:")]
     assert len(line) == 1 and f"{sample['rec'].n} records" in line[0] and "runs" in line[0] and "chunks" in line[0] and f"{len(sample['ref'])} bytes" in line[0], r.stderr
     assert not [f for f in os.listdir(d) if ".tmp." in f]
+    # one block per chunk: every block's file offset reaches the index through a staged chunk's table of its own
+    r = _run(["extract", "-g", sample["bed"], "--write-index", "--index-out", str(d / "one.bai"), bam, str(d / "one.bin")], env={"STRL_CHUNK_BLOCKS": "1"})
+    assert r.returncode == 0, r.stderr
+    assert open(d / "one.bai", "rb").read() == sample["ref"] and open(d / "one.bin", "rb").read() == sample["plain"]
     # `call` on that index writes the same three files as on bamindex's
     outs = {}
     for tag, bai in (("a", None), ("b", sample["ref"])):
