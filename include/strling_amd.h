@@ -736,6 +736,49 @@ int strl_bamindex_fetch(strl_ctx *ctx, uint8_t *out, uint64_t cap);
  * end's chunk buffers stay with the context */
 int strl_bamindex_end(strl_ctx *ctx);
 
+/* ---- `strling call --sweep`: the evidence of every bound from ONE pass over the BAM (replaces, for all bounds at once, the loop
+ * call.nim:196-218 runs per bound: htslib's indexed query(tid, left - window, right + window) and spanners(), collect.nim:130-182).
+ * The per-bound path (strl_regions_evidence) inflates every bound's blocks, overlapping bounds the same blocks again; here the
+ * file goes through the front end's copy + inflate + CRC + record scan once, chunk by chunk like strl_bamindex_push, and behind
+ * each chunk's scan the device finds, for every bound whose query ends inside the chunk, the byte range of its records --
+ *   i1 = the first record with tid > b.tid, or tid == b.tid and pos >= right + window
+ *   i0 = the first record of b.tid whose running maximum of bam_endpos exceeds max(0, left - window)
+ * -- and runs strl_evidence_records' kernel over [i0, i1) where the records lie.  A bound is decided in the first chunk that
+ * holds its i1, or in the chunk pushed with last_chunk != 0, where the end of the records closes every open bound.
+ *   strl_sweep_begin    n_ref, first_record_offset as strl_bamindex_begin; bounds / window / frag / min_mapq as strl_spanners.
+ *                       STRL_ERR_ARG for a bound with left > right.
+ *   strl_sweep_reserve  (optional, after _begin) as strl_front_reserve
+ *   strl_sweep_push     comp .. crc32 as strl_front_push (crc32 may be NULL: not checked); blocks in file order, each once, none
+ *                       empty.  push(i) enqueues chunk i's copy + inflate + scan, then sweeps chunk i - 1.  last_chunk != 0: no
+ *                       chunk follows; a push of no blocks with last_chunk != 0 says so of the chunk pushed before (a reader that
+ *                       learns of the end of the file only behind its last chunk).
+ *   strl_sweep_finish   sweeps what is in flight.  Results in the caller's order of `bounds`, laid out as strl_evidence_records'
+ *                       (support_off has n_bounds + 1 entries).  status[r] = 0: answered -- the Support list and the summary are
+ *                       field for field what strl_evidence_records returns for the bound and exactly the bytes of records
+ *                       [i0, i1), `rec` = the ordinal counted from i0; but for `rec`, what strl_spanners returns for htslib's
+ *                       query.  1: a seam -- records of the bound's reference in an earlier chunk reach past
+ *                       max(0, left - window), so part of the range has left the device -- or the bound never closed (no chunk was
+ *                       pushed as the last one, a reference outside the header): read the region the old way.  2: as
+ *                       strl_evidence_records.  Nothing is truncated, nothing answered approximately.
+ *                       STRL_ERR_CAPACITY when cap is too small: support_off[n_bounds] = the entries needed; call again.
+ *   strl_sweep_end      gives the sweep up (also after an error): what it had in flight has completed on return.
+ * STRL_ERR_FORMAT: a file that is not coordinate sorted (the message names the record), a refID outside the header, a malformed
+ * record, invalid DEFLATE data, a file that ends inside a record; STRL_ERR_CRC; STRL_ERR_NOMEM.  After an error every later
+ * push / finish repeats it; strl_sweep_end, and the context takes the next file. */
+typedef struct {
+  uint64_t n_answered, n_seam, n_passed_on;  /* bounds with status 0 / 1 / 2 */
+  uint64_t n_chunks, n_records;              /* chunks pushed, records swept */
+  double sweep_ms, evidence_ms;              /* HIP-event time of the sweep's own kernels / of the evidence kernel */
+} strl_sweep_info;
+int strl_sweep_begin(strl_ctx *ctx, int32_t n_ref, uint64_t first_record_offset, const strl_bounds *bounds, uint32_t n_bounds, int32_t window,
+                     const uint32_t frag[4096], uint8_t min_mapq);
+int strl_sweep_reserve(strl_ctx *ctx, uint32_t max_blocks, uint64_t max_comp_bytes);
+int strl_sweep_push(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                    const uint32_t *crc32, uint32_t n_blocks, int last_chunk);
+int strl_sweep_finish(strl_ctx *ctx, strl_support *out, uint64_t cap, uint64_t *support_off, strl_span_summary *summary, uint8_t *status,
+                      strl_sweep_info *info);
+int strl_sweep_end(strl_ctx *ctx);
+
 /* ---- the .bai as a by-product of `strling extract`'s own pass (`strling extract --write-index`) ----
  * strl_front_push already copies, inflates, CRC-checks, record-scans and parses every block; the index needs of a record only
  * where it starts, refID, pos, end and flag, and the parse has just written those as dense columns.  A builder attached to the

@@ -59,6 +59,11 @@ class BamindexInfo(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_no_coor", C.c_uint64), ("n_runs", C.c_uint64), ("n_chunks", C.c_uint64)]
 
 
+class SweepInfo(C.Structure):
+    _fields_ = [("n_answered", C.c_uint64), ("n_seam", C.c_uint64), ("n_passed_on", C.c_uint64), ("n_chunks", C.c_uint64), ("n_records", C.c_uint64),
+                ("sweep_ms", C.c_double), ("evidence_ms", C.c_double)]
+
+
 def _front_chunk(c):
     return {k: int(getattr(c, k)) for k, _ in FrontChunk._fields_}
 
@@ -135,6 +140,7 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_extract_device", "strl_treads_fetch", "strl_ctx_pair_times", "strl_sort_pairs", "strl_cluster_resident", "strl_ctx_cluster_times", "strl_pair_rows", "strl_extract_begin", "strl_extract_add", "strl_extract_finish", "strl_pair_rule", "strl_bounds_bare", "strl_ctx_treads_device", "strl_cluster_gathered", "strl_inflate_blocks", "strl_ctx_inflate_ms", "strl_regions_fetch", "strl_evidence_records", "strl_regions_evidence", "strl_front_begin", "strl_front_push", "strl_front_push_after", "strl_front_reserve", "strl_front_stage", "strl_front_enqueue_after", "strl_front_collect", "strl_ctxs_extract_gather", "strl_front_finish", "strl_front_fragwords", "strl_front_fragwords_async", "strl_event_wait", "strl_front_records", "strl_front_tids", "strl_front_qnames", "strl_front_treads_named", "strl_pinned_alloc", "strl_pinned_free", "strl_comm_unique_id", "strl_ctx_comm_init", "strl_ctxs_comm_init", "strl_ctx_comm_info", "strl_cluster_exchange", "strl_ctxs_cluster_exchange", "strl_exchange_treads", "strl_ctx_set_treads", "strl_cluster_collect", "strl_ctx_tail_stream", "strl_ctx_mem_info", "strl_bin_peek", "strl_front_trim_next", "strl_front_tail_bytes", "strl_ctx_blocking_waits", "strl_score_read_host", "strl_front_end",
            "strl_bamindex_begin", "strl_bamindex_reserve", "strl_bamindex_push", "strl_bamindex_finish", "strl_bamindex_fetch", "strl_bamindex_end",
            "strl_front_index_begin", "strl_front_index_blocks", "strl_front_index_finish", "strl_bamindex_begin_csi", "strl_front_index_begin_csi",
+           "strl_sweep_begin", "strl_sweep_reserve", "strl_sweep_push", "strl_sweep_finish", "strl_sweep_end",
            "strl_pull_select", "strl_pull_mates", "strl_pull_select_host", "strl_pull_counts_host", "strl_pull_mates_host", "strl_pull_order"]
 
 
@@ -251,6 +257,11 @@ def load(build_if_missing=True):
     L.strl_bamindex_finish.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(BamindexInfo)]
     L.strl_bamindex_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.strl_bamindex_end.argtypes = [C.c_void_p]
+    L.strl_sweep_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8]
+    L.strl_sweep_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    L.strl_sweep_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
+    L.strl_sweep_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SweepInfo)]
+    L.strl_sweep_end.argtypes = [C.c_void_p]
     L.strl_front_index_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.strl_bamindex_begin_csi.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32]
     L.strl_front_index_begin_csi.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32]
@@ -948,6 +959,37 @@ class Context:
         finally:
             self.L.strl_bamindex_end(self.h)
         return out[:nbytes.value].tobytes(), {k: int(getattr(info, k)) for k, _ in BamindexInfo._fields_}
+
+    def sweep(self, path, bounds, window, frag, min_mapq=20, chunk_blocks=16384, check_crc=True):
+        """the evidence of every bound from one pass over a coordinate-sorted BAM FILE (strl_sweep_begin / _push / _finish):
+        bounds = BOUNDS_DTYPE records in any order -> (list of (support array, median_depth, expected_spanners, status) in that
+        order, dict of strl_sweep_info); status 0 = answered, 1 = seam / never closed, 2 = passed on to spanners()"""
+        B = self._bam_blocks(path)
+        bb = np.ascontiguousarray(bounds, BOUNDS_DTYPE).reshape(-1)
+        n = bb.size
+        frag = np.ascontiguousarray(frag, np.uint32)
+        _check(self.L.strl_sweep_begin(self.h, B["n_ref"], B["first_off"], bb.ctypes.data if n else None, n, window, frag.ctypes.data, min_mapq))
+        try:
+            data, blocks, keep = B["data"], B["blocks"], []
+            for s0 in range(B["b0"], len(blocks), chunk_blocks):
+                cb = blocks[s0:s0 + chunk_blocks]
+                lo, hi = cb[0][0], cb[-1][0] + cb[-1][1]
+                comp = np.ascontiguousarray(data[lo:hi])
+                coff = np.array([b[0] - lo for b in cb], np.uint64)
+                clen = np.array([b[1] for b in cb], np.uint32)
+                isz = np.array([b[2] for b in cb], np.uint32)
+                crc = np.array([b[3] for b in cb], np.uint32)
+                keep = (keep + [(comp, coff, clen, isz, crc)])[-3:]      # pageable memory: the copy is staged by the runtime
+                _check(self.L.strl_sweep_push(self.h, comp.ctypes.data, comp.size, _ptr(coff), _ptr(clen), _ptr(isz), _ptr(crc) if check_crc else None,
+                                              len(cb), int(s0 + chunk_blocks >= len(blocks))))
+            info = SweepInfo()
+
+            def call(sup, cap, soff, sm, st):
+                return self.L.strl_sweep_finish(self.h, sup.ctypes.data, cap, _ptr(soff), sm.ctypes.data, _ptr(st), C.byref(info))
+            res = self._evidence_call(n, call, 64 * n + 64)
+        finally:
+            self.L.strl_sweep_end(self.h)
+        return res, {k: getattr(info, k) for k, _ in SweepInfo._fields_}
 
     def inflate_ms(self):
         """kernel time (ms) of the last inflate_blocks call"""

@@ -23,6 +23,7 @@
 #include "front.h"
 #include "sort.h"
 #include "device_util.h"
+#include "bam_rec.h"
 
 namespace strl {
 
@@ -87,17 +88,8 @@ __device__ __forceinline__ void bai_read(const uint8_t *U, uint32_t q, BaiRec &r
   const uint8_t *R = U + q;
   r.bs = ld32u(R);
   r.tid = (int32_t)ld32u(R + 4); r.pos = (int32_t)ld32u(R + 8);
-  const uint32_t l_qname = R[12], n_cigar = ld16u(R + 16);
   r.flag = ld16u(R + 18);
-  int64_t rl = 0;
-  if (!(r.flag & 4u)) {
-    const uint8_t *cg = R + 36 + l_qname;       // (inside the record: rec_header's rule, checked by the scan's walk)
-    for (uint32_t j = 0; j < n_cigar; ++j) {
-      const uint32_t c = ld32u(cg + 4u * j), op = c & 15u;
-      if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) rl += c >> 4;
-    }
-  }
-  const int64_t e = (int64_t)r.pos + (rl ? rl : 1);
+  const int64_t e = bam_rec_end(R);             // (the CIGAR lies inside the record: rec_header's rule, checked by the scan's walk)
   r.end = e > 0x7fffffffll ? 0x7fffffff : (int32_t)e;
 }
 // the record's five numbers: from its bytes, or (COLS) from the parse's columns -- the byte length is the distance to the next

@@ -1841,6 +1841,56 @@ static bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, c
   return true;
 }
 
+// `strling call --sweep`: the evidence of all of `bounds` from one pass over the BAM (strl_sweep_*; replaces, for every bound it
+// answers, the indexed query + spanners() of call.nim:196-218).  Fed like the fragment-length sample: BgzfFeed walks the block
+// headers, the compressed bytes go into page-locked buffers (`pins`: chunk_blocks blocks each), chunk ci + 1 is read beside the
+// push of chunk ci.  false: `why` says what the file was refused for; the caller goes on without the sweep.
+struct SweepAnswers {
+  std::vector<uint8_t> status;              // per bound: 0 answered | 1 seam | 2 passed on
+  std::vector<strl_support> sup;
+  std::vector<uint64_t> off;                // [n + 1]
+  std::vector<strl_span_summary> sum;
+  strl_sweep_info info{};
+  double seconds = 0;
+};
+static bool sweep_evidence(strl_ctx *ctx, const std::string &bam, const std::vector<strl_bounds> &bounds, int window, const uint32_t frag[4096], uint8_t min_mapq,
+                           const PinnedRing &pins, size_t chunk_blocks, size_t chunk_bytes, SweepAnswers &A, std::string &why) {
+  const auto t0 = std::chrono::steady_clock::now();
+  BgzfFeed feed;
+  std::string err;
+  if (!feed.open(bam, err)) { why = err.empty() ? "couldn't open bam" : "couldn't open bam: " + err; return false; }
+  auto fail = [&](const char *what) { why = std::string(what) + ": " + strl_last_error(); (void)strl_sweep_end(ctx); return false; };
+  if (strl_sweep_begin(ctx, (int32_t)feed.targets().size(), feed.first_record_offset(), bounds.data(), (uint32_t)bounds.size(), window, frag, min_mapq) ||
+      strl_sweep_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes))
+    return fail("sweep");
+  ThreadPool pool(std::min(decode_threads(), 12));
+  ChunkAhead ring(feed, pool, pins.data.data(), pins.meta.data(), chunk_blocks, chunk_bytes);
+  ring.stage(0, 0);
+  for (uint64_t ci = 0;; ++ci) {
+    const StagedChunk cur = ring.at(ci);
+    if (cur.nb < 0 || cur.short_read) { why = cur.nb < 0 ? cur.err : "short read"; (void)strl_sweep_end(ctx); return false; }
+    if (cur.nb == 0) break;
+    ring.stage_ahead(ci + 1, (ci + 1) % 3);
+    const ChunkTables t = ring.tables(cur);
+    const int rc = strl_sweep_push(ctx, ring.data(cur), cur.bytes(), t.coff, t.clen, t.isz, t.crc, (uint32_t)cur.nb, 0);
+    ring.join();
+    if (rc) return fail("sweep");
+  }
+  if (strl_sweep_push(ctx, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 1)) return fail("sweep");      // the chunk pushed last was the file's last
+  const size_t n = bounds.size();
+  A.status.assign(std::max<size_t>(n, 1), 1); A.off.assign(n + 1, 0); A.sum.assign(std::max<size_t>(n, 1), strl_span_summary{});
+  A.sup.resize(64 * n + 1024);
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    const int rc = strl_sweep_finish(ctx, A.sup.data(), A.sup.size(), A.off.data(), A.sum.data(), A.status.data(), &A.info);
+    if (!rc) break;
+    if (rc != STRL_ERR_CAPACITY || attempt || A.off[n] <= A.sup.size()) return fail("sweep");
+    A.sup.resize((size_t)A.off[n] + 64);
+  }
+  if (strl_sweep_end(ctx)) { why = strl_last_error(); return false; }
+  A.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return true;
+}
+
 // the index `samtools index` writes (htslib sam_index_build); the reference only reads one (call.nim:101-102)
 static int bamindex_main(int argc, char **argv) {
   const char *usage =
@@ -1887,11 +1937,13 @@ static int call_main(int argc, char **argv) {
       "  -b, --bounds=BOUNDS        STRling -bounds.txt file (usually produced by strling merge) specifying additional STR loci to genotype.\n"
       "  -o, --output-prefix=OUTPUT_PREFIX\n                             prefix for output files (default: strling)\n"
       "      --make-index           when the bam has no index, build one on the GPU and write it beside the bam: a .bai, or a .csi\n"
-      "                             when a reference is longer than 2^29 bases (default: exit)\n  -v, --verbose\n  -h, --help                 Show this help\n";
+      "                             when a reference is longer than 2^29 bases (default: exit)\n"
+      "      --sweep                collect the evidence of all bounds in one pass over the bam on the GPU instead of one indexed read\n"
+      "                             per bound (same output; for many thousands of bounds. also: STRL_CALL_EVIDENCE=sweep)\n  -v, --verbose\n  -h, --help                 Show this help\n";
   if (argc <= 2) { fputs(usage, stdout); return 0; }
   const Args a = parse(argc, argv, 2, {{"fasta", 'f', true}, {"min-support", 'm', true}, {"min-clip", 'c', true}, {"min-clip-total", 't', true},
                                        {"min-mapq", 'q', true}, {"loci", 'l', true}, {"bounds", 'b', true}, {"output-prefix", 'o', true},
-                                       {"verbose", 'v', false}, {"device", 'D', true}, {"make-index", 0, false}}, usage);
+                                       {"verbose", 'v', false}, {"device", 'D', true}, {"make-index", 0, false}, {"sweep", 0, false}}, usage);
   if (a.pos.size() != 2) quit("expected 2 arguments (bam, bin)\n%s", usage);
   set_device0(a.get("device", ""));
   if (a.flag("loci") && !file_exists(a.get("loci", ""))) quit("couldn't open loci file");          // call.nim:81-87
@@ -2076,6 +2128,13 @@ static int call_main(int argc, char **argv) {
   const bool device_regions = !rd.is_cram() && !(regions_env && !strcmp(regions_env, "host"));
   const char *evidence_env = getenv("STRL_CALL_EVIDENCE");
   const bool device_evidence = device_regions && evidence_env && !strcmp(evidence_env, "device");   // opt-in until measured on a device
+  // --sweep / STRL_CALL_EVIDENCE=sweep: one pass over the file answers the bounds of both task lists (sweep_evidence); what it
+  // leaves (seams, bounds beyond the capacity rule) takes the paths below.  Opt-in: where it overtakes them has not been measured.
+  bool sweep = a.flag("sweep") || (evidence_env && !strcmp(evidence_env, "sweep"));
+  if (sweep && !device_regions) {
+    if (verbose) fprintf(stderr, "[strling] --sweep ignored: %s\n", rd.is_cram() ? "the input is a CRAM (the sweep reads BGZF blocks of BAM records)" : "STRL_CALL_REGIONS=host keeps every region on the host");
+    sweep = false;
+  }
   uint64_t n_ev_device = 0, n_ev_passed = 0;
   double t_ev_kernels = 0;
   const uint64_t batch_inflated = getenv("STRL_CALL_BATCH_MB") ? (uint64_t)atoll(getenv("STRL_CALL_BATCH_MB")) << 20 : (uint64_t)384 << 20;
@@ -2100,11 +2159,8 @@ static int call_main(int argc, char **argv) {
         if (!pin_out[k]) pin_out_cap[k] = 0;
       }
     });
-  auto run_tasks = [&](const std::vector<Task> &tasks) {
-    if (region_pin_thread.joinable()) region_pin_thread.join();
-    if (tasks.empty()) return;
-    const auto te0 = std::chrono::steady_clock::now();
-    std::vector<Done> done(tasks.size());
+  // the evidence and the rows of `tasks` into `done`, by the paths above
+  auto run_core = [&](const std::vector<Task> &tasks, std::vector<Done> &done) {
     std::mutex wm;
     std::vector<int> free_w;
     for (int k = n_workers - 1; k >= 0; --k) free_w.push_back(k);
@@ -2342,6 +2398,38 @@ static int call_main(int argc, char **argv) {
       fetcher2.join();
     }
     if (failed.load()) quit("%s", fail_msg.c_str());
+  };
+  // pre / base: the sweep's answers, task j's at pre->...[base + j]: an answered bound goes straight to genotype() and the row
+  auto run_tasks = [&](const std::vector<Task> &tasks, const SweepAnswers *pre = nullptr, size_t base = 0) {
+    if (region_pin_thread.joinable()) region_pin_thread.join();
+    if (tasks.empty()) return;
+    const auto te0 = std::chrono::steady_clock::now();
+    std::vector<Done> done(tasks.size());
+    if (!pre) run_core(tasks, done);
+    else {
+      std::vector<Task> rest;
+      std::vector<size_t> rest_at;
+      for (size_t j = 0; j < tasks.size(); ++j) if (pre->status[base + j] != 0) { rest.push_back(tasks[j]); rest_at.push_back(j); }
+      std::mutex em;
+      std::string emsg;
+      const size_t per = 64;
+      ev_pool.parallel_for((tasks.size() + per - 1) / per, [&](size_t blk) {
+        Worker w;
+        const auto tw1 = std::chrono::steady_clock::now();
+        for (size_t j = blk * per; j < std::min(tasks.size(), (blk + 1) * per); ++j) {
+          if (pre->status[base + j] != 0) continue;
+          std::string werr;
+          if (!genotype_row(w, tasks[j], done[j], pre->sup.data() + pre->off[base + j], pre->sum[base + j], werr)) { std::lock_guard<std::mutex> lk(em); if (emsg.empty()) emsg = werr; break; }
+        }
+        ns_rules += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tw1).count();
+      });
+      if (!emsg.empty()) quit("%s", emsg.c_str());
+      if (!rest.empty()) {
+        std::vector<Done> rest_done(rest.size());
+        run_core(rest, rest_done);
+        for (size_t k = 0; k < rest.size(); ++k) done[rest_at[k]] = std::move(rest_done[k]);
+      }
+    }
     for (const Done &d : done) {
       if (!d.keep) continue;
       calls.push_back(d.c);
@@ -2355,6 +2443,7 @@ static int call_main(int argc, char **argv) {
   // loci handed in with -l / -b are genotyped first and take their reads out of the table (call.nim:150-218)
   std::vector<strl_locus> given;
   std::vector<uint32_t> assigned;
+  std::vector<Task> given_tasks;                       // --sweep: the tasks of the given loci, run behind the clustering
   {
     std::vector<strl_locus> loci;
     if (a.flag("loci")) { loci = parse_bed(a.get("loci", ""), rd.targets(), (uint32_t)window); fprintf(stderr, "Read %zu loci from %s\n", loci.size(), a.get("loci", "").c_str()); }
@@ -2380,7 +2469,8 @@ static int call_main(int argc, char **argv) {
         if (L.b.right - L.b.left > 1000u) { fprintf(stderr, "large bounds: %s:%u-%u skipping\n", rd.targets()[(size_t)L.b.tid].name.c_str(), L.b.left, L.b.right); continue; }
         tasks.push_back(Task{L.b, L.name, &assigned, aoff[j], aoff[j + 1], taken_copy.data()});
       }
-      run_tasks(tasks);
+      if (sweep) given_tasks = std::move(tasks);       // (their evidence comes from the same pass as the clustered bounds')
+      else run_tasks(tasks);
     }
   }
 
@@ -2403,7 +2493,32 @@ static int call_main(int argc, char **argv) {
     std::vector<Task> tasks;
     tasks.reserve((size_t)nb);
     for (uint64_t j = 0; j < nb; ++j) tasks.push_back(Task{bounds[(size_t)j], nullptr, &members, moff[(size_t)j], moff[(size_t)j + 1], treads.data()});
-    run_tasks(tasks);
+    SweepAnswers swept;
+    if (sweep) {
+      // both task lists, one pass: the page-locked buffers of the fragment-length sample serve again where they fit
+      std::vector<strl_bounds> all;
+      all.reserve(given_tasks.size() + tasks.size());
+      for (const Task &t : given_tasks) all.push_back(t.b);
+      for (const Task &t : tasks) all.push_back(t.b);
+      const char *env_blocks = getenv("STRL_CHUNK_BLOCKS");       // tests: tiny chunks put the bounds on seams
+      const size_t sw_blocks = env_blocks && atoi(env_blocks) > 0 ? (size_t)atoi(env_blocks) : fr_blocks;
+      const size_t sw_bytes = std::max<size_t>((size_t)1 << 20, sw_blocks * 20000);
+      PinnedRing sw_pins;
+      const bool reuse = fr_pins.ok() && sw_blocks == fr_blocks;
+      if (!reuse) sw_pins.alloc(3, sw_blocks, sw_bytes);
+      std::string why = "page-locked memory for the chunks";
+      if (all.empty()) sweep = false;
+      else if ((!reuse && !sw_pins.ok()) || !sweep_evidence(ctx, bam, all, window, frag, min_mapq, reuse ? fr_pins : sw_pins, sw_blocks, sw_bytes, swept, why)) {
+        fprintf(stderr, "[strling] call --sweep refused: %s; the bounds take the default path\n", why.c_str());
+        sweep = false;
+      } else if (verbose)
+        fprintf(stderr, "[strling] sweep: bounds answered by the sweep %llu, seam bounds %llu, passed on (beyond 4096 records or a span of 9190) %llu, chunks %llu, records %llu, seconds: the pass %.3f, "
+                "sweep kernels %.3f, evidence kernels %.3f\n", (unsigned long long)swept.info.n_answered, (unsigned long long)swept.info.n_seam, (unsigned long long)swept.info.n_passed_on,
+                (unsigned long long)swept.info.n_chunks, (unsigned long long)swept.info.n_records, swept.seconds, swept.info.sweep_ms * 1e-3, swept.info.evidence_ms * 1e-3);
+      // (sw_pins is left to the end of the process, like the other page-locked buffers: unlocking stalls the device)
+    }
+    run_tasks(given_tasks, sweep ? &swept : nullptr, 0);
+    run_tasks(tasks, sweep ? &swept : nullptr, given_tasks.size());
   }
   if (verbose)
     fprintf(stderr, "[strling] seconds: device context + .bin + index side by side, the fragment-length sample behind the context %.3f (context %.3f | .bin %.3f | context + sample + index %.3f)  clustering (upload, sort, sweep, bounds, members) %.3f  evidence + genotypes of %llu bounds on %d threads %.3f (summed over the threads: region records %.3f, spanners + genotype %.3f; regions through the device %llu, on the host %llu: "

@@ -24,13 +24,14 @@
 #include "common.h"
 #include "nim_tables.h"
 #include "regions.h"
+#include "bam_rec.h"
 
 #pragma clang fp contract(off)
 
 namespace strl {
 
 constexpr uint32_t EV_THREADS = 256, EV_WIN = 4096, EV_SLOTS = 8192, EV_DEPTH_CAP = 9192;
-constexpr uint16_t EVF_UNMAP = 0x4, EVF_REVERSE = 0x10, EVF_SECONDARY = 0x100, EVF_DUP = 0x400, EVF_SUPPL = 0x800;
+constexpr uint16_t EVF_REVERSE = 0x10, EVF_SECONDARY = 0x100, EVF_DUP = 0x400, EVF_SUPPL = 0x800;
 
 struct EvBound {          // a bound as the kernel needs it, made on the host
   int64_t left, right, wl;   // wl = left - window
@@ -68,12 +69,7 @@ struct EvRec {            // the core fields of the record whose block_size word
   __device__ const uint8_t *qname() const { return p + 36; }
   __device__ uint32_t qname_len() const { return l_name ? l_name - 1u : 0u; }
   __device__ int base(int64_t j) const { return (p[36 + l_name + 4u * n_cig + (uint32_t)(j >> 1)] >> ((~j & 1) << 2)) & 0xf; }
-  __device__ int64_t stop() const {   // bam_endpos, with Rec::stop's rule for unmapped / zero-length
-    int64_t rl = 0;
-    if (!(flag & EVF_UNMAP))
-      for (uint32_t j = 0; j < n_cig; ++j) { const uint32_t c = cig(j); if (ev_cons_ref((int)(c & 0xf))) rl += c >> 4; }
-    return (int64_t)pos + (rl ? rl : 1);
-  }
+  __device__ int64_t stop() const { return bam_rec_end(p); }   // bam_endpos, with Rec::stop's rule for unmapped / zero-length
 };
 
 // spanning.nim:22-49
@@ -337,7 +333,7 @@ static int64_t ev_slop(const strl_bounds &b, int k) {   // bound_slop, collect.n
 
 int evidence_run(RegionJob &J, const uint8_t *d_u, uint64_t u_readable, const RegionWalk *d_range, const RegionWalk *h_range, uint32_t n_regions,
                  const strl_bounds *bounds, int32_t window, const uint32_t frag[4096], uint8_t min_mapq, strl_support *out, uint64_t cap,
-                 uint64_t *support_off, strl_span_summary *summary, uint8_t *status, double *kernel_ms) {
+                 uint64_t *support_off, strl_span_summary *summary, uint8_t *status, double *kernel_ms, const uint32_t *h_count) {
   if (kernel_ms) *kernel_ms = 0;
   std::vector<EvBound> eb(n_regions);
   uint64_t row_cap = 0;
@@ -359,7 +355,8 @@ int evidence_run(RegionJob &J, const uint8_t *d_u, uint64_t u_readable, const Re
     if (!E.status && (window < 0 || span < 1 || span > EV_MAX_SPAN || wr > INT32_MAX || E.k < 1)) E.status = 2;
     E.depth_n = E.status ? 0 : (int32_t)span;
     // rows for every record the region can hold (a record is 37 bytes or more); more than EV_MAX_RECORDS pass the region on
-    if (!E.status) row_cap += std::min<uint64_t>(EV_MAX_RECORDS, (h_range[r].stop - h_range[r].start) / 37 + 1);
+    // (h_count: the caller knows the number of records in the range -- the sweep's i1 - i0 -- and the rows are reserved from it)
+    if (!E.status) row_cap += std::min<uint64_t>(EV_MAX_RECORDS, h_count ? (uint64_t)h_count[r] : (h_range[r].stop - h_range[r].start) / 37 + 1);
   }
   if (row_cap > 0xfffffff0ull) { set_error("evidence: %llu rows in one call", (unsigned long long)row_cap); return STRL_ERR_LIMIT; }
   strl_ctx::RegionSlot *slot = J.slot;

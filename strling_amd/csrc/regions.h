@@ -57,8 +57,9 @@ const float *frag_cd(const uint32_t frag[4096]);
 int evidence_finish(const EvRow *rows, uint32_t n, const strl_bounds &b, const uint32_t frag[4096], strl_support *out, uint64_t cap, uint64_t *n_out,
                     float *expected_spanners);
 // evidence.hip: the evidence of n_regions regions whose record bytes are u[range[r].start, range[r].stop) on the device
+// (h_count, if given: the number of records in each range, from which the rows are reserved instead of from the bytes)
 int evidence_run(RegionJob &J, const uint8_t *d_u, uint64_t u_readable, const RegionWalk *d_range, const RegionWalk *h_range, uint32_t n_regions,
                  const strl_bounds *bounds, int32_t window, const uint32_t frag[4096], uint8_t min_mapq, strl_support *out, uint64_t cap,
-                 uint64_t *support_off, strl_span_summary *summary, uint8_t *status, double *kernel_ms);
+                 uint64_t *support_off, strl_span_summary *summary, uint8_t *status, double *kernel_ms, const uint32_t *h_count = nullptr);
 
 }  // namespace strl
