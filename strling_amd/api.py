@@ -218,6 +218,7 @@ def load(build_if_missing=True):
     L.strl_extract_add.argtypes = [C.c_void_p, C.POINTER(CReadSoa), C.POINTER(CPairSoa)]
     L.strl_extract_finish.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64]
     L.strl_pair_rule.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Opts), C.c_uint32, C.POINTER(C.c_int)]
+    L.strl_pair_rules_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Opts), C.c_void_p]
     L.strl_bounds_bare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint16, C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_int)]
     L.strl_ctx_treads_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]
     L.strl_cluster_gathered.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int32, C.c_int, C.c_uint32,
@@ -1210,6 +1211,30 @@ def pair_rule(ctx, op, A, B, opts, B_position=0):
     res = C.c_int(0)
     _check(load().strl_pair_rule(ctx.h if ctx is not None else None, op, a.ctypes.data, b.ctypes.data, C.byref(o), int(B_position), C.byref(res)))
     return res.value, a[0]
+
+
+def pair_rules(ctx, op, A, B, opts, B_position=None):
+    """n cases of one pair rule: arrays of treads A, B and of B_position.  ctx = a Context: ONE launch of the device functions,
+    one lane per case (strl_pair_rules_device, test-only); ctx = None: the host twins, case by case (strl_pair_rule).
+    -> (results int32[n], A after)"""
+    a = np.ascontiguousarray(A, TREAD_DTYPE).copy()
+    b = np.ascontiguousarray(B, TREAD_DTYPE)
+    n = a.size
+    assert b.size == n
+    bp = np.zeros(n, np.uint32) if B_position is None else np.ascontiguousarray(B_position, np.uint32)
+    assert bp.size == n
+    o = Opts(int(opts[2]), float(opts[0]), int(opts[1]))
+    res = np.zeros(n, np.int32)
+    L = load()
+    if ctx is not None:
+        _check(L.strl_pair_rules_device(ctx.h, op, _ptr(a), _ptr(b), _ptr(bp), n, C.byref(o), _ptr(res)))
+        return res, a
+    r = C.c_int(0)
+    pa, pb, sz = a.ctypes.data, b.ctypes.data, TREAD_DTYPE.itemsize
+    for i in range(n):
+        _check(L.strl_pair_rule(None, op, pa + i * sz, pb + i * sz, C.byref(o), int(bp[i]), C.byref(r)))
+        res[i] = r.value
+    return res, a
 
 
 def pull_select_host(raw, tile, base_off=0):

@@ -674,37 +674,50 @@ __device__ inline void dtread_to(const DTread &d, strl_tread &t) {
   t.align_length = d.align_length;
   for (int j = 0; j < 6; ++j) t.repeat[j] = (uint32_t)j < d.k ? "CATG"[(d.code >> (2 * (d.k - 1 - j))) & 3u] : (char)0;
 }
-__global__ void pair_rules_kernel(int op, strl_tread *A, const strl_tread *B, PairParams P, uint32_t B_position, int *res) {
-  DTread a = dtread_from(*A);
-  const DTread b = dtread_from(*B);
-  if (op == 0) *res = adjust_by(a, b, P, B_position) ? 1 : 0;
-  else if (op == 1) *res = unplaced_pair(a, b, P) ? 1 : 0;
-  else { a.code = canonical_repeat(a.code, a.k); *res = 0; }
-  dtread_to(a, *A);
+__global__ __launch_bounds__(256) void pair_rules_kernel(int op, strl_tread *A, const strl_tread *B, PairParams P, const uint32_t *B_position, uint32_t n,
+                                                         int *res) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;      // one lane per case
+  if (i >= n) return;
+  DTread a = dtread_from(A[i]);
+  const DTread b = dtread_from(B[i]);
+  if (op == 0) res[i] = adjust_by(a, b, P, B_position[i]) ? 1 : 0;
+  else if (op == 1) res[i] = unplaced_pair(a, b, P) ? 1 : 0;
+  else { a.code = canonical_repeat(a.code, a.k); res[i] = 0; }
+  dtread_to(a, A[i]);
 }
 
 }  // namespace strl
 
 using namespace strl;
 
-extern "C" int strl_pair_rule_device(strl_ctx *c, int op, strl_tread *A, const strl_tread *B, const strl_opts *o, uint32_t B_position, int *result) {
-  if (!c || !A || !B || !o || !result || op < 0 || op > 2) { set_error("bad argument"); return STRL_ERR_ARG; }
+// n cases of one rule in one launch (test-only, like strl_pair_rule_device): A[i] is updated in place, res[i] = the rule's result
+extern "C" int strl_pair_rules_device(strl_ctx *c, int op, strl_tread *A, const strl_tread *B, const uint32_t *B_position, uint64_t n, const strl_opts *o,
+                                      int *res) {
+  if (!c || !o || op < 0 || op > 2 || n > 0x7fffffffull || (n && (!A || !B || !B_position || !res))) { set_error("bad argument"); return STRL_ERR_ARG; }
+  if (!n) return STRL_OK;
   STRL_HIP(hipSetDevice(c->device));
   DevBuf buf;
   int rc;
-  if ((rc = buf.reserve(2 * sizeof(strl_tread) + 16))) return rc;
-  strl_tread *dA = buf.as<strl_tread>(), *dB = dA + 1;
-  int *dres = reinterpret_cast<int *>(dB + 1);
-  STRL_HIP(hipMemcpyAsync(dA, A, sizeof *A, hipMemcpyHostToDevice, c->stream));
-  STRL_HIP(hipMemcpyAsync(dB, B, sizeof *B, hipMemcpyHostToDevice, c->stream));
+  if ((rc = buf.reserve((size_t)n * (2 * sizeof(strl_tread) + 8)))) return rc;
+  strl_tread *dA = buf.as<strl_tread>(), *dB = dA + n;
+  uint32_t *dpos = reinterpret_cast<uint32_t *>(dB + n);
+  int *dres = reinterpret_cast<int *>(dpos + n);
+  STRL_HIP(hipMemcpyAsync(dA, A, (size_t)n * sizeof *A, hipMemcpyHostToDevice, c->stream));
+  STRL_HIP(hipMemcpyAsync(dB, B, (size_t)n * sizeof *B, hipMemcpyHostToDevice, c->stream));
+  STRL_HIP(hipMemcpyAsync(dpos, B_position, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   PairParams P{};
   P.p = o->proportion_repeat; P.min_mapq = o->min_mapq; P.frag_median = o->median_fragment_length;
-  hipLaunchKernelGGL(pair_rules_kernel, dim3(1), dim3(1), 0, c->stream, op, dA, dB, P, B_position, dres);
+  hipLaunchKernelGGL(pair_rules_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, op, dA, dB, P, dpos, (uint32_t)n, dres);
   STRL_HIP(hipGetLastError());
-  STRL_HIP(hipMemcpyAsync(A, dA, sizeof *A, hipMemcpyDeviceToHost, c->stream));
-  STRL_HIP(hipMemcpyAsync(result, dres, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  STRL_HIP(hipMemcpyAsync(A, dA, (size_t)n * sizeof *A, hipMemcpyDeviceToHost, c->stream));
+  STRL_HIP(hipMemcpyAsync(res, dres, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   STRL_HIP(hipStreamSynchronize(c->stream));
   return STRL_OK;
+}
+
+extern "C" int strl_pair_rule_device(strl_ctx *c, int op, strl_tread *A, const strl_tread *B, const strl_opts *o, uint32_t B_position, int *result) {
+  if (!A || !B || !result) { set_error("bad argument"); return STRL_ERR_ARG; }
+  return strl_pair_rules_device(c, op, A, B, &B_position, 1, o, result);
 }
 
 // Treads of the last strl_pair_device call into the order of the reference's .bin file (c->treads); idempotent.

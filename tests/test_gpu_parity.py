@@ -435,12 +435,17 @@ def test_pair_logic_corner_cases_on_the_device(ctx, oracle):
 @pytest.mark.parametrize("n", [16, 200, 700])
 def test_many_records_under_one_qname(ctx, oracle, n):
     """one qname on n primary records: up to 512 join items the device replays the run (a block of its own, pair_long_kernel);
-    beyond, it reports the run and strl_extract repeats the batch on the host's string-keyed Cache"""
+    beyond, it reports the run and strl_extract repeats the batch on the host's string-keyed Cache.  The records alternate
+    before / after their mate, so that each two of them pair up and emit (with every record before its mate the table entry
+    only toggles and nothing at all is emitted)"""
     C_ = "CAG" * 50
-    rec = RecordBatch.from_fields([0] * n, list(range(100, 100 + n)), [0] * n, [5000] * n, [99] * n, [60] * n, ["150M"] * n, [C_] * n, ["dup"] * n)
+    even = [j % 2 == 0 for j in range(n)]
+    rec = RecordBatch.from_fields([0] * n, [100 + j if e else 6000 + j for j, e in enumerate(even)], [0] * n, [5000 if e else 100 for e in even],
+                                  [99 if e else 147 for e in even], [60] * n, ["150M"] * n, [C_] * n, ["dup"] * n)
     ctx.set_opts(0.8, 40, 350)
     ctx.set_genome(None)
     exp = oracle.extract(rec, None, oracle.make_opts(350, 0.8, 40))
+    assert len(exp) == n
     soa = api.Soa(rec)
     cp, keep = _pair_soa(rec, soa)
     ctx.extract_device(soa.c_struct(), cp, 0)
