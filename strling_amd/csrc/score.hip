@@ -384,22 +384,40 @@ __global__ __launch_bounds__(1024) void compact_kernel(ScoreParams P) {
 }
 
 // Soft-clip items of the scored reads: flag byte + the read's queue entry -> segment items {id << 1 | side, seq_off, first
-// base, length} in the soft queue (left clip before right clip, reads in queue order within a block round).  One
-// queue-space atomic per 8192 reads.
+// base, length} in the soft queue.  One queue-space atomic per 8192 reads.
+//
+// Inside the range [base, base + tot) a block round reserves, the items lie BY LENGTH CLASS, shortest class first (eight
+// bases per class up to 160 bases, one class for everything longer), in no particular order inside a class: the segment
+// scorer's work follows the longest segment of a wave (its square, for the k = 5, 6 counts), and a wave takes 64 consecutive
+// items, so neighbours should be alike.  A lane-private rank from an LDS counter per class places an item; the round's range
+// is filled as a permutation of what queue order would have put there, so every reader that identifies a record by its
+// read_side (all of them: the entry point's host sort, the pair logic's hash keys and replay, the chunk append and the
+// multi-GPU rebase) sees the same set of records.  A round that would run past `scap` keeps queue order (left clip before
+// right clip, reads in queue order): the batch ends in STRL_ERR_CAPACITY and what is dropped there stays what it was.
+constexpr int SOFT_NCLS = 22;
+__device__ __forceinline__ uint32_t soft_len_class(uint32_t len) { return len <= 160u ? (len + 7u) >> 3 : (uint32_t)SOFT_NCLS - 1u; }
 __global__ __launch_bounds__(1024) void soft_compact_kernel(ScoreParams P) {
   __shared__ uint32_t wcnt[128];
-  __shared__ uint32_t base_sh;
+  __shared__ uint32_t ccnt[SOFT_NCLS];
+  __shared__ uint32_t base_sh, tot_sh;
   constexpr int U = 8;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned long long below = (1ull << lane) - 1ull;
   const uint32_t n_src = P.counters[CNT_QUEUE];
   for (uint32_t b0 = blockIdx.x * (1024u * U); b0 < n_src; b0 += gridDim.x * (1024u * U)) {
-    uint32_t f[U];
+    uint32_t f[U], rank[U];
+    uint4 e[U];
     unsigned long long m0[U], m1[U];
+    if (threadIdx.x < SOFT_NCLS) ccnt[threadIdx.x] = 0;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t i = b0 + 1024u * u + threadIdx.x;
       f[u] = i < n_src ? (uint32_t)P.soft_flag[i] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      e[u] = make_uint4(0, 0, 0, 0);
+      if (f[u]) e[u] = P.queue[b0 + 1024u * u + threadIdx.x];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -408,21 +426,40 @@ __global__ __launch_bounds__(1024) void soft_compact_kernel(ScoreParams P) {
       if (lane == 0) wcnt[u * 16 + wave] = (uint32_t)(__popcll(m0[u]) + __popcll(m1[u]));
     }
     __syncthreads();
+    // the clipped lengths, and each item's rank in its class (left | right << 16: a round has at most 16 384 items)
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t L = e[u].z & 0xffffu, cl = min(e[u].z >> 16, L), cr = min(e[u].w & 0xffffu, L);
+      rank[u] = 0;
+      if (f[u] & 1u) rank[u] = atomicAdd(&ccnt[soft_len_class(cl)], 1u);
+      if (f[u] & 2u) rank[u] |= atomicAdd(&ccnt[soft_len_class(cr)], 1u) << 16;
+    }
+    __syncthreads();
     if (threadIdx.x == 0) {
       uint32_t tot = 0;
       for (int w = 0; w < 16 * U; ++w) { const uint32_t c = wcnt[w]; wcnt[w] = tot; tot += c; }
+      uint32_t at = 0;
+      for (int c = 0; c < SOFT_NCLS; ++c) { const uint32_t k = ccnt[c]; ccnt[c] = at; at += k; }   // (at == tot)
       base_sh = tot ? atomicAdd(&P.counters[CNT_SOFT], tot) : 0u;
+      tot_sh = tot;
     }
     __syncthreads();
+    const uint32_t base = base_sh;
+    const bool binned = (uint64_t)base + tot_sh <= P.scap;   // block-uniform
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (f[u]) {
-        const uint32_t i = b0 + 1024u * u + threadIdx.x;
-        const uint4 e = P.queue[i];
-        const uint32_t L = e.z & 0xffffu, cl = e.z >> 16, cr = e.w & 0xffffu;
-        uint32_t d = base_sh + wcnt[u * 16 + wave] + (uint32_t)(__popcll(m0[u] & below) + __popcll(m1[u] & below));
-        if (f[u] & 1u) { if (d < P.scap) P.soft_queue[d] = make_uint4(e.x << 1, e.y, 0u, cl < L ? cl : L); ++d; }
-        if (f[u] & 2u) { const uint32_t c2 = cr < L ? cr : L; if (d < P.scap) P.soft_queue[d] = make_uint4((e.x << 1) | 1u, e.y, L - c2, c2); }
+        const uint32_t L = e[u].z & 0xffffu, cl = min(e[u].z >> 16, L), cr = min(e[u].w & 0xffffu, L);
+        uint32_t d = base + wcnt[u * 16 + wave] + (uint32_t)(__popcll(m0[u] & below) + __popcll(m1[u] & below));
+        if (f[u] & 1u) {
+          const uint32_t at = binned ? base + ccnt[soft_len_class(cl)] + (rank[u] & 0xffffu) : d;
+          if (at < P.scap) P.soft_queue[at] = make_uint4(e[u].x << 1, e[u].y, 0u, cl);
+          ++d;
+        }
+        if (f[u] & 2u) {
+          const uint32_t at = binned ? base + ccnt[soft_len_class(cr)] + (rank[u] >> 16) : d;
+          if (at < P.scap) P.soft_queue[at] = make_uint4((e[u].x << 1) | 1u, e[u].y, L - cr, cr);
+        }
       }
     }
     __syncthreads();

@@ -414,22 +414,23 @@ STRL_DEV void hist_pass_a(const Seg<NW> &sg, bool active, uint32_t *bins0, uint3
 }
 
 // k = 5, 6 (stage B)
-template <int K, int NW, int SLOTS>
-STRL_DEV void hist_pass(const Seg<NW> &sg, bool active, uint32_t *tab, const uint16_t *lut, int &cmax, uint32_t &imax) {
-  static_assert(K >= 5, "stage B");
-  constexpr uint32_t MASK = (1u << (2 * K)) - 1u;
+// In registers (reads <= 160 bases): the rows of the all-pairs count in blocks of HB56 windows, starting at window B0.  A block
+// whose first window lies at or past `umax` = lb.hi / K -- no lane of the wave has it -- ends the pass (wave-uniform), so the
+// work follows the square of the wave's longest segment, not of the class's 160 bases.  The blocks nest (each is entered from
+// inside the one before it) instead of being skipped one by one: a block then only ever reads codes that were computed on
+// the way to it, code[] stays statically indexed registers, and no code at or past the bound is computed or read.  What
+// a lane counts depends on `i < nwin` alone, so any umax >= nwin gives the same result.
+constexpr int HB56 = 4;
+template <int K, int NW, int B0>
+STRL_DEV void hist56_blocks(const Seg<NW> &sg, const uint16_t *lk, int nwin, int umax, uint32_t (&code)[NW * 16 / K], int &cmax, uint32_t &imax) {
   constexpr int NWIN = NW * 16 / K;
-  constexpr int B = 8;
-  const uint16_t *lk = lut + LutOff<K>::v;
-  const int nwin = active ? sg.len / K : 0;
-  cmax = 0;
-  imax = MASK;
-  if (NW <= 10) {
-    uint32_t code[NWIN];
+  if constexpr (B0 < NWIN) {
+    if (B0 >= umax) return;   // wave-uniform
+    constexpr int B1 = B0 + HB56 < NWIN ? B0 + HB56 : NWIN;
 #pragma unroll
-    for (int i = 0; i < NWIN; ++i) code[i] = window_code<K, NW>(sg, lk, i);
+    for (int i = B0; i < B1; ++i) code[i] = window_code<K, NW>(sg, lk, i);
 #pragma unroll
-    for (int i = 0; i < NWIN; ++i) {
+    for (int i = B0; i < B1; ++i) {
       uint32_t ne = 0;  // earlier windows that differ (pure VALU: xor, min, add -- no compare-to-SGPR round trips)
 #pragma unroll
       for (int j = 0; j < i; ++j) {
@@ -439,6 +440,23 @@ STRL_DEV void hist_pass(const Seg<NW> &sg, bool active, uint32_t *tab, const uin
       const int newc = 1 + i - (int)ne;
       if (i < nwin && newc > cmax) { cmax = newc; imax = code[i]; }
     }
+    hist56_blocks<K, NW, B1>(sg, lk, nwin, umax, code, cmax, imax);
+  }
+}
+
+template <int K, int NW, int SLOTS>
+STRL_DEV void hist_pass(const Seg<NW> &sg, bool active, uint32_t *tab, const uint16_t *lut, const LenBounds &lb, int &cmax, uint32_t &imax) {
+  static_assert(K >= 5, "stage B");
+  constexpr uint32_t MASK = (1u << (2 * K)) - 1u;
+  constexpr int NWIN = NW * 16 / K;
+  constexpr int B = 8;
+  const uint16_t *lk = lut + LutOff<K>::v;
+  const int nwin = active ? sg.len / K : 0;
+  cmax = 0;
+  imax = MASK;
+  if constexpr (NW <= 10) {
+    uint32_t code[NWIN];
+    hist56_blocks<K, NW, 0>(sg, lk, nwin, lb.hi / K, code, cmax, imax);
     return;
   }
 #pragma unroll
@@ -469,88 +487,84 @@ STRL_DEV void hist_pass(const Seg<NW> &sg, bool active, uint32_t *tab, const uin
 
 // ---- greedy non-overlapping literal count of the decoded unit (strutils.count, utils.nim:254) ----
 // lo_len: a wave-uniform lower bound of the lengths of the lanes that call (0: unknown) -- words that lie wholly below it
-// need no end-of-read mask.
-template <int K, int NW> STRL_DEV int recount(const Seg<NW> &sg, uint32_t code, int lo_len) {
-  uint32_t acc[NW];
+// need no end-of-read mask.  hi_len: a wave-uniform upper bound of them -- a word that starts at or past it (16 w >= hi_len)
+// holds no base of any calling lane, hence no match: the walk ends in front of it.
+//
+// One word at a time, front to back, each word entered from inside the one before it (like the k = 5, 6 blocks above: the
+// trip counts are constants, everything indexes registers statically, and nothing at or past the bound is computed or
+// read): compare, mask the end of the read, count.  What runs from word to word is the count and, for the collision rules,
+// one word of history:
+//   K = 2  : two matches collide only when adjacent (homodimer unit), and greedy left-to-right then keeps every other
+//            match of a run.  Runs are resolved with one multi-word addition: adding a run's start bit to the run
+//            (both bits of every pair filled) carries through exactly that run, which tells every pair the parity of
+//            its run's start.  Exact for hetero-dimers too (their runs have length 1).  The chain ends with the last word
+//            walked: a carry out of it belongs to no pair, and the words behind it hold no match.
+//   K >= 3 : only a unit that overlaps a shifted copy of itself can collide; if no lane of the wave has one (`walk` false)
+//            the count is the population count of the match bits, else (rare: periodic units whose shorter period did not
+//            already win) the literal greedy walk, which carries the bases to skip at the start of the next word.
+struct RecountRun { uint32_t prev, carry; int skip, cnt; };
+template <int K, int NW, int W>
+STRL_DEV void recount_words(const Seg<NW> &sg, const uint32_t (&pat)[K], const uint32_t (&iv)[NW], bool walk, int lo_len, int hi_len, RecountRun &r) {
+  if constexpr (W < NW) {
+    if (16 * W >= hi_len) return;   // wave-uniform
+    const uint32_t lo = sg.seq[W], hi = (W + 1 < NW) ? sg.seq[W + 1] : 0u;   // (a word past the bound is zero: no base there)
+    uint32_t acc = 0;
 #pragma unroll
-  for (int w = 0; w < NW; ++w) acc[w] = 0;
-  // rare per lane (every other wave though): a non-ACGT base inside the window kills the match.  The words are fetched from
-  // the lane's slot first, so that the round trip runs beside the comparison below.
+    for (int j = 0; j < K; ++j) acc |= strl_funnel_r(lo, hi, 2 * j) ^ pat[j];
+    if (sg.has_inv()) {   // rare per lane: a non-ACGT base inside the window kills the match
+      const uint32_t ilo = iv[W], ihi = (W + 1 < NW) ? iv[W + 1] : 0u;
+#pragma unroll
+      for (int j = 0; j < K; ++j) acc |= strl_funnel_r(ilo, ihi, 2 * j);
+    }
+    uint32_t m = ~(acc | (acc >> 1)) & 0x55555555u;   // bit 2i set <=> the unit matches at base 16 W + i
+    if (16 * (W + 1) > lo_len - K + 1) {   // wave-uniform
+      const int nv = sg.len - K + 1 - 16 * W;   // start positions left from this word on
+      if (nv < 16) m &= (nv <= 0) ? 0u : ((1u << (2 * nv)) - 1u);
+    }
+    if (K == 2) {
+      const uint32_t start = m & ~((m << 2) | (r.prev >> 30));          // first match of a run
+      const uint32_t fill = m | (m << 1);                                // runs as solid bit strings
+      const uint64_t t = (uint64_t)fill + (start & 0x11111111u) + r.carry;  // only runs starting on an even pair
+      r.carry = (uint32_t)(t >> 32);
+      const uint32_t even_runs = fill & ~(uint32_t)t;                    // bits those runs lost to the carry
+      const uint32_t sel = (m & even_runs & 0x11111111u) | (m & ~even_runs & 0x44444444u);
+      r.cnt += strl_popc(sel);
+      r.prev = m;
+    } else if (!walk) {
+      r.cnt += strl_popc(m);
+    } else {
+      uint32_t x = m & ~((1u << (2 * r.skip)) - 1u);
+      r.skip = 0;
+      while (x) {
+        const int i = (strl_ffs(x) - 1) >> 1;
+        ++r.cnt;
+        const int nx = i + K;
+        if (nx >= 16) { r.skip = nx - 16; x = 0; }
+        else x &= ~((1u << (2 * nx)) - 1u);
+      }
+    }
+    recount_words<K, NW, W + 1>(sg, pat, iv, walk, lo_len, hi_len, r);
+  }
+}
+
+template <int K, int NW> STRL_DEV int recount(const Seg<NW> &sg, uint32_t code, int lo_len, int hi_len) {
+  // The not-ACGT words are fetched from the lane's slot first (rare per lane, every other wave though), so that the round
+  // trip runs beside the comparison of the first words.
   uint32_t iv[NW];
   if (sg.has_inv()) inv_load<NW>(sg, iv);
+  uint32_t pat[K];
 #pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const uint32_t pat = ((code >> (2 * (K - 1 - j))) & 3u) * 0x55555555u;  // unit base j replicated
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const uint32_t lo = sg.seq[w], hi = (w + 1 < NW) ? sg.seq[w + 1] : 0u;
-      acc[w] |= strl_funnel_r(lo, hi, 2 * j) ^ pat;
-    }
-  }
-  if (sg.has_inv()) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        const uint32_t lo = iv[w], hi = (w + 1 < NW) ? iv[w + 1] : 0u;
-        acc[w] |= strl_funnel_r(lo, hi, 2 * j);
-      }
-    }
-  }
-  const int limit = sg.len - K + 1;  // number of start positions
-  uint32_t m[NW];                    // bit 2i of m[w] set <=> the unit matches at base 16w + i
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    uint32_t x = ~(acc[w] | (acc[w] >> 1)) & 0x55555555u;
-    if (16 * (w + 1) > lo_len - K + 1) {   // wave-uniform
-      const int nv = limit - 16 * w;
-      if (nv < 16) x &= (nv <= 0) ? 0u : ((1u << (2 * nv)) - 1u);
-    }
-    m[w] = x;
-  }
-  int cnt = 0;
-  if (K == 2) {
-    // Two matches collide only when adjacent (homodimer unit), and greedy left-to-right then keeps every other
-    // match of a run.  Runs are resolved with one multi-word addition: adding a run's start bit to the run
-    // (both bits of every pair filled) carries through exactly that run, which tells every pair the parity of
-    // its run's start.  Exact for hetero-dimers too (their runs have length 1).
-    uint32_t carry = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const uint32_t prev = w ? m[w - 1] : 0u;
-      const uint32_t start = m[w] & ~((m[w] << 2) | (prev >> 30));   // first match of a run
-      const uint32_t fill = m[w] | (m[w] << 1);                        // runs as solid bit strings
-      const uint64_t t = (uint64_t)fill + (start & 0x11111111u) + carry;  // only runs starting on an even pair
-      carry = (uint32_t)(t >> 32);
-      const uint32_t even_runs = fill & ~(uint32_t)t;                  // bits those runs lost to the carry
-      const uint32_t sel = (m[w] & even_runs & 0x11111111u) | (m[w] & ~even_runs & 0x44444444u);
-      cnt += strl_popc(sel);
-    }
-  } else {
-    // does the unit overlap a shifted copy of itself (s[0..K-d) == s[d..K))?  Only then can matches collide.
-    bool border = false;
+  for (int j = 0; j < K; ++j) pat[j] = ((code >> (2 * (K - 1 - j))) & 3u) * 0x55555555u;  // unit base j replicated
+  // does the unit overlap a shifted copy of itself (s[0..K-d) == s[d..K))?  Only then can matches collide.
+  bool border = false;
+  if (K > 2) {
 #pragma unroll
     for (int d = 1; d < K; ++d) border |= (code >> (2 * d)) == (code & ((1u << (2 * (K - d))) - 1u));
-    if (!strl_any(border)) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) cnt += strl_popc(m[w]);
-    } else {  // rare (periodic units whose shorter period did not already win): literal greedy walk
-      int skip = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        uint32_t x = m[w] & ~((1u << (2 * skip)) - 1u);
-        skip = 0;
-        while (x) {
-          const int i = (strl_ffs(x) - 1) >> 1;
-          ++cnt;
-          const int nx = i + K;
-          if (nx >= 16) { skip = nx - 16; x = 0; }
-          else x &= ~((1u << (2 * nx)) - 1u);
-        }
-      }
-    }
   }
-  return cnt;
+  const bool walk = K > 2 && strl_any(border);
+  RecountRun r = {0u, 0u, 0, 0};
+  recount_words<K, NW, 0>(sg, pat, iv, walk, lo_len, hi_len, r);
+  return r.cnt;
 }
 
 // cooperative zeroing of `rows` rows ([row][lane] dwords) of this wave's table region
@@ -601,7 +615,7 @@ STRL_DEV void score_k(const Seg<NW> &sg, ScoreState &st, uint32_t *wave_tab, int
   int c;
   uint32_t code;
   if constexpr (K <= 4) hist_pass_a<K, NW>(sg, st.alive, bins0, (uint32_t)((wave_tab - bins0) + lane) * 4u, static_cast<const uint32_t *>(tables), lb, c, code);
-  else hist_pass<K, NW, SLOTS>(sg, st.alive, wave_tab + lane, static_cast<const uint16_t *>(tables), c, code);
+  else hist_pass<K, NW, SLOTS>(sg, st.alive, wave_tab + lane, static_cast<const uint16_t *>(tables), lb, c, code);
   STRL_PH(st, 2 + 2 * (K - 2));
   if (st.alive) {
     int score = c * K;
@@ -618,7 +632,7 @@ STRL_DEV void score_k(const Seg<NW> &sg, ScoreState &st, uint32_t *wave_tab, int
                                     // ceiling of anything that would pool them over a block's lanes (profiles/r06/stage_a_recount_bound.txt)
       if (K != 3 && K != 4)
 #endif
-      c = recount<K, NW>(sg, code, lb.lo == 0x7fffffff ? 0 : lb.lo);  // utils.nim:254
+      c = recount<K, NW>(sg, code, lb.lo == 0x7fffffff ? 0 : lb.lo, lb.hi);  // utils.nim:254
       score = c * K;
       if (score >= st.best) {  // :256
         st.best = score;
