@@ -26,10 +26,18 @@ def sam_header(targets, sort_order="coordinate"):
     return f"@HD\tVN:1.6\tSO:{sort_order}\n" + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in targets)
 
 
-def write_bam(path, rec, header_text=None, level=1, block=0xFF00, index=True, repeat=1):
+def write_bam(path, rec, header_text=None, level=1, block=0xFF00, index=True, repeat=1, extra=None, quals=None, cuts=None):
     """index: True = <path>.bai, "csi" = <path>.csi (min_shift 14, samtools' depth rule), False = none.
     repeat > 1 (benchmarks only): the header gets its own BGZF blocks and the record blocks are written `repeat` times;
-    such a file is not coordinate sorted and gets no index."""
+    such a file is not coordinate sorted and gets no index.
+    extra: {record: bytes} or a list -- bytes behind a record's qualities (its aux data; the caller keeps them well-formed).
+    quals: the same for a record's quality bytes (l_seq of them) instead of 0xff.
+    cuts: ascending offsets of the inflated stream at which BGZF blocks end, instead of one every `block` bytes (the last block
+    takes the rest); such a file gets no index."""
+    def per_record(v, i):
+        if v is None:
+            return None
+        return v.get(i) if isinstance(v, dict) else v[i]
     targets = rec.targets
     text = (header_text if header_text is not None else sam_header(targets)).encode()
     out = bytearray()
@@ -49,11 +57,25 @@ def write_bam(path, rec, header_text=None, level=1, block=0xFF00, index=True, re
         if l_seq & 1 and seq:
             seq = seq[:-1] + bytes([seq[-1] & 0xF0])
         cig = rec.cigar[c0:c1].astype("<u4").tobytes()
-        qual = b"\xff" * l_seq
+        qual = per_record(quals, i)
+        if qual is None:
+            qual = b"\xff" * l_seq
+        elif len(qual) != l_seq:
+            raise ValueError(f"quals of record {i}: {len(qual)} bytes for l_seq {l_seq}")
         body = struct.pack("<iiBBHHHiiii", int(rec.tid[i]), int(rec.pos[i]), len(qn), int(rec.mapq[i]), 4680, c1 - c0,
-                           int(rec.flag[i]), l_seq, int(rec.mtid[i]), int(rec.mpos[i]), int(isize[i])) + qn + cig + seq + qual
+                           int(rec.flag[i]), l_seq, int(rec.mtid[i]), int(rec.mpos[i]), int(isize[i])) + qn + cig + seq + bytes(qual) + \
+            bytes(per_record(extra, i) or b"")
         out += struct.pack("<i", len(body)) + body
     rec_off.append(len(out))
+    if cuts is not None:
+        edges = [0] + [int(c) for c in cuts] + [len(out)]
+        if repeat > 1 or any(b <= a or b - a > 0xFF00 for a, b in zip(edges[:-1], edges[1:])):
+            raise ValueError("cuts: ascending offsets inside the stream, at most 0xFF00 bytes apart, and no repeat")
+        with open(path, "wb") as f:
+            for a, b in zip(edges[:-1], edges[1:]):
+                f.write(_bgzf_block(bytes(out[a:b]), level))
+            f.write(_EOF)
+        return text.decode()
     if repeat > 1:
         n_hdr = rec_off[0]
         with open(path, "wb") as f:

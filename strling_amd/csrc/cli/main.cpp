@@ -1166,7 +1166,7 @@ int ExtractFront::feed_shares() {
   for (int g = 0; g < n_shares; ++g) {
     const Share &Z = shares[(size_t)g];
     if (Z.rc == STRL_ERR_NOMEM) nomem = true;
-    if (Z.rc == STRL_ERR_FORMAT || Z.rc == STRL_ERR_LIMIT || Z.rc == STRL_ERR_NOMEM || Z.fallback || (g + 1 < n_shares && Z.tail)) again = true;
+    if (Z.rc == STRL_ERR_FORMAT || Z.rc == STRL_ERR_LIMIT || Z.rc == STRL_ERR_NOMEM || Z.fallback || Z.tail) again = true;      // (the last share's tail: the file ends inside a record)
     else if (Z.rc == STRL_ERR_CRC) quit("[strling] error reading %s: %s", bam.c_str(), Z.err.c_str());
     else if (Z.rc) quit("[strling] %s (status %d)", Z.err.c_str(), Z.rc);
   }
@@ -1174,9 +1174,11 @@ int ExtractFront::feed_shares() {
     // a share that did not end on the next one's first record (a stale index), a block or record the device front end
     // refuses, too many records for one pass: the chunk-by-chunk run sorts out which, with its own ways out
     for (int g = 0; g < n_shares; ++g)
-      if (shares[(size_t)g].rc || shares[(size_t)g].fallback || (g + 1 < n_shares && shares[(size_t)g].tail))
+      if (shares[(size_t)g].rc || shares[(size_t)g].fallback || shares[(size_t)g].tail)
         fprintf(stderr, "[strling] share %d of %d: %s; repeating the extraction chunk by chunk\n", g, n_shares,
-                shares[(size_t)g].rc || shares[(size_t)g].fallback ? shares[(size_t)g].err.c_str() : "the .bai's record start is not where the share's records end");
+                shares[(size_t)g].rc || shares[(size_t)g].fallback ? shares[(size_t)g].err.c_str()
+                : g + 1 < n_shares                                 ? "the .bai's record start is not where the share's records end"
+                                                                   : "the BAM ends inside a record (truncated file)");
     return abandon(nomem ? EXTRACT_AGAIN_ON_HOST : EXTRACT_AGAIN_BY_CHUNKS);      // (out of device memory: the chunk-by-chunk run would need as much)
   }
   for (int g = 0; g < n_shares; ++g) tally.owner.insert(tally.owner.end(), tally.by_ctx[(size_t)g].size(), (uint32_t)g);
@@ -1215,6 +1217,14 @@ int ExtractFront::feed_by_chunks(ThreadPool &copy_pool) {
   if (frag_thread.joinable()) frag_thread.join();
   tf = tick();
   for (int g = 0; g < G; ++g) FRONT_CHECK(finish_front(ctxs[(size_t)g], tally.by_ctx[(size_t)g]));
+  // Bytes behind the last complete record of the file's last chunk: the file ends inside a record.  The host reader refuses such a
+  // file (as htslib does), bamindex and the sweep refuse it; this pass used to drop the partial record and write a .bin.  The host
+  // reader gets the file, and its verdict is the run's.
+  if (!tally.owner.empty()) {
+    uint32_t tail = 0;
+    FRONT_CHECK(strl_front_tail_bytes(ctxs[(size_t)tally.owner.back()], &tail));
+    if (tail) return front_failed(STRL_ERR_FORMAT, "the BAM ends inside a record (truncated file)");
+  }
   tally.account(verbose, t0);
   return 0;
 }

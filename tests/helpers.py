@@ -75,3 +75,39 @@ def device_batch(torch, dev, soa, rows, qh, with_meta=True):
     cp = api.CPairSoa(drows.data_ptr(), dqh.data_ptr())
     torch.cuda.synchronize()
     return cs, cp, [d, drows, dqh]
+
+
+FRONT_FIELDS = ("tid", "position", "repeat", "flag", "split", "mapping_quality", "repeat_count", "align_length", "qname_id")
+
+
+def check_front_extract(ctx, rec, g, path, chunk_blocks, exp):
+    """`ctx.extract_bam_device(path)` (inflate, record scan, parse, scorer, pair logic on the device) against the treads `exp` of
+    the records the file was written from: every field in .bin order, the qnames, the fragment-length words of every record, the
+    chunk summaries' counts, the contigs seen -> what the device returned"""
+    from oracle import oracle as O
+    from strling_amd import synth
+    med = O.median(synth.frag_hist(rec))
+    ctx.set_opts(0.8, 40, med)
+    ctx.set_genome(g)
+    got = ctx.extract_bam_device(path, chunk_blocks=chunk_blocks)
+    assert got["n_records"] == rec.n
+    assert [t[0] for t in got["targets"]] == [t[0] for t in rec.targets]
+    for f in FRONT_FIELDS:
+        assert np.array_equal(got["treads"][f], exp[f]), (f, chunk_blocks)
+    assert got["qnames"] == [rec.qname(int(i)) for i in exp["qname_id"]]
+    isz = rec.isize if rec.isize is not None else np.zeros(rec.n, np.int32)
+    fw = rec.flag.astype(np.uint32) | (np.where((isz >= 0) & (isz <= 4095), isz, 0xffff).astype(np.uint32) << 16)
+    assert np.array_equal(got["fragwords"], fw)
+    prim = (rec.flag & 0x900) == 0
+    assert sum(c["n_primary"] for c in got["chunks"]) == int(prim.sum())
+    n_tail = 0
+    while n_tail < rec.n and rec.tid[rec.n - 1 - n_tail] < 0:
+        n_tail += 1
+    assert got["n_tail"] == n_tail
+    if n_tail < rec.n:      # the last chunk with a placed record counts the primary records behind it
+        last = [c for c in got["chunks"] if c["last_placed"] >= 0][-1]
+        assert last["tail_primary"] <= int(prim[rec.n - n_tail:].sum())
+    seen = np.zeros(len(rec.targets), np.uint8)
+    seen[np.unique(rec.tid[prim & (rec.tid >= 0)])] = 1
+    assert np.array_equal(got["tids_seen"], seen)
+    return got

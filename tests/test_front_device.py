@@ -7,10 +7,9 @@ import numpy as np
 import pytest
 
 from strling_amd import api, bamio, synth
+from helpers import FRONT_FIELDS as FIELDS, check_front_extract as _check
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("tid", "position", "repeat", "flag", "split", "mapping_quality", "repeat_count", "align_length", "qname_id")
 
 
 @pytest.fixture(scope="module")
@@ -25,35 +24,6 @@ def _host_reference(ctx, rec, g, med):
     ctx.set_genome(g)
     exp, _ = ctx.extract(rec)
     return exp
-
-
-def _check(ctx, rec, g, path, chunk_blocks, exp):
-    from oracle import oracle as O
-    med = O.median(synth.frag_hist(rec))
-    ctx.set_opts(0.8, 40, med)
-    ctx.set_genome(g)
-    got = ctx.extract_bam_device(path, chunk_blocks=chunk_blocks)
-    assert got["n_records"] == rec.n
-    assert [t[0] for t in got["targets"]] == [t[0] for t in rec.targets]
-    for f in FIELDS:
-        assert np.array_equal(got["treads"][f], exp[f]), (f, chunk_blocks)
-    assert got["qnames"] == [rec.qname(int(i)) for i in exp["qname_id"]]
-    isz = rec.isize if rec.isize is not None else np.zeros(rec.n, np.int32)
-    fw = rec.flag.astype(np.uint32) | (np.where((isz >= 0) & (isz <= 4095), isz, 0xffff).astype(np.uint32) << 16)
-    assert np.array_equal(got["fragwords"], fw)
-    prim = (rec.flag & 0x900) == 0
-    assert sum(c["n_primary"] for c in got["chunks"]) == int(prim.sum())
-    n_tail = 0
-    while n_tail < rec.n and rec.tid[rec.n - 1 - n_tail] < 0:
-        n_tail += 1
-    assert got["n_tail"] == n_tail
-    if n_tail < rec.n:      # the last chunk with a placed record counts the primary records behind it
-        last = [c for c in got["chunks"] if c["last_placed"] >= 0][-1]
-        assert last["tail_primary"] <= int(prim[rec.n - n_tail:].sum())
-    seen = np.zeros(len(rec.targets), np.uint8)
-    seen[np.unique(rec.tid[prim & (rec.tid >= 0)])] = 1
-    assert np.array_equal(got["tids_seen"], seen)
-    return got
 
 
 @pytest.mark.parametrize("n_pairs,block,chunk_blocks", [(3000, 0xFF00, 16384), (6000, 4099, 7), (6000, 0xFF00, 3), (20000, 30011, 5)])
