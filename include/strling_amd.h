@@ -466,6 +466,23 @@ typedef struct {
 int strl_assign_reads_loci(strl_tread *treads, uint64_t n, int mode, strl_locus *loci, uint64_t n_loci, uint64_t *assigned_off,
                            uint32_t *assigned, uint64_t cap);
 
+/* The same on the device, for lists of many thousands of loci: one sort of the treads by (tid, unit, position, input order),
+ * two binary searches per locus, and the taking itself one wave per (tid, unit) group, the groups side by side (assign.hip;
+ * the rule: assign_core.h).  The contract is strl_assign_reads_loci's, field for field: `treads` (host) is marked in place,
+ * the loci are recounted (the uint16 counts wrap as there), assigned_off[n_loci + 1] is filled; assigned may be NULL (no
+ * lists), and STRL_ERR_CAPACITY names the entries needed when `cap` is too small (everything else is filled as on success).
+ * STRL_ERR_ARG, as strl_cluster gives it and with nothing written: a tread whose unit is not a NUL-padded ACGT string, a
+ * tid < -1, n > 2^31 - 16.  A locus whose unit is not made of ACGT, or whose tid no tread has, receives nothing.  After an
+ * error the context goes on working.  strl_assign_info_last: the figures of the context's last call. */
+typedef struct {
+  uint64_t n_loci, n_groups; /* loci given; (tid, unit) groups with treads that at least one locus names */
+  uint64_t n_assigned, n_lost;
+  double seconds; /* the whole call on the host's clock */
+} strl_assign_info;
+int strl_assign_reads_loci_device(strl_ctx *ctx, strl_tread *treads, uint64_t n, int mode, strl_locus *loci, uint64_t n_loci,
+                                  uint64_t *assigned_off, uint32_t *assigned, uint64_t cap);
+int strl_assign_info_last(strl_ctx *ctx, strl_assign_info *info);
+
 /* Re-run the device side of the last strl_cluster call (sorts, sweep, bounds) over the treads still resident on
  * the device, asynchronously on the context stream and without host synchronisation.  For timing. */
 int strl_cluster_replay(strl_ctx *ctx);

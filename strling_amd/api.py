@@ -79,6 +79,10 @@ class ClusterStats(C.Structure):
                 ("n_tie_fixups", C.c_uint64), ("ms_sort", C.c_float), ("ms_sweep", C.c_float), ("ms_bounds", C.c_float)]
 
 
+class AssignInfo(C.Structure):
+    _fields_ = [("n_loci", C.c_uint64), ("n_groups", C.c_uint64), ("n_assigned", C.c_uint64), ("n_lost", C.c_uint64), ("seconds", C.c_double)]
+
+
 class BinInfo(C.Structure):
     _fields_ = [("proportion_repeat", C.c_float), ("min_mapq", C.c_uint8), ("frag", C.c_uint32 * 4096),
                 ("header_len", C.c_int32), ("n_reads", C.c_int32), ("qnames_bytes", C.c_uint64)]
@@ -136,7 +140,7 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_ctx_enable_timing", "strl_ctx_kernel_times", "strl_ctx_kernel_times_detail", "strl_pair_reads", "strl_pairer_create", "strl_pairer_destroy", "strl_pairer_add",
            "strl_pairer_result", "strl_qname_hash", "strl_extract", "strl_cluster", "strl_cluster_replay", "strl_frag_median",
            "strl_bin_write", "strl_bin_read", "strl_bounds_row", "strl_cluster_members", "strl_spanners", "strl_genotype",
-           "strl_calls_finish", "strl_unplaced_order", "strl_call_row", "strl_canonical_repeat", "strl_assign_reads_loci", "strl_group_order",
+           "strl_calls_finish", "strl_unplaced_order", "strl_call_row", "strl_canonical_repeat", "strl_assign_reads_loci", "strl_assign_reads_loci_device", "strl_assign_info_last", "strl_group_order",
            "strl_extract_device", "strl_treads_fetch", "strl_ctx_pair_times", "strl_sort_pairs", "strl_cluster_resident", "strl_ctx_cluster_times", "strl_pair_rows", "strl_extract_begin", "strl_extract_add", "strl_extract_finish", "strl_pair_rule", "strl_bounds_bare", "strl_ctx_treads_device", "strl_cluster_gathered", "strl_inflate_blocks", "strl_ctx_inflate_ms", "strl_regions_fetch", "strl_evidence_records", "strl_regions_evidence", "strl_front_begin", "strl_front_push", "strl_front_push_after", "strl_front_reserve", "strl_front_stage", "strl_front_enqueue_after", "strl_front_collect", "strl_ctxs_extract_gather", "strl_front_finish", "strl_front_fragwords", "strl_front_fragwords_async", "strl_event_wait", "strl_front_records", "strl_front_tids", "strl_front_qnames", "strl_front_treads_named", "strl_pinned_alloc", "strl_pinned_free", "strl_comm_unique_id", "strl_ctx_comm_init", "strl_ctxs_comm_init", "strl_ctx_comm_info", "strl_cluster_exchange", "strl_ctxs_cluster_exchange", "strl_exchange_treads", "strl_ctx_set_treads", "strl_cluster_collect", "strl_ctx_tail_stream", "strl_ctx_mem_info", "strl_bin_peek", "strl_front_trim_next", "strl_front_tail_bytes", "strl_ctx_blocking_waits", "strl_score_read_host", "strl_front_end",
            "strl_bamindex_begin", "strl_bamindex_reserve", "strl_bamindex_push", "strl_bamindex_finish", "strl_bamindex_fetch", "strl_bamindex_end",
            "strl_front_index_begin", "strl_front_index_blocks", "strl_front_index_finish", "strl_bamindex_begin_csi", "strl_front_index_begin_csi",
@@ -203,6 +207,8 @@ def load(build_if_missing=True):
     L.strl_canonical_repeat.restype = None
     L.strl_group_order.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.strl_assign_reads_loci.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_assign_reads_loci_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_assign_info_last.argtypes = [C.c_void_p, C.POINTER(AssignInfo)]
     L.strl_extract_device.argtypes = [C.c_void_p, C.POINTER(CReadSoa), C.POINTER(CPairSoa), C.c_int64, C.c_uint64, C.c_uint64]
     L.strl_treads_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(ScoreStats)]
     L.strl_ctx_pair_times.argtypes = [C.c_void_p, C.POINTER(C.c_double * 5)]
@@ -1310,6 +1316,25 @@ def assign_reads_loci(treads, loci, mode):
     idx = np.zeros(max(1, t.size), np.uint32)
     _check(L.strl_assign_reads_loci(t.ctypes.data, t.size, mode, lo.ctypes.data, lo.size, off.ctypes.data, idx.ctypes.data, idx.size))
     return t, lo, [idx[int(off[j]):int(off[j + 1])].copy() for j in range(lo.size)]
+
+
+def assign_reads_loci_device(ctx, treads, loci, mode, cap=None):
+    """assign_reads_loci on the device (strl_assign_reads_loci_device): the same three results.  cap: entries the assigned
+    array may take (default: one per tread, which always suffices)"""
+    t = np.ascontiguousarray(treads, TREAD_DTYPE).copy()
+    lo = np.ascontiguousarray(loci, LOCUS_DTYPE).copy()
+    off = np.zeros(lo.size + 1, np.uint64)
+    idx = np.zeros(max(1, t.size if cap is None else cap), np.uint32)
+    _check(ctx.L.strl_assign_reads_loci_device(ctx.h, _ptr(t), t.size, mode, _ptr(lo), lo.size, off.ctypes.data, idx.ctypes.data,
+                                               idx.size if cap is None else cap))
+    return t, lo, [idx[int(off[j]):int(off[j + 1])].copy() for j in range(lo.size)]
+
+
+def assign_info_last(ctx):
+    """figures of the context's last assign_reads_loci_device call -> AssignInfo"""
+    info = AssignInfo()
+    _check(ctx.L.strl_assign_info_last(ctx.h, C.byref(info)))
+    return info
 
 
 def spanners(rec: RecordBatch, bound, window, frag, min_mapq=20):

@@ -68,6 +68,19 @@ static int device_of(int g) { return (g_device0 + g) % std::max(1, strl_device_c
     if (rc__ != 0) quit("[strling] %s (status %d)", strl_last_error(), rc__); \
   } while (0)
 
+// STRL_ASSIGN=device: the loci of call -l / -b and merge -l take their reads through strl_assign_reads_loci_device.  Asked for,
+// not the default, as STRL_CALL_EVIDENCE=device is (figures: profiles/assign/README.md); the outputs are the same.
+static bool assign_on_device() {
+  const char *e = getenv("STRL_ASSIGN");
+  return e && !strcmp(e, "device");
+}
+static void report_assign(strl_ctx *ctx) {
+  strl_assign_info I;
+  CHECK(strl_assign_info_last(ctx, &I));
+  fprintf(stderr, "[strling] loci take their reads on the device (STRL_ASSIGN=device): %llu loci, %llu groups with loci, %llu reads assigned, %llu lost, %.3f s\n",
+          (unsigned long long)I.n_loci, (unsigned long long)I.n_groups, (unsigned long long)I.n_assigned, (unsigned long long)I.n_lost, I.seconds);
+}
+
 struct Args {
   std::map<std::string, std::string> opt;
   std::vector<std::string> pos;
@@ -1610,14 +1623,22 @@ static int merge_main(int argc, char **argv) {
     loci = parse_bed(a.get("bed", ""), targets, (uint32_t)window);
     if (have_req) loci.erase(std::remove_if(loci.begin(), loci.end(), [&](const strl_locus &L) { return L.b.tid != requested_tid; }), loci.end());   // cluster.nim:139
     std::vector<uint64_t> aoff(loci.size() + 1);
-    CHECK(strl_assign_reads_loci(all.data(), all.size(), STRL_MODE_MERGE, loci.data(), loci.size(), aoff.data(), nullptr, 0));
+    if (assign_on_device() && gpus_early == 1) {       // the stage needs the context: its join comes forward on this path only
+      ctx_thread.join();
+      if (ctx_early_rc) quit("[strling] %s (status %d)", ctx_early_err.c_str(), ctx_early_rc);
+      CHECK(strl_assign_reads_loci_device(ctx_early, all.data(), all.size(), STRL_MODE_MERGE, loci.data(), loci.size(), aoff.data(), nullptr, 0));
+      if (verbose) report_assign(ctx_early);
+    } else {
+      if (verbose && assign_on_device()) fprintf(stderr, "[strling] STRL_ASSIGN=device is for --gpus 1: the loci take their reads on the host\n");
+      CHECK(strl_assign_reads_loci(all.data(), all.size(), STRL_MODE_MERGE, loci.data(), loci.size(), aoff.data(), nullptr, 0));
+    }
   }
   strl_ctx *ctx = nullptr;
   rvec<strl_bounds> bounds(std::max<size_t>(all.size(), 16));      // (left uninitialised: rows [0, nb) are written by the pass)
   uint64_t nb = 0, nu = 0;
   const int gpus = std::max(1, atoi(a.get("gpus", "1").c_str()));
   const auto tm1 = std::chrono::steady_clock::now();
-  ctx_thread.join();
+  if (ctx_thread.joinable()) ctx_thread.join();
   g_bg_init = nullptr;
   const auto tm2 = std::chrono::steady_clock::now();
   if (gpus == 1) {
@@ -2471,7 +2492,11 @@ static int call_main(int argc, char **argv) {
       taken_copy = treads;
       std::vector<uint64_t> aoff(given.size() + 1);
       assigned.resize((size_t)std::max<uint64_t>(nt, 1));
-      CHECK(strl_assign_reads_loci(treads.data(), nt, STRL_MODE_CALL, given.data(), given.size(), aoff.data(), assigned.data(), assigned.size()));
+      if (assign_on_device()) {                        // (the context is up: its thread was joined in front of the fragment lengths)
+        CHECK(strl_assign_reads_loci_device(ctx, treads.data(), nt, STRL_MODE_CALL, given.data(), given.size(), aoff.data(), assigned.data(), assigned.size()));
+        if (verbose) report_assign(ctx);
+      } else
+        CHECK(strl_assign_reads_loci(treads.data(), nt, STRL_MODE_CALL, given.data(), given.size(), aoff.data(), assigned.data(), assigned.size()));
       // the reads keep the split they had: strl_assign_reads_loci only re-marks its own copies in `treads`
       std::vector<Task> tasks;
       for (size_t j = 0; j < given.size(); ++j) {

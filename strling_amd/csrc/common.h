@@ -200,6 +200,9 @@ struct strl_ctx : TailSet, HeadSet {
   strl::strl_comm *comm = nullptr;     // multi-GPU exchange (comm.hip): RCCL communicator / local group of this context
   // staging of the pairing arrays for host-memory batches
   strl::DevBuf st_mtid, st_qhash;
+  // strl_assign_reads_loci_device (assign.hip): its buffers, kept between calls, and the figures of the last call
+  strl::DevBuf as_buf[24];
+  strl_assign_info as_info{};
 };
 
 // pair.hip: enqueue the device pair logic behind a scoring pass of the same batch
