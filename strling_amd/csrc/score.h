@@ -20,6 +20,9 @@ constexpr uint64_t RING = 256;
 // compaction | stage A, compaction, stage B (segments)
 constexpr int EV_PER = 9;
 
+// grid of a compaction kernel (compact_kernel, soft_compact_kernel, pair_soft_items_kernel): STRL_GRID_K when set, else `dflt`
+int compact_grid(int dflt);
+
 }  // namespace strl
 
 // one scoring pass over a device-resident batch (classify, scorer, segments, the long reads), enqueued on the context's stream

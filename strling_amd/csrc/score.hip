@@ -761,17 +761,24 @@ template <int MODE> static int launch_score_class(strl_ctx *ctx, const ScorePara
       return STRL_OK;
     }
   }
+  // (a grid given by the environment is the grid of every length class: tests and sweeps put a lane through many turns of its loop)
   if (max_l <= 160) rc = launch_score<10, 64, MODE, 0, 256>(ctx, P, ga);
-  else if (max_l <= 256) rc = launch_score<16, 128, MODE, 0, 256>(ctx, P, std::max(256, ga / 4));
-  else rc = launch_score<32, 256, MODE, 0, 64>(ctx, P, std::max(512, ga / 2));
+  else if (max_l <= 256) rc = launch_score<16, 128, MODE, 0, 256>(ctx, P, env_a > 0 ? env_a : std::max(256, ga / 4));
+  else rc = launch_score<32, 256, MODE, 0, 64>(ctx, P, env_a > 0 ? env_a : std::max(512, ga / 2));
   if (rc) return rc;
   if (ev) STRL_HIP(hipEventRecord(ev[0], ctx->stream));
-  hipLaunchKernelGGL((compact_kernel<1, MODE>), dim3(512), dim3(1024), 0, ctx->stream, P);
+  hipLaunchKernelGGL((compact_kernel<1, MODE>), dim3(compact_grid(512)), dim3(1024), 0, ctx->stream, P);
   STRL_HIP(hipGetLastError());
   if (ev) STRL_HIP(hipEventRecord(ev[1], ctx->stream));
   if (max_l <= 160) return launch_score<10, 64, MODE, 1, 256>(ctx, P, gb);
-  if (max_l <= 256) return launch_score<16, 128, MODE, 1, 256>(ctx, P, std::max(256, gb / 4));
-  return launch_score<32, 256, MODE, 1, 64>(ctx, P, std::max(512, gb / 2));
+  if (max_l <= 256) return launch_score<16, 128, MODE, 1, 256>(ctx, P, env_b > 0 ? env_b : std::max(256, gb / 4));
+  return launch_score<32, 256, MODE, 1, 64>(ctx, P, env_b > 0 ? env_b : std::max(512, gb / 2));
+}
+
+// STRL_GRID_K (tests, grid sweeps): the grid of the three compaction kernels, whose fixed grids cover millions of slots per round
+int compact_grid(int dflt) {
+  static const int env_k = getenv("STRL_GRID_K") ? atoi(getenv("STRL_GRID_K")) : 0;
+  return env_k > 0 ? env_k : dflt;
 }
 
 }  // namespace strl
@@ -985,7 +992,7 @@ int score_device(strl_ctx *c, const strl_read_soa *s, uint32_t *whole, strl_soft
   else if (tev) { STRL_HIP(hipEventRecord(tev[2], c->stream)); STRL_HIP(hipEventRecord(tev[3], c->stream)); }
   if (tev) STRL_HIP(hipEventRecord(tev[4], c->stream));
   if (n && soft_cap) {
-    hipLaunchKernelGGL(soft_compact_kernel, dim3(1024), dim3(1024), 0, c->stream, P);
+    hipLaunchKernelGGL(soft_compact_kernel, dim3(strl::compact_grid(1024)), dim3(1024), 0, c->stream, P);
     STRL_HIP(hipGetLastError());
     if (tev) STRL_HIP(hipEventRecord(tev[5], c->stream));
     if ((rc = launch_score_class<1>(c, P, class_l, tev ? tev + 6 : nullptr))) return rc;

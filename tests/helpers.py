@@ -59,14 +59,23 @@ def bounds_rows(bounds, targets, row_fn):
     return [row_fn(b, targets[int(b["tid"])][0]) for b in bounds]
 
 
-def device_batch(torch, dev, soa, rows, qh, with_meta=True):
+def device_batch(torch, dev, soa, rows, qh, with_meta=True, offset=0):
     """the arrays of a host batch uploaded to the device -> (CReadSoa, CPairSoa, keep-alive list): device-resident input
-    is what makes strl_extract_device overlap a batch's pair logic with the next batch's scorer"""
+    is what makes strl_extract_device overlap a batch's pair logic with the next batch's scorer.
+    offset: every per-read column starts `offset` elements into its allocation (offset=1: no column is 16-byte aligned, so the
+    skip-predicate pass takes its scalar variant); SEQ, the packed rows and the pairing arrays, which are read 16 bytes at a time,
+    stay where the allocator put them"""
     from strling_amd import api
 
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    d = {k: up(getattr(soa, k)) for k in ("tid", "pos", "end", "seq_off", "l_seq", "clip_l", "clip_r", "mapq", "cig", "seq4")}
+    def up(a, off=0):
+        a = np.ascontiguousarray(a)
+        if not off:
+            return torch.from_numpy(a).to(dev)
+        padded = np.zeros(a.size + off, a.dtype)
+        padded[off:] = a
+        return torch.from_numpy(padded).to(dev)[off:]
+    d = {k: up(getattr(soa, k), offset) for k in ("tid", "pos", "end", "seq_off", "l_seq", "clip_l", "clip_r", "mapq", "cig")}
+    d["seq4"] = up(soa.seq4)
     drows, dqh = up(rows.view(np.uint8)), up(qh)
     d["meta"] = up(soa.meta_rows().view(np.int32)) if with_meta else None
     cs = api.CReadSoa(soa.n, d["tid"].data_ptr(), d["pos"].data_ptr(), d["end"].data_ptr(), d["seq_off"].data_ptr(), d["l_seq"].data_ptr(),
