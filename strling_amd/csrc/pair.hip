@@ -474,7 +474,11 @@ template <class Ctx> __device__ inline void replay_run(Ctx &G, int m, const Emit
 // gathers of the block in flight together).  Phase 2: the lane of the first item of a run (equal low 32 hash bits)
 // replays Cache.add for the run out of LDS; emitted treads are staged in LDS.  Phase 3: one atomic reserves the block's
 // output space, all lanes copy the staging area out.
-__global__ __launch_bounds__(PG_BLOCK) void pair_groups_kernel(PairParams P) {
+// The launch waits on its gathers and on the serial replay (VALU 0.41 of the issue slots), so it runs as fast as the CU has
+// blocks to switch between.  Six waves per SIMD = three blocks per CU (80 registers; the LDS would take four); left to itself
+// the compiler takes 99 registers = two blocks.  At -O3 the bound costs 36 bytes of scratch per lane; optimised for size
+// (minsize: the replay's loops stay rolled) it is 77 registers and none.  162 -> 126 us (profiles/pair_replay).
+__global__ __launch_bounds__(PG_BLOCK, 6) __attribute__((minsize)) void pair_groups_kernel(PairParams P) {
   extern __shared__ __attribute__((aligned(16))) uint8_t pg_lds[];
   PItem *items = reinterpret_cast<PItem *>(pg_lds);
   strl_tread *st_t = reinterpret_cast<strl_tread *>(pg_lds + sizeof(PItem) * (PG_BLOCK + PG_HALO));
@@ -818,7 +822,9 @@ int strl_pair_device(strl_ctx *c, uint64_t n, const strl_pair_soa *pp, const uin
       STRL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pair_groups_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_shmem));
       c->pg_attr_done = true;
     }
-    hipLaunchKernelGGL(pair_groups_kernel, dim3((unsigned)std::min<uint32_t>((icap + PG_BLOCK - 1) / PG_BLOCK, 8192)), dim3(PG_BLOCK), pg_shmem, st, P);
+    static const int env_g = getenv("STRL_GRID_G") ? atoi(getenv("STRL_GRID_G")) : 0;      // (tests: a block takes many tiles)
+    const uint32_t gblocks = std::min<uint32_t>((icap + PG_BLOCK - 1) / PG_BLOCK, env_g > 0 ? (uint32_t)env_g : 8192);
+    hipLaunchKernelGGL(pair_groups_kernel, dim3(gblocks), dim3(PG_BLOCK), pg_shmem, st, P);
     STRL_HIP(hipGetLastError());
     hipLaunchKernelGGL(pair_long_kernel, dim3(64), dim3(PAIR_LONG_MAX), 0, st, P);      // (no spilled runs: 64 blocks read one counter)
     STRL_HIP(hipGetLastError());
