@@ -16,31 +16,25 @@
 //        its probe run for the smallest row whose qname BYTES equal its own -- the hash only narrows the compare.
 //   What depends on the order of Nim's tables (the fold per qname, the float32 sum in slot order, the pair list, the
 //   spanning fragments) is finished on the host from the rows (call_logic.cpp evidence_finish), a few dozen bytes a record.
+// What the kernel decides about ONE record against ONE bound -- the header test of step 1, step 2's keep test with its depth
+// slots, step 3's row -- is evidence_core.h, which compiles for the host too (tests/emu/evidence_emu.cpp); this file keeps what
+// belongs to a workgroup: the window walk, the ballots and ranks, the row reservation, the depth scan, the hash table.
 // Nothing here re-sums floats: cd[] comes from the host as frag_tables() makes it; the only floating-point operations on the
 // device are the IEEE subtraction 1.0f - cd[dist], the double product / quotient of the 70 % cut and the median's compare.
 #include <string.h>
 #include <algorithm>
 #include <vector>
+#pragma clang fp contract(off)
 #include "common.h"
 #include "nim_tables.h"
 #include "regions.h"
 #include "bam_rec.h"
-
-#pragma clang fp contract(off)
+#include "evidence_core.h"   // the per-record rule: EvBound, EvRec, ev_header_ok, ev_keep, ev_row (host and device)
 
 namespace strl {
 
 constexpr uint32_t EV_THREADS = 256, EV_WIN = 4096, EV_SLOTS = 8192, EV_DEPTH_CAP = 9192;
-constexpr uint16_t EVF_REVERSE = 0x10, EVF_SECONDARY = 0x100, EVF_DUP = 0x400, EVF_SUPPL = 0x800;
 
-struct EvBound {          // a bound as the kernel needs it, made on the host
-  int64_t left, right, wl;   // wl = left - window
-  int32_t tid, beg, end;     // the query: [max(0, left - window), right + window)
-  int32_t depth_n;           // right - left + 2 * window
-  int32_t k, slop;           // unit length, bound_slop (collect.nim:97-104)
-  uint32_t status;           // != 0: not for the device (1: the walk's verdict; 2: beyond the capacity rule)
-  uint64_t unit;             // its bytes, the first in the low byte (a register: a char array indexed by a loop counter would be spilled to LDS)
-};
 struct EvOut { int32_t median; uint32_t n_rows, row_base, status; };
 struct EvParams {
   const uint8_t *u; uint64_t u_readable;
@@ -48,85 +42,6 @@ struct EvParams {
   EvRow *rows; uint32_t row_cap; uint32_t *cursor; EvOut *eo;
   uint32_t min_mapq;
 };
-
-__device__ __forceinline__ uint32_t ev_ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint32_t ev_ld16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ bool ev_cons_query(int op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
-__device__ __forceinline__ bool ev_cons_ref(int op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
-
-struct EvRec {            // the core fields of the record whose block_size word sits at p (the walk has checked that it parses)
-  const uint8_t *p;
-  int32_t tid, pos, l_seq, mtid, isize;
-  uint32_t l_name, n_cig, flag, mapq;
-  __device__ void load(const uint8_t *at) {
-    p = at;
-    tid = (int32_t)ev_ld32(p + 4); pos = (int32_t)ev_ld32(p + 8);
-    l_name = p[12]; mapq = p[13];
-    n_cig = ev_ld16(p + 16); flag = ev_ld16(p + 18);
-    l_seq = (int32_t)ev_ld32(p + 20); mtid = (int32_t)ev_ld32(p + 24); isize = (int32_t)ev_ld32(p + 32);
-  }
-  __device__ uint32_t cig(uint32_t j) const { return ev_ld32(p + 36 + l_name + 4u * j); }
-  __device__ const uint8_t *qname() const { return p + 36; }
-  __device__ uint32_t qname_len() const { return l_name ? l_name - 1u : 0u; }
-  __device__ int base(int64_t j) const { return (p[36 + l_name + 4u * n_cig + (uint32_t)(j >> 1)] >> ((~j & 1) << 2)) & 0xf; }
-  __device__ int64_t stop() const { return bam_rec_end(p); }   // bam_endpos, with Rec::stop's rule for unmapped / zero-length
-};
-
-// spanning.nim:22-49
-__device__ float ev_expected_spanning_probability(const float *cd, int64_t start, int64_t stop, bool reverse, int64_t ev_start, int64_t ev_stop) {
-  const int64_t msb = 20;
-  int64_t dist;
-  if (start < ev_stop - msb) {
-    if (reverse) return 0.f;
-    dist = ev_start - start;
-  } else {
-    if (!reverse) return 0.f;
-    dist = stop - ev_stop;
-  }
-  if (dist < 0) return 0.f;
-  if (dist + (ev_stop - ev_start) < msb) return 0.f;
-  dist += msb + (ev_stop - ev_start);
-  if (dist < 0 || dist > 4095) return 0.f;
-  return 1.0f - cd[dist];
-}
-// collect.nim:50-72
-__device__ int64_t ev_find_read_position(const EvRec &R, int64_t position) {
-  int64_t r_off = R.pos, q_off = 0;
-  for (uint32_t j = 0; j < R.n_cig; ++j) {
-    if (r_off > position) return -1;
-    const uint32_t c = R.cig(j);
-    const int op = (int)(c & 0xf);
-    const int64_t len = c >> 4;
-    if (ev_cons_query(op)) q_off += len;
-    if (ev_cons_ref(op)) r_off += len;
-    if (r_off < position) continue;
-    const int64_t over = r_off - position;
-    if (over > q_off) return -1;
-    if (!ev_cons_query(op)) return -1;
-    return q_off - over;
-  }
-  return -1;
-}
-// collect.nim:75-93; *bad: the CIGAR names bases the record's SEQ does not hold (the host's reader has the word on that one)
-__device__ int ev_count_in_bounds(const EvRec &R, const EvBound &B, bool *bad) {
-  const int64_t dlen = R.l_seq;
-  int64_t rl = ev_find_read_position(R, B.left), rr = ev_find_read_position(R, B.right);
-  if (rl >= 0 && rr < 0) rr = dlen;
-  if (rl < 0 && rr < 0) return 0;
-  if (rl < 0) rl = 0;
-  const int64_t slen = rr - rl > 0 ? rr - rl : 0;
-  if (slen > 0 && rl + slen > dlen) { *bad = true; return 0; }
-  const int k = B.k;
-  const char *nt = "=ACMGRSVTWYHKDBN";
-  int result = 0;
-  for (int64_t p = rl; p + k <= rl + slen;) {
-    bool eq = true;
-    for (int j = 0; j < k && eq; ++j) eq = nt[R.base(p + j)] == (char)(B.unit >> (8 * j));
-    if (eq) { ++result; p += k; } else ++p;
-  }
-  if (result < (int)((double)slen * 0.7 / (double)k)) result = 0;
-  return result;
-}
 
 __global__ __launch_bounds__(EV_THREADS) void evidence_kernel(EvParams P) {
   __shared__ uint32_t off[EV_MAX_RECORDS];                     // byte offset of every record behind the region's start
@@ -170,12 +85,8 @@ __global__ __launch_bounds__(EV_THREADS) void evidence_kernel(EvParams P) {
         __builtin_amdgcn_wave_barrier();
         if (p + 36 > w1) { st = 2; break; }
       }
-      const uint8_t *h = U.win + (p - w0);
-      const uint32_t bs = ev_ld32(h);
-      if (bs < 32u || bs > (1u << 28) || p + 4 + bs > s1) { st = 2; break; }
-      const uint64_t l_name = h[12], n_cig = ev_ld16(h + 16);
-      const int32_t l_seq = (int32_t)ev_ld32(h + 20);
-      if (l_seq < 0 || 32ull + l_name + 4ull * n_cig + (uint64_t)(((int64_t)l_seq + 1) / 2) > bs) { st = 2; break; }   // append_record's check
+      uint32_t bs;
+      if (!ev_header_ok(U.win + (p - w0), s1 - p, &bs)) { st = 2; break; }
       if (n == EV_MAX_RECORDS) { st = 2; break; }
       if (lane == 0) off[n] = (uint32_t)(p - s0);
       ++n;
@@ -201,14 +112,9 @@ __global__ __launch_bounds__(EV_THREADS) void evidence_kernel(EvParams P) {
     if (i < n) {
       EvRec R;
       R.load(u + s0 + off[i]);
-      const int64_t start = R.pos, stop = R.stop();
-      kept = R.tid == B.tid && start < (int64_t)B.end && stop > (int64_t)B.beg && !(R.flag & (EVF_SECONDARY | EVF_SUPPL | EVF_DUP)) && R.mapq >= P.min_mapq;
+      int32_t a, b;
+      kept = ev_keep(R, R.stop(), B, P.min_mapq, &a, &b);
       if (kept) {
-        int64_t a = start - B.wl - 1, b = stop - B.wl - 1;
-        if (a < 0) a = 0;
-        if (a > D - 1) a = D - 1;                              // (cannot happen: start < end = wl + D; keeps the store inside the array whatever comes)
-        if (b > D - 1) b = D - 1;
-        if (b < 0) b = 0;
         atomicAdd(&U.depth[a], 1);
         atomicSub(&U.depth[b], 1);
       }
@@ -242,29 +148,7 @@ __global__ __launch_bounds__(EV_THREADS) void evidence_kernel(EvParams P) {
     const uint32_t k = rank0[w] + (uint32_t)__popcll(mask[w] & ((1ull << lane) - 1ull));
     EvRec R;
     R.load(u + s0 + off[i]);
-    const int64_t start = R.pos, stop = R.stop();
-    EvRow row;
-    row.ord = i; row.name_id = k;
-    row.hash = (uint32_t)nim::hash_bytes(R.qname(), (int)R.qname_len());
-    row.prob = ev_expected_spanning_probability(P.cd, start, stop, (R.flag & EVF_REVERSE) != 0, B.left, B.right);
-    row.start = R.pos; row.isize = R.isize; row.stop = stop;
-    row.flags = 0; row.type = 0; row.repeat_count = 0; row.cigar_ins = 0; row.cigar_del = 0; row.pad[0] = 0; row.pad[1] = 0;
-    if ((start > B.left ? start : B.left) <= (stop < B.right ? stop : B.right)) {   // collect.nim:97-119 (the record's tid is the bound's)
-      row.flags |= EV_OVERLAP;
-      row.type = STRL_OVERLAPPING_READ;
-      row.repeat_count = (uint8_t)ev_count_in_bounds(R, B, &bad);
-      if (start < B.left - B.slop && stop > B.right + B.slop) {
-        row.type = STRL_SPANNING_READ;
-        for (uint32_t j = 0; j < R.n_cig; ++j) {
-          const uint32_t c = R.cig(j);
-          if ((c & 0xf) == 1u) row.cigar_ins = (uint8_t)(row.cigar_ins + (uint8_t)(c >> 4));
-          if ((c & 0xf) == 2u) row.cigar_del = (uint8_t)(row.cigar_del + (uint8_t)(c >> 4));
-        }
-      }
-    }
-    const int64_t tl = R.isize < 0 ? -(int64_t)R.isize : (int64_t)R.isize;
-    if (R.tid == R.mtid && tl <= 5000) row.flags |= EV_PAIR;
-    rows[k] = row;
+    rows[k] = ev_row(R, R.stop(), B, P.cd, i, k, &bad);
   }
   if (bad) s_bad = 1;                                           // (every writer stores the same value; read behind the barriers below)
   // ---- 4. depths, their histogram, the median (utils.nim:148-158)
@@ -324,13 +208,6 @@ __global__ __launch_bounds__(EV_THREADS) void evidence_kernel(EvParams P) {
   if (t == 0) P.eo[r] = EvOut{s_median, total, s_base, 0u};
 }
 
-static int64_t ev_slop(const strl_bounds &b, int k) {   // bound_slop, collect.nim:97-104
-  const int64_t width = (int64_t)b.right - (int64_t)b.left;
-  int64_t slop = (int64_t)k - 1;
-  if (width < 5) slop += 5 - width;
-  return slop;
-}
-
 int evidence_run(RegionJob &J, const uint8_t *d_u, uint64_t u_readable, const RegionWalk *d_range, const RegionWalk *h_range, uint32_t n_regions,
                  const strl_bounds *bounds, int32_t window, const uint32_t frag[4096], uint8_t min_mapq, strl_support *out, uint64_t cap,
                  uint64_t *support_off, strl_span_summary *summary, uint8_t *status, double *kernel_ms, const uint32_t *h_count) {
@@ -340,20 +217,7 @@ int evidence_run(RegionJob &J, const uint8_t *d_u, uint64_t u_readable, const Re
   for (uint32_t r = 0; r < n_regions; ++r) {
     const strl_bounds &b = bounds[r];
     if (b.left > b.right) { set_error("bound with left > right"); return STRL_ERR_ARG; }
-    EvBound &E = eb[r];
-    memset(&E, 0, sizeof E);
-    E.left = b.left; E.right = b.right; E.wl = (int64_t)b.left - window;
-    const int64_t wr = (int64_t)b.right + window, span = wr - E.wl;
-    E.tid = b.tid;
-    E.beg = (int32_t)std::max<int64_t>(0, E.wl);
-    E.end = (int32_t)std::min<int64_t>(wr, INT32_MAX);
-    E.k = (int)strnlen(b.repeat, 6);
-    memcpy(&E.unit, b.repeat, 6);
-    E.slop = (int32_t)ev_slop(b, E.k);
-    E.status = status[r];
-    // the capacity rule: a depth array of 1 .. EV_MAX_SPAN entries in LDS (and a query that is one: window >= 0, a unit to count)
-    if (!E.status && (window < 0 || span < 1 || span > EV_MAX_SPAN || wr > INT32_MAX || E.k < 1)) E.status = 2;
-    E.depth_n = E.status ? 0 : (int32_t)span;
+    const EvBound &E = eb[r] = ev_bound_make(b, window, status[r]);   // (with the capacity rule: status 2 beyond it)
     // rows for every record the region can hold (a record is 37 bytes or more); more than EV_MAX_RECORDS pass the region on
     // (h_count: the caller knows the number of records in the range -- the sweep's i1 - i0 -- and the rows are reserved from it)
     if (!E.status) row_cap += std::min<uint64_t>(EV_MAX_RECORDS, h_count ? (uint64_t)h_count[r] : (h_range[r].stop - h_range[r].start) / 37 + 1);

@@ -3,6 +3,7 @@
 #pragma once
 #include <vector>
 #include "common.h"
+#include "evidence_core.h"
 
 namespace strl {
 
@@ -32,22 +33,7 @@ int regions_inflate_walk(RegionJob &J, const uint8_t *comp, uint64_t comp_bytes,
                          const uint32_t *crc32, uint32_t n_blocks, const strl_region_req *req, uint32_t n_regions, uint8_t *status);
 
 // ---- evidence around a bound (evidence.hip) ----
-constexpr uint32_t EV_MAX_RECORDS = 4096;   // records in a region's byte range the device path takes
-constexpr int64_t EV_MAX_SPAN = 9190;       // right - left + 2 * window it takes: 1000 (callclusters.nim:52-66) + 2 * 4095 (the fragment histogram's bins)
-constexpr uint8_t EV_OVERLAP = 1, EV_PAIR = 2;
-// What the device returns of a record that passes spanners()' filters (collect.nim:138-141), in record order.
-struct EvRow {
-  uint32_t ord;        // ordinal of the record in the region's bytes
-  uint32_t name_id;    // row (of this region) of the first kept record with the same qname bytes
-  uint32_t hash;       // Nim's murmur hash of the qname
-  float prob;          // expected_spanning_probability (spanning.nim:22-49): 1.0f - cd[dist], or 0
-  int32_t start, isize;
-  int64_t stop;        // bam_endpos
-  uint8_t flags;       // EV_OVERLAP: overlapping_read() holds, the four fields below are its Support; EV_PAIR: tid == mtid and |isize| <= 5000
-  uint8_t type, repeat_count, cigar_ins, cigar_del;
-  uint8_t pad[2];
-};
-static_assert(sizeof(EvRow) == 40, "EvRow layout");
+// (EV_MAX_RECORDS, EV_MAX_SPAN, EvRow: evidence_core.h, which the host emulation of the per-record rule reads too)
 
 // call_logic.cpp: the tables spanners() derives from the fragment histogram (made once per histogram and thread), and the
 // order-dependent steps of spanners() -- the fold per qname in record order, the float32 sum in Table slot order, the pair
