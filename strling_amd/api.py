@@ -288,6 +288,9 @@ def load(build_if_missing=True):
     L.strl_pair_rows.argtypes = [C.POINTER(CRecords)] + [C.c_void_p] * 5
     L.strl_ctx_cluster_times.argtypes = [C.c_void_p, C.POINTER(C.c_double * 3)]
     L.strl_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int]
+    L.strl_sort_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_int,
+                                  C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint64)]
     L.strl_outliers_row_medians.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int]
     L.strl_outliers_huber.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -486,8 +489,28 @@ class Context:
         """stable LSD radix sort of (uint64 key, uint32 value) pairs on the device (strl_sort_pairs) -> (keys, vals)"""
         k = np.ascontiguousarray(keys, np.uint64).copy()
         v = np.ascontiguousarray(vals, np.uint32).copy()
-        _check(self.L.strl_sort_pairs(self.h, _ptr(k), _ptr(v), k.size, n_max or k.size, bit_lo, bits))
+        _check(self.L.strl_sort_pairs(self.h, _ptr(k), _ptr(v), k.size, k.size if n_max is None else n_max, bit_lo, bits))
         return k, v
+
+    def sort_probe(self, keys, vals, alt_keys, alt_vals, d_n, n_max, stages, scratch_skew=0, scratch_delta=0, poison=0, layout_bits=None):
+        """radix_sort_pairs as the device pipelines call it (strl_sort_probe, test-only): four arrays of `cap` elements for the two
+        buffer pairs, *d_n = d_n whatever n_max <= cap is, stages = [(bit_lo, bits, tables_zeroed), ...] chained on one poisoned
+        scratch without a sync.  layout_bits = b: nothing is launched, only the table layout of a b-bit sort is reported.
+        -> (keys, vals, alt_keys, alt_vals after, dict(result_in_alt, rc[stage], tables_off, tables_bytes, guard_bad))"""
+        a = [np.ascontiguousarray(x, t).copy() for x, t in ((keys, np.uint64), (vals, np.uint32), (alt_keys, np.uint64), (alt_vals, np.uint32))]
+        cap = a[0].size
+        assert all(x.size == cap for x in a)
+        n_stages = 0 if layout_bits is not None else len(stages)
+        st = np.ascontiguousarray([(0, layout_bits, 0)] if layout_bits is not None else stages, np.int32).reshape(-1, 3)
+        assert st.shape[0] == max(n_stages, 1)
+        rc = np.zeros(st.shape[0], np.int32)
+        in_alt, off, tb, bad = C.c_int(0), C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.L.strl_sort_probe(self.h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), cap, int(d_n), int(n_max), st.ctypes.data, n_stages,
+                                      int(scratch_skew), int(scratch_delta), int(poison), C.byref(in_alt), rc.ctypes.data, C.byref(off), C.byref(tb),
+                                      C.byref(bad)))
+        return a[0], a[1], a[2], a[3], dict(result_in_alt=bool(in_alt.value), rc=[int(x) for x in rc[:n_stages]], tables_off=off.value,
+                                            tables_bytes=tb.value, guard_bad=bad.value)
+
 
     # ---- the outlier stage (strling-outliers.py; csrc/outliers.hip): host arrays in and out
 

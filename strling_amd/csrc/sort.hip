@@ -275,3 +275,91 @@ extern "C" int strl_sort_pairs(strl_ctx *c, uint64_t *keys, uint32_t *vals, uint
   STRL_HIP(hipStreamSynchronize(c->stream));
   return STRL_OK;
 }
+
+// The sort as the device pipelines call it (test-only and undeclared, like strl_pair_rules_device): a device count that is
+// independent of n_max, a scratch that is dirty, skewed and exactly sized, tables zeroed by the caller, stages chained
+// without a sync.
+//   keys, vals, alt_keys, alt_vals: host arrays of `cap` elements, uploaded whole to the two buffer pairs, downloaded whole.
+//   *d_n on the device = d_n; the launches are sized by n_max <= cap.
+//   stages[s] = {bit_lo, bits, tables_zeroed}: enqueued back to back on the context's stream; the buffers that hold a
+//   stage's result are the next stage's input, the others its alternates.  A stage with tables_zeroed != 0 first zeroes
+//   exactly the region radix_sort_tables reports, in one zero_words2 launch beside a counter region, as pair.hip and
+//   cluster.hip do.  n_stages == 0: nothing is launched, stages[0] only gives the `bits` of the reported layout.
+//   scratch = a 256-byte aligned address + scratch_skew (0..255), handed as radix_sort_scratch_bytes(n_max, widest stage)
+//   + scratch_delta bytes; the allocation (64 guard bytes behind the scratch included) is filled with `poison` first.
+//   -> *result_in_alt: the result lies in (alt_keys, alt_vals); rc_stage[s]: hipError_t of stage s (-1: not enqueued, an
+//   earlier stage failed to launch); *tables_off, *tables_bytes: radix_sort_tables' answer for stage 0, relative to scratch;
+//   *guard_bad: bytes in front of and behind the scratch that no longer hold `poison`.
+extern "C" int strl_sort_probe(strl_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t *alt_keys, uint32_t *alt_vals, uint64_t cap, uint32_t d_n,
+                               uint64_t n_max, const int32_t *stages, int n_stages, int scratch_skew, int64_t scratch_delta, int poison,
+                               int *result_in_alt, int *rc_stage, int64_t *tables_off, uint64_t *tables_bytes, uint64_t *guard_bad) {
+  using namespace strl;
+  constexpr size_t GUARD = 64;
+  if (!c || !stages || n_stages < 0 || !result_in_alt || !tables_off || !tables_bytes || !guard_bad || (n_stages && !rc_stage) ||
+      !keys || !vals || !alt_keys || !alt_vals) { set_error("null argument"); return STRL_ERR_ARG; }
+  if (!cap || n_max > cap ||cap > 0x7fffffffull || scratch_skew < 0 || scratch_skew > 255 || poison < 0 || poison > 255) { set_error("bad sort probe arguments"); return STRL_ERR_ARG; }
+  int wide = 0;
+  for (int s = 0; s < (n_stages ? n_stages : 1); ++s) {
+    const int lo = stages[3 * s], bits = stages[3 * s + 1];
+    if (lo < 0 || bits < 0 || lo + bits > 64) { set_error("bad sort arguments"); return STRL_ERR_ARG; }
+    wide = std::max(wide, bits);
+  }
+  const size_t need = radix_sort_scratch_bytes((uint32_t)n_max, wide);
+  if (scratch_delta < -(int64_t)need || scratch_delta > (1 << 20)) { set_error("bad scratch_delta"); return STRL_ERR_ARG; }
+  const size_t sb = (size_t)((int64_t)need + scratch_delta);
+  STRL_HIP(hipSetDevice(c->device));
+  DevBuf k0, k1, v0, v1, sc, dn, cnt;
+  const size_t sc_bytes = 256 + (size_t)scratch_skew + sb + GUARD;
+  int rc;
+  if ((rc = k0.reserve(cap * 8)) || (rc = k1.reserve(cap * 8)) || (rc = v0.reserve(cap * 4)) || (rc = v1.reserve(cap * 4)) ||
+      (rc = sc.reserve(sc_bytes)) || (rc = dn.reserve(256)) || (rc = cnt.reserve(256)))
+    return rc;
+  uint8_t *base = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(sc.p) + 255) & ~(uintptr_t)255);
+  uint8_t *scratch = base + scratch_skew;
+  const size_t lead = (size_t)(scratch - sc.as<uint8_t>());   // poisoned bytes in front of the scratch
+  void *tp = nullptr;
+  size_t tb = 0;
+  radix_sort_tables(scratch, (uint32_t)n_max, stages[1], &tp, &tb);
+  *tables_off = tp ? (int64_t)(static_cast<uint8_t *>(tp) - scratch) : -1;
+  *tables_bytes = tb;
+  *result_in_alt = 0;
+  *guard_bad = 0;
+  if (!n_stages) return STRL_OK;
+  hipStream_t st = c->stream;
+  STRL_HIP(hipMemsetAsync(sc.p, poison, sc_bytes, st));
+  STRL_HIP(hipMemcpyAsync(k0.p, keys, cap * 8, hipMemcpyHostToDevice, st));
+  STRL_HIP(hipMemcpyAsync(v0.p, vals, cap * 4, hipMemcpyHostToDevice, st));
+  STRL_HIP(hipMemcpyAsync(k1.p, alt_keys, cap * 8, hipMemcpyHostToDevice, st));
+  STRL_HIP(hipMemcpyAsync(v1.p, alt_vals, cap * 4, hipMemcpyHostToDevice, st));
+  STRL_HIP(hipMemcpyAsync(dn.p, &d_n, 4, hipMemcpyHostToDevice, st));
+  uint64_t *kin = k0.as<uint64_t>(), *kalt = k1.as<uint64_t>();
+  uint32_t *vin = v0.as<uint32_t>(), *valt = v1.as<uint32_t>();
+  bool dead = false;
+  for (int s = 0; s < n_stages; ++s) {
+    if (dead) { rc_stage[s] = -1; continue; }
+    const int lo = stages[3 * s], bits = stages[3 * s + 1];
+    const bool zeroed = stages[3 * s + 2] != 0;
+    if (zeroed) {
+      radix_sort_tables(scratch, (uint32_t)n_max, bits, &tp, &tb);
+      const hipError_t e = sb >= radix_sort_scratch_bytes((uint32_t)n_max, bits) ? zero_words2(cnt.p, 64 * 4, tp, tb, st) : hipSuccess;
+      if (e != hipSuccess) { rc_stage[s] = (int)e; dead = true; continue; }
+    }
+    uint64_t *ok = nullptr;
+    uint32_t *ov = nullptr;
+    const int e = radix_sort_pairs(st, dn.as<uint32_t>(), (uint32_t)n_max, kin, vin, kalt, valt, scratch, sb, lo, bits, &ok, &ov, zeroed);
+    rc_stage[s] = e;
+    if (e) { dead = e != (int)hipErrorInvalidValue; continue; }   // the refused scratch launches nothing: the chain goes on
+    if (ok != kin) { kalt = kin; valt = vin; kin = ok; vin = ov; }
+  }
+  *result_in_alt = kin == k1.as<uint64_t>();
+  std::vector<uint8_t> g(lead + GUARD);
+  STRL_HIP(hipMemcpyAsync(keys, k0.p, cap * 8, hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipMemcpyAsync(vals, v0.p, cap * 4, hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipMemcpyAsync(alt_keys, k1.p, cap * 8, hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipMemcpyAsync(alt_vals, v1.p, cap * 4, hipMemcpyDeviceToHost, st));
+  if (lead) STRL_HIP(hipMemcpyAsync(g.data(), sc.p, lead, hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipMemcpyAsync(g.data() + lead, scratch + sb, GUARD, hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipStreamSynchronize(st));
+  for (uint8_t b : g) *guard_bad += b != (uint8_t)poison;
+  return STRL_OK;
+}
