@@ -211,14 +211,26 @@ __global__ __launch_bounds__(256) void pair_probe_kernel(PairParams P) {
 }
 
 // ---- the replay of Cache.add for one qname group ------------------------------------------------------------------
-struct DTread {   // tread (cluster.nim:23-32) with the unit as (length, kmer code)
+// tread (cluster.nim:23-32) with the unit as (length, kmer code).  The small fields share three words: a head holds three
+// treads (stored, mate, self), and as bit-fields they leave pair_groups_kernel at 64 registers (one field per register: 77).
+// mrc, cls and half follow from (count, k, align_length, code) alone: prepare_tread works them out once per record, the
+// replay never does.  No rule changes any of the four except `code`, and a tread whose code was changed is emitted, not
+// judged again.
+struct DTread {
   int32_t tid;
   uint32_t position;
-  uint32_t k, code;
-  uint16_t flag;
-  uint8_t split, mapq, count, align_length;
+  uint32_t code : 12;
+  uint32_t mrc : 12;     // min_rev_complement(code, k)
+  uint32_t k : 3;
+  uint32_t cls : 3;      // CLS_*
+  uint32_t flag : 16, split : 8, mapq : 8;
+  uint32_t count : 8, align_length : 8;
+  uint32_t half : 8;     // adjust_by's share of the read that lies beyond its start
   uint32_t qid;
 };
+constexpr uint8_t CLS_HI = 1;         // p_repeat > proportion_repeat
+constexpr uint8_t CLS_LO = 2;         // p_repeat < 0.2
+constexpr uint8_t CLS_CANON_MRC = 4;  // canonical_repeat is the reverse complement's rotation, not the unit itself
 
 __device__ __forceinline__ double p_repeat(const DTread &t) {   // extract.nim:56-58 (uint8 product)
   const uint8_t prod = (uint8_t)(t.count * (uint8_t)t.k);
@@ -238,9 +250,9 @@ __device__ inline uint32_t min_rev_complement(uint32_t code, uint32_t k) {
   }
   return best;
 }
-// canonical_repeat, utils.nim:291-316: the rev-comp rotation minimum if it is ASCII-smaller (A < C < G < T)
-__device__ inline uint32_t canonical_repeat(uint32_t code, uint32_t k) {
-  const uint32_t r = min_rev_complement(code, k);
+// canonical_repeat, utils.nim:291-316: the rev-comp rotation minimum r = min_rev_complement(code, k) if it is ASCII-smaller
+// (A < C < G < T)
+__device__ inline uint32_t canonical_repeat(uint32_t code, uint32_t k, uint32_t r) {
   for (uint32_t j = 0; j < k; ++j) {
     const uint32_t a = (r >> (2 * (k - 1 - j))) & 3u, b = (code >> (2 * (k - 1 - j))) & 3u;
     // code -> ASCII rank: C(0) -> 1, A(1) -> 0, T(2) -> 3, G(3) -> 2
@@ -249,15 +261,26 @@ __device__ inline uint32_t canonical_repeat(uint32_t code, uint32_t k) {
   }
   return code;
 }
+// The per-record part of the rules: the two proportion classes with p_repeat's own uint8 product and float64 quotient, the
+// half of adjust_by, both forms of the unit.  The replay's gather runs it for every item on the item's own lane; the rules
+// below read its results.
+__device__ inline void prepare_tread(DTread &t, double p) {
+  const double pr = p_repeat(t);
+  const uint32_t r = min_rev_complement(t.code, t.k);
+  t.mrc = (uint16_t)r;
+  t.half = (uint8_t)(uint32_t)((double)t.align_length / 2.0 + 0.5);
+  t.cls = (uint8_t)((pr > p ? CLS_HI : 0) | (pr < 0.2 ? CLS_LO : 0) | (canonical_repeat(t.code, t.k, r) != t.code ? CLS_CANON_MRC : 0));
+}
+__device__ __forceinline__ uint32_t canonical_code(const DTread &t) { return (t.cls & CLS_CANON_MRC) ? (uint32_t)t.mrc : t.code; }
 __device__ __forceinline__ bool should_reverse(uint16_t f) {   // extract.nim:134-139
   const bool r = !(f & F_MREVERSE);
   return (f & F_REVERSE) ? !r : r;
 }
-// adjust_by, extract.nim:141-179
+// adjust_by, extract.nim:141-179, on prepared treads
 __device__ inline bool adjust_by(DTread &A, const DTread &B, const PairParams &P, uint32_t B_position) {
   if (A.count == 0) return false;
-  const uint32_t half = (uint32_t)((double)A.align_length / 2.0 + 0.5);
-  if (B.mapq > P.min_mapq && ((p_repeat(A) > P.p && p_repeat(B) < 0.2) || (!(A.flag & F_PROPER) && A.mapq < P.min_mapq))) {
+  const uint32_t half = A.half;
+  if (B.mapq > P.min_mapq && (((A.cls & CLS_HI) && (B.cls & CLS_LO)) || (!(A.flag & F_PROPER) && A.mapq < P.min_mapq))) {
     if (B.flag & F_REVERSE) {
       A.position = B_position - (uint32_t)P.frag_median + B.align_length + half;
       if (B.split == STRL_SOFT_NONE_LEFT) A.position = B_position;
@@ -268,7 +291,7 @@ __device__ inline bool adjust_by(DTread &A, const DTread &B, const PairParams &P
     A.split = STRL_SOFT_NONE;
     A.tid = B.tid;
     A.mapq = A.mapq > B.mapq ? A.mapq : B.mapq;
-    if (should_reverse(A.flag)) A.code = min_rev_complement(A.code, A.k);
+    if (should_reverse(A.flag)) A.code = A.mrc;
   } else if (A.mapq >= P.min_mapq || (A.flag & F_PROPER)) {
     A.position += half;
     A.mapq = A.mapq > B.mapq ? A.mapq : B.mapq;
@@ -276,31 +299,58 @@ __device__ inline bool adjust_by(DTread &A, const DTread &B, const PairParams &P
   return true;
 }
 __device__ inline bool unplaced_pair(const DTread &A, const DTread &B, const PairParams &P) {   // extract.nim:182-190
-  if (p_repeat(A) > P.p && p_repeat(B) > P.p) return true;
-  if (p_repeat(A) > P.p && B.mapq < P.min_mapq) return true;
-  if (p_repeat(B) > P.p && A.mapq < P.min_mapq) return true;
-  return false;
+  const bool a = A.cls & CLS_HI, b = B.cls & CLS_HI;
+  return (a && b) || (a && B.mapq < P.min_mapq) || (b && A.mapq < P.min_mapq);
 }
 
-// One sorted join item with everything the replay needs, gathered by the item's own lane (coalesced over the block) and
-// kept in LDS: the head lane of a run then works out of LDS instead of chasing a dozen arrays per record.
+// One sorted join item with everything the replay needs, gathered AND prepared by the item's own lane (coalesced over the
+// block) and kept in LDS: the head lane of a run then works out of LDS instead of chasing a dozen arrays per record, and
+// finds there, worked out once by a lane of its own, whatever depends on the one record alone (prepare_tread, the unpacked
+// scorer words).  The heads only read it.
 struct PItem {   // 48 bytes
   uint64_t key;      // mixed qname hash
   uint32_t val;      // read index, or 0x80000000 | soft record index
-  int32_t tid, pos, mtid, mpos, end;      // soft record: tid = read_side, pos = res_first, mtid = res_after
-  uint32_t whole;
-  uint16_t flag, clip_l, clip_r, l_seq;
+  int32_t tid, pos, mtid, mpos, end;      // soft record: tid = read_side, mpos / end = SW_* words of res_first / res_after
+  uint32_t prep;     // read: RW_* word
+  uint16_t flag, clip_l, clip_r;
   uint8_t mapq, cig;
-  uint16_t pad;
+  uint8_t count, al, half, split;         // read: the tread's repeat_count, align_length, split and adjust_by's half
 };
 static_assert(sizeof(PItem) == 48, "PItem layout");
+// RW: code | mrc << 12 | k << 24 | cls << 27 | (count >= 256) << 30
+constexpr uint32_t RW_GE256 = 1u << 30;
+// SW: code | k << 12 | (uint8) count << 16 | (count != 0) << 24 | (count >= 256) << 25
+constexpr uint32_t SW_NONZERO = 1u << 24, SW_GE256 = 1u << 25;
 
 constexpr int PG_BLOCK = 512;                // items per block
 constexpr int PG_HALO = 16;                  // a run that starts in the block may reach this far into the next one
-constexpr int PG_EMIT = 256;                 // treads one block may emit (LDS staging; 35 KB per block in all: four blocks per CU)
+constexpr int PG_EMIT = 256;                 // treads one block may emit (LDS staging; 33 KB per block in all: four blocks per CU)
+
+// A tread as the replay emits it: the unit still a code.  The lanes that copy the stage out build the strl_tread.
+struct STread {   // 24 bytes
+  int32_t tid;
+  uint32_t position, qid;
+  uint32_t unit;     // code | k << 12
+  uint16_t flag;
+  uint8_t split, mapq, count, align_length;
+  uint16_t pad;
+};
+static_assert(sizeof(STread) == 24, "STread layout");
+// the 32 bytes of the strl_tread, unit spelled out in "CATG" order, padding zero
+__device__ inline void format_tread(const STread &s, uint4 &lo, uint4 &hi) {
+  const uint32_t k = s.unit >> 12, code = s.unit & 0xfffu;
+  uint64_t rep = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 6; ++j)
+    if (j < k) rep |= (uint64_t)((0x47544143u >> (8u * ((code >> (2 * (k - 1 - j))) & 3u))) & 0xffu) << (8 * j);
+  lo = make_uint4((uint32_t)s.tid, s.position, (uint32_t)rep, (uint32_t)(rep >> 32) | ((uint32_t)s.flag << 16));
+  hi = make_uint4((uint32_t)s.split | ((uint32_t)s.mapq << 8) | ((uint32_t)s.count << 16) | ((uint32_t)s.align_length << 24), 0u, s.qid, 0u);
+}
+static_assert(sizeof(strl_tread) == 32 && offsetof(strl_tread, repeat) == 8 && offsetof(strl_tread, flag) == 14 && offsetof(strl_tread, split) == 16 &&
+              offsetof(strl_tread, align_length) == 19 && offsetof(strl_tread, qname_id) == 24, "format_tread writes this layout");
 
 struct EmitStage {   // block-wide staging of the emitted treads in LDS
-  strl_tread *t;
+  STread *t;
   uint64_t *key;
   uint32_t *count;
   const PairParams *P;
@@ -308,23 +358,43 @@ struct EmitStage {   // block-wide staging of the emitted treads in LDS
 __device__ inline void emit(const EmitStage &E, const DTread &d, uint64_t vidx, uint32_t &seq, uint32_t &err) {
   const uint32_t slot = atomicAdd(E.count, 1u);
   const uint32_t k = seq++;
-  strl_tread t;
+  STread t;
   t.tid = d.tid;
   t.position = d.position;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) t.repeat[j] = (uint32_t)j < d.k ? "CATG"[(d.code >> (2 * (d.k - 1 - j))) & 3u] : (char)0;
+  t.qid = d.qid;
+  t.unit = d.code | (d.k << 12);
   t.flag = d.flag;
   t.split = d.split;
-  t.mapping_quality = d.mapq;
-  t.repeat_count = d.count;
+  t.mapq = d.mapq;
+  t.count = d.count;
   t.align_length = d.align_length;
-  t.qname_id = (int64_t)d.qid;
+  t.pad = 0;
   const uint64_t key = (vidx << 2) | (uint64_t)(k & 3u);
   if (slot < (uint32_t)PG_EMIT) { E.t[slot] = t; E.key[slot] = key; return; }
   // the block's staging area is full (nearly every group of this block emits): straight to the output, one atomic each
   const uint32_t g = atomicAdd(&E.P->pc[PC_EMIT], 1u);
-  if (g < E.P->emit_cap) { E.P->emit[g] = t; E.P->emit_key[g] = key; E.P->emit_val[g] = g; }
+  if (g < E.P->emit_cap) {
+    uint4 lo, hi;
+    format_tread(t, lo, hi);
+    uint4 *dst = reinterpret_cast<uint4 *>(E.P->emit + g);
+    dst[0] = lo; dst[1] = hi;
+    E.P->emit_key[g] = key; E.P->emit_val[g] = g;
+  }
   else err |= PAIR_ERR_EMIT;
+}
+// all lanes of a block: the staged treads [0, ne) to the output from `base` on
+__device__ inline void copy_out(const PairParams &P, const STread *st_t, const uint64_t *st_k, uint32_t ne, uint32_t base) {
+  for (uint32_t e = threadIdx.x; e < ne; e += blockDim.x) {
+    const uint32_t d = base + e;
+    if (d < P.emit_cap) {
+      uint4 lo, hi;
+      format_tread(st_t[e], lo, hi);
+      uint4 *dst = reinterpret_cast<uint4 *>(P.emit + d);
+      dst[0] = lo; dst[1] = hi;
+      P.emit_key[d] = st_k[e];
+      P.emit_val[d] = d;
+    } else atomicOr(&P.pc[PC_ERR], PAIR_ERR_EMIT);
+  }
 }
 
 struct GroupCtx {
@@ -337,28 +407,67 @@ struct GroupCtx {
   __device__ const PItem &item(int j) const { return ident ? it[base + j] : it[base + (int)((perm >> (4 * j)) & 15u)]; }
 };
 
-// to_tread, extract.nim:63-87, from the packed scorer word and the SoA metadata
-__device__ inline DTread to_tread(const PItem &x, uint32_t &err) {
-  const uint32_t w = x.whole;
-  DTread t;
+__device__ __forceinline__ uint32_t soft_word(uint32_t w) {
+  const uint32_t cnt = STRL_RES_COUNT(w);
+  return STRL_RES_CODE(w) | (STRL_RES_K(w) << 12) | ((cnt & 0xffu) << 16) | (cnt ? SW_NONZERO : 0u) | (cnt >= 256 ? SW_GE256 : 0u);
+}
+// Sorted item i with its metadata, on the item's own lane.  A read gets the whole of to_tread (extract.nim:63-87, from the
+// packed scorer word and the SoA metadata) and prepare_tread; the doAssert of :72 is only noted (RW_GE256): it belongs to the
+// record the reference reaches, and which that is the replay decides.
+__device__ inline PItem gather_item(const PairParams &P, uint32_t i) {
+  PItem x{};
+  x.key = P.item_key[i];
+  x.val = P.item_val[i];
+  if (x.val & 0x80000000u) {
+    const strl_soft_rec s = P.soft[x.val & 0x7fffffffu];
+    x.tid = (int32_t)s.read_side; x.mpos = (int32_t)soft_word(s.res_first); x.end = (int32_t)soft_word(s.res_after);
+    return x;
+  }
+  const uint32_t r = x.val;
+  const uint4 *rp = reinterpret_cast<const uint4 *>(P.rec + r);
+  union { uint4 q[2]; strl_pair_rec o; } u;
+  u.q[0] = rp[0];
+  u.q[1] = rp[1];
+  const uint32_t w = P.whole[r];
+  x.tid = u.o.tid; x.pos = u.o.pos; x.mtid = u.o.mtid; x.mpos = u.o.mpos; x.end = u.o.end;
+  x.flag = u.o.flag; x.clip_l = u.o.clip_l; x.clip_r = u.o.clip_r; x.mapq = u.o.mapq; x.cig = u.o.cig;
+  DTread t{};
   t.k = STRL_RES_K(w);
   t.code = STRL_RES_CODE(w);
   const uint32_t cnt = STRL_RES_COUNT(w);
-  if (cnt >= 256) err |= PAIR_ERR_ASSERT;   // doAssert extract.nim:72
   const uint32_t cg = x.cig;
   // extract.nim:33 / :38: the M length of a skipped read (clip_l carries it for single-M cigars), else len(read)
-  const uint32_t al = (w & STRL_RES_SKIPPED) ? (uint32_t)x.clip_l : (uint32_t)x.l_seq;
+  const uint32_t al = (w & STRL_RES_SKIPPED) ? (uint32_t)x.clip_l : (uint32_t)u.o.l_seq;
+  t.count = (uint8_t)cnt;
+  t.align_length = (uint8_t)al;
+  prepare_tread(t, P.p);
+  x.split = STRL_SOFT_NONE;
+  const bool multi = !(cg & (STRL_CIG_ONE_OP | STRL_CIG_NONE));
+  if (multi && (cg & STRL_CIG_FIRST_S) && x.clip_l > 16) x.split = STRL_SOFT_NONE_LEFT;
+  if (multi && (cg & STRL_CIG_LAST_S) && x.clip_r > 16) x.split = STRL_SOFT_NONE_RIGHT;
+  x.count = t.count; x.al = t.align_length; x.half = t.half;
+  x.prep = t.code | ((uint32_t)t.mrc << 12) | (t.k << 24) | ((uint32_t)t.cls << 27) | (cnt >= 256 ? RW_GE256 : 0u);
+  return x;
+}
+
+// the tread of a read item, as its lane prepared it; this is where the reference's to_tread asserts
+__device__ inline DTread to_tread(const PItem &x, uint32_t &err) {
+  const uint32_t w = x.prep;
+  if (w & RW_GE256) err |= PAIR_ERR_ASSERT;   // doAssert extract.nim:72
+  DTread t;
+  t.code = w & 0xfffu;
+  t.mrc = (uint16_t)((w >> 12) & 0xfffu);
+  t.k = (w >> 24) & 7u;
+  t.cls = (uint8_t)((w >> 27) & 7u);
   t.tid = x.tid;
   t.position = (uint32_t)(x.pos > 0 ? x.pos : 0);
   t.flag = x.flag;
-  t.count = (uint8_t)cnt;
-  t.align_length = (uint8_t)al;
-  t.split = STRL_SOFT_NONE;
+  t.count = x.count;
+  t.align_length = x.al;
+  t.half = x.half;
+  t.split = x.split;
   t.mapq = x.mapq;
   t.qid = x.val;
-  const bool multi = !(cg & (STRL_CIG_ONE_OP | STRL_CIG_NONE));
-  if (multi && (cg & STRL_CIG_FIRST_S) && x.clip_l > 16) t.split = STRL_SOFT_NONE_LEFT;
-  if (multi && (cg & STRL_CIG_LAST_S) && x.clip_r > 16) t.split = STRL_SOFT_NONE_RIGHT;
   return t;
 }
 
@@ -380,24 +489,23 @@ __device__ inline void add_soft(const GroupCtx &G, const PItem &x, bool first_se
     for (int j = G.i0; j < G.i1; ++j) {
       const PItem &s = G.item(j);
       if (!(s.val & 0x80000000u)) continue;
-      if ((uint32_t)s.tid == want) { w = first_seen ? (uint32_t)s.pos : (uint32_t)s.mtid; break; }
+      if ((uint32_t)s.tid == want) { w = first_seen ? (uint32_t)s.mpos : (uint32_t)s.end; break; }
     }
-    const uint32_t cnt = STRL_RES_COUNT(w);
-    if (cnt == 0) continue;
-    if (cnt >= 256) *G.err |= PAIR_ERR_ASSERT;
-    DTread t;
-    t.k = STRL_RES_K(w);
-    t.code = STRL_RES_CODE(w);
+    if (!(w & SW_NONZERO)) continue;
+    if (w & SW_GE256) *G.err |= PAIR_ERR_ASSERT;
+    DTread t{};
+    t.k = (w >> 12) & 7u;
+    t.code = w & 0xfffu;
     t.tid = x.tid;
     const int32_t p = side == 0 ? x.pos : x.end;
     t.position = (uint32_t)(p > 0 ? p : 0);
     t.flag = x.flag;
-    t.count = (uint8_t)cnt;
+    t.count = (uint8_t)(w >> 16);
     t.align_length = (uint8_t)clen;
     t.split = side == 0 ? STRL_SOFT_LEFT : STRL_SOFT_RIGHT;
     t.mapq = x.mapq;
     t.qid = x.val;
-    if (p_repeat(t) < 0.9) continue;
+    if (p_repeat(t) < 0.9) continue;   // the one quotient left to the heads: the clip's length is the read's, the count the record's
     emit(E, t, vidx, seq, *G.err);
   }
 }
@@ -417,10 +525,10 @@ __device__ inline void cache_add(const GroupCtx &G, const PItem &x, uint64_t vid
     if (mate.count == 0 && self.count == 0) return;
     if (unplaced_pair(self, mate, P)) {
       if (self.k == 0 || mate.k == 0) return;
-      self.code = canonical_repeat(self.code, self.k);
+      self.code = canonical_code(self);
       self.position = 0;
       self.tid = -1;
-      mate.code = canonical_repeat(mate.code, mate.k);
+      mate.code = canonical_code(mate);
       mate.position = 0;
       mate.tid = -1;
       emit(E, self, vidx, seq, *G.err);
@@ -470,18 +578,20 @@ template <class Ctx> __device__ inline void replay_run(Ctx &G, int m, const Emit
 }
 
 
-// A block takes 1024 consecutive sorted items.  Phase 1: every lane gathers the metadata of ITS item into LDS (all
-// gathers of the block in flight together).  Phase 2: the lane of the first item of a run (equal low 32 hash bits)
-// replays Cache.add for the run out of LDS; emitted treads are staged in LDS.  Phase 3: one atomic reserves the block's
-// output space, all lanes copy the staging area out.
+// A block takes 512 consecutive sorted items.  Phase 1: every lane gathers the metadata of ITS item (all gathers of the
+// block in flight together), works out what depends on that one record alone and leaves the prepared item in LDS
+// (gather_item; the halo's 16 slots included, and afresh for every tile a block takes).  Phase 2: the lane of the first item
+// of a run (equal low 32 hash bits) replays Cache.add for the run out of LDS -- the state machine only; emitted treads are
+// staged in LDS as codes.  Phase 3: one atomic reserves the block's output space, all lanes spell the staged treads out.
 // The launch waits on its gathers and on the serial replay (VALU 0.41 of the issue slots), so it runs as fast as the CU has
-// blocks to switch between.  Six waves per SIMD = three blocks per CU (80 registers; the LDS would take four); left to itself
-// the compiler takes 99 registers = two blocks.  At -O3 the bound costs 36 bytes of scratch per lane; optimised for size
-// (minsize: the replay's loops stay rolled) it is 77 registers and none.  162 -> 126 us (profiles/pair_replay).
-__global__ __launch_bounds__(PG_BLOCK, 6) __attribute__((minsize)) void pair_groups_kernel(PairParams P) {
+// blocks to switch between: two blocks per CU 162 us, three 127 us (profiles/pair_replay).  With the per-record work done in
+// phase 1 and the treads' small fields packed, the heads' routine fits 64 registers without scratch: eight waves per SIMD =
+// the four blocks per CU the LDS (33 KB per block) was sized for.  127 -> 109 us at three blocks, 100 us at four
+// (profiles/pair_prep).  Optimised for size the bound costs 16 bytes of scratch per lane, so the kernel is built at -O3.
+__global__ __launch_bounds__(PG_BLOCK, 8) void pair_groups_kernel(PairParams P) {
   extern __shared__ __attribute__((aligned(16))) uint8_t pg_lds[];
   PItem *items = reinterpret_cast<PItem *>(pg_lds);
-  strl_tread *st_t = reinterpret_cast<strl_tread *>(pg_lds + sizeof(PItem) * (PG_BLOCK + PG_HALO));
+  STread *st_t = reinterpret_cast<STread *>(pg_lds + sizeof(PItem) * (PG_BLOCK + PG_HALO));
   uint64_t *st_k = reinterpret_cast<uint64_t *>(st_t + PG_EMIT);
   uint32_t *sh = reinterpret_cast<uint32_t *>(st_k + PG_EMIT);   // [0] emitted count, [1] output base
   uint32_t n_items = P.pc[PC_ITEMS];
@@ -489,28 +599,12 @@ __global__ __launch_bounds__(PG_BLOCK, 6) __attribute__((minsize)) void pair_gro
   const EmitStage E{st_t, st_k, sh, &P};
   for (uint32_t b0 = blockIdx.x * (uint32_t)PG_BLOCK; b0 < n_items; b0 += gridDim.x * (uint32_t)PG_BLOCK) {
     if (threadIdx.x == 0) sh[0] = 0;
-    // ---- phase 1: gather ----
+    // ---- phase 1: gather and prepare ----
     for (uint32_t l = threadIdx.x; l < (uint32_t)(PG_BLOCK + PG_HALO); l += PG_BLOCK) {
       const uint32_t i = b0 + l;
       PItem x{};
       x.key = ~0ull;
-      if (i < n_items) {
-        x.key = P.item_key[i];
-        x.val = P.item_val[i];
-        if (x.val & 0x80000000u) {
-          const strl_soft_rec s = P.soft[x.val & 0x7fffffffu];
-          x.tid = (int32_t)s.read_side; x.pos = (int32_t)s.res_first; x.mtid = (int32_t)s.res_after;
-        } else {
-          const uint32_t r = x.val;
-          const uint4 *rp = reinterpret_cast<const uint4 *>(P.rec + r);
-          union { uint4 q[2]; strl_pair_rec o; } u;
-          u.q[0] = rp[0];
-          u.q[1] = rp[1];
-          x.tid = u.o.tid; x.pos = u.o.pos; x.mtid = u.o.mtid; x.mpos = u.o.mpos; x.end = u.o.end;
-          x.whole = P.whole[r]; x.flag = u.o.flag; x.clip_l = u.o.clip_l; x.clip_r = u.o.clip_r; x.l_seq = u.o.l_seq;
-          x.mapq = u.o.mapq; x.cig = u.o.cig;
-        }
-      }
+      if (i < n_items) x = gather_item(P, i);
       items[l] = x;
     }
     __syncthreads();
@@ -558,17 +652,7 @@ __global__ __launch_bounds__(PG_BLOCK, 6) __attribute__((minsize)) void pair_gro
     if (ne > (uint32_t)PG_EMIT) ne = PG_EMIT;
     if (threadIdx.x == 0) sh[1] = ne ? atomicAdd(&P.pc[PC_EMIT], ne) : 0u;
     __syncthreads();
-    const uint32_t base = sh[1];
-    for (uint32_t e = threadIdx.x; e < ne; e += PG_BLOCK) {
-      const uint32_t d = base + e;
-      if (d < P.emit_cap) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(st_t + e);
-        uint4 *dst = reinterpret_cast<uint4 *>(P.emit + d);
-        dst[0] = src[0]; dst[1] = src[1];
-        P.emit_key[d] = st_k[e];
-        P.emit_val[d] = d;
-      } else atomicOr(&P.pc[PC_ERR], PAIR_ERR_EMIT);
-    }
+    copy_out(P, st_t, st_k, ne, sh[1]);
     __syncthreads();
   }
 }
@@ -579,7 +663,7 @@ __global__ __launch_bounds__(PG_BLOCK, 6) __attribute__((minsize)) void pair_gro
 // Runs beyond PAIR_LONG_MAX items set PAIR_ERR_RUN (the caller falls back to the host's string-keyed Cache).
 __global__ __launch_bounds__(PAIR_LONG_MAX) void pair_long_kernel(PairParams P) {
   __shared__ PItem raw[PAIR_LONG_MAX], srt[PAIR_LONG_MAX];
-  __shared__ strl_tread st_t[PG_EMIT];
+  __shared__ STread st_t[PG_EMIT];
   __shared__ uint64_t st_k[PG_EMIT];
   __shared__ uint32_t sh[4];
   uint32_t n_items = P.pc[PC_ITEMS];
@@ -601,21 +685,7 @@ __global__ __launch_bounds__(PAIR_LONG_MAX) void pair_long_kernel(PairParams P) 
     const bool beyond = m == (uint32_t)PAIR_LONG_MAX && i0 + PAIR_LONG_MAX < n_items && (uint32_t)P.item_key[i0 + PAIR_LONG_MAX] == lo;
     uint32_t err = 0;
     if (beyond) { if (threadIdx.x == 0) atomicOr(&P.pc[PC_ERR], PAIR_ERR_RUN); __syncthreads(); continue; }
-    if (threadIdx.x < m) {
-      PItem x{};
-      x.key = P.item_key[i];
-      x.val = P.item_val[i];
-      if (x.val & 0x80000000u) {
-        const strl_soft_rec s = P.soft[x.val & 0x7fffffffu];
-        x.tid = (int32_t)s.read_side; x.pos = (int32_t)s.res_first; x.mtid = (int32_t)s.res_after;
-      } else {
-        const strl_pair_rec o = P.rec[x.val];
-        x.tid = o.tid; x.pos = o.pos; x.mtid = o.mtid; x.mpos = o.mpos; x.end = o.end;
-        x.whole = P.whole[x.val]; x.flag = o.flag; x.clip_l = o.clip_l; x.clip_r = o.clip_r; x.l_seq = o.l_seq;
-        x.mapq = o.mapq; x.cig = o.cig;
-      }
-      raw[threadIdx.x] = x;
-    }
+    if (threadIdx.x < m) raw[threadIdx.x] = gather_item(P, i);
     __syncthreads();
     if (threadIdx.x < m) {      // rank sort by (hash, value): (key, val) pairs are distinct
       const PItem x = raw[threadIdx.x];
@@ -637,12 +707,7 @@ __global__ __launch_bounds__(PAIR_LONG_MAX) void pair_long_kernel(PairParams P) 
     if (ne > (uint32_t)PG_EMIT) ne = PG_EMIT;
     if (threadIdx.x == 0) sh[1] = ne ? atomicAdd(&P.pc[PC_EMIT], ne) : 0u;
     __syncthreads();
-    const uint32_t base = sh[1];
-    for (uint32_t k = threadIdx.x; k < ne; k += blockDim.x) {
-      const uint32_t d = base + k;
-      if (d < P.emit_cap) { P.emit[d] = st_t[k]; P.emit_key[d] = st_k[k]; P.emit_val[d] = d; }
-      else atomicOr(&P.pc[PC_ERR], PAIR_ERR_EMIT);
-    }
+    copy_out(P, st_t, st_k, ne, sh[1]);
     __syncthreads();
   }
 }
@@ -684,10 +749,12 @@ __global__ __launch_bounds__(256) void pair_rules_kernel(int op, strl_tread *A, 
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;      // one lane per case
   if (i >= n) return;
   DTread a = dtread_from(A[i]);
-  const DTread b = dtread_from(B[i]);
+  DTread b = dtread_from(B[i]);
+  prepare_tread(a, P.p);      // as the replay's gather does for every record
+  prepare_tread(b, P.p);
   if (op == 0) res[i] = adjust_by(a, b, P, B_position[i]) ? 1 : 0;
   else if (op == 1) res[i] = unplaced_pair(a, b, P) ? 1 : 0;
-  else { a.code = canonical_repeat(a.code, a.k); res[i] = 0; }
+  else { a.code = canonical_code(a); res[i] = 0; }
   dtread_to(a, A[i]);
 }
 
@@ -817,7 +884,7 @@ int strl_pair_device(strl_ctx *c, uint64_t n, const strl_pair_soa *pp, const uin
   uint32_t *evl = in0 ? c->p_val1.as<uint32_t>() : c->p_val0.as<uint32_t>();
   P.emit_key = ek; P.emit_val = evl;
   if (n) {
-    const size_t pg_shmem = sizeof(PItem) * (PG_BLOCK + PG_HALO) + (sizeof(strl_tread) + 8) * PG_EMIT + 16;
+    const size_t pg_shmem = sizeof(PItem) * (PG_BLOCK + PG_HALO) + (sizeof(STread) + 8) * PG_EMIT + 16;
     if (!c->pg_attr_done) {      // (per context: contexts may sit on different devices)
       STRL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pair_groups_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_shmem));
       c->pg_attr_done = true;
