@@ -30,6 +30,7 @@
 #include "bam_reader.h"
 #include "bgzf_feed.h"
 #include "chunk_feed.h"
+#include "region_feed.h"
 #include "cram_reader.h"
 #include "cram_codecs.h"
 
@@ -1714,11 +1715,6 @@ static int merge_main(int argc, char **argv) {
   return end_process(ctx);
 }
 
-// The run of BGZF blocks the walk of one region query (BamReader::read_region) passes through, as far as the .bai linear
-// index can bound it: from the block of the index offset of `beg`'s window up to the block that holds the first record
-// overlapping a later window than `end`'s -- and the one behind it --, their sizes read from the block headers and trailers
-// (18 + 8 bytes per block).  ok = false: the index does not bound the region, the file is laid out unusually (other extra
-// subfields than BC), the run is longer than 8 MB: such a region is read by the host reader.
 // fragment_length_distribution (utils.nim:86-111; call.nim:92) through the device front end: the first ~2.2 M records' flag / isize
 // words come from the parse kernel (the words `strling extract` makes its histogram from), so the host inflates nothing -- on
 // 16 CPUs the host's inflate of that sample was 3 of the 4.7 CPU-seconds `strling call`'s start-up consists of (context, `.bin`
@@ -1780,35 +1776,6 @@ static bool fragment_lengths_on_device(strl_ctx *ctx, const std::string &bam, ui
   lap("front end given up");
   fl.finish(frag);
   return true;
-}
-
-struct RegionPlan { bool ok = false; uint64_t c_beg = 0, c_end = 0; uint32_t in_block = 0; std::vector<uint32_t> hdr, bsize, isz, crc; };
-// `more` (1 = the plan `strling call` uses): that many times the inflated bytes and blocks, and blocks behind the hinted one
-static void plan_region(const BamReader &rd, int fd, int32_t tid, int64_t beg, int64_t end, RegionPlan &P, int more = 1) {
-  uint64_t c_hint = 0;
-  P.ok = false;
-  if (!rd.region_span(tid, beg, end, P.c_beg, P.in_block, c_hint)) return;
-  uint64_t o = P.c_beg, infl = 0;
-  int beyond = 0;
-  bool good = true;
-  while (beyond < 2 * more && infl < ((uint64_t)8 << 20) * (uint64_t)more && P.bsize.size() < (size_t)4096 * (size_t)more) {   // (a window of 30x data is ~1 MB)
-    uint8_t h[18], tr[8];
-    if (pread(fd, h, 18, (off_t)o) != 18) break;                                  // end of the file
-    const uint32_t xlen = h[10] | (h[11] << 8);
-    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || xlen != 6 || h[12] != 'B' || h[13] != 'C') { good = false; break; }
-    const uint32_t bsize = (h[16] | (h[17] << 8)) + 1u;
-    if (bsize < 26 || pread(fd, tr, 8, (off_t)(o + bsize - 8)) != 8) { good = false; break; }
-    uint32_t crc, isz;
-    memcpy(&crc, tr, 4); memcpy(&isz, tr + 4, 4);
-    if (isz > 65536u) { good = false; break; }
-    P.hdr.push_back(18); P.bsize.push_back(bsize); P.isz.push_back(isz); P.crc.push_back(crc);
-    infl += isz;
-    if (o >= c_hint) ++beyond;
-    o += bsize;
-  }
-  P.c_end = o;
-  // the first block must hold the index offset; a run that did not reach the hinted block goes to the host reader
-  P.ok = good && beyond >= 1 && !P.bsize.empty() && P.in_block <= P.isz[0];
 }
 
 // `strling bamindex` / `strling call --make-index`: the .bai of a BAM built on the device (strl_bamindex_*; what `samtools index`
@@ -2139,19 +2106,16 @@ static int call_main(int argc, char **argv) {
   // left with genotype() and the row); a region the device passes on (status 2: more records or a wider span than its
   // capacity rule takes) goes to the host path like one the index cannot bound.  Asked for with STRL_CALL_EVIDENCE=device;
   // without it (or with =host) the records come back to strl_spanners on the workers.
-  struct Batch {
+  struct Batch : RegionBlocks {             // (the block tables, req, comp_bytes and inflated are RegionBlocks')
     size_t t0 = 0, t1 = 0;
     std::vector<uint32_t> which;            // tasks of [t0, t1) that go through the device
-    std::vector<uint64_t> coff, out_off, out_len;
-    std::vector<uint32_t> clen, isize, crc;
-    std::vector<strl_region_req> req;
+    std::vector<uint64_t> out_off, out_len;
     std::vector<uint8_t> status;
     std::vector<strl_bounds> bnd;           // device evidence: the regions' bounds, their Support lists and summaries
     std::vector<strl_support> sup;
     std::vector<uint64_t> sup_off;
     std::vector<strl_span_summary> sum;
     double ev_ms = 0;
-    uint64_t comp_bytes = 0, inflated = 0;
     int rc = 0;
     std::string err;
   };
@@ -2232,13 +2196,17 @@ static int call_main(int argc, char **argv) {
       const auto tp0 = std::chrono::steady_clock::now();
       if (region_fd < 0) region_fd = open(bam.c_str(), O_RDONLY);
       if (region_fd < 0) quit("couldn't open bam");
+      // a bound's query, stated once for the plan and for the request the device walks by
+      auto query_of = [&](const Task &t) {
+        strl_region_req q{};
+        q.tid = t.b.tid; q.beg = (int32_t)std::max<int64_t>(0, (int64_t)t.b.left - window); q.end = (int32_t)std::min<int64_t>((int64_t)t.b.right + window, INT32_MAX);
+        return q;
+      };
       std::vector<RegionPlan> plan(tasks.size());
       ev_pool.parallel_for((tasks.size() + 63) / 64, [&](size_t blk) {
         for (size_t j = blk * 64; j < std::min(tasks.size(), (blk + 1) * 64); ++j) {
-          const Task &t = tasks[j];
-          RegionPlan &P = plan[j];
-          const int64_t wl = std::max<int64_t>(0, (int64_t)t.b.left - window), wr = (int64_t)t.b.right + window;
-          plan_region(rd, region_fd, t.b.tid, wl, std::min<int64_t>(wr, INT32_MAX), P);
+          const strl_region_req q = query_of(tasks[j]);
+          plan_region(rd, region_fd, q.tid, q.beg, q.end, plan[j]);
         }
       });
       t_plan += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count();
@@ -2250,22 +2218,7 @@ static int call_main(int argc, char **argv) {
         while (j < tasks.size() && (B.inflated < batch_inflated || B.which.empty())) {
           const RegionPlan &P = plan[j];
           if (P.ok) {
-            strl_region_req q{};
-            q.first_block = (uint32_t)B.clen.size(); q.n_blocks = (uint32_t)P.bsize.size(); q.in_block = P.in_block;
-            q.tid = tasks[j].b.tid;
-            q.beg = (int32_t)std::max<int64_t>(0, (int64_t)tasks[j].b.left - window);
-            q.end = (int32_t)std::min<int64_t>((int64_t)tasks[j].b.right + window, INT32_MAX);
-            uint64_t o = 0;
-            for (size_t k = 0; k < P.bsize.size(); ++k) {
-              B.coff.push_back(B.comp_bytes + o + P.hdr[k]);
-              B.clen.push_back(P.bsize[k] - P.hdr[k] - 8);
-              B.isize.push_back(P.isz[k]);
-              B.crc.push_back(P.crc[k]);
-              B.inflated += P.isz[k];
-              o += P.bsize[k];
-            }
-            B.comp_bytes += (o + 15) & ~(uint64_t)15;
-            B.req.push_back(q);
+            B.add(P, query_of(tasks[j]));
             if (device_evidence) B.bnd.push_back(tasks[j].b);
             B.which.push_back((uint32_t)j);
           }
@@ -2307,18 +2260,7 @@ static int call_main(int argc, char **argv) {
             if (!pin_comp[s] || (!device_evidence && !pin_out[s])) { B.rc = STRL_ERR_HIP; B.err = "page-locked memory for the region reads"; }
             else {
               std::atomic<bool> io_bad{false};
-              io_pool.parallel_for((B.which.size() + 15) / 16, [&](size_t blk) {
-                for (size_t k = blk * 16; k < std::min(B.which.size(), (blk + 1) * 16); ++k) {
-                  const RegionPlan &P = plan[B.which[k]];
-                  const uint64_t at = B.coff[B.req[k].first_block] - P.hdr[0], len = P.c_end - P.c_beg;
-                  uint64_t got = 0;
-                  while (got < len) {
-                    const ssize_t r = pread(region_fd, pin_comp[s] + at + got, (size_t)(len - got), (off_t)(P.c_beg + got));
-                    if (r <= 0) { io_bad = true; break; }
-                    got += (uint64_t)r;
-                  }
-                }
-              });
+              io_pool.parallel_for((B.which.size() + 15) / 16, [&](size_t blk) { if (!B.read(region_fd, pin_comp[s], blk * 16, std::min(B.which.size(), (blk + 1) * 16))) io_bad = true; });
               if (io_bad.load()) { B.rc = STRL_ERR_IO; B.err = "reading " + bam; }
             }
             t_pread += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr1).count();
@@ -2672,43 +2614,14 @@ static int region_main(int argc, char **argv) {
     plan_region(rd, fd, tid, beg, end, P);
     if (!P.ok) { fprintf(stderr, "plan: host reader\n"); got = rd.read_region(b, tid, beg, end, err); }
     else {
-      std::vector<uint8_t> comp((size_t)(P.c_end - P.c_beg)), u;
-      if (pread(fd, comp.data(), comp.size(), (off_t)P.c_beg) != (ssize_t)comp.size()) quit("short read");
-      size_t o = 0;
-      for (size_t k = 0; k < P.bsize.size(); ++k) {
-        const size_t at = u.size();
-        u.resize(at + P.isz[k]);
-        z_stream zs;
-        memset(&zs, 0, sizeof zs);
-        if (inflateInit2(&zs, -15) != Z_OK) quit("zlib");
-        zs.next_in = comp.data() + o + P.hdr[k]; zs.avail_in = P.bsize[k] - P.hdr[k] - 8;
-        zs.next_out = u.data() + at; zs.avail_out = P.isz[k];
-        if (inflate(&zs, Z_FINISH) != Z_STREAM_END || zs.total_out != P.isz[k]) quit("inflate");
-        inflateEnd(&zs);
-        if ((uint32_t)crc32(0, u.data() + at, P.isz[k]) != P.crc[k]) quit("crc");
-        o += P.bsize[k];
-      }
-      size_t p = P.in_block, keep = SIZE_MAX;
-      bool stopped = false;
-      while (p + 36 <= u.size()) {
-        int32_t bs, ref, pos;
-        memcpy(&bs, &u[p], 4); memcpy(&ref, &u[p + 4], 4); memcpy(&pos, &u[p + 8], 4);
-        if (bs < 32) break;
-        if (ref != tid || pos >= end) { stopped = true; break; }
-        if (p + 4 + (size_t)bs > u.size()) break;
-        if (keep == SIZE_MAX) {
-          const uint32_t l_name = u[p + 12];
-          uint16_t n_cig;
-          memcpy(&n_cig, &u[p + 16], 2);
-          int64_t span = 1;
-          for (uint32_t k = 0; k < n_cig; ++k) { uint32_t c; memcpy(&c, &u[p + 36 + l_name + 4 * k], 4); span += c >> 4; }
-          if ((int64_t)pos + span > beg) keep = p;
-        }
-        p += 4 + (size_t)bs;
-      }
-      if (!stopped) { fprintf(stderr, "plan: blocks end before the query does, host reader\n"); got = rd.read_region(b, tid, beg, end, err); }
+      RegionBlocks B;
+      B.add(P, strl_region_req{});
+      std::vector<uint8_t> comp((size_t)B.comp_bytes), u;
+      if (!B.read(fd, comp.data(), 0, 1)) quit("short read");
+      if (const char *bad = region_inflate(B, 0, comp.data(), u)) quit("%s", bad);
+      size_t keep = 0, p = 0;
+      if (!region_walk(u, P.in_block, tid, beg, end, keep, p)) { fprintf(stderr, "plan: blocks end before the query does, host reader\n"); got = rd.read_region(b, tid, beg, end, err); }
       else {
-        if (keep == SIZE_MAX) keep = p;
         fprintf(stderr, "plan: %zu blocks, %zu inflated bytes, records in [%zu, %zu)\n", P.bsize.size(), u.size(), keep, p);
         got = BamReader::append_records(b, u.data() + keep, p - keep, err);
       }
@@ -2955,28 +2868,10 @@ static int pull_main(int argc, char **argv) {
   std::vector<uint8_t> names;
   std::vector<uint32_t> req_row;                    // the kept record that asks
   auto keep_bytes = [&](strl_pull_row &r, const uint8_t *from) { const uint64_t at = store.size(); store.insert(store.end(), from + r.off, from + r.off + r.size); r.off = at; };
-  // The blocks of several region queries, read and laid out as the region entry points take them
-  struct Blocks {
-    std::vector<uint8_t> comp; std::vector<uint64_t> coff; std::vector<uint32_t> clen, isize, crc; uint64_t inflated = 0;
-    void clear() { comp.clear(); coff.clear(); clen.clear(); isize.clear(); crc.clear(); inflated = 0; }
-  };
-  auto add_blocks = [&](Blocks &B, const RegionPlan &P, strl_region_req &q) -> bool {
-    q.first_block = (uint32_t)B.clen.size(); q.n_blocks = (uint32_t)P.bsize.size(); q.in_block = P.in_block;
-    const size_t at = B.comp.size(), len = (size_t)(P.c_end - P.c_beg);
-    B.comp.resize(at + ((len + 15) & ~(size_t)15));
-    for (size_t got = 0; got < len;) {
-      const ssize_t n = pread(fd, B.comp.data() + at + got, len - got, (off_t)(P.c_beg + got));
-      if (n <= 0) return false;
-      got += (size_t)n;
-    }
-    uint64_t o = 0;
-    for (size_t k = 0; k < P.bsize.size(); ++k) {
-      B.coff.push_back(at + o + P.hdr[k]); B.clen.push_back(P.bsize[k] - P.hdr[k] - 8); B.isize.push_back(P.isz[k]); B.crc.push_back(P.crc[k]);
-      B.inflated += P.isz[k];
-      o += P.bsize[k];
-    }
-    return true;
-  };
+  // the compressed bytes of a batch's blocks (region_feed.h), read at once into `comp`; false: those regions go down the ladder
+  std::vector<uint8_t> comp;
+  auto read_blocks = [&](const RegionBlocks &B) { comp.assign((size_t)B.comp_bytes, 0); return B.read(fd, comp.data(), 0, B.slices.size()); };
+  auto bounded = [&](int32_t tid, int64_t beg, int64_t end) { uint64_t cb, ch; uint32_t ib; return rd.region_span(tid, beg, end, cb, ib, ch); };
   const uint64_t batch_inflated = getenv("STRL_PULL_BATCH_MB") ? (uint64_t)atoll(getenv("STRL_PULL_BATCH_MB")) << 20 : (uint64_t)128 << 20;
   bool nomem = false;
 
@@ -2998,19 +2893,15 @@ static int pull_main(int argc, char **argv) {
   // the tiles `which` through the device; the ones it passes on come back in `failed`
   auto device_tiles = [&](const std::vector<size_t> &which, int more, std::vector<size_t> &failed) {
     for (size_t j = 0; j < which.size() && !nomem;) {
-      Blocks B;
+      RegionBlocks B;
       std::vector<size_t> in;
-      std::vector<strl_region_req> rq;
       std::vector<strl_pull_tile> tl;
       while (j < which.size() && (B.inflated < batch_inflated || in.empty())) {
         const size_t t = which[j++];
-        RegionPlan P;
-        plan_region(rd, fd, tiles[t].tid, tile_req[t].beg, tile_req[t].end, P, more);
-        strl_region_req q = tile_req[t];
-        if (!P.ok || !add_blocks(B, P, q)) { failed.push_back(t); continue; }
-        in.push_back(t); rq.push_back(q); tl.push_back(tiles[t]);
+        if (!B.plan_add(rd, fd, tile_req[t], more)) { failed.push_back(t); continue; }
+        in.push_back(t); tl.push_back(tiles[t]);
       }
-      if (in.empty()) continue;
+      if (in.empty() || !read_blocks(B)) { failed.insert(failed.end(), in.begin(), in.end()); continue; }
       // rows and bytes sized from the blocks' ISIZE sum, which always suffices (a record is 36 bytes or more and is kept once)
       std::vector<strl_pull_row> rows((size_t)(B.inflated / 36) + in.size() + 1);
       std::vector<uint8_t> bytes((size_t)(2 * B.inflated) + 64);
@@ -3018,14 +2909,12 @@ static int pull_main(int argc, char **argv) {
       std::vector<uint8_t> status(in.size(), 1);
       uint64_t n_rows = 0, n_bytes = 0;
       double ms = 0;
-      const int rc = strl_pull_select(ctx, B.comp.data(), B.comp.size(), B.coff.data(), B.clen.data(), B.isize.data(), B.crc.data(), (uint32_t)B.clen.size(), rq.data(), tl.data(),
+      const int rc = strl_pull_select(ctx, comp.data(), comp.size(), B.coff.data(), B.clen.data(), B.isize.data(), B.crc.data(), (uint32_t)B.clen.size(), B.req.data(), tl.data(),
                                       (uint32_t)in.size(), rows.data(), rows.size(), &n_rows, tile_rows.data(), bytes.data(), bytes.size(), &n_bytes, status.data(), &ms);
       ++S.select_calls;
       if (rc == STRL_ERR_NOMEM) { nomem = true; return; }
-      if (rc == STRL_ERR_FORMAT || rc == STRL_ERR_CRC || rc == STRL_ERR_CAPACITY) {      // the host reader, zlib behind it, has the last word
-        for (size_t t : in) failed.push_back(t);
-        continue;
-      }
+      // the host reader, zlib behind it, has the last word
+      if (rc == STRL_ERR_FORMAT || rc == STRL_ERR_CRC || rc == STRL_ERR_CAPACITY) { failed.insert(failed.end(), in.begin(), in.end()); continue; }
       if (rc) quit("[strling] pull: %s (status %d)", strl_last_error(), rc);
       S.select_ms += ms;
       for (size_t k = 0; k < in.size(); ++k) {
@@ -3040,14 +2929,8 @@ static int pull_main(int argc, char **argv) {
   std::vector<size_t> all_tiles(tiles.size());
   for (size_t t = 0; t < tiles.size(); ++t) all_tiles[t] = t;
   if (use_device) {
-    std::vector<size_t> failed, failed2;
-    device_tiles(all_tiles, 1, failed);
-    // a tile whose blocks ended before its query did (a pile-up larger than the plan's run of blocks): once more with eight
-    // times the blocks, then the host reader
-    std::vector<size_t> again;
-    for (size_t t : failed) { uint64_t cb, ch; uint32_t ib; if (rd.region_span(tiles[t].tid, tile_req[t].beg, tile_req[t].end, cb, ib, ch)) again.push_back(t); else failed2.push_back(t); }
-    S.retried = again.size();
-    if (!nomem && !again.empty()) device_tiles(again, 8, failed2);
+    // (device_tiles does nothing more once nomem is set)
+    const std::vector<size_t> failed2 = region_ladder(all_tiles, [&](size_t t) { return bounded(tiles[t].tid, tile_req[t].beg, tile_req[t].end); }, device_tiles, &S.retried);
     if (!nomem) for (size_t t : failed2) host_tile(t);
     if (!nomem && verbose && !failed2.empty()) fprintf(stderr, "[strling] pull: %zu of %zu tiles read on the host (blocks the index cannot bound, or passed on by the device)\n", failed2.size(), tiles.size());
     one_device_call = !nomem && S.select_calls == 1 && S.host_tiles == 0;
@@ -3105,40 +2988,35 @@ static int pull_main(int argc, char **argv) {
   };
   auto device_windows = [&](const std::vector<size_t> &which, int more, std::vector<size_t> &failed) {
     for (size_t j = 0; j < which.size() && !nomem;) {
-      Blocks B;
+      RegionBlocks B;
       std::vector<size_t> in;
-      std::vector<strl_region_req> rq;
       std::vector<uint32_t> win_off{0};
       std::vector<strl_pull_req> rr;
       while (j < which.size() && (B.inflated < batch_inflated || in.empty())) {
         const size_t w = which[j++];
         const Window &W = windows[w];
-        RegionPlan P;
-        plan_region(rd, fd, W.tid, W.beg, W.end, P, more);
         strl_region_req q{};
         q.tid = W.tid; q.beg = W.beg; q.end = W.end;
-        if (!P.ok || !add_blocks(B, P, q)) { failed.push_back(w); continue; }
-        in.push_back(w); rq.push_back(q);
+        if (!B.plan_add(rd, fd, q, more)) { failed.push_back(w); continue; }
+        in.push_back(w);
         rr.insert(rr.end(), wreqs.begin() + W.q0, wreqs.begin() + W.q1);
         win_off.push_back((uint32_t)rr.size());
       }
-      if (in.empty()) continue;
+      if (in.empty() || !read_blocks(B)) { failed.insert(failed.end(), in.begin(), in.end()); continue; }
       std::vector<strl_pull_row> rows(rr.size());
       std::vector<uint8_t> bytes(rr.size() * 640 + 4096), status(in.size(), 1);
       uint64_t n_bytes = 0;
       double ms = 0;
       int rc = 0;
       for (int attempt = 0; attempt < 2; ++attempt) {
-        rc = strl_pull_mates(ctx, B.comp.data(), B.comp.size(), B.coff.data(), B.clen.data(), B.isize.data(), B.crc.data(), (uint32_t)B.clen.size(), rq.data(), win_off.data(),
+        rc = strl_pull_mates(ctx, comp.data(), comp.size(), B.coff.data(), B.clen.data(), B.isize.data(), B.crc.data(), (uint32_t)B.clen.size(), B.req.data(), win_off.data(),
                              (uint32_t)in.size(), rr.data(), names.data(), names.size(), rows.data(), bytes.data(), bytes.size(), &n_bytes, status.data(), &ms);
         if (rc != STRL_ERR_CAPACITY) break;
         bytes.resize((size_t)n_bytes + 64);
       }
       ++S.mate_calls;
-      if (rc == STRL_ERR_NOMEM || rc == STRL_ERR_FORMAT || rc == STRL_ERR_CRC || rc == STRL_ERR_CAPACITY) {   // (so late, memory too: these windows on the host)
-        for (size_t w : in) failed.push_back(w);
-        continue;
-      }
+      // (so late, memory too: these windows on the host)
+      if (rc == STRL_ERR_NOMEM || rc == STRL_ERR_FORMAT || rc == STRL_ERR_CRC || rc == STRL_ERR_CAPACITY) { failed.insert(failed.end(), in.begin(), in.end()); continue; }
       if (rc) quit("[strling] pull: %s (status %d)", strl_last_error(), rc);
       S.mates_ms += ms;
       for (size_t k = 0; k < in.size(); ++k) {
@@ -3155,10 +3033,7 @@ static int pull_main(int argc, char **argv) {
   std::vector<size_t> all_windows(windows.size());
   for (size_t w = 0; w < windows.size(); ++w) all_windows[w] = w;
   if (use_device) {
-    std::vector<size_t> failed, failed2, again;
-    device_windows(all_windows, 1, failed);
-    for (size_t w : failed) { uint64_t cb, ch; uint32_t ib; if (rd.region_span(windows[w].tid, windows[w].beg, windows[w].end, cb, ib, ch)) again.push_back(w); else failed2.push_back(w); }
-    if (!again.empty()) device_windows(again, 8, failed2);
+    const std::vector<size_t> failed2 = region_ladder(all_windows, [&](size_t w) { return bounded(windows[w].tid, windows[w].beg, windows[w].end); }, device_windows);
     for (size_t w : failed2) host_window(windows[w]);
     if (verbose && !failed2.empty()) fprintf(stderr, "[strling] pull: %zu of %zu mate windows searched on the host\n", failed2.size(), windows.size());
   } else
