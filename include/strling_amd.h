@@ -558,6 +558,9 @@ int strl_ctx_inflate_ms(strl_ctx *ctx, double *ms);
  * order) from the first record that may reach past `beg` up to, not including, the first record with another refID or
  * pos >= end -- a superset of htslib's iterator filter (tid equal, pos < end, bam_endpos > beg), which strl_spanners applies.
  * status[r] = 0: complete; 1: the blocks handed over end before such a record (or do not parse): read that region on the host.
+ * "May reach past beg": pos + 1 + the lengths of ALL its CIGAR operations > beg.  A block_size outside 32 .. 2^28 does not parse
+ * (status 1); a record whose CIGAR would leave it (36 + l_read_name + 4 n_cigar_op > 4 + block_size) is kept without its CIGAR
+ * being read -- whoever parses the returned bytes (strl_spanners, strl_evidence_records, the pull passes) reports it.
  * out_cap = the sum over the regions of their blocks' ISIZE + 32 bytes per region always suffices; STRL_ERR_CAPACITY leaves the
  * bytes needed in out_off[0].  STRL_ERR_FORMAT / STRL_ERR_CRC as for the front end. */
 typedef struct {

@@ -317,7 +317,9 @@ def index_regions(seq, words, window=100, step=60):
 
 def _check(rc):
     if rc != 0:
-        raise StrlingError(f"strling_amd error {rc}: {load().strl_last_error().decode()}")
+        e = StrlingError(f"strling_amd error {rc}: {load().strl_last_error().decode()}")
+        e.code = rc
+        raise e
 
 
 def _ptr(a):
@@ -678,9 +680,11 @@ class Context:
         _check(self.L.strl_bounds_bare(self.h, p.ctypes.data, sp.ctypes.data, p.size, min_clip, min_clip_total, max_clip_dist, out.ctypes.data, C.byref(good)))
         return out[0], bool(good.value)
 
-    def regions_fetch(self, streams, sizes, regions, crcs=None):
+    def regions_fetch(self, streams, sizes, regions, crcs=None, cap=None, layout=False):
         """strl_regions_fetch: `streams` / `sizes` = raw DEFLATE payloads + ISIZE of BGZF blocks; regions = list of
-        (first_block, n_blocks, in_block, tid, beg, end) -> list of (record bytes, status)"""
+        (first_block, n_blocks, in_block, tid, beg, end) -> list of (record bytes, status); layout=True: that list, out_off and
+        out_len.  cap = the bytes of `out` (default: what the header says always suffices); a StrlingError of STRL_ERR_CAPACITY
+        carries the bytes needed (out_off[0]) as `.needed`"""
         comp = np.frombuffer(b"".join(streams) + b"\0" * 8, np.uint8)
         clen = np.array([len(x) for x in streams], np.uint32)
         coff = np.zeros(len(streams), np.uint64)
@@ -689,15 +693,22 @@ class Context:
         req = np.zeros(len(regions), REGION_REQ_DTYPE)
         for k, r in enumerate(regions):
             req[k] = tuple(r)
-        cap = sum(int(isz[r[0]:r[0] + r[1]].sum()) + 32 for r in regions) + 64
-        out = np.zeros(cap, np.uint8)
+        if cap is None:
+            cap = sum(int(isz[r[0]:r[0] + r[1]].sum()) + 32 for r in regions) + 64
+        out = np.zeros(max(1, cap), np.uint8)
         off = np.zeros(len(regions), np.uint64)
         ln = np.zeros(len(regions), np.uint64)
         st = np.zeros(len(regions), np.uint8)
         crc = None if crcs is None else np.asarray(crcs, np.uint32)
-        _check(self.L.strl_regions_fetch(self.h, comp.ctypes.data, int(clen.sum()), _ptr(coff), _ptr(clen), _ptr(isz), None if crc is None else _ptr(crc), len(streams),
-                                         req.ctypes.data, len(regions), out.ctypes.data, cap, _ptr(off), _ptr(ln), _ptr(st)))
-        return [(out[int(o):int(o) + int(n)].tobytes(), int(x)) for o, n, x in zip(off, ln, st)]
+        try:
+            _check(self.L.strl_regions_fetch(self.h, comp.ctypes.data, int(clen.sum()), _ptr(coff), _ptr(clen), _ptr(isz), None if crc is None else _ptr(crc), len(streams),
+                                             req.ctypes.data, len(regions), out.ctypes.data, cap, _ptr(off), _ptr(ln), _ptr(st)))
+        except StrlingError as e:
+            if e.code == -4 and len(regions):
+                e.needed = int(off[0])
+            raise
+        got = [(out[int(o):int(o) + int(n)].tobytes(), int(x)) for o, n, x in zip(off, ln, st)]
+        return (got, off, ln) if layout else got
 
     def _evidence_call(self, n, call, cap):
         """the support / summary / status buffers of the evidence entry points, grown once if `cap` proves short"""

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64) void region_walk_kernel(const uint8_t *u, uint6
         if (p + need > w1 && need <= RW_WIN - 16) { load_win(p); h = win + (p - w0); }
         if (p + need <= w1) for (uint32_t k = 0; k < n_cig; ++k) span += rg_ld32(h + 36 + l_name + 4u * k) >> 4;
         else for (uint32_t k = 0; k < n_cig; ++k) span += rg_ld32(u + p + 36 + l_name + 4u * k) >> 4;      // (a cigar of a thousand operations)
-      } else span = 1ll << 40;                         // malformed: keep it, the host's parser reports it
+      } else span = 1ll << 40;                         // a cigar that leaves its record is never read: the record is kept, and the parser behind the walk reports it
       if ((int64_t)pos + span > (int64_t)q.beg) keep = p;
     }
     p += 4ull + bs;

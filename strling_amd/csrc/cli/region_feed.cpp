@@ -54,16 +54,17 @@ bool region_walk(const std::vector<uint8_t> &u, size_t p, int32_t tid, int64_t b
   while (p + 36 <= u.size()) {
     int32_t bs, ref, pos;
     memcpy(&bs, &u[p], 4); memcpy(&ref, &u[p + 4], 4); memcpy(&pos, &u[p + 8], 4);
-    if (bs < 32) break;
+    if (bs < 32 || bs > (1 << 28)) break;                                        // not a record: the blocks "end" here, as on the device
     if (ref != tid || pos >= end) { stopped = true; break; }
     if (p + 4 + (size_t)bs > u.size()) break;
     if (keep == SIZE_MAX) {
       const uint32_t l_name = u[p + 12];
       uint16_t n_cig;
       memcpy(&n_cig, &u[p + 16], 2);
-      if (36 + (size_t)l_name + 4 * (size_t)n_cig > 4 + (size_t)bs) break;      // (a cigar that leaves its record: not a BAM record)
       int64_t span = 1;
-      for (uint32_t k = 0; k < n_cig; ++k) { uint32_t c; memcpy(&c, &u[p + 36 + l_name + 4 * k], 4); span += c >> 4; }
+      if (36 + (size_t)l_name + 4 * (size_t)n_cig <= 4 + (size_t)bs)
+        for (uint32_t k = 0; k < n_cig; ++k) { uint32_t c; memcpy(&c, &u[p + 36 + l_name + 4 * k], 4); span += c >> 4; }
+      else span = (int64_t)1 << 40;              // a cigar that leaves its record is never read: the record is kept, and the parser behind the walk reports it
       if ((int64_t)pos + span > beg) keep = p;
     }
     p += 4 + (size_t)bs;

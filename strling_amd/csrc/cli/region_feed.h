@@ -62,6 +62,8 @@ struct RegionBlocks {
 // nullptr, or what failed ("zlib", "inflate", "crc").  region_walk: strl_regions_fetch's rule over those bytes from p (the request's in_block) on --
 // keep from the first record whose cigar could reach past `beg`, stop at the first record on another reference or at / behind
 // `end` -- the records are u[keep, stop); false: the blocks end before the query does (the device passes such a region on).
+// As on the device a block_size outside 32 .. 2^28 ends the bytes, and a record whose cigar would leave it is kept without its
+// cigar being read: the parser behind the walk reports it (tests/test_region_cases.py holds the two side by side).
 const char *region_inflate(const RegionBlocks &B, size_t r, const uint8_t *comp, std::vector<uint8_t> &u);
 bool region_walk(const std::vector<uint8_t> &u, size_t p, int32_t tid, int64_t beg, int64_t end, size_t &keep, size_t &stop);
 

@@ -10,6 +10,7 @@ import zlib
 import numpy as np
 import pytest
 
+import region_cases as rc
 from strling_amd import api, bamio, build, synth
 
 CLI = build.CLI
@@ -64,6 +65,9 @@ def test_regions_fetch_matches_a_python_walk(block, tmp_path):
     recs, _ = _records(u, at)
     assert len(recs) == rec.n
     ustart = np.concatenate([[0], np.cumsum([len(x) for x in infl])])
+    model = rc.Call("file")                                       # the walk of tests/region_cases.py over the file's blocks
+    model.blocks = infl
+    model._lay()
     rng = np.random.default_rng(3)
     regions, expect = [], []
     for _ in range(60):
@@ -74,21 +78,9 @@ def test_regions_fetch_matches_a_python_walk(block, tmp_path):
         beg = pos + int(rng.integers(-50, 400))
         end = beg + int(rng.integers(1, 1500))
         regions.append((fb, nb, o - int(ustart[fb]), ref, beg, end))
-        lim = int(ustart[fb + nb])
-        keep, stop, status = None, None, 1
-        for (ro, bs, rr, rp, ub) in recs[k:]:
-            if ro + 36 > lim:
-                break
-            if rr != ref or rp >= end:
-                stop, status = ro, 0
-                break
-            if ro + 4 + bs > lim:
-                break
-            if keep is None and ub > beg:
-                keep = ro
-        if status == 0 and keep is None:
-            keep = stop
-        expect.append((u[keep:stop] if status == 0 else b"", status))
+        t = rc.walk(model, regions[-1])
+        assert t.lim == int(ustart[fb + nb]) and t.p0 == o
+        expect.append((u[t.keep:t.stop] if t.status == 0 else b"", t.status))
     ctx = api.Context(0)
     got = ctx.regions_fetch([b[1] for b in blks], [b[2] for b in blks], regions, crcs=[b[3] for b in blks])
     assert sum(1 for e in expect if e[1] == 0 and e[0]) >= 10 and sum(1 for e in expect if e[1] == 1) >= 3
