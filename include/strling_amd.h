@@ -548,6 +548,24 @@ int strl_inflate_blocks(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes,
 /* HIP-event time (ms) of the inflate kernel of the last strl_inflate_blocks call (copies excluded). */
 int strl_ctx_inflate_ms(strl_ctx *ctx, double *ms);
 
+/* ---- BGZF output on the device (the reference writes its BAMs through htslib, i.e. zlib on the host) ----
+ * Compress in[0, in_bytes) into BGZF members of block_bytes input bytes each (the last one shorter), written back to back
+ * into out, WITHOUT the EOF block: one workgroup per member.  Every member is the 18-byte header with BSIZE, one final DEFLATE
+ * block -- dynamic Huffman, or stored when that would be no smaller -- CRC-32 and ISIZE; members are compressed independently.
+ * block_bytes in [1, 0xFF00], else STRL_ERR_ARG.  out_cap < strl_bgzf_deflate_bound() is STRL_ERR_CAPACITY before anything is
+ * launched or written.  csize[k] = the size of member k (may be NULL), *n_stored = the members that went out stored,
+ * *out_bytes = the bytes written; no byte of out behind them is touched.  in_bytes == 0: no member, STRL_OK.
+ * The bytes are a function of the input alone: strl_bgzf_deflate_host gives the same ones. */
+int strl_bgzf_deflate(strl_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+                      uint32_t *csize, uint32_t *n_stored);
+/* The output bytes that always suffice for strl_bgzf_deflate: every member stored, in_bytes + 31 bytes a member (0 for a block_bytes outside [1, 0xFF00]). */
+uint64_t strl_bgzf_deflate_bound(uint64_t in_bytes, uint32_t block_bytes);
+/* strl_bgzf_deflate on the calling thread, without a device: the same rule (csrc/deflate_core.h), the same bytes, the same refusals. */
+int strl_bgzf_deflate_host(const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
+                           uint32_t *n_stored);
+/* HIP-event time (ms) of the kernels of the last strl_bgzf_deflate call (copies excluded). */
+int strl_ctx_deflate_ms(strl_ctx *ctx, double *ms);
+
 /* ---- `strling call`'s evidence reads on the device (replaces the per-bound `for aln in ibam.query(tid, left - window,
  * right + window)` of call.nim:196-218 / collect.nim:132-141, i.e. htslib's indexed iterator: bgzf seek + inflate + bam_read1
  * from the .bai linear-index offset up to the first record at or behind `end`) for many bounds at once.

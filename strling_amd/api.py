@@ -145,7 +145,8 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_bamindex_begin", "strl_bamindex_reserve", "strl_bamindex_push", "strl_bamindex_finish", "strl_bamindex_fetch", "strl_bamindex_end",
            "strl_front_index_begin", "strl_front_index_blocks", "strl_front_index_finish", "strl_bamindex_begin_csi", "strl_front_index_begin_csi",
            "strl_sweep_begin", "strl_sweep_reserve", "strl_sweep_push", "strl_sweep_finish", "strl_sweep_end",
-           "strl_pull_select", "strl_pull_mates", "strl_pull_select_host", "strl_pull_counts_host", "strl_pull_mates_host", "strl_pull_order"]
+           "strl_pull_select", "strl_pull_mates", "strl_pull_select_host", "strl_pull_counts_host", "strl_pull_mates_host", "strl_pull_order",
+           "strl_bgzf_deflate", "strl_bgzf_deflate_bound", "strl_bgzf_deflate_host", "strl_ctx_deflate_ms"]
 
 
 def lib_path():
@@ -232,6 +233,11 @@ def load(build_if_missing=True):
                                         C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(ClusterStats)]
     L.strl_inflate_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
     L.strl_ctx_inflate_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.strl_bgzf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint32)]
+    L.strl_bgzf_deflate_host.argtypes = L.strl_bgzf_deflate.argtypes[1:]
+    L.strl_bgzf_deflate_bound.argtypes = [C.c_uint64, C.c_uint32]
+    L.strl_bgzf_deflate_bound.restype = C.c_uint64
+    L.strl_ctx_deflate_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.strl_regions_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                      C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.strl_evidence_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8, C.c_void_p,
@@ -1032,6 +1038,16 @@ class Context:
             self.L.strl_sweep_end(self.h)
         return res, {k: getattr(info, k) for k, _ in SweepInfo._fields_}
 
+    def bgzf_deflate(self, data, block=0xFF00, out=None):
+        """bytes -> (BGZF members back to back, without the EOF block; csize uint32[members]; members that went out stored), on the device (strl_bgzf_deflate)"""
+        return _bgzf_deflate(lambda *a: self.L.strl_bgzf_deflate(self.h, *a), data, block, out)
+
+    def deflate_ms(self):
+        """kernel time (ms) of the last bgzf_deflate call"""
+        ms = C.c_double(0)
+        _check(self.L.strl_ctx_deflate_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def inflate_ms(self):
         """kernel time (ms) of the last inflate_blocks call"""
         ms = C.c_double(0)
@@ -1275,6 +1291,27 @@ def pair_rules(ctx, op, A, B, opts, B_position=None):
         _check(L.strl_pair_rule(None, op, pa + i * sz, pb + i * sz, C.byref(o), int(bp[i]), C.byref(r)))
         res[i] = r.value
     return res, a
+
+
+def bgzf_deflate_bound(n, block=0xFF00):
+    """the output bytes that always suffice for bgzf_deflate of n bytes (strl_bgzf_deflate_bound)"""
+    return int(load().strl_bgzf_deflate_bound(n, block))
+
+
+def _bgzf_deflate(call, data, block, out):
+    """`out`: a caller's uint8 array to write into (tests of the capacity rule and of what is left untouched); default = the bound"""
+    src = np.frombuffer(bytes(data), np.uint8)
+    if out is None:
+        out = np.empty(bgzf_deflate_bound(src.size, block) if 1 <= block <= 0xFF00 else 0, np.uint8)
+    csize = np.zeros((src.size + block - 1) // block if block > 0 else 0, np.uint32)
+    nb, stored = C.c_uint64(0), C.c_uint32(0)
+    _check(call(_ptr(src), src.size, block, out.ctypes.data, out.size, C.byref(nb), _ptr(csize), C.byref(stored)))
+    return out[:nb.value].tobytes(), csize, stored.value
+
+
+def bgzf_deflate_host(data, block=0xFF00, out=None):
+    """Context.bgzf_deflate without a device: the same rule on the calling thread, the same bytes (strl_bgzf_deflate_host)"""
+    return _bgzf_deflate(load().strl_bgzf_deflate_host, data, block, out)
 
 
 def pull_select_host(raw, tile, base_off=0):

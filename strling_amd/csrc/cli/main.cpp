@@ -99,6 +99,13 @@ static Args parse(int argc, char **argv, int first, const std::vector<OptSpec> &
     if (s == "-h" || s == "--help") { fputs(usage, stdout); exit(0); }
     const OptSpec *sp = nullptr;
     if (s.size() > 2 && s[0] == '-' && s[1] == '-') {
+      const size_t eq = s.find('=');                          // --name=VALUE, as the usage texts write the options that take one
+      if (eq != std::string::npos) {
+        for (auto &x : specs) if (x.value && s.substr(2, eq - 2) == x.longn) sp = &x;
+        if (!sp) quit("unknown option %s\n%s", s.c_str(), usage);
+        a.opt[sp->longn] = s.substr(eq + 1);
+        continue;
+      }
       for (auto &x : specs) if (s.substr(2) == x.longn) sp = &x;
       if (!sp) quit("unknown option %s\n%s", s.c_str(), usage);
     } else if (s.size() == 2 && s[0] == '-' && s[1] != '-') {
@@ -2752,6 +2759,19 @@ static PullRegion parse_pull_region(const std::string &s, const std::vector<BamT
   return PullRegion{tid, beg, end};
 }
 
+// BGZF members, in pieces, and the EOF block behind them
+static bool write_members(const std::string &path, const std::vector<std::vector<uint8_t>> &pieces, std::string &why) {
+  static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  FILE *f = fopen(path.c_str(), "wb");
+  if (!f) { why = std::string("cannot write ") + path + ": " + strerror(errno); return false; }
+  bool ok = true;
+  for (auto &o : pieces) ok = ok && fwrite(o.data(), 1, o.size(), f) == o.size();
+  ok = ok && fwrite(eof, 1, 28, f) == 28;
+  ok = (fclose(f) == 0) && ok;
+  if (!ok) why = std::string("cannot write ") + path + ": " + strerror(errno);
+  return ok;
+}
+
 // the output (extract_region.nim:70-80): BGZF blocks of at most 0xFF00 input bytes, deflated on the pool, and the EOF block
 static bool write_bgzf(const std::string &path, const std::vector<uint8_t> &payload, ThreadPool &pool, std::string &why) {
   const size_t BLK = 0xFF00, nb = (payload.size() + BLK - 1) / BLK;
@@ -2780,15 +2800,51 @@ static bool write_bgzf(const std::string &path, const std::vector<uint8_t> &payl
     o.resize(18 + clen + 8);
   });
   if (bad.load()) { why = "deflate failed"; return false; }
-  static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  FILE *f = fopen(path.c_str(), "wb");
-  if (!f) { why = std::string("cannot write ") + path + ": " + strerror(errno); return false; }
-  bool ok = true;
-  for (auto &o : blocks) ok = ok && fwrite(o.data(), 1, o.size(), f) == o.size();
-  ok = ok && fwrite(eof, 1, 28, f) == 28;
-  ok = (fclose(f) == 0) && ok;
-  if (!ok) why = std::string("cannot write ") + path + ": " + strerror(errno);
-  return ok;
+  return write_members(path, blocks, why);
+}
+
+// --deflate=device: the output's members from the BGZF compressor of deflate.hip on pull's context, at most `batch` bytes of
+// payload a call (whole blocks of 0xFF00, so the cuts fall where one call's would); from its host twin -- the same bytes -- when
+// there is no context or a call runs out of device memory.
+struct DeflateStats { const char *form = "zlib"; uint32_t stored = 0; double kernel_ms = 0; };
+static bool write_bgzf_core(const std::string &path, const std::vector<uint8_t> &payload, strl_ctx *ctx, bool verbose, DeflateStats &D, std::string &why) {
+  const uint64_t BLK = 0xFF00;
+  // (STRL_DEFLATE_BATCH_MB: a smaller cut, fractions allowed, for tests of the seam between two calls)
+  const double mb = getenv("STRL_DEFLATE_BATCH_MB") ? atof(getenv("STRL_DEFLATE_BATCH_MB")) : 128.0;
+  const uint64_t asked = mb > 0 && mb < 128.0 ? (uint64_t)(mb * 1048576.0) : (uint64_t)128 << 20;
+  const uint64_t batch = std::max<uint64_t>(BLK, std::min<uint64_t>(asked, (uint64_t)128 << 20) / BLK * BLK);
+  std::vector<std::vector<uint8_t>> pieces(1);
+  std::vector<uint8_t> &out = pieces[0];
+  out.resize((size_t)strl_bgzf_deflate_bound(payload.size(), (uint32_t)BLK));
+  uint64_t at = 0;
+  bool on_device = ctx != nullptr;
+  for (uint64_t off = 0; off < payload.size(); off += batch) {
+    const uint64_t len = std::min<uint64_t>(batch, payload.size() - off);
+    uint64_t got = 0;
+    uint32_t stored = 0;
+    int rc = STRL_ERR_NOMEM;
+    if (on_device) {
+      rc = strl_bgzf_deflate(ctx, payload.data() + off, len, (uint32_t)BLK, out.data() + at, out.size() - at, &got, nullptr, &stored);
+      if (rc == STRL_ERR_NOMEM) {
+        on_device = false;
+        if (verbose) fprintf(stderr, "[strling] pull: the device has no memory for the output's deflate (%s), deflating on the host\n", strl_last_error());
+      } else if (rc != STRL_OK) { why = std::string("device deflate: ") + strl_last_error(); return false; }
+      else {
+        double ms = 0;
+        (void)strl_ctx_deflate_ms(ctx, &ms);
+        D.kernel_ms += ms;
+      }
+    }
+    if (rc == STRL_ERR_NOMEM && (rc = strl_bgzf_deflate_host(payload.data() + off, len, (uint32_t)BLK, out.data() + at, out.size() - at, &got, nullptr, &stored)) != STRL_OK) {
+      why = std::string("deflate: ") + strl_last_error();
+      return false;
+    }
+    at += got;
+    D.stored += stored;
+  }
+  D.form = on_device ? "device" : "core-host";
+  out.resize((size_t)at);
+  return write_members(path, pieces, why);
 }
 
 static int pull_main(int argc, char **argv) {
@@ -2797,10 +2853,15 @@ static int pull_main(int argc, char **argv) {
       "  region           NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive)\n\nOptions:\n"
       "  -o, --output-bam=OUT.bam   path to output bam (default: extracted.bam)\n  -L, --regions=BED          regions as BED rows: chrom start end\n"
       "  -f, --fasta=FASTA          accepted for the reference's command line; a bam needs none\n"
+      "      --deflate=host|device  who compresses the output.  host (default): zlib at its default level.  device: the GPU's BGZF\n"
+      "                             compressor, whose greedy parse gives about zlib level 1's bytes; level 6 gives 0.86 of those,\n"
+      "                             so the file is about 1.15 x as large (same records)\n"
       "  -v, --verbose\n  -h, --help                 Show this help\n";
   if (argc <= 2) { fputs(usage, stdout); return 0; }
-  const Args a = parse(argc, argv, 2, {{"output-bam", 'o', true}, {"regions", 'L', true}, {"fasta", 'f', true}, {"verbose", 'v', false}}, usage);
+  const Args a = parse(argc, argv, 2, {{"output-bam", 'o', true}, {"regions", 'L', true}, {"fasta", 'f', true}, {"verbose", 'v', false}, {"deflate", 0, true}}, usage);
   if (a.pos.empty()) quit("expected a bam\n%s", usage);
+  const std::string deflate = a.get("deflate", "host");
+  if (deflate != "host" && deflate != "device") quit("--deflate must be host or device\n%s", usage);
   const std::string bam = a.pos[0], out_path = a.get("output-bam", "extracted.bam");
   const bool verbose = a.flag("verbose");
   if (!file_exists(bam)) quit("could not open bam");                                                   // :41
@@ -3078,15 +3139,20 @@ static int pull_main(int argc, char **argv) {
     for (uint32_t i : order) payload.insert(payload.end(), store.begin() + (ptrdiff_t)all[i].off, store.begin() + (ptrdiff_t)(all[i].off + all[i].size));
   }
   std::string why;
-  if (!write_bgzf(out_path, payload, pool, why)) quit("couldn't open output bam: %s", why.c_str());       // :72-73
+  DeflateStats DS;
+  if (deflate == "device") {
+    if (!ctx && verbose)
+      fprintf(stderr, "[strling] pull: deflating the output on the host (%s)\n", mode && !strcmp(mode, "host") ? "STRL_PULL=host" : strl_device_count() > 0 ? "no context" : "no device");
+    if (!write_bgzf_core(out_path, payload, ctx, verbose, DS, why)) quit("couldn't open output bam: %s", why.c_str());
+  } else if (!write_bgzf(out_path, payload, pool, why)) quit("couldn't open output bam: %s", why.c_str());       // :72-73
   if (verbose)
     fprintf(stderr,
             "[strling] pull: {\"regions\": %zu, \"tiles\": %zu, \"device_tiles\": %llu, \"host_tiles\": %llu, \"retried_tiles\": %llu, \"kept\": %zu, \"requests\": %zu, "
             "\"windows\": %zu, \"device_windows\": %llu, \"host_windows\": %llu, \"unplaced_requests\": %zu, \"mates\": %zu, \"select_kernel_ms\": %.3f, "
-            "\"mates_kernel_ms\": %.3f, \"device_counts\": %s, \"seconds\": %.3f}\n",
+            "\"mates_kernel_ms\": %.3f, \"device_counts\": %s, \"deflate\": \"%s\", \"deflate_stored_blocks\": %u, \"deflate_kernel_ms\": %.3f, \"seconds\": %.3f}\n",
             regions.size(), tiles.size(), (unsigned long long)S.dev_tiles, (unsigned long long)S.host_tiles, (unsigned long long)S.retried, kept.size(), reqs.size(),
             windows.size(), (unsigned long long)S.dev_windows, (unsigned long long)S.host_windows, unplaced.size(), all.size() - kept.size(), S.select_ms, S.mates_ms,
-            one_device_call ? "true" : "false", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+            one_device_call ? "true" : "false", DS.form, DS.stored, DS.kernel_ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
   return ctx ? end_process(ctx) : 0;
 }
 

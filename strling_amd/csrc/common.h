@@ -194,6 +194,9 @@ struct strl_ctx : TailSet, HeadSet {
   bool pg_attr_done = false;
   hipEvent_t pev[6] = {};
   double inflate_ms = 0;           // kernel time of the last strl_inflate_blocks call
+  // strl_bgzf_deflate (deflate.hip): input, member slots, token slices, sizes and offsets, packed output, CRC tables; kept between calls
+  strl::DevBuf dfl_in, dfl_slots, dfl_tok, dfl_meta, dfl_pack, dfl_crc;
+  double deflate_ms = 0;           // kernel time of the last strl_bgzf_deflate call
   strl::strl_front *front = nullptr;   // device BAM front end (front.h), created by strl_front_begin
   strl::strl_bai *bai = nullptr;       // BAI builder behind the front end's record scan (bamindex.hip), created by strl_bamindex_begin
   strl::strl_sweep *sweep = nullptr;   // `call --sweep`: the evidence of many bounds behind the front end's record scan (sweep.hip), created by strl_sweep_begin
