@@ -135,9 +135,10 @@ __global__ __launch_bounds__(256) void pull_keys_kernel(const strl_pull_row *row
 }
 
 __device__ bool pl_same_name(const uint8_t *u, const strl_pull_row &a, const strl_pull_row &b) {
-  if (a.l_name != b.l_name) return false;
+  const uint32_t ln = a.l_name ? a.l_name - 1u : 0u;           // PlRec::name_len: l_read_name 0 and 1 both carry the name ""
+  if (ln != (b.l_name ? b.l_name - 1u : 0u)) return false;
   const uint8_t *x = u + a.off + 36, *y = u + b.off + 36;
-  for (uint32_t j = 0; j + 1u < a.l_name; ++j) if (x[j] != y[j]) return false;
+  for (uint32_t j = 0; j < ln; ++j) if (x[j] != y[j]) return false;
   return true;
 }
 // one lane per run of equal hash (the lane of the run's first element): counts[qname] over the name's BYTES
