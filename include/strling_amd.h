@@ -817,6 +817,64 @@ int strl_sweep_finish(strl_ctx *ctx, strl_support *out, uint64_t cap, uint64_t *
                       strl_sweep_info *info);
 int strl_sweep_end(strl_ctx *ctx);
 
+/* ---- `strling sort`: a BAM coordinate-sorted on the device, the whole file resident (csrc/bamsort.hip) ----
+ * What `samtools sort` does on the host.  The rule is csrc/bamsort_core.h's, one source for host and device:
+ *   key = tid_u << 33 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1),  tid_u = refID < 0 ? n_ref : refID
+ * -- (reference, position, forward before reverse), records without a reference last, the input order among equal keys (the
+ * sort is stable).  The output stream is the header bytes the caller hands over followed by the records in that order, each
+ * with its block_size word; it is never held whole, pieces of it are gathered on request.
+ *   strl_bamsort_begin      starts a sort; the front end is set up as strl_bamindex_begin sets it up, and like every *_begin of a
+ *                           pass over a file it takes the context's front end over from whatever pass had it.
+ *                           arena_limit_bytes: the most the record arena may hold; 0 = what the device has free, less the
+ *                           finish step's needs.  STRL_SORT_SLAB_MB (tests; default 4096): the size of an arena slab.
+ *   strl_bamsort_reserve    as strl_bamindex_reserve.
+ *   strl_bamsort_push       as strl_sweep_push (without last_chunk): copy, inflate, CRC and record scan of chunk i are enqueued,
+ *                           then key, length and arena position of every record of chunk i - 1 are written and its complete
+ *                           records copied into the arena.  STRL_ERR_NOMEM when the next slab would pass the limit or cannot
+ *                           be allocated: the message gives the bytes held and the bytes needed.
+ *   strl_bamsort_finish     the stable radix sort of (key, ordinal) over the 33 + bits(n_ref) key bits, and the layout: where
+ *                           every record starts in the stream behind `header`'s header_bytes (strl_bamsort_header makes them).
+ *                           STRL_ERR_FORMAT: a refID outside [-1, n_ref) (the message names the record's ordinal), a malformed
+ *                           record, invalid DEFLATE data, a file that ends inside a record; STRL_ERR_CRC;
+ *                           STRL_ERR_LIMIT: more than 2^32 - 2 records.
+ *   strl_bamsort_fetch      out[0, bytes) = the stream's bytes [off, off + bytes); bytes < 4 GiB.
+ *   strl_bamsort_fetch_bgzf the same bytes as BGZF members of 0xFF00 input bytes from the device compressor (the bytes
+ *                           strl_bgzf_deflate gives for them), packed; off must be a multiple of 0xFF00; out_cap >=
+ *                           strl_bgzf_deflate_bound(bytes, 0xFF00).  No EOF block.
+ *   strl_bamsort_order      perm[j] = the input ordinal of the record of output rank j.
+ *   strl_bamsort_info_now   the figures again, gather_ms summed over the fetches so far.
+ *   strl_bamsort_end        gives the sort up (also after an error): what it had in flight has completed on return, arena and
+ *                           tables are freed, and the context takes the next file.
+ * After an error every later push / finish repeats it. */
+typedef struct {
+  uint64_t n_records;      /* records of the file */
+  uint64_t n_no_ref;       /* those without a reference (sorted last) */
+  uint64_t stream_bytes;   /* header_bytes + the bytes of all records */
+  uint32_t already_sorted; /* 1: the permutation is the identity, the input was in order */
+  uint32_t n_slabs;        /* slabs of the arena */
+  uint64_t arena_bytes;    /* ... and their bytes */
+  double sort_ms, layout_ms, gather_ms;   /* HIP-event time of the radix sort, of the layout, of the gathers of all fetches so far */
+} strl_bamsort_info;
+int strl_bamsort_begin(strl_ctx *ctx, int32_t n_ref, uint64_t first_record_offset, uint64_t arena_limit_bytes);
+int strl_bamsort_reserve(strl_ctx *ctx, uint32_t max_blocks, uint64_t max_comp_bytes);
+int strl_bamsort_push(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                      const uint32_t *crc32, uint32_t n_blocks);
+int strl_bamsort_finish(strl_ctx *ctx, const uint8_t *header, uint64_t header_bytes, strl_bamsort_info *info);
+int strl_bamsort_fetch(strl_ctx *ctx, uint64_t off, uint64_t bytes, uint8_t *out);
+int strl_bamsort_fetch_bgzf(strl_ctx *ctx, uint64_t off, uint64_t bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *n_stored);
+int strl_bamsort_order(strl_ctx *ctx, uint32_t *perm, uint64_t cap);
+int strl_bamsort_info_now(strl_ctx *ctx, strl_bamsort_info *info);
+int strl_bamsort_end(strl_ctx *ctx);
+/* The rule without a device.  strl_bamsort_key: the key of the record whose first 20 bytes behind block_size are rec20
+ * (STRL_ERR_FORMAT for a refID outside [-1, n_ref)); strl_bamsort_key_bits: 33 + bits(n_ref), the bits the sort runs over.
+ * strl_bamsort_header: the output's header bytes (magic, l_text, text, reference list) from the input's -- the @HD line's SO:
+ * set to coordinate (added when missing), GO: and SS: dropped, everything else byte for byte, "@HD\tVN:1.6\tSO:coordinate\n" in
+ * front of a text without @HD.  `in` may hold more than the header.  *out_bytes = the bytes needed; STRL_ERR_CAPACITY when cap
+ * is smaller (nothing written). */
+int strl_bamsort_key(const uint8_t *rec20, int32_t n_ref, uint64_t *key);
+int strl_bamsort_key_bits(int32_t n_ref);
+int strl_bamsort_header(const uint8_t *in, uint64_t in_bytes, uint8_t *out, uint64_t cap, uint64_t *out_bytes);
+
 /* ---- the .bai as a by-product of `strling extract`'s own pass (`strling extract --write-index`) ----
  * strl_front_push already copies, inflates, CRC-checks, record-scans and parses every block; the index needs of a record only
  * where it starts, refID, pos, end and flag, and the parse has just written those as dense columns.  A builder attached to the

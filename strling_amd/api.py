@@ -59,6 +59,11 @@ class BamindexInfo(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_no_coor", C.c_uint64), ("n_runs", C.c_uint64), ("n_chunks", C.c_uint64)]
 
 
+class BamsortInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_no_ref", C.c_uint64), ("stream_bytes", C.c_uint64), ("already_sorted", C.c_uint32), ("n_slabs", C.c_uint32),
+                ("arena_bytes", C.c_uint64), ("sort_ms", C.c_double), ("layout_ms", C.c_double), ("gather_ms", C.c_double)]
+
+
 class SweepInfo(C.Structure):
     _fields_ = [("n_answered", C.c_uint64), ("n_seam", C.c_uint64), ("n_passed_on", C.c_uint64), ("n_chunks", C.c_uint64), ("n_records", C.c_uint64),
                 ("sweep_ms", C.c_double), ("evidence_ms", C.c_double)]
@@ -146,7 +151,9 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_front_index_begin", "strl_front_index_blocks", "strl_front_index_finish", "strl_bamindex_begin_csi", "strl_front_index_begin_csi",
            "strl_sweep_begin", "strl_sweep_reserve", "strl_sweep_push", "strl_sweep_finish", "strl_sweep_end",
            "strl_pull_select", "strl_pull_mates", "strl_pull_select_host", "strl_pull_counts_host", "strl_pull_mates_host", "strl_pull_order",
-           "strl_bgzf_deflate", "strl_bgzf_deflate_bound", "strl_bgzf_deflate_host", "strl_ctx_deflate_ms"]
+           "strl_bgzf_deflate", "strl_bgzf_deflate_bound", "strl_bgzf_deflate_host", "strl_ctx_deflate_ms",
+           "strl_bamsort_begin", "strl_bamsort_reserve", "strl_bamsort_push", "strl_bamsort_finish", "strl_bamsort_fetch", "strl_bamsort_fetch_bgzf", "strl_bamsort_order",
+           "strl_bamsort_info_now", "strl_bamsort_end", "strl_bamsort_key", "strl_bamsort_key_bits", "strl_bamsort_header"]
 
 
 def lib_path():
@@ -270,6 +277,19 @@ def load(build_if_missing=True):
     L.strl_bamindex_finish.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(BamindexInfo)]
     L.strl_bamindex_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.strl_bamindex_end.argtypes = [C.c_void_p]
+    L.strl_bamsort_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64]
+    L.strl_bamsort_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    L.strl_bamsort_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.strl_bamsort_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BamsortInfo)]
+    L.strl_bamsort_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.strl_bamsort_fetch_bgzf.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    L.strl_bamsort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_bamsort_info_now.argtypes = [C.c_void_p, C.POINTER(BamsortInfo)]
+    L.strl_bamsort_end.argtypes = [C.c_void_p]
+    L.strl_bamsort_key.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
+    L.strl_bamsort_key_bits.argtypes = [C.c_int32]
+    L.strl_bamsort_header.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.strl_bamsort_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     L.strl_sweep_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8]
     L.strl_sweep_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
     L.strl_sweep_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
@@ -838,7 +858,7 @@ class Context:
     def _bam_blocks(path):
         """the host side of the device front end in Python: BGZF block table (payload offset, payload length, isize, crc), the
         header (inflated here) -> dict(data, blocks, block_off = file offset of each block of the table, n_ref, targets, text, b0 = the block the first record
-        starts in, first_off)"""
+        starts in, first_off, header_raw = the header's inflated bytes)"""
         import struct, zlib
         data = np.fromfile(path, np.uint8)
         raw = data.tobytes()
@@ -878,7 +898,7 @@ class Context:
         while b0 < len(blocks) and cum + blocks[b0][2] <= at:
             cum += blocks[b0][2]
             b0 += 1
-        return dict(data=data, raw=raw, blocks=blocks, block_off=block_off, n_ref=n_ref, targets=targets, text=text, b0=b0, first_off=at - cum)
+        return dict(data=data, raw=raw, blocks=blocks, block_off=block_off, n_ref=n_ref, targets=targets, text=text, b0=b0, first_off=at - cum, header_raw=hdr[:at])
 
     def _front_push_blocks(self, B, c0, c1, chunk_blocks, check_crc, trim=0, index=False, no_offsets_at=None):
         """blocks [c0, c1) of the table through strl_front_push in chunks; trim = inflated bytes at the end of the LAST block that
@@ -1006,6 +1026,88 @@ class Context:
         finally:
             self.L.strl_bamindex_end(self.h)
         return out[:nbytes.value].tobytes(), {k: int(getattr(info, k)) for k, _ in BamindexInfo._fields_}
+
+    # ---- `strling sort` on the device (strl_bamsort_*): the ABI's steps one by one, and the whole sort of a file
+    def bamsort_begin(self, n_ref, first_off, arena_limit_bytes=0):
+        _check(self.L.strl_bamsort_begin(self.h, int(n_ref), int(first_off), int(arena_limit_bytes)))
+
+    def bamsort_reserve(self, max_blocks, max_comp_bytes):
+        _check(self.L.strl_bamsort_reserve(self.h, int(max_blocks), int(max_comp_bytes)))
+
+    def bamsort_push(self, comp, coff, clen, isize, crc=None):
+        """one chunk of BGZF blocks: comp uint8 (pageable memory: the runtime stages the copy), coff uint64 / clen / isize / crc uint32 per block"""
+        _check(self.L.strl_bamsort_push(self.h, comp.ctypes.data, comp.size, _ptr(coff), _ptr(clen), _ptr(isize), _ptr(crc) if crc is not None else None, len(coff)))
+
+    def bamsort_finish(self, header):
+        """header: the output's header bytes (bamsort_header) -> dict of strl_bamsort_info"""
+        h = np.frombuffer(bytes(header), np.uint8)
+        info = BamsortInfo()
+        _check(self.L.strl_bamsort_finish(self.h, _ptr(h), h.size, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in BamsortInfo._fields_}
+
+    def bamsort_info(self):
+        info = BamsortInfo()
+        _check(self.L.strl_bamsort_info_now(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in BamsortInfo._fields_}
+
+    def bamsort_fetch(self, off, nbytes):
+        out = np.zeros(max(1, nbytes), np.uint8)
+        _check(self.L.strl_bamsort_fetch(self.h, int(off), int(nbytes), out.ctypes.data))
+        return out[:nbytes].tobytes()
+
+    def bamsort_fetch_bgzf(self, off, nbytes):
+        """-> (BGZF members of the stream's bytes [off, off + nbytes) from the device compressor, members stored)"""
+        out = np.zeros(max(1, bgzf_deflate_bound(nbytes)), np.uint8)
+        nb, stored = C.c_uint64(0), C.c_uint32(0)
+        _check(self.L.strl_bamsort_fetch_bgzf(self.h, int(off), int(nbytes), out.ctypes.data, out.size, C.byref(nb), C.byref(stored)))
+        return out[:nb.value].tobytes(), stored.value
+
+    def bamsort_order(self, n):
+        perm = np.zeros(max(1, n), np.uint32)
+        _check(self.L.strl_bamsort_order(self.h, perm.ctypes.data, n))
+        return perm[:n]
+
+    def bamsort_end(self):
+        self.L.strl_bamsort_end(self.h)
+
+    def bamsort_probe(self, lens, base, lo, hi):
+        """test-only (strl_bamsort_probe): the layout and the piece search over caller-given lengths and a 64-bit base
+        -> (off uint64[n + 1], (first, end) of the touched records, parts uint64[touched, 3] = source skip, destination, bytes)"""
+        l = np.ascontiguousarray(lens, np.uint32)
+        off = np.zeros(l.size + 1, np.uint64)
+        rng = np.zeros(2, np.uint64)
+        parts = np.zeros((max(1, l.size), 3), np.uint64)
+        _check(self.L.strl_bamsort_probe(self.h, _ptr(l), l.size, int(base), int(lo), int(hi), off.ctypes.data, rng.ctypes.data, parts.ctypes.data, l.size))
+        a, b = int(rng[0]), int(rng[1])
+        return off, (a, b), parts[:b - a]
+
+    def bamsort(self, path, chunk_blocks=16384, check_crc=True, arena_limit_bytes=0, keep_open=False):
+        """a BAM FILE coordinate-sorted on the device -> (the output stream: header || records in sorted order, strl_bamsort_info as a
+        dict, the permutation).  keep_open: the sort is left on the context for further fetches (bamsort_end ends it)."""
+        B = self._bam_blocks(path)
+        header = bamsort_header(B["header_raw"])
+        self.bamsort_begin(B["n_ref"], B["first_off"], arena_limit_bytes)
+        try:
+            data, blocks, keep = B["data"], B["blocks"], []
+            for s0 in range(B["b0"], len(blocks), chunk_blocks):
+                cb = blocks[s0:s0 + chunk_blocks]
+                lo, hi = cb[0][0], cb[-1][0] + cb[-1][1]
+                comp = np.ascontiguousarray(data[lo:hi])
+                coff = np.array([b[0] - lo for b in cb], np.uint64)
+                clen = np.array([b[1] for b in cb], np.uint32)
+                isz = np.array([b[2] for b in cb], np.uint32)
+                crc = np.array([b[3] for b in cb], np.uint32)
+                keep = (keep + [(comp, coff, clen, isz, crc)])[-3:]      # pageable memory: the copy is staged by the runtime
+                self.bamsort_push(comp, coff, clen, isz, crc if check_crc else None)
+            info = self.bamsort_finish(header)
+            stream = self.bamsort_fetch(0, info["stream_bytes"])
+            perm = self.bamsort_order(info["n_records"])
+        except Exception:
+            self.bamsort_end()
+            raise
+        if not keep_open:
+            self.bamsort_end()
+        return stream, info, perm
 
     def sweep(self, path, bounds, window, frag, min_mapq=20, chunk_blocks=16384, check_crc=True):
         """the evidence of every bound from one pass over a coordinate-sorted BAM FILE (strl_sweep_begin / _push / _finish):
@@ -1291,6 +1393,32 @@ def pair_rules(ctx, op, A, B, opts, B_position=None):
         _check(L.strl_pair_rule(None, op, pa + i * sz, pb + i * sz, C.byref(o), int(bp[i]), C.byref(r)))
         res[i] = r.value
     return res, a
+
+
+def bamsort_key(rec20, n_ref):
+    """the sort key of a record from its first 20 bytes behind block_size (strl_bamsort_key; csrc/bamsort_core.h)"""
+    b = np.frombuffer(bytes(rec20[:20]), np.uint8)
+    if b.size != 20:
+        raise ValueError("20 bytes of a record are needed")
+    key = C.c_uint64(0)
+    _check(load().strl_bamsort_key(b.ctypes.data, int(n_ref), C.byref(key)))
+    return key.value
+
+
+def bamsort_key_bits(n_ref):
+    return int(load().strl_bamsort_key_bits(int(n_ref)))
+
+
+def bamsort_header(raw):
+    """the header bytes of `strling sort`'s output from the input's inflated bytes (which may go on behind the header): strl_bamsort_header"""
+    src = np.frombuffer(bytes(raw), np.uint8)
+    n = C.c_uint64(0)
+    rc = load().strl_bamsort_header(_ptr(src), src.size, None, 0, C.byref(n))
+    if rc not in (0, -4):
+        _check(rc)
+    out = np.zeros(max(1, n.value), np.uint8)
+    _check(load().strl_bamsort_header(_ptr(src), src.size, out.ctypes.data, out.size, C.byref(n)))
+    return out[:n.value].tobytes()
 
 
 def bgzf_deflate_bound(n, block=0xFF00):

@@ -1,0 +1,126 @@
+// bamsort_core.h -- the rule of `strling sort` (coordinate order of a BAM), one source for the host path (cli/sort_cli.cpp), the
+// device path (bamsort.hip), the library's host entries (strl_bamsort_key / strl_bamsort_header) and the stand-alone test
+// program (tests/emu/bamsort_core_main.cpp): the key of a record, the output's header, and where the records that touch a piece
+// [lo, hi) of the output stream lie.  DESIGN section 24.
+//
+//   key    = tid_u << 33 | (uint32)(pos + 1) << 1 | reverse strand,  tid_u = refID < 0 ? n_ref : refID
+//            -> (reference, position, forward before reverse), records without a reference last; a STABLE sort keeps the
+//            input order among equal keys.  This is the comparator samtools documents for `sort` without -n / -t.
+//   stream = header bytes || records in sorted order, each with its block_size word; cut into BGZF members of 0xFF00 bytes.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+#if defined(__HIPCC__)
+#define BSORT_HD __host__ __device__
+#else
+#define BSORT_HD
+#endif
+#include <string>
+#include <vector>
+
+namespace strl {
+
+constexpr uint32_t BSORT_BLK = 0xFF00;                   // input bytes of a BGZF member of the output (write_bgzf's cut)
+constexpr uint64_t BSORT_MAX_RECORDS = 0xfffffffeull;    // radix_sort_pairs counts in 32 bits
+constexpr uint32_t BSORT_KEY_BYTES = 20;                 // bytes behind block_size the key is made from
+constexpr uint32_t BSORT_MIN_REC = 36;                   // block_size word + the 32 fixed bytes of a record
+
+BSORT_HD inline uint32_t bsort_ld32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// bits needed to write x (0 for 0)
+BSORT_HD inline int bsort_bits(uint32_t x) { int b = 0; while (x) { ++b; x >>= 1; } return b; }
+// the key bits that can differ: what the sort runs over
+BSORT_HD inline int bsort_key_bits(int32_t n_ref) { return 33 + bsort_bits((uint32_t)n_ref); }
+
+// key of the record whose first 20 bytes behind block_size are `body` (refID, pos, l_read_name, mapq, bin, n_cigar_op, flag, l_seq).
+// false: the refID is not one of the header's (refID >= n_ref or refID < -1); *key is then the key of a record without a reference
+BSORT_HD inline bool bsort_key(const uint8_t *body, int32_t n_ref, uint64_t *key) {
+  const int32_t tid = (int32_t)bsort_ld32(body), pos = (int32_t)bsort_ld32(body + 4);
+  const uint32_t flag = (uint32_t)body[14] | (uint32_t)body[15] << 8;
+  const bool ok = tid >= -1 && tid < n_ref;
+  const uint64_t tid_u = (tid < 0 || !ok) ? (uint64_t)(uint32_t)n_ref : (uint64_t)(uint32_t)tid;
+  *key = tid_u << 33 | (uint64_t)(uint32_t)(pos + 1) << 1 | (uint64_t)(flag >> 4 & 1u);
+  return ok;
+}
+
+// ---- pieces of the output stream -------------------------------------------------------------------------------------------
+// off[0 .. n]: off[j] = stream offset of the record of rank j, off[n] = the stream's end (ascending; every record has bytes).
+// The records that touch [lo, hi), lo < hi: ranks [bsort_first_touch, bsort_end_touch).
+BSORT_HD inline uint64_t bsort_first_touch(const uint64_t *off, uint64_t n, uint64_t lo) {      // the first j with off[j + 1] > lo (n: none)
+  uint64_t a = 0, b = n;
+  while (a < b) { const uint64_t m = a + (b - a) / 2; if (off[m + 1] > lo) b = m; else a = m + 1; }
+  return a;
+}
+BSORT_HD inline uint64_t bsort_end_touch(const uint64_t *off, uint64_t n, uint64_t hi) {        // the first j with off[j] >= hi (n: none)
+  uint64_t a = 0, b = n;
+  while (a < b) { const uint64_t m = a + (b - a) / 2; if (off[m] >= hi) b = m; else a = m + 1; }
+  return a;
+}
+// the part of a record [beg, end) of the stream that lies inside the piece: bytes to skip at its start, where they go in the
+// piece, how many
+struct BsortPart { uint64_t skip, dst, bytes; };
+BSORT_HD inline BsortPart bsort_part(uint64_t beg, uint64_t end, uint64_t lo, uint64_t hi) {
+  const uint64_t a = beg > lo ? beg : lo, b = end < hi ? end : hi;
+  BsortPart p;
+  p.skip = a - beg; p.dst = a - lo; p.bytes = b > a ? b - a : 0;
+  return p;
+}
+
+// ---- the header (host) ------------------------------------------------------------------------------------------------------------
+// The text of the output: the input's, with the @HD line's SO: set to coordinate (added at the end of the line when the line has
+// none), GO: and SS: dropped, the line's other fields and every other line byte for byte; a text whose first line is not @HD
+// gets "@HD\tVN:1.6\tSO:coordinate\n" in front.
+inline std::string bsort_header_text(const std::string &text) {
+  const bool hd = text.size() >= 3 && !text.compare(0, 3, "@HD") && (text.size() == 3 || text[3] == '\t' || text[3] == '\n');
+  if (!hd) return "@HD\tVN:1.6\tSO:coordinate\n" + text;
+  size_t eol = text.find('\n');
+  const bool has_nl = eol != std::string::npos;
+  if (!has_nl) { eol = text.size(); while (eol > 3 && text[eol - 1] == '\0') --eol; }      // (NUL padding behind a last line without \n stays behind it)
+  std::string line = "@HD";
+  bool so = false;
+  size_t at = 3;
+  while (at < eol) {                         // text[at] == '\t'
+    size_t e = text.find('\t', at + 1);
+    if (e == std::string::npos || e > eol) e = eol;
+    const std::string f = text.substr(at + 1, e - at - 1);
+    if (!f.compare(0, 3, "SO:")) { if (!so) line += "\tSO:coordinate"; so = true; }
+    else if (f.compare(0, 3, "GO:") && f.compare(0, 3, "SS:")) line += "\t" + f;
+    at = e;
+  }
+  if (!so) line += "\tSO:coordinate";
+  return line + text.substr(eol);
+}
+
+// The output's header bytes (magic, l_text, text, n_ref, the reference list) from the input's: the text by the rule above,
+// l_text to match, the binary reference list byte for byte.  `in` may hold bytes behind the header (records); *used = bytes of the
+// input's header.  false: `err` says what is wrong with the input's header.
+inline bool bsort_header(const uint8_t *in, size_t in_bytes, std::vector<uint8_t> &out, int32_t *n_ref, size_t *used, std::string &err) {
+  if (in_bytes < 12 || memcmp(in, "BAM\1", 4)) { err = "not a BAM header (magic)"; return false; }
+  const uint32_t l_text = bsort_ld32(in + 4);
+  if ((uint64_t)l_text + 12 > in_bytes) { err = "BAM header: l_text reaches past the bytes given"; return false; }
+  size_t at = 8 + (size_t)l_text;
+  const int32_t nr = (int32_t)bsort_ld32(in + at);
+  if (nr < 0) { err = "BAM header: negative n_ref"; return false; }
+  const size_t refs = at;
+  at += 4;
+  for (int32_t t = 0; t < nr; ++t) {
+    if (at + 4 > in_bytes) { err = "BAM header: the reference list reaches past the bytes given"; return false; }
+    const uint32_t l_name = bsort_ld32(in + at);
+    if ((uint64_t)at + 8 + l_name > in_bytes) { err = "BAM header: the reference list reaches past the bytes given"; return false; }
+    at += 8 + (size_t)l_name;
+  }
+  const std::string text = bsort_header_text(std::string(reinterpret_cast<const char *>(in + 8), l_text));
+  if (text.size() > 0x7fffffffu) { err = "BAM header: text of more than 2^31 bytes"; return false; }
+  out.clear();
+  out.reserve(8 + text.size() + (at - refs));
+  out.insert(out.end(), in, in + 4);
+  const uint32_t lt = (uint32_t)text.size();
+  for (int k = 0; k < 4; ++k) out.push_back((uint8_t)(lt >> (8 * k)));
+  out.insert(out.end(), text.begin(), text.end());
+  out.insert(out.end(), in + refs, in + at);
+  if (n_ref) *n_ref = nr;
+  if (used) *used = at;
+  return true;
+}
+
+}  // namespace strl

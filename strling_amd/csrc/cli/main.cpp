@@ -33,13 +33,14 @@
 #include "region_feed.h"
 #include "cram_reader.h"
 #include "cram_codecs.h"
+#include "cli_shared.h"
 
 using namespace strl;
 using Tick = std::chrono::steady_clock::time_point;
 static Tick tick() { return std::chrono::steady_clock::now(); }
 static double span(Tick x, Tick y) { return std::chrono::duration<double>(y - x).count(); }
 
-static std::thread *g_bg_init = nullptr;   // device bring-up running beside the first host pass; exit() waits for it
+std::thread *g_bg_init = nullptr;   // device bring-up running beside the first host pass; exit() waits for it
 static std::function<void()> g_bg_abort;   // ... after telling it to stop waiting for what the quitting thread will never publish
 // --device K (or STRL_DEVICE=K): the device the first context of this process sits on; --gpus N takes K, K + 1, ... (mod the
 // devices there are).  A pipeline that runs one `strling` process per sample (pipelines/bpipe.config:4) gives every process its
@@ -47,13 +48,13 @@ static std::function<void()> g_bg_abort;   // ... after telling it to stop waiti
 static double since_exec();
 static double g_main_at = -1;      // seconds between exec and main()
 static int g_device0 = 0;
-static void set_device0(const std::string &v) {
+void set_device0(const std::string &v) {
   const char *e = getenv("STRL_DEVICE");
   g_device0 = std::max(0, atoi(!v.empty() ? v.c_str() : (e ? e : "0")));
 }
-static int device_of(int g) { return (g_device0 + g) % std::max(1, strl_device_count()); }
+int device_of(int g) { return (g_device0 + g) % std::max(1, strl_device_count()); }
 
-[[noreturn]] static void quit(const char *fmt, ...) {   // Nim `quit msg`: message on stderr, exit code 1
+[[noreturn]] void quit(const char *fmt, ...) {   // Nim `quit msg`: message on stderr, exit code 1
   va_list ap;
   va_start(ap, fmt);
   vfprintf(stderr, fmt, ap);
@@ -82,17 +83,7 @@ static void report_assign(strl_ctx *ctx) {
           (unsigned long long)I.n_loci, (unsigned long long)I.n_groups, (unsigned long long)I.n_assigned, (unsigned long long)I.n_lost, I.seconds);
 }
 
-struct Args {
-  std::map<std::string, std::string> opt;
-  std::vector<std::string> pos;
-  bool flag(const char *k) const { return opt.count(k) != 0; }
-  std::string get(const char *k, const char *dflt) const { auto it = opt.find(k); return it == opt.end() ? dflt : it->second; }
-};
-
-// long name -> (short name, takes value)
-struct OptSpec { const char *longn; char shortn; bool value; };
-
-static Args parse(int argc, char **argv, int first, const std::vector<OptSpec> &specs, const char *usage) {
+Args parse(int argc, char **argv, int first, const std::vector<OptSpec> &specs, const char *usage) {
   Args a;
   for (int i = first; i < argc; ++i) {
     std::string s = argv[i];
@@ -182,7 +173,7 @@ static void quit_open(const std::string &path, const std::string &err) {
   quit("couldn't open bam");
 }
 
-static int decode_threads() {
+int decode_threads() {
   const char *e = getenv("STRL_THREADS");
   if (e && atoi(e) > 0) return atoi(e);
   // 1.5 threads per granted CPU: decode threads stall on page faults of the file mapping and on memory, so a modest
@@ -224,7 +215,7 @@ static void fragment_length_distribution(const std::string &bam, uint32_t frag[4
 // The FASTA is read front to back with zlib (plain, gzip or bgzip), one contig in memory at a time, in file order --
 // the order hts-nim's Fai enumerates.  Windows are scored on the device (strl_index_chrom); merging + trimming is
 // strl_index_regions.  Returns the number of rows written.
-static bool file_exists(const std::string &p) { return access(p.c_str(), F_OK) == 0; }
+bool file_exists(const std::string &p) { return access(p.c_str(), F_OK) == 0; }
 
 static uint64_t build_genome_index(strl_ctx *ctx, const std::string &fasta, const std::string &bed_path) {
   gzFile in = gzopen(fasta.c_str(), "rb");
@@ -671,31 +662,6 @@ static int extract_main(int argc, char **argv) {
   return 0;
 }
 
-static int end_process(strl_ctx *ctx);
-
-// N page-locked chunk buffers and their N block tables (chunk_feed.h), allocated on a thread per buffer: the time is the kernel's,
-// faulting and locking the pages.  Nothing is freed unless release() is called: `call` and `bamindex` leave theirs to the end of
-// the process on purpose.
-struct PinnedRing {
-  std::vector<uint8_t *> data, meta;
-  void alloc(size_t n, size_t chunk_blocks, size_t chunk_bytes) {
-    data.assign(n, nullptr); meta.assign(n, nullptr);
-    auto one = [&](size_t k) {
-      data[k] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_data_bytes(chunk_bytes)));
-      meta[k] = static_cast<uint8_t *>(strl_pinned_alloc(chunk_table_bytes(chunk_blocks)));
-    };
-    std::vector<std::thread> each;
-    for (size_t k = 1; k < n; ++k) each.emplace_back(one, k);
-    one(0);
-    for (auto &t : each) t.join();
-  }
-  bool ok() const { return !data.empty() && !std::count(data.begin(), data.end(), nullptr) && !std::count(meta.begin(), meta.end(), nullptr); }
-  void release_except(const void *a, const void *b) {      // (freeing twice is harmless: the pointers are nulled)
-    for (auto *v : {&data, &meta})
-      for (uint8_t *&q : *v) if (q && q != a && q != b) { strl_pinned_free(q); q = nullptr; }
-  }
-  void release() { release_except(nullptr, nullptr); }
-};
 
 // `strling extract` with the BAM front end on the device: this thread walks BGZF headers and copies compressed bytes into
 // page-locked buffers; inflate, record scan, parse, scorer, pair logic all run on the GPU (extract.nim:275-348).
@@ -1419,7 +1385,7 @@ static int extract_front(const Args &a, const std::string &bam, const std::strin
 // The end of a `strling` process whose outputs are closed: the driver reclaims device and page-locked memory faster than the
 // runtime's own shutdown does piece by piece (~0.15 s and more with gigabytes mapped).  Under a profiler the normal exit path is
 // kept -- its tool library writes its files from an exit handler -- and STRL_TEARDOWN=1 asks for it explicitly.
-static int end_process(strl_ctx *ctx) {
+int end_process(strl_ctx *ctx) {
   const char *pre = getenv("LD_PRELOAD");
   if (getenv("STRL_TEARDOWN") || (pre && strstr(pre, "rocprof")) || getenv("ROCP_TOOL_LIBRARIES") || getenv("ROCPROFILER_LIBRARY_CTOR")) {
     if (ctx) strl_ctx_destroy(ctx);
@@ -2772,6 +2738,28 @@ static bool write_members(const std::string &path, const std::vector<std::vector
   return ok;
 }
 
+// one BGZF member of `len` <= 0xFF00 input bytes: zlib at its default level (what htslib writes)
+bool bgzf_member_zlib(const uint8_t *src, size_t len, std::vector<uint8_t> &o) {
+  o.resize(18 + compressBound((uLong)len) + 64 + 8);
+  z_stream zs;
+  memset(&zs, 0, sizeof zs);
+  if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+  zs.next_in = const_cast<uint8_t *>(src); zs.avail_in = (uInt)len;
+  zs.next_out = o.data() + 18; zs.avail_out = (uInt)(o.size() - 26);
+  const int rc = deflate(&zs, Z_FINISH);
+  const size_t clen = zs.total_out;
+  deflateEnd(&zs);
+  if (rc != Z_STREAM_END || 18 + clen + 8 > 65536) return false;
+  const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+  memcpy(o.data(), hdr, 16);
+  const uint16_t bsize = (uint16_t)(18 + clen + 8 - 1);
+  memcpy(o.data() + 16, &bsize, 2);
+  const uint32_t crc = (uint32_t)crc32(crc32(0, nullptr, 0), src, (uInt)len), isz = (uint32_t)len;
+  memcpy(o.data() + 18 + clen, &crc, 4); memcpy(o.data() + 18 + clen + 4, &isz, 4);
+  o.resize(18 + clen + 8);
+  return true;
+}
+
 // the output (extract_region.nim:70-80): BGZF blocks of at most 0xFF00 input bytes, deflated on the pool, and the EOF block
 static bool write_bgzf(const std::string &path, const std::vector<uint8_t> &payload, ThreadPool &pool, std::string &why) {
   const size_t BLK = 0xFF00, nb = (payload.size() + BLK - 1) / BLK;
@@ -2780,24 +2768,7 @@ static bool write_bgzf(const std::string &path, const std::vector<uint8_t> &payl
   pool.parallel_for(nb, [&](size_t k) {
     const uint8_t *src = payload.data() + k * BLK;
     const size_t len = std::min(BLK, payload.size() - k * BLK);
-    std::vector<uint8_t> &o = blocks[k];
-    o.resize(18 + compressBound((uLong)len) + 64 + 8);
-    z_stream zs;
-    memset(&zs, 0, sizeof zs);
-    if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { bad = true; return; }
-    zs.next_in = const_cast<uint8_t *>(src); zs.avail_in = (uInt)len;
-    zs.next_out = o.data() + 18; zs.avail_out = (uInt)(o.size() - 26);
-    const int rc = deflate(&zs, Z_FINISH);
-    const size_t clen = zs.total_out;
-    deflateEnd(&zs);
-    if (rc != Z_STREAM_END || 18 + clen + 8 > 65536) { bad = true; return; }
-    const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-    memcpy(o.data(), hdr, 16);
-    const uint16_t bsize = (uint16_t)(18 + clen + 8 - 1);
-    memcpy(o.data() + 16, &bsize, 2);
-    const uint32_t crc = (uint32_t)crc32(crc32(0, nullptr, 0), src, (uInt)len), isz = (uint32_t)len;
-    memcpy(o.data() + 18 + clen, &crc, 4); memcpy(o.data() + 18 + clen + 4, &isz, 4);
-    o.resize(18 + clen + 8);
+    if (!bgzf_member_zlib(src, len, blocks[k])) bad = true;
   });
   if (bad.load()) { why = "deflate failed"; return false; }
   return write_members(path, blocks, why);
@@ -3184,7 +3155,8 @@ int main(int argc, char **argv) {
       "  index    :   identify large STRs in the reference genome, to produce ref.fasta.str.\n"
       "  outliers :   cohort STR outlier scores from the call outputs of many samples (scripts/strling-outliers.py).\n"
       "  bamindex :   build the index (.bai, or .csi with --csi) of a coordinate-sorted BAM on the GPU (what `samtools index` writes).\n"
-      "  pull     :   write a region's reads and their mates to a small BAM, for debugging (the reference's pull_region).\n";      // strling.nim:18-24
+      "  pull     :   write a region's reads and their mates to a small BAM, for debugging (the reference's pull_region).\n"
+      "  sort     :   coordinate-sort a BAM on the GPU (what `samtools sort` writes).\n";      // strling.nim:18-24
   if (argc < 2) { fputs(top, stdout); return 1; }
   const std::string cmd = argv[1];
   if (cmd == "extract") return extract_main(argc, argv);
@@ -3194,6 +3166,7 @@ int main(int argc, char **argv) {
   if (cmd == "outliers") return outliers_main(argc, argv);
   if (cmd == "bamindex") return bamindex_main(argc, argv);
   if (cmd == "pull") return pull_main(argc, argv);
+  if (cmd == "sort") return sort_main(argc, argv);
   if (cmd == "_dump") return dump_main(argc, argv);
   if (cmd == "_decode") return decode_main(argc, argv);
   if (cmd == "_region") return region_main(argc, argv);

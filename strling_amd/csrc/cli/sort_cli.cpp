@@ -1,0 +1,342 @@
+// sort_cli.cpp -- `strling sort`: a BAM coordinate-sorted, the step between the aligner and `strling extract` (the reference's
+// simulator shells out to `samtools sort` for it, simulate_reads.nim:178).  The rule is csrc/bamsort_core.h's.
+//
+// Device path: fed exactly as `strling bamindex` is (BgzfFeed, ChunkAhead, STRL_CHUNK_BLOCKS, the context brought up on a thread
+// beside the first chunk's read); strl_bamsort_* keeps key, length and the records themselves on the device, sorts, and the output
+// stream is fetched piece by piece -- the fetch of piece k + 1 beside the host's deflate / write of piece k.
+// Host path (STRL_SORT=host, or no device): the host BAM reader, std::stable_sort on the same key, the same header, the same
+// stream, the same member cuts -- with --deflate=host the two paths write the same bytes.
+// The output is written under a temporary name and renamed at the end: a failed run leaves no file.
+#include <errno.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+#include <algorithm>
+#include <chrono>
+#include <functional>
+#include <numeric>
+#include <string>
+#include <thread>
+#include <vector>
+#include "cli_shared.h"
+#include "bam_reader.h"
+#include "bgzf_feed.h"
+#include "cram_reader.h"
+#include "../bamsort_core.h"
+#include "../front.h"
+
+using namespace strl;
+
+namespace {
+
+using Clock = std::chrono::steady_clock;
+double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
+
+const char *USAGE =
+    "strling sort\n\nUsage:\n  strling sort [options] -o OUT.bam IN.bam\n\nArguments:\n  IN.bam           path to a bam file, in any order\n\nOptions:\n"
+    "  -o, --output=OUT.bam       required; written through a temporary name, so a failed run leaves no file\n"
+    "      --deflate=host|device  host (default): zlib at its default level on the pool, as pull.  device: the GPU's compressor (about 1.15 x the bytes)\n"
+    "  -D, --device=K             GPU to use (default: 0)\n"
+    "  -v, --verbose              one JSON line on stderr\n  -h, --help                 Show this help\n";
+
+struct Seconds { double read = 0, sort = 0, gather = 0, deflate = 0, write = 0; };
+
+// the output file: members appended under a temporary name, the EOF block and the rename at the end
+struct SortOut {
+  std::string path, tmp;
+  FILE *f = nullptr;
+  bool open(const std::string &out, std::string &why) {
+    path = out;
+    tmp = out + ".tmp." + std::to_string((long long)getpid());
+    f = fopen(tmp.c_str(), "wb");
+    if (!f) why = "cannot write " + tmp + ": " + strerror(errno);
+    return f != nullptr;
+  }
+  bool put(const uint8_t *p, size_t n, std::string &why) {
+    if (n && fwrite(p, 1, n, f) != n) { why = "cannot write " + tmp + ": " + strerror(errno); return false; }
+    return true;
+  }
+  bool close(std::string &why) {
+    static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool ok = put(eof, 28, why);
+    ok = (fclose(f) == 0) && ok;
+    f = nullptr;
+    if (ok && rename(tmp.c_str(), path.c_str()) != 0) ok = false;
+    if (!ok) { if (why.empty()) why = "cannot write " + path + ": " + strerror(errno); unlink(tmp.c_str()); }
+    return ok;
+  }
+  void drop() { if (f) { fclose(f); f = nullptr; } if (!tmp.empty()) unlink(tmp.c_str()); }
+};
+
+// the members of a piece of the stream (whole 0xFF00 blocks but for the stream's last), on the pool: zlib, or the compressor's host twin
+bool deflate_piece(const uint8_t *p, size_t n, bool core, ThreadPool &pool, std::vector<uint8_t> &out, uint32_t &stored, std::string &why) {
+  const size_t nb = (n + BSORT_BLK - 1) / BSORT_BLK;
+  std::vector<std::vector<uint8_t>> blocks(nb);
+  std::vector<uint32_t> st(nb, 0);
+  std::vector<int> bad(nb, 0);
+  pool.parallel_for(nb, [&](size_t k) {
+    const uint8_t *src = p + k * BSORT_BLK;
+    const size_t len = std::min<size_t>(BSORT_BLK, n - k * BSORT_BLK);
+    if (!core) { bad[k] = !bgzf_member_zlib(src, len, blocks[k]); return; }
+    blocks[k].resize((size_t)strl_bgzf_deflate_bound(len, BSORT_BLK));
+    uint64_t got = 0;
+    bad[k] = strl_bgzf_deflate_host(src, len, BSORT_BLK, blocks[k].data(), blocks[k].size(), &got, nullptr, &st[k]) != 0;
+    blocks[k].resize((size_t)got);
+  });
+  out.clear();
+  for (size_t k = 0; k < nb; ++k) {
+    if (bad[k]) { why = "deflate failed"; return false; }
+    out.insert(out.end(), blocks[k].begin(), blocks[k].end());
+    stored += st[k];
+  }
+  return true;
+}
+
+uint64_t piece_bytes() {
+  const char *e = getenv("STRL_SORT_PIECE_KB");                // tests: pieces that cut records, block_size words and the header
+  const uint64_t want = e && atof(e) > 0 ? (uint64_t)(atof(e) * 1024.0) : (uint64_t)128 << 20;
+  return std::max<uint64_t>(BSORT_BLK, want / BSORT_BLK * BSORT_BLK);
+}
+
+struct Result {
+  uint64_t records = 0, no_ref = 0, stream_bytes = 0, slabs = 0, out_bytes = 0;
+  bool already_sorted = false;
+  const char *deflate = "zlib";
+  uint32_t stored = 0;
+  Seconds s;
+};
+
+// ---- the host path ---------------------------------------------------------------------------------------------------------------
+bool sort_on_host(const std::string &bam, const std::vector<uint8_t> &header, int32_t n_ref, bool core, SortOut &out, Result &R, std::string &why, int &status) {
+  auto t0 = Clock::now();
+  BamReader rd;
+  std::string err;
+  status = STRL_ERR_FORMAT;
+  if (!rd.open(bam, err)) { why = err.empty() ? "couldn't open bam" : err; return false; }
+  std::vector<uint8_t> raw;
+  for (;;) {
+    const int64_t got = rd.read_raw(raw, 1 << 20, err);
+    if (got < 0) { why = err.empty() ? "malformed BAM (truncated file or invalid BGZF block)" : err; return false; }
+    if (!got) break;
+  }
+  std::vector<uint64_t> at, key;
+  for (size_t q = 0; q < raw.size();) {
+    const uint32_t bs = bsort_ld32(raw.data() + q);
+    if ((uint64_t)bs + 4 > FRONT_CARRY_MAX) { why = "BAM record of more than " + std::to_string(FRONT_CARRY_MAX) + " bytes"; return false; }
+    uint64_t k = 0;
+    if (!bsort_key(raw.data() + q + 4, n_ref, &k)) {
+      why = "malformed BAM record " + std::to_string(at.size()) + ": its refID is not one of the header's " + std::to_string(n_ref) + " references";
+      return false;
+    }
+    if (at.size() >= BSORT_MAX_RECORDS) { why = "more than 2^32 - 2 records: beyond one sort"; status = STRL_ERR_LIMIT; return false; }
+    R.no_ref += (int32_t)bsort_ld32(raw.data() + q + 4) < 0;
+    at.push_back(q); key.push_back(k);
+    q += 4 + (size_t)bs;
+  }
+  R.s.read = since(t0);
+  t0 = Clock::now();
+  const size_t n = at.size();
+  std::vector<uint32_t> perm(n);
+  std::iota(perm.begin(), perm.end(), 0u);
+  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+  R.already_sorted = true;
+  std::vector<uint64_t> off(n + 1);
+  uint64_t run = header.size();
+  for (size_t j = 0; j < n; ++j) {
+    off[j] = run;
+    run += 4 + (uint64_t)bsort_ld32(raw.data() + at[perm[j]]);
+    if (perm[j] != j) R.already_sorted = false;
+  }
+  off[n] = run;
+  R.records = n; R.stream_bytes = run;
+  R.s.sort = since(t0);
+  ThreadPool pool(std::min(decode_threads(), 16));
+  const uint64_t piece = piece_bytes();
+  std::vector<uint8_t> buf, members;
+  status = STRL_ERR_IO;
+  for (uint64_t lo = 0; lo < run; lo += piece) {
+    const uint64_t hi = std::min(run, lo + piece);
+    t0 = Clock::now();
+    buf.resize((size_t)(hi - lo));
+    if (lo < header.size()) memcpy(buf.data(), header.data() + lo, (size_t)(std::min<uint64_t>(hi, header.size()) - lo));
+    const uint64_t a = bsort_first_touch(off.data(), n, lo), b = bsort_end_touch(off.data(), n, hi);
+    for (uint64_t j = a; j < b; ++j) {
+      const BsortPart p = bsort_part(off[j], off[j + 1], lo, hi);
+      memcpy(buf.data() + p.dst, raw.data() + at[perm[j]] + p.skip, (size_t)p.bytes);
+    }
+    R.s.gather += since(t0);
+    t0 = Clock::now();
+    if (!deflate_piece(buf.data(), buf.size(), core, pool, members, R.stored, why)) return false;
+    R.s.deflate += since(t0);
+    t0 = Clock::now();
+    if (!out.put(members.data(), members.size(), why)) return false;
+    R.out_bytes += members.size();
+    R.s.write += since(t0);
+  }
+  R.deflate = core ? "core-host" : "zlib";
+  status = 0;
+  return true;
+}
+
+// ---- the device path -------------------------------------------------------------------------------------------------------------
+bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::vector<uint8_t> &header, bool core, SortOut &out, Result &R,
+                    std::string &why, int &status) {
+  auto t0 = Clock::now();
+  status = STRL_ERR_IO;
+  BgzfFeed feed;
+  std::string err;
+  if (!feed.open(bam, err)) { why = err.empty() ? "couldn't open bam" : "couldn't open bam: " + err; return false; }
+  static const char *env_blocks = getenv("STRL_CHUNK_BLOCKS");     // tests: tiny chunks put records across pushes
+  const size_t auto_blocks = std::min<size_t>(16384, std::max<size_t>(2048, feed.file_bytes() / 16384 / 12));
+  const size_t chunk_blocks = env_blocks && atoi(env_blocks) > 0 ? (size_t)atoi(env_blocks) : auto_blocks;
+  const size_t chunk_bytes = std::max<size_t>((size_t)1 << 20, chunk_blocks * 20000);
+  PinnedRing pins;
+  pins.alloc(3, chunk_blocks, chunk_bytes);
+  if (!pins.ok()) { why = "page-locked memory for the chunks"; pins.release(); return false; }
+  strl_ctx *ctx = nullptr;
+  auto fail = [&](int rc) { why = strl_last_error(); status = rc; (void)strl_bamsort_end(ctx); pins.release(); return false; };
+  ThreadPool pool(std::min(decode_threads(), 12));
+  {
+    ChunkAhead ring(feed, pool, pins.data.data(), pins.meta.data(), chunk_blocks, chunk_bytes);
+    ring.stage(0, 0);
+    if (!(ctx = get_ctx(why))) { status = STRL_ERR_NO_DEVICE; pins.release(); return false; }
+    const char *cap = getenv("STRL_SORT_ARENA_MB");                // tests of the refusal
+    const uint64_t limit = cap && atof(cap) > 0 ? (uint64_t)(atof(cap) * 1048576.0) : 0;
+    int rc = strl_bamsort_begin(ctx, (int32_t)feed.targets().size(), feed.first_record_offset(), limit);
+    if (!rc) rc = strl_bamsort_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes);
+    if (rc) return fail(rc);
+    for (uint64_t ci = 0;; ++ci) {
+      const StagedChunk cur = ring.at(ci);
+      if (cur.nb < 0 || cur.short_read) { why = cur.nb < 0 ? cur.err : "short read"; status = STRL_ERR_FORMAT; (void)strl_bamsort_end(ctx); pins.release(); return false; }
+      if (cur.nb == 0) break;
+      ring.stage_ahead(ci + 1, (ci + 1) % 3);
+      const ChunkTables t = ring.tables(cur);
+      rc = strl_bamsort_push(ctx, ring.data(cur), cur.bytes(), t.coff, t.clen, t.isz, t.crc, (uint32_t)cur.nb);
+      ring.join();
+      if (rc) return fail(rc);
+    }
+  }
+  R.s.read = since(t0);
+  t0 = Clock::now();
+  strl_bamsort_info info;
+  int rc = strl_bamsort_finish(ctx, header.data(), header.size(), &info);
+  if (rc) return fail(rc);
+  R.s.sort = since(t0);
+  R.records = info.n_records; R.no_ref = info.n_no_ref; R.stream_bytes = info.stream_bytes; R.already_sorted = info.already_sorted != 0; R.slabs = info.n_slabs;
+  // pieces: the fetch of piece k + 1 on a thread beside the deflate / write of piece k
+  const uint64_t piece = piece_bytes(), total = info.stream_bytes, n_pieces = (total + piece - 1) / piece;
+  const uint64_t room = core ? strl_bgzf_deflate_bound(std::min(piece, total), BSORT_BLK) : std::min(piece, total);
+  uint8_t *buf[2] = {static_cast<uint8_t *>(strl_pinned_alloc(room + 64)), static_cast<uint8_t *>(strl_pinned_alloc(room + 64))};
+  if (!buf[0] || !buf[1]) { why = "page-locked memory for the pieces"; status = STRL_ERR_NOMEM; (void)strl_bamsort_end(ctx); return false; }
+  struct Fetched { int rc = 0; std::string err; uint64_t bytes = 0; uint32_t stored = 0; double s = 0; } got[2];
+  auto fetch = [&](uint64_t k) {
+    Fetched &F = got[k & 1];
+    const auto f0 = Clock::now();
+    const uint64_t lo = k * piece, len = std::min(piece, total - lo);
+    F = Fetched{};
+    if (core) F.rc = strl_bamsort_fetch_bgzf(ctx, lo, len, buf[k & 1], room, &F.bytes, &F.stored);
+    else { F.rc = strl_bamsort_fetch(ctx, lo, len, buf[k & 1]); F.bytes = len; }
+    if (F.rc) F.err = strl_last_error();
+    F.s = since(f0);
+  };
+  std::vector<uint8_t> members;
+  ThreadPool zpool(std::min(decode_threads(), 16));              // the deflate's pool, as the host path's and pull's
+  if (n_pieces) fetch(0);
+  for (uint64_t k = 0; k < n_pieces; ++k) {
+    std::thread ahead;
+    if (k + 1 < n_pieces) ahead = std::thread(fetch, k + 1);
+    const Fetched &F = got[k & 1];
+    bool ok = !F.rc;
+    if (!ok) { why = F.err; status = F.rc; }
+    R.s.gather += F.s;
+    const uint8_t *p = buf[k & 1];
+    size_t n = (size_t)F.bytes;
+    if (ok && !core) {
+      t0 = Clock::now();
+      status = STRL_ERR_IO;
+      ok = deflate_piece(p, n, false, zpool, members, R.stored, why);
+      p = members.data(); n = members.size();
+      R.s.deflate += since(t0);
+    } else if (ok) R.stored += F.stored;
+    if (ok) {
+      t0 = Clock::now();
+      status = STRL_ERR_IO;
+      ok = out.put(p, n, why);
+      R.out_bytes += n;
+      R.s.write += since(t0);
+    }
+    if (ahead.joinable()) ahead.join();
+    if (!ok) { (void)strl_bamsort_end(ctx); return false; }
+  }
+  if (core) { strl_bamsort_info now; if (!strl_bamsort_info_now(ctx, &now)) { R.s.deflate = std::max(0.0, R.s.gather - now.gather_ms / 1e3); R.s.gather = now.gather_ms / 1e3; } }
+  R.deflate = core ? "device" : "zlib";
+  (void)strl_bamsort_end(ctx);
+  // (the page-locked buffers are left to the end of the process: unlocking them stalls the device, as `bamindex` leaves its own)
+  status = 0;
+  return true;
+}
+
+}  // namespace
+
+int sort_main(int argc, char **argv) {
+  if (argc <= 2) { fputs(USAGE, stdout); return 0; }
+  const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"deflate", 0, true}, {"device", 'D', true}, {"verbose", 'v', false}}, USAGE);
+  if (a.pos.size() != 1) quit("expected 1 argument (bam)\n%s", USAGE);
+  if (!a.flag("output")) quit("[strling] sort: -o OUT.bam is required\n%s", USAGE);
+  const std::string bam = a.pos[0], out_path = a.get("output", ""), form = a.get("deflate", "host");
+  if (form != "host" && form != "device") quit("--deflate must be host or device (got %s)", form.c_str());
+  const bool core = form == "device";
+  if (CramFile::is_cram(bam)) quit("[strling] sort: %s is a CRAM; sorting one is out of scope: this command sorts a BAM", bam.c_str());
+  if (!file_exists(bam)) quit("couldn't open bam");
+  const auto t_all = Clock::now();
+  // the header, by the host reader, and the output's from it
+  std::vector<uint8_t> header;
+  int32_t n_ref = 0;
+  {
+    BamReader rd;
+    std::string err;
+    if (!rd.open(bam, err)) quit("[strling] sort: %s (status %d)", err.empty() ? "malformed BAM header (truncated file or invalid BGZF block)" : err.c_str(), STRL_ERR_FORMAT);
+    const std::vector<uint8_t> &h = rd.header_bytes();
+    if (!bsort_header(h.data(), h.size(), header, &n_ref, nullptr, err)) quit("[strling] sort: %s (status %d)", err.c_str(), STRL_ERR_FORMAT);
+  }
+  const char *where = getenv("STRL_SORT");
+  const bool on_host = (where && !strcmp(where, "host")) || strl_device_count() <= 0;
+  SortOut out;
+  std::string why;
+  int status = 0;
+  Result R;
+  strl_ctx *ctx = nullptr;
+  bool ok;
+  if (on_host) {
+    if (!out.open(out_path, why)) quit("[strling] sort: %s (status %d)", why.c_str(), STRL_ERR_IO);
+    ok = sort_on_host(bam, header, n_ref, core, out, R, why, status);
+  } else {
+    set_device0(a.get("device", ""));
+    // the HIP runtime and the context come up on a thread beside the header walk, the page-locked buffers and the first chunk's read
+    int ctx_rc = 0;
+    std::string ctx_err;
+    std::thread ctx_thread([&] { ctx_rc = strl_ctx_create(device_of(0), &ctx); if (ctx_rc) ctx_err = strl_last_error(); });
+    g_bg_init = &ctx_thread;
+    auto get_ctx = [&](std::string &w) -> strl_ctx * { if (ctx_thread.joinable()) ctx_thread.join(); if (ctx_rc) w = ctx_err; return ctx_rc ? nullptr : ctx; };
+    ok = out.open(out_path, why);
+    if (!ok) status = STRL_ERR_IO;
+    else ok = sort_on_device(get_ctx, bam, header, core, out, R, why, status);
+    if (ctx_thread.joinable()) ctx_thread.join();
+    g_bg_init = nullptr;
+  }
+  if (ok && !out.close(why)) { ok = false; status = STRL_ERR_IO; }
+  if (!ok) {
+    out.drop();
+    if (ctx) strl_ctx_destroy(ctx);
+    if (status == STRL_ERR_NOMEM) quit("[strling] sort: %s; sort this file with samtools, or on a device with more memory (status %d)", why.c_str(), status);
+    quit("[strling] sort: %s (status %d)", why.c_str(), status);
+  }
+  if (a.flag("verbose"))
+    fprintf(stderr,
+            "{\"command\": \"sort\", \"path\": \"%s\", \"records\": %llu, \"no_reference\": %llu, \"stream_bytes\": %llu, \"out_bytes\": %llu, \"already_sorted\": %s, \"slabs\": %llu, "
+            "\"seconds\": %.3f, \"read_s\": %.3f, \"sort_s\": %.3f, \"gather_s\": %.3f, \"deflate_s\": %.3f, \"write_s\": %.3f, \"deflate\": \"%s\", \"stored\": %u}\n",
+            on_host ? "host" : "device", (unsigned long long)R.records, (unsigned long long)R.no_ref, (unsigned long long)R.stream_bytes, (unsigned long long)R.out_bytes,
+            R.already_sorted ? "true" : "false", (unsigned long long)R.slabs, since(t_all), R.s.read, R.s.sort, R.s.gather, R.s.deflate, R.s.write, R.deflate, R.stored);
+  return end_process(ctx);
+}

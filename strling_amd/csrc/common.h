@@ -95,7 +95,7 @@ inline uint64_t strl_record_limit() {
   return v;
 }
 
-namespace strl { struct strl_front; struct strl_comm; void comm_destroy(strl_comm *m); struct strl_bai; void bai_destroy(strl_bai *b); struct strl_sweep; void sweep_destroy(strl_sweep *w); }
+namespace strl { struct strl_front; struct strl_comm; void comm_destroy(strl_comm *m); struct strl_bai; void bai_destroy(strl_bai *b); struct strl_sweep; void sweep_destroy(strl_sweep *w); struct strl_bsort; void bsort_destroy(strl_bsort *b); }
 struct strl_ctx;
 int side_join(strl_ctx *c);   // main stream waits for the side streams' pending work (context.hip)
 int side_streams(strl_ctx *c);   // the side streams of the overlapped mode, made at its first use (context.hip)
@@ -200,6 +200,7 @@ struct strl_ctx : TailSet, HeadSet {
   strl::strl_front *front = nullptr;   // device BAM front end (front.h), created by strl_front_begin
   strl::strl_bai *bai = nullptr;       // BAI builder behind the front end's record scan (bamindex.hip), created by strl_bamindex_begin
   strl::strl_sweep *sweep = nullptr;   // `call --sweep`: the evidence of many bounds behind the front end's record scan (sweep.hip), created by strl_sweep_begin
+  strl::strl_bsort *bsort = nullptr;   // `strling sort`: keys, arena and layout of a coordinate sort behind the front end's record scan (bamsort.hip), created by strl_bamsort_begin
   strl::strl_comm *comm = nullptr;     // multi-GPU exchange (comm.hip): RCCL communicator / local group of this context
   // staging of the pairing arrays for host-memory batches
   strl::DevBuf st_mtid, st_qhash;
@@ -208,6 +209,9 @@ struct strl_ctx : TailSet, HeadSet {
   strl_assign_info as_info{};
 };
 
+// deflate.hip: strl_bgzf_deflate over input that lies on the device already (bamsort.hip's gathered pieces); the same kernels, the same bytes
+namespace strl { int bgzf_deflate_device(strl_ctx *c, const uint8_t *d_in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
+                                         uint32_t *n_stored); }
 // pair.hip: enqueue the device pair logic behind a scoring pass of the same batch
 int strl_pair_order(strl_ctx *c, hipStream_t on_stream = nullptr);   // nullptr = the main stream (after a side_join)
 int strl_pair_device(strl_ctx *c, uint64_t n, const strl_pair_soa *pp, const uint32_t *whole, const strl_soft_rec *soft,

@@ -83,8 +83,9 @@ extern "C" int strl_bgzf_deflate_host(const uint8_t *in, uint64_t in_bytes, uint
   return deflate_refusal(dfl_deflate_host(in, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored), in_bytes, block_bytes, out_cap);
 }
 
-extern "C" int strl_bgzf_deflate(strl_ctx *c, const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
-                                 uint32_t *csize, uint32_t *n_stored) {
+// strl_bgzf_deflate; on_device: `in` lies on the context's device already (written on its stream): no copy in
+static int deflate_run(strl_ctx *c, const uint8_t *in, bool on_device, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+                       uint32_t *csize, uint32_t *n_stored) {
   if (!c) { set_error("null argument"); return STRL_ERR_ARG; }
   if (block_bytes < 1u || block_bytes > DFL_MAX_BLOCK || !out_bytes || (in_bytes && (!in || !out))) return deflate_refusal(STRL_ERR_ARG, in_bytes, block_bytes, out_cap);
   if (out_cap < dfl_bound(in_bytes, block_bytes)) return deflate_refusal(STRL_ERR_CAPACITY, in_bytes, block_bytes, out_cap);
@@ -98,7 +99,7 @@ extern "C" int strl_bgzf_deflate(strl_ctx *c, const uint8_t *in, uint64_t in_byt
   const uint64_t stride = ((uint64_t)block_bytes + DFL_MEMBER_EXTRA + 15) & ~(uint64_t)15;
   STRL_HIP(hipSetDevice(c->device));
   int rc;
-  if ((rc = c->dfl_in.reserve(in_bytes + 16)) || (rc = c->dfl_slots.reserve(nb * stride)) || (rc = c->dfl_tok.reserve((size_t)grid * block_bytes * 4)) ||
+  if ((!on_device && (rc = c->dfl_in.reserve(in_bytes + 16))) || (rc = c->dfl_slots.reserve(nb * stride)) || (rc = c->dfl_tok.reserve((size_t)grid * block_bytes * 4)) ||
       (rc = c->dfl_meta.reserve((size_t)nb * 12 + 64)))
     return rc;
   hipStream_t st = c->stream;
@@ -113,8 +114,8 @@ extern "C" int strl_bgzf_deflate(strl_ctx *c, const uint8_t *in, uint64_t in_byt
   auto drop_events = [&] { for (hipEvent_t &e : ev) (void)hipEventDestroy(e); };
   auto fail = [&](hipError_t e, const char *what) { set_error("bgzf deflate: %s failed: %s", what, hipGetErrorString(e)); drop_events(); return STRL_ERR_HIP; };
   hipError_t he;
-  if ((he = hipMemcpyAsync(c->dfl_in.p, in, in_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(he, "copy in");
-  DeflateParams P{c->dfl_in.as<uint8_t>(), in_bytes, block_bytes, nb, c->dfl_tok.as<uint32_t>(), c->dfl_slots.as<uint8_t>(), stride, d_csize, c->dfl_crc.as<DflCrc>()};
+  if (!on_device && (he = hipMemcpyAsync(c->dfl_in.p, in, in_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(he, "copy in");
+  DeflateParams P{on_device ? in : c->dfl_in.as<uint8_t>(), in_bytes, block_bytes, nb, c->dfl_tok.as<uint32_t>(), c->dfl_slots.as<uint8_t>(), stride, d_csize, c->dfl_crc.as<DflCrc>()};
   (void)hipEventRecord(ev[0], st);
   hipLaunchKernelGGL(deflate_kernel, dim3(grid), dim3(DFL_THREADS), 0, st, P);
   if ((he = hipGetLastError()) != hipSuccess) return fail(he, "deflate_kernel");
@@ -150,6 +151,15 @@ extern "C" int strl_bgzf_deflate(strl_ctx *c, const uint8_t *in, uint64_t in_byt
   if (n_stored) *n_stored = stored;
   *out_bytes = total;
   return STRL_OK;
+}
+
+extern "C" int strl_bgzf_deflate(strl_ctx *c, const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+                                 uint32_t *csize, uint32_t *n_stored) {
+  return deflate_run(c, in, false, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
+}
+int strl::bgzf_deflate_device(strl_ctx *c, const uint8_t *d_in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
+                              uint32_t *n_stored) {
+  return deflate_run(c, d_in, true, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
 }
 
 // HIP-event time (ms) of the kernels of the last strl_bgzf_deflate call on this context (copies excluded).

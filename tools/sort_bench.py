@@ -1,0 +1,141 @@
+"""`strling sort` on a shuffled BAM: the device path with both --deflate forms beside the host path (STRL_SORT=host), JSON lines.
+
+    python tools/sort_bench.py [--pairs N] [--repeats K] [--trace OUTDIR] [--dir D] [--slab-mb M] [--lanes 16,32,64]
+
+The input is a file of --pairs pairs from bamio.write_bam_slabs (30x geometry, qualities, aux tags), its records put into a random
+order (a seeded permutation of the whole file, the header's SO: set to unsorted) and written again at zlib level 1.  One after the
+other on one box, one process at a time, K runs each (the first pays for the page cache and the driver):
+  * `strling sort -v --deflate=host`, `strling sort -v --deflate=device`, `STRL_SORT=host strling sort -v`; every run's own JSON
+    line is kept; the three outputs must inflate to the same stream, and the --deflate=host file must be the host path's file;
+  * the gather's rate: stream bytes / the HIP-event time of all gathers, from a run through the ABI (api.Context.bamsort:
+    one fetch of the whole stream when it holds less than 4 GiB), for every group size in --lanes (STRL_SORT_GATHER_LANES);
+  * one more device run with STRL_ALLOC_TIMING=1: the library's own timing of every hipMalloc of 64 MB and more, the arena's slabs among them;
+  * --slab-mb: one more device run with slabs of that size (default 4096), to see what allocating the arena slab by slab costs;
+  * --trace: one more run under `rocprofv3 --kernel-trace --stats` (a run of its own): OUTDIR/kernel_stats.csv.
+`samtools sort` is not on these machines: nothing here compares with it.  No threshold is asserted.
+"""
+import argparse
+import glob
+import gzip
+import json
+import os
+import shutil
+import struct
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import e2e_bench  # noqa: E402
+
+
+def shuffled_copy(src, dst, seed=7):
+    """the records of the BAM at src in a random order -> dst (BGZF level 1); -> (records, inflated bytes)"""
+    from strling_amd import bamio
+    raw = gzip.decompress(open(src, "rb").read())
+    l_text = struct.unpack_from("<i", raw, 4)[0]
+    text = raw[8:8 + l_text].decode().replace("SO:coordinate", "SO:unsorted")
+    at = 8 + l_text
+    n_ref = struct.unpack_from("<i", raw, at)[0]
+    r0 = at
+    at += 4
+    for _ in range(n_ref):
+        at += 8 + struct.unpack_from("<i", raw, at)[0]
+    head = b"BAM\1" + struct.pack("<i", len(text)) + text.encode() + raw[r0:at]
+    offs = []
+    while at < len(raw):
+        offs.append(at)
+        at += 4 + struct.unpack_from("<i", raw, at)[0]
+    offs.append(at)
+    perm = np.random.default_rng(seed).permutation(len(offs) - 1)
+    mv = memoryview(raw)
+    out = head + b"".join(mv[offs[i]:offs[i + 1]] for i in perm)
+    comp, _ = bamio.bgzf_compress(np.frombuffer(out, np.uint8), 1, 0xFF00)
+    with open(dst, "wb") as f:
+        f.write(comp.tobytes())
+        f.write(bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0]))
+    return len(offs) - 1, len(out)
+
+
+def _run(cmd, env=None):
+    t = time.time()
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500)
+    if r.returncode != 0:
+        sys.stderr.write(r.stderr[-4000:])
+        sys.exit(r.returncode)
+    return json.loads(r.stderr.strip().splitlines()[-1]), round(time.time() - t, 3)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--pairs", type=int, default=2 ** 20)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--trace", default="")
+    ap.add_argument("--dir", default=None)
+    ap.add_argument("--slab-mb", default="")
+    ap.add_argument("--lanes", default="16,32,64")
+    a = ap.parse_args()
+    t0 = time.time()
+    inp = e2e_bench.make_input(a.pairs, d=a.dir, level=1)
+    work = tempfile.mkdtemp(prefix="sort_bench_", dir=os.path.dirname(inp["bam"]))
+    src = os.path.join(work, "shuffled.bam")
+    n, inflated = shuffled_copy(inp["bam"], src)
+    cli = os.path.join(ROOT, "strling_amd", "lib", "strling")
+    base = {"tool": "sort_bench", "reads": n, "inflated_bytes": inflated, "bam_bytes": os.path.getsize(src), "input_s": round(time.time() - t0, 1)}
+    print(json.dumps(base), flush=True)
+    outs = {}
+    forms = (("device_zlib", ["--deflate=host"], {}), ("device_core", ["--deflate=device"], {}), ("host_zlib", ["--deflate=host"], {"STRL_SORT": "host"}))
+    for k in range(a.repeats):
+        for tag, opts, env in forms:
+            outs[tag] = os.path.join(work, tag + ".bam")
+            says, wall = _run([cli, "sort", "-v", *opts, "-o", outs[tag], src], dict(os.environ, **env))
+            print(json.dumps({"run": tag, "repeat": k, "wall_s": wall, "says": says}), flush=True)
+    same_file = open(outs["device_zlib"], "rb").read() == open(outs["host_zlib"], "rb").read()
+    same_stream = gzip.decompress(open(outs["device_core"], "rb").read()) == gzip.decompress(open(outs["host_zlib"], "rb").read())
+    print(json.dumps({"check": "outputs", "device_zlib_file_equals_host_file": same_file, "device_core_stream_equals_host_stream": same_stream,
+                      "out_bytes": {t: os.path.getsize(p) for t, p in outs.items()}}), flush=True)
+    # what allocating the arena costs: the library's own timing of every hipMalloc of 64 MB and more (STRL_ALLOC_TIMING)
+    r = subprocess.run([cli, "sort", "-v", "-o", outs["device_zlib"], src], capture_output=True, text=True, env=dict(os.environ, STRL_ALLOC_TIMING="1"), timeout=1500)
+    print(json.dumps({"run": "device_zlib", "STRL_ALLOC_TIMING": 1, "hipMalloc": [x for x in r.stderr.splitlines() if "hipMalloc" in x], "says": json.loads(r.stderr.strip().splitlines()[-1])}), flush=True)
+    if a.slab_mb:
+        says, wall = _run([cli, "sort", "-v", "-o", outs["device_zlib"], src], dict(os.environ, STRL_SORT_SLAB_MB=a.slab_mb))
+        print(json.dumps({"run": "device_zlib", "STRL_SORT_SLAB_MB": a.slab_mb, "wall_s": wall, "says": says}), flush=True)
+    # the gather alone, through the ABI: one process per group size (the variable is read once)
+    code = f"""
+import sys, json
+sys.path.insert(0, {ROOT!r})
+from strling_amd import api
+c = api.Context(0)
+s, i, p = c.bamsort({src!r}, keep_open=True)
+n = min(i['stream_bytes'], (1 << 32) - 65536)
+for k in range(3):
+    b = c.bamsort_info()['gather_ms']
+    c.bamsort_fetch(0, n)
+    g = c.bamsort_info()['gather_ms'] - b
+    print(json.dumps({{'gather_ms': round(g, 3), 'bytes': n, 'GB_per_s': round(n / g / 1e6, 1), 'sort_ms': round(i['sort_ms'], 3), 'layout_ms': round(i['layout_ms'], 3)}}))
+c.bamsort_end()
+"""
+    if inflated < (1 << 32) - 65536:
+        for lanes in [x for x in a.lanes.split(",") if x]:
+            r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, STRL_SORT_GATHER_LANES=lanes), timeout=900)
+            lines = [json.loads(x) for x in r.stdout.strip().splitlines() if x.startswith("{")]
+            print(json.dumps({"gather": "one fetch of the whole stream, three times", "lanes_per_record": int(lanes), "runs": lines, "error": r.stderr[-300:] if r.returncode else None}), flush=True)
+    if a.trace:
+        os.makedirs(a.trace, exist_ok=True)
+        kt = os.path.join(work, "kt")
+        r = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", kt, "-o", "run", "--", cli, "sort", "--deflate=device", "-o", outs["device_core"], src],
+                           capture_output=True, text=True, env=dict(os.environ, STRL_TEARDOWN="1"), timeout=900)
+        f = glob.glob(os.path.join(kt, "**", "run_kernel_stats.csv"), recursive=True)
+        if r.returncode == 0 and f:
+            shutil.copy(f[0], os.path.join(a.trace, "kernel_stats.csv"))
+        print(json.dumps({"trace": "kernel_stats.csv" if (r.returncode == 0 and f) else (r.stderr or "no kernel table")[-500:]}), flush=True)
+    shutil.rmtree(work, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -43,5 +43,18 @@ if command -v samtools > /dev/null 2>&1 && "$S" bamindex 2> /dev/null | grep -q 
 else
   echo "SKIP  csi    (needs samtools and a strling with bamindex --csi: the CSI writer and reader stay checked against the specification, bamio.write_csi and the .bai only)"
 fi
+# ---- sort: `strling sort` against `samtools sort` of the same name-ordered file: the records, in order, must be equal (the header's @HD / @PG lines may differ).
+# verify/run_reference.sh /path/to/strling_amd/lib/strling (needs samtools on PATH; runs on the host path where there is no GPU); skipped otherwise.
+# No machine this project was developed on had samtools: this comparison has never been run.
+if command -v samtools > /dev/null 2>&1 && "$S" sort 2> /dev/null | grep -q -- --deflate; then
+  samtools sort -n -o "$T/sort_in.bam" "$D/widths.bam" > "$T/sort.log" 2>&1
+  samtools sort -o "$T/sort_theirs.bam" "$T/sort_in.bam" >> "$T/sort.log" 2>&1
+  "$S" sort -o "$T/sort_ours.bam" "$T/sort_in.bam" >> "$T/sort.log" 2>&1 || echo "      (sort: strling sort exited non-zero, see $T/sort.log)"
+  samtools view "$T/sort_theirs.bam" > "$T/sort_theirs.sam" 2>> "$T/sort.log"; samtools view "$T/sort_ours.bam" > "$T/sort_ours.sam" 2>> "$T/sort.log"
+  check sort "$T/sort_ours.sam" "$T/sort_theirs.sam" "(reference, position, forward before reverse, then input order) is samtools sort's order"
+  samtools view -H "$T/sort_ours.bam" | grep -q "^@HD.*SO:coordinate" && echo "PASS  sort_header   (@HD SO:coordinate)" || { echo "FAIL  sort_header   (no @HD SO:coordinate in strling sort's output)"; fail=1; }
+else
+  echo "SKIP  sort   (needs samtools and a strling with the sort command: the order stays checked against its own statement in tests/sort_bam_cases.py only)"
+fi
 if [ $fail = 0 ]; then echo "all assumptions confirmed"; else echo "outputs kept in $T (the .tsv beside an expected .bin lists its treads)"; fi
 exit $fail
