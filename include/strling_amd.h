@@ -874,6 +874,28 @@ int strl_bamsort_end(strl_ctx *ctx);
 int strl_bamsort_key(const uint8_t *rec20, int32_t n_ref, uint64_t *key);
 int strl_bamsort_key_bits(int32_t n_ref);
 int strl_bamsort_header(const uint8_t *in, uint64_t in_bytes, uint8_t *out, uint64_t cap, uint64_t *out_bytes);
+/* The index of the sort's output from the sort's own pass (`strling sort --write-index`): after the last fetch and before
+ * strl_bamsort_end the records, their order and their offsets in the stream are still on the device, and the index is one more
+ * pass over them instead of a second read, inflate and scan of the file just written.  The stream is cut into members of exactly
+ * 0xFF00 bytes, so the caller tells where it wrote them and a virtual offset is arithmetic:
+ *   member_off[0 .. n_members]  file offset of every member, the last entry the EOF block's; n_members = ceil(stream_bytes / 0xFF00)
+ *   voff(s) = member_off[s / 0xFF00] << 16 | s % 0xFF00, 0 <= s < stream_bytes; voff(stream_bytes) = member_off[n_members] << 16
+ *   (a byte on a member boundary belongs to the member that starts there, the stream's end to the EOF block: strl_bamindex_*'s
+ *   virtual offsets for the same file, so the bytes are the ones it gives)
+ *   strl_bamsort_index        l_ref[n_ref] as strl_bamindex_begin; csi_min_shift < 0: a .bai, else the CSI scheme (csi_min_shift,
+ *                             csi_depth), csi_depth < 0 = samtools' rule, as strl_bamindex_begin_csi.  The refusals, their words
+ *                             and statuses are strl_bamindex_finish's, the ordinal the record's rank in the output; a refusal
+ *                             leaves the sort as it was (fetches, another strl_bamsort_index, strl_bamsort_end).  STRL_ERR_ARG: a
+ *                             table that does not ascend, does not fit 48 bits, or whose n_members is not the stream's.
+ *                             STRL_SORT_INDEX_TILE (tests; default 2^22): records per launch of the per-record step.
+ *   strl_bamsort_index_fetch  the bytes, as strl_bamindex_fetch gives them (a .bai, or the uncompressed CSI payload).
+ * strl_bamsort_end frees the builder with the sort.  strl_bamsort_voff / strl_bamsort_members: the rule and the walk of the members
+ * in a buffer of written bytes (BSIZE at byte 16; file_off = where the buffer's first byte lies in the file), without a device. */
+int strl_bamsort_index(strl_ctx *ctx, const int32_t *l_ref, int32_t csi_min_shift, int32_t csi_depth, const uint64_t *member_off, uint64_t n_members,
+                       uint64_t *index_bytes, strl_bamindex_info *info);
+int strl_bamsort_index_fetch(strl_ctx *ctx, uint8_t *out, uint64_t cap);
+int strl_bamsort_voff(const uint64_t *member_off, uint64_t n_members, uint64_t stream_bytes, uint64_t s, uint64_t *voff);
+int strl_bamsort_members(const uint8_t *bytes, uint64_t n, uint64_t file_off, uint64_t *member_off, uint64_t cap, uint64_t *n_out);
 
 /* ---- the .bai as a by-product of `strling extract`'s own pass (`strling extract --write-index`) ----
  * strl_front_push already copies, inflates, CRC-checks, record-scans and parses every block; the index needs of a record only

@@ -153,7 +153,8 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_pull_select", "strl_pull_mates", "strl_pull_select_host", "strl_pull_counts_host", "strl_pull_mates_host", "strl_pull_order",
            "strl_bgzf_deflate", "strl_bgzf_deflate_bound", "strl_bgzf_deflate_host", "strl_ctx_deflate_ms",
            "strl_bamsort_begin", "strl_bamsort_reserve", "strl_bamsort_push", "strl_bamsort_finish", "strl_bamsort_fetch", "strl_bamsort_fetch_bgzf", "strl_bamsort_order",
-           "strl_bamsort_info_now", "strl_bamsort_end", "strl_bamsort_key", "strl_bamsort_key_bits", "strl_bamsort_header"]
+           "strl_bamsort_info_now", "strl_bamsort_end", "strl_bamsort_key", "strl_bamsort_key_bits", "strl_bamsort_header",
+           "strl_bamsort_index", "strl_bamsort_index_fetch", "strl_bamsort_voff", "strl_bamsort_members"]
 
 
 def lib_path():
@@ -289,6 +290,10 @@ def load(build_if_missing=True):
     L.strl_bamsort_key.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
     L.strl_bamsort_key_bits.argtypes = [C.c_int32]
     L.strl_bamsort_header.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.strl_bamsort_index.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(BamindexInfo)]
+    L.strl_bamsort_index_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_bamsort_voff.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.strl_bamsort_members.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.strl_bamsort_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     L.strl_sweep_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8]
     L.strl_sweep_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
@@ -1067,6 +1072,20 @@ class Context:
         _check(self.L.strl_bamsort_order(self.h, perm.ctypes.data, n))
         return perm[:n]
 
+    def bamsort_index(self, member_off, l_ref, csi=None):
+        """the index of the finished sort's output from what the sort still holds (strl_bamsort_index / _index_fetch), after the last
+        fetch and before bamsort_end.  member_off: the file offset of every member the stream was written as (0xFF00 bytes each),
+        the EOF block's last; l_ref: the references' lengths; csi = (min_shift, depth) as bamindex's
+        -> (bytes of the .bai / of the CSI payload, dict(n_records, n_no_coor, n_runs, n_chunks))"""
+        m = np.ascontiguousarray(member_off, np.uint64)
+        lr = np.ascontiguousarray(list(l_ref) + [0], np.int32)
+        nbytes, info = C.c_uint64(0), BamindexInfo()
+        ms, dp = (-1, -1) if csi is None else (int(csi[0]), -1 if csi[1] is None else int(csi[1]))
+        _check(self.L.strl_bamsort_index(self.h, _ptr(lr), ms, dp, _ptr(m) if m.size else None, max(int(m.size), 1) - 1, C.byref(nbytes), C.byref(info)))
+        out = np.zeros(max(1, nbytes.value), np.uint8)
+        _check(self.L.strl_bamsort_index_fetch(self.h, out.ctypes.data, out.size))
+        return out[:nbytes.value].tobytes(), {k: int(getattr(info, k)) for k, _ in BamindexInfo._fields_}
+
     def bamsort_end(self):
         self.L.strl_bamsort_end(self.h)
 
@@ -1081,9 +1100,12 @@ class Context:
         a, b = int(rng[0]), int(rng[1])
         return off, (a, b), parts[:b - a]
 
-    def bamsort(self, path, chunk_blocks=16384, check_crc=True, arena_limit_bytes=0, keep_open=False):
+    def bamsort(self, path, chunk_blocks=16384, check_crc=True, arena_limit_bytes=0, keep_open=False, index=None):
         """a BAM FILE coordinate-sorted on the device -> (the output stream: header || records in sorted order, strl_bamsort_info as a
-        dict, the permutation).  keep_open: the sort is left on the context for further fetches (bamsort_end ends it)."""
+        dict, the permutation).  keep_open: the sort is left on the context for further fetches (bamsort_end ends it).
+        index = "bai" or ("csi", min_shift, depth): the stream is also deflated here (the compressor's host twin, members of 0xFF00
+        bytes, the EOF block) and indexed from the sort (bamsort_index) -> a fourth item (the file's bytes, the index's bytes, its
+        info); a refusal of the index raises, with the sort ended unless keep_open."""
         B = self._bam_blocks(path)
         header = bamsort_header(B["header_raw"])
         self.bamsort_begin(B["n_ref"], B["first_off"], arena_limit_bytes)
@@ -1105,9 +1127,20 @@ class Context:
         except Exception:
             self.bamsort_end()
             raise
+        extra = ()
+        if index is not None:
+            try:
+                body = bgzf_deflate_host(stream)[0]
+                member_off = bamsort_members(body, 0) + [len(body)]
+                got, idx_info = self.bamsort_index(member_off, [t[1] for t in B["targets"]], None if index == "bai" else (index[1], index[2] if len(index) > 2 else None))
+                extra = ((body + _BGZF_EOF, got, idx_info),)
+            except Exception:
+                if not keep_open:
+                    self.bamsort_end()
+                raise
         if not keep_open:
             self.bamsort_end()
-        return stream, info, perm
+        return (stream, info, perm) + extra
 
     def sweep(self, path, bounds, window, frag, min_mapq=20, chunk_blocks=16384, check_crc=True):
         """the evidence of every bound from one pass over a coordinate-sorted BAM FILE (strl_sweep_begin / _push / _finish):
@@ -1435,6 +1468,28 @@ def _bgzf_deflate(call, data, block, out):
     nb, stored = C.c_uint64(0), C.c_uint32(0)
     _check(call(_ptr(src), src.size, block, out.ctypes.data, out.size, C.byref(nb), _ptr(csize), C.byref(stored)))
     return out[:nb.value].tobytes(), csize, stored.value
+
+
+_BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bamsort_members(data, file_off=0):
+    """the file offset of every BGZF member in `data`, which lies at file_off in its file (strl_bamsort_members: the walk `strling
+    sort --write-index` runs over the bytes it writes)"""
+    src = np.frombuffer(bytes(data), np.uint8)
+    out = np.zeros(len(src) // 26 + 1, np.uint64)
+    n = C.c_uint64(0)
+    _check(load().strl_bamsort_members(_ptr(src) if src.size else None, src.size, int(file_off), out.ctypes.data, out.size, C.byref(n)))
+    return [int(x) for x in out[:n.value]]
+
+
+def bamsort_voff(member_off, stream_bytes, s):
+    """the virtual offset of stream offset s of a sort's output (strl_bamsort_voff; csrc/bamsort_core.h): member_off = the file offset
+    of every member of 0xFF00 bytes, the EOF block's last"""
+    m = np.ascontiguousarray(member_off, np.uint64)
+    v = C.c_uint64(0)
+    _check(load().strl_bamsort_voff(_ptr(m) if m.size else None, max(int(m.size), 1) - 1, int(stream_bytes), int(s), C.byref(v)))
+    return int(v.value)
 
 
 def bgzf_deflate_host(data, block=0xFF00, out=None):

@@ -1,10 +1,11 @@
 // bam_rec.h -- the one statement of a BAM record's end on the reference that the device kernels share (evidence.hip step 2,
-// bamindex.hip bai_read, sweep_core.h sweep_keys_body).  Compiles for the host too (STRL_EMU: tests/emu/sweep_emu.cpp).
+// bamindex.hip bai_read, bamindex_core.h bai_read_bounded, sweep_core.h sweep_keys_body).  Compiles for the host too (the host index
+// builder; STRL_EMU: tests/emu/sweep_emu.cpp).
 #pragma once
 #include <stdint.h>
 
 #if defined(__HIPCC__) && !defined(STRL_EMU)
-#define STRL_REC_FN __device__ __forceinline__
+#define STRL_REC_FN __host__ __device__ inline __attribute__((always_inline))
 #else
 #define STRL_REC_FN inline
 #endif

@@ -17,6 +17,10 @@
 // The same builder also hangs off `strling extract`'s own pass (strl_front_index_*): behind rec_parse_kernel the
 // per-record step reads the dense columns the parse has just written instead of the records, the run base is a running total in
 // the device's state words, and the host learns of counts and refusals one chunk late, from a copy it never waits for.
+//
+// And off a finished `strling sort` (strl_bamsort_index): the records are those of the sort's arena in sorted
+// order, a launch of the per-record step takes a tile of them, and a virtual offset is arithmetic on the record's offset in the
+// output stream plus one load from the table of the members the host wrote (bamsort_core.h bsort_voff).
 #include <string.h>
 #include <algorithm>
 #include <deque>
@@ -24,22 +28,12 @@
 #include "sort.h"
 #include "device_util.h"
 #include "bam_rec.h"
+#include "bamindex_core.h"
+#include "bamsort_core.h"
 
 namespace strl {
 
-constexpr uint32_t BAI_ERR_KINDS = 5;
-constexpr uint32_t BAI_E_UNSORTED = 0, BAI_E_RANGE = 1, BAI_E_TID = 2, BAI_E_LREF = 3, BAI_E_NEGPOS = 4;
-constexpr uint64_t BAI_KEY_NONE = ~0ull;
-constexpr int32_t BAI_MAX_POS = 1 << 29;       // what the five-level binning scheme of a .bai addresses
-constexpr int64_t BAI_LREF_SLACK = 1 << 20;    // bases of the linear index kept behind l_ref: max(1, 2^20 >> min_shift) windows (64 of a .bai)
-constexpr int32_t CSI_MIN_SHIFT_LO = 8, CSI_MIN_SHIFT_HI = 24, CSI_DEPTH_HI = 8;      // schemes strl_*_begin_csi accepts
-constexpr int32_t CSI_MAX_END = 0x7ffffffe;    // bai_read clamps an end to 2^31 - 1: an end of that value may be a clamped one and is refused
-
-// The binning scheme (CSIv1): windows of 2^min_shift bases, `depth` levels of bins below bin 0.  A .bai is (14, 5).  A bin number is
-// below 2^(3 depth + 1), so the bin field of a run's key has key_shift = 3 depth + 1 bits (16 for a .bai).
-struct BaiScheme { int32_t min_shift, depth, key_shift, max_end; };   // max_end: the largest end of a record the scheme (and a BAM position) holds
 struct BaiRun { uint64_t key, beg_v, end_v, beg_abs, end_abs; };   // key = tid << key_shift | bin; virtual offsets; offsets in the inflated stream
-struct BaiChunk { uint64_t key, beg_v, end_v; };
 struct BaiLast {          // the last record so far
   uint64_t key, end_v, end_abs;
   int32_t tid, pos, end_win, pad;
@@ -58,6 +52,13 @@ struct BaiCols {           // the parse kernel's dense columns of the chunk's re
   const uint32_t *fragw;   // flag in the low 16 bits
   uint32_t rec_end;        // buffer offset behind the chunk's last complete record
 };
+struct BaiSorted {         // the records of a finished sort (bamsort.hip): record i of the launch is the record of rank j0 + i
+  BsortView V;
+  uint64_t j0;
+  const uint64_t *member_off;      // [n_members + 1] file offset of every member of the output, the EOF block's last
+  uint64_t n_members;
+};
+constexpr int BAI_SRC_BYTES = 0, BAI_SRC_COLS = 1, BAI_SRC_SORTED = 2;      // where the per-record step takes its records from
 struct BaiPush {
   const uint8_t *U;
   const uint32_t *recoff;
@@ -79,10 +80,9 @@ struct BaiPush {
   const uint64_t *run_acc;  // ... else &BaiState::run_base on the device
   uint64_t run_cap;         // slots of runs[]
   BaiCols C;
+  BaiSorted Z;
   BaiScheme sch;            // read by the kernels only where the scheme is not a .bai's (template parameter BAI)
 };
-
-struct BaiRec { int32_t tid, pos, end; uint32_t flag, bs; };
 
 __device__ __forceinline__ void bai_read(const uint8_t *U, uint32_t q, BaiRec &r) {
   const uint8_t *R = U + q;
@@ -93,9 +93,20 @@ __device__ __forceinline__ void bai_read(const uint8_t *U, uint32_t q, BaiRec &r
   r.end = e > 0x7fffffffll ? 0x7fffffff : (int32_t)e;
 }
 // the record's five numbers: from its bytes, or (COLS) from the parse's columns -- the byte length is the distance to the next
-// record (records lie back to back), end is bam_endpos as rec_parse_kernel computed it
-template <bool COLS> __device__ __forceinline__ void bai_fetch(const BaiPush &P, uint32_t i, BaiRec &r) {
-  if constexpr (COLS) {
+// record (records lie back to back), end is bam_endpos as rec_parse_kernel computed it --, or (SORTED) from the sort's arena:
+// slab, offset and length are held against the slab's used bytes as bsort_gather_kernel holds them, the CIGAR walk against the
+// length; a record that fails either is refused as one without a valid refID (the sort's own checks leave none)
+template <int SRC> __device__ __forceinline__ void bai_fetch(const BaiPush &P, uint32_t i, BaiRec &r) {
+  if constexpr (SRC == BAI_SRC_SORTED) {
+    const BsortView &V = P.Z.V;
+    r = BaiRec{-2, -1, 0, 0, 0};
+    const uint32_t p = V.perm[P.Z.j0 + i];
+    if (p >= V.n_records) return;
+    const uint64_t s = V.src[p], sl = s >> BSORT_SLAB_SHIFT, so = s & BSORT_SLAB_MASK;
+    const uint32_t len = V.len[p];
+    if (sl >= V.n_slabs || so > V.slab_used[sl] || len > V.slab_used[sl] - so) return;
+    if (!bai_read_bounded(V.slab[sl] + so, len, r)) r = BaiRec{-2, -1, 0, 0, 0};
+  } else if constexpr (SRC == BAI_SRC_COLS) {
     r.tid = P.C.tid[i]; r.pos = P.C.pos[i]; r.end = P.C.end[i]; r.flag = P.C.fragw[i] & 0xffffu;
     if (r.end <= r.pos) r.end = 0x7fffffff;     // (a reference span that left 31 bits: bai_read's clamp)
     r.bs = (i + 1u < P.n ? P.recoff[i + 1u] : P.C.rec_end) - P.recoff[i] - 4u;
@@ -103,42 +114,11 @@ template <bool COLS> __device__ __forceinline__ void bai_fetch(const BaiPush &P,
     bai_read(P.U, P.recoff[i], r);
   }
 }
-__device__ __forceinline__ uint32_t bai_reg2bin(int32_t beg, int32_t end) {      // SAM spec 5.3
-  --end;
-  if (beg >> 14 == end >> 14) return 4681u + (uint32_t)(beg >> 14);
-  if (beg >> 17 == end >> 17) return 585u + (uint32_t)(beg >> 17);
-  if (beg >> 20 == end >> 20) return 73u + (uint32_t)(beg >> 20);
-  if (beg >> 23 == end >> 23) return 9u + (uint32_t)(beg >> 23);
-  if (beg >> 26 == end >> 26) return 1u + (uint32_t)(beg >> 26);
-  return 0u;
-}
-// the CSI specification's reg2bin for (min_shift, depth); every lane makes all `depth` trips (at most 8), shifts in 64 bits
-// (min_shift + 3 (depth - 1) reaches 45).  depth 0: no trip, bin 0
-__device__ __forceinline__ uint32_t csi_reg2bin(int32_t beg, int32_t end, int32_t min_shift, int32_t depth) {
-  const uint64_t b = (uint64_t)(uint32_t)beg, e = (uint64_t)(uint32_t)(end - 1);
-  uint32_t t = (uint32_t)(((1ull << (3 * depth)) - 1ull) / 7ull), bin = 0;
-  int32_t s = min_shift;
-  bool found = false;
-  for (int32_t l = depth; l > 0; --l) {
-    const bool hit = !found && (b >> s) == (e >> s);
-    bin = hit ? t + (uint32_t)(b >> s) : bin;
-    found = found || hit;
-    s += 3;
-    t -= 1u << (3 * (l - 1));
-  }
-  return bin;
-}
 template <bool BAI> __device__ __forceinline__ int32_t bai_shift(const BaiPush &P) { return BAI ? 14 : P.sch.min_shift; }
 // a record the index can hold: a reference of the header, 0 <= pos, end <= what the scheme addresses (2^29 for a .bai), its last
 // window one of the reference's (l_ref and 1 Mbase behind it: aligners do leave reads that hang over the end of a contig).  else the kind of refusal
 template <bool BAI> __device__ __forceinline__ int bai_refusal(const BaiRec &r, const BaiPush &P) {
-  if (r.tid < -1 || r.tid >= P.n_ref) return (int)BAI_E_TID;
-  if (r.tid < 0) return -1;
-  if (r.pos < 0) return (int)BAI_E_NEGPOS;
-  const int32_t max_end = BAI ? BAI_MAX_POS : P.sch.max_end;
-  if (r.pos >= max_end || r.end > max_end) return (int)BAI_E_RANGE;
-  if ((uint64_t)((r.end - 1) >> bai_shift<BAI>(P)) >= P.win_off[r.tid + 1] - P.win_off[r.tid]) return (int)BAI_E_LREF;
-  return -1;
+  return bai_refusal_rule(r.tid, r.pos, r.end, P.n_ref, BAI ? BAI_MAX_POS : P.sch.max_end, bai_shift<BAI>(P), [&](int32_t t) { return P.win_off[t + 1] - P.win_off[t]; });
 }
 template <bool BAI> __device__ __forceinline__ uint64_t bai_key(const BaiRec &r, const BaiPush &P, bool indexable) {
   const int32_t ks = BAI ? 16 : P.sch.key_shift;
@@ -155,15 +135,24 @@ __device__ __forceinline__ uint64_t bai_voff(const int64_t *vrel, const uint64_t
   return (vfoff[lo] << 16) | (uint64_t)(q - vrel[lo]);
 }
 
-// the per-record step; the rules (refusals, bin, windows, virtual offsets, run heads) are this one body for both sources
-template <bool COLS, bool BAI> __device__ __forceinline__ void bai_record_body(const BaiPush &P) {
+// where record i begins / the byte behind it: virtual offset, offset in the inflated stream
+template <int SRC> __device__ __forceinline__ void bai_beg(const BaiPush &P, uint32_t i, uint64_t &v, uint64_t &abs) {
+  if constexpr (SRC == BAI_SRC_SORTED) { abs = P.Z.V.off[P.Z.j0 + i]; v = bsort_voff(P.Z.member_off, P.Z.n_members, P.Z.V.stream_bytes, abs); }
+  else { const uint32_t q = P.recoff[i]; v = bai_voff(P.vrel, P.vfoff, P.vm, (int64_t)q); abs = (uint64_t)(P.abs0 + (int64_t)q); }
+}
+template <int SRC> __device__ __forceinline__ void bai_end(const BaiPush &P, uint32_t i, const BaiRec &r, uint64_t &v, uint64_t &abs) {
+  if constexpr (SRC == BAI_SRC_SORTED) { abs = P.Z.V.off[P.Z.j0 + i + 1]; v = bsort_voff(P.Z.member_off, P.Z.n_members, P.Z.V.stream_bytes, abs); }
+  else { const int64_t e = (int64_t)P.recoff[i] + 4 + (int64_t)r.bs; v = bai_voff(P.vrel, P.vfoff, P.vm, e); abs = (uint64_t)(P.abs0 + e); }
+}
+
+// the per-record step; the rules (refusals, bin, windows, virtual offsets, run heads) are this one body for every source
+template <int SRC, bool BAI> __device__ __forceinline__ void bai_record_body(const BaiPush &P) {
   const int32_t m = bai_shift<BAI>(P);
   const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
   const bool act = i < P.n;
   BaiRec r{-1, -1, 0, 0, 0};
-  uint32_t q = 0;
   int bad = -1;
-  if (act) { q = P.recoff[i]; bai_fetch<COLS>(P, i, r); bad = bai_refusal<BAI>(r, P); }
+  if (act) { bai_fetch<SRC>(P, i, r); bad = bai_refusal<BAI>(r, P); }
   const bool placed = act && r.tid >= 0 && bad < 0;
   const uint64_t key = act ? bai_key<BAI>(r, P, bad < 0) : BAI_KEY_NONE;
   const int32_t end_win = placed ? (r.end - 1) >> m : -1;
@@ -174,13 +163,13 @@ template <bool COLS, bool BAI> __device__ __forceinline__ void bai_record_body(c
     if (i == 0) { const BaiLast &L = P.S->last[P.par]; ptid = L.tid; ppos = L.pos; pwin = L.end_win; pkey = L.key; }
     else {
       BaiRec p;
-      bai_fetch<COLS>(P, i - 1u, p);
+      bai_fetch<SRC>(P, i - 1u, p);
       const bool pok = bai_refusal<BAI>(p, P) < 0;
       ptid = p.tid; ppos = p.pos; pkey = bai_key<BAI>(p, P, pok);
       pwin = (p.tid >= 0 && pok) ? (p.end - 1) >> m : -1;
     }
   }
-  uint64_t beg_v = 0, end_v = 0;
+  uint64_t beg_v = 0, end_v = 0, beg_abs = 0, end_abs = 0;
   if (act) {
     const uint64_t ord = P.ord0 + i;
     if (bad >= 0) atomicMin(reinterpret_cast<unsigned long long *>(&P.S->err_ord[bad]), (unsigned long long)ord);
@@ -188,8 +177,8 @@ template <bool COLS, bool BAI> __device__ __forceinline__ void bai_record_body(c
     const uint32_t uc = (uint32_t)r.tid, up = (uint32_t)ptid;
     if (pkey != BAI_KEY_NONE && (uc < up || (uc == up && r.tid >= 0 && r.pos < ppos)))
       atomicMin(reinterpret_cast<unsigned long long *>(&P.S->err_ord[BAI_E_UNSORTED]), (unsigned long long)ord);
-    beg_v = bai_voff(P.vrel, P.vfoff, P.vm, (int64_t)q);
-    end_v = bai_voff(P.vrel, P.vfoff, P.vm, (int64_t)q + 4 + (int64_t)r.bs);
+    bai_beg<SRC>(P, i, beg_v, beg_abs);
+    bai_end<SRC>(P, i, r, end_v, end_abs);
   }
   // linear index: the windows no record in front of this one has reached (in a sorted stream the lane below covers all
   // but the window a record is the first to enter; an N skip of hundreds of kilobases enters many)
@@ -227,14 +216,15 @@ template <bool COLS, bool BAI> __device__ __forceinline__ void bai_record_body(c
   if (threadIdx.x == 0) P.blk_cnt[blockIdx.x] = (uint32_t)heads;
   if (act && i == P.n - 1) {
     BaiLast L;
-    L.key = key; L.end_v = end_v; L.end_abs = (uint64_t)(P.abs0 + (int64_t)q + 4 + (int64_t)r.bs);
+    L.key = key; L.end_v = end_v; L.end_abs = end_abs;
     L.tid = r.tid; L.pos = r.pos; L.end_win = end_win; L.pad = 0;
     P.S->last[P.par ^ 1u] = L;
   }
 }
 // <BAI>: the scheme is a .bai's (14, 5), compiled in -- the code of that path is what it was before schemes; else read from P.sch
-template <bool BAI> __global__ __launch_bounds__(256) void bai_record_kernel(BaiPush P) { bai_record_body<false, BAI>(P); }
-template <bool BAI> __global__ __launch_bounds__(256) void bai_record_cols_kernel(BaiPush P) { bai_record_body<true, BAI>(P); }
+template <bool BAI> __global__ __launch_bounds__(256) void bai_record_kernel(BaiPush P) { bai_record_body<BAI_SRC_BYTES, BAI>(P); }
+template <bool BAI> __global__ __launch_bounds__(256) void bai_record_cols_kernel(BaiPush P) { bai_record_body<BAI_SRC_COLS, BAI>(P); }
+template <bool BAI> __global__ __launch_bounds__(256) void bai_record_sorted_kernel(BaiPush P) { bai_record_body<BAI_SRC_SORTED, BAI>(P); }
 
 // One block: cnt[0, n) -> exclusive sums in place, the total to *total; acc (if given): acc[0] = the running total so far (the
 // base of this chunk's runs), acc[1] += total -- the host is not asked
@@ -263,23 +253,24 @@ __device__ __forceinline__ uint32_t bai_block_rank(bool f) {
   return r;
 }
 
-template <bool COLS, bool BAI> __device__ __forceinline__ void bai_emit_body(const BaiPush &P) {
+template <int SRC, bool BAI> __device__ __forceinline__ void bai_emit_body(const BaiPush &P) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const bool head = i < P.n && P.flag[i];
   const uint32_t rank = bai_block_rank(head);
   if (!head) return;
   const uint64_t slot = (P.run_acc ? *P.run_acc : P.run_base) + P.blk_cnt[blockIdx.x] + rank;
   if (slot >= P.run_cap) { P.S->overflow = 1u; return; }       // (the host sizes the table for every record of the chunk: not reached)
-  const uint32_t q = P.recoff[i];
   BaiRec r;
-  bai_fetch<COLS>(P, i, r);
-  const uint64_t beg_v = bai_voff(P.vrel, P.vfoff, P.vm, (int64_t)q), beg_abs = (uint64_t)(P.abs0 + (int64_t)q);
+  bai_fetch<SRC>(P, i, r);
+  uint64_t beg_v, beg_abs;
+  bai_beg<SRC>(P, i, beg_v, beg_abs);
   BaiRun &R = P.runs[slot];
   R.key = bai_key<BAI>(r, P, bai_refusal<BAI>(r, P) < 0); R.beg_v = beg_v; R.beg_abs = beg_abs;
   if (slot) { BaiRun &B = P.runs[slot - 1]; B.end_v = beg_v; B.end_abs = beg_abs; }
 }
-template <bool BAI> __global__ __launch_bounds__(256) void bai_emit_kernel(BaiPush P) { bai_emit_body<false, BAI>(P); }
-template <bool BAI> __global__ __launch_bounds__(256) void bai_emit_cols_kernel(BaiPush P) { bai_emit_body<true, BAI>(P); }
+template <bool BAI> __global__ __launch_bounds__(256) void bai_emit_kernel(BaiPush P) { bai_emit_body<BAI_SRC_BYTES, BAI>(P); }
+template <bool BAI> __global__ __launch_bounds__(256) void bai_emit_cols_kernel(BaiPush P) { bai_emit_body<BAI_SRC_COLS, BAI>(P); }
+template <bool BAI> __global__ __launch_bounds__(256) void bai_emit_sorted_kernel(BaiPush P) { bai_emit_body<BAI_SRC_SORTED, BAI>(P); }
 
 // finish: the open run ends behind the last record; sort keys of the runs
 __global__ void bai_keys_kernel(BaiRun *runs, uint32_t n, const BaiState *S, uint32_t par, uint64_t *keys, uint32_t *vals) {
@@ -365,26 +356,12 @@ void bai_destroy(strl_bai *B) {
 }
 
 static int bai_refuse(const strl_bai *B, const BaiState &S) {
-  uint32_t kind = BAI_ERR_KINDS;
-  for (uint32_t k = 0; k < BAI_ERR_KINDS; ++k)
-    if (S.err_ord[k] != ~0ull && (kind == BAI_ERR_KINDS || S.err_ord[k] < S.err_ord[kind])) kind = k;
+  const uint32_t kind = bai_first_refusal(S.err_ord);
   if (kind == BAI_ERR_KINDS) return STRL_OK;
-  const unsigned long long at = (unsigned long long)S.err_ord[kind];
-  switch (kind) {
-    case BAI_E_UNSORTED: set_error("the BAM is not coordinate sorted: record %llu comes behind a record of a later position (or behind an unplaced one); sort it first", at); return STRL_ERR_FORMAT;
-    case BAI_E_RANGE:
-      if (!B->csi) set_error("record %llu lies at or reaches past position 2^29 = 536870912, which a .bai cannot address; a CSI index can: `strling bamindex --csi` (strl_bamindex_begin_csi)", at);
-      else if (B->sch.max_end == CSI_MAX_END) set_error("record %llu reaches position 2^31 - 1 = 2147483647 or past it, which a BAM position cannot hold; not indexed", at);
-      else if (B->auto_depth)
-        set_error("record %llu lies at or reaches past position 2^%d = %lld, which the CSI scheme (min_shift %d, depth %d: chosen for the longest reference of the header) cannot "
-                  "address: the record lies past the end of its reference", at, B->sch.min_shift + 3 * B->sch.depth, (long long)B->sch.max_end, B->sch.min_shift, B->sch.depth);
-      else set_error("record %llu lies at or reaches past position 2^%d = %lld, which the CSI scheme (min_shift %d, depth %d) cannot address; a greater depth can", at,
-                     B->sch.min_shift + 3 * B->sch.depth, (long long)B->sch.max_end, B->sch.min_shift, B->sch.depth);
-      return STRL_ERR_LIMIT;
-    case BAI_E_TID: set_error("malformed BAM record %llu: its refID is not one of the header's %d references", at, B->n_ref); return STRL_ERR_FORMAT;
-    case BAI_E_LREF: set_error("record %llu reaches more than %lld bases past the end of its reference as the header gives it (l_ref); not indexed", at, (long long)std::max<int64_t>(BAI_LREF_SLACK, 1ll << B->sch.min_shift)); return STRL_ERR_FORMAT;
-    default: set_error("record %llu has a reference but a negative position; not indexed", at); return STRL_ERR_FORMAT;
-  }
+  std::string msg;
+  const int rc = bai_refusal_text(kind, S.err_ord[kind], B->csi, B->auto_depth, B->sch, B->n_ref, msg);
+  set_error("%s", msg.c_str());
+  return rc;
 }
 
 // the runs of the chunk in slot si (its record scan was enqueued by the push before): waits on the host for the scan's counts
@@ -436,50 +413,28 @@ static int bai_index_chunk(strl_ctx *c, strl_front *F, strl_bai *B, int si) {
   return STRL_OK;
 }
 
-static void put32(std::vector<uint8_t> &o, uint32_t v) { for (int k = 0; k < 4; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
-static void put64(std::vector<uint8_t> &o, uint64_t v) { for (int k = 0; k < 8; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
-
 }  // namespace strl
 
 using namespace strl;
 
-// the schemes the builder takes: window tables and bin numbers stay small (depth < 0: the rule, see bai_setup)
+// the schemes the builder takes (depth < 0: the rule, see bai_scheme_make)
 static int csi_check(int32_t m, int32_t d) {
-  if (m >= CSI_MIN_SHIFT_LO && m <= CSI_MIN_SHIFT_HI && d <= CSI_DEPTH_HI) return STRL_OK;
-  set_error("CSI scheme: min_shift must be in [%d, %d] and depth at most %d (got min_shift %d, depth %d)", CSI_MIN_SHIFT_LO, CSI_MIN_SHIFT_HI, CSI_DEPTH_HI, m, d);
+  std::string err;
+  if (csi_scheme_ok(m, d, err)) return STRL_OK;
+  set_error("%s", err.c_str());
   return STRL_ERR_ARG;
 }
-// the resident tables of a new builder (linear index, per-reference words, state words) on the context; replaces c->bai.
+// the resident tables of a new builder B (linear index, per-reference words, state words), which its owner already holds.
 // csi: null = a .bai; else {min_shift, depth}, depth < 0 = samtools' rule (the smallest depth whose scheme reaches max(l_ref) + 256)
-static int bai_setup(strl_ctx *c, int32_t n_ref, const int32_t *l_ref, const int32_t *csi) {
+static int bai_tables(strl_ctx *c, strl_bai *B, int32_t n_ref, const int32_t *l_ref, const int32_t *csi) {
   int rc;
-  BaiScheme sch{14, 5, 16, BAI_MAX_POS};
-  if (csi) {
-    int32_t m = csi[0], d = csi[1];
-    if ((rc = csi_check(m, d))) return rc;
-    if (d < 0) {
-      int64_t max_len = 0;
-      for (int32_t t = 0; t < n_ref; ++t) max_len = std::max<int64_t>(max_len, l_ref[t]);
-      max_len += 256;
-      for (d = 0; d < CSI_DEPTH_HI && (1ll << (m + 3 * d)) < max_len; ++d) {}
-    }
-    sch = BaiScheme{m, d, 3 * d + 1, (int32_t)std::min<int64_t>(1ll << (m + 3 * d), CSI_MAX_END)};
-  }
-  if (c->bai) { bai_destroy(c->bai); c->bai = nullptr; }
-  strl_bai *B = new strl_bai();
-  c->bai = B;
+  std::string err;
+  if (!bai_scheme_make(csi, n_ref, l_ref, B->sch, err)) { set_error("%s", err.c_str()); return STRL_ERR_ARG; }
   B->n_ref = n_ref;
-  B->sch = sch;
   B->csi = csi != nullptr;
   B->auto_depth = csi && csi[1] < 0;
   B->l_ref.assign(l_ref, l_ref + n_ref);
-  B->win_off.assign((size_t)n_ref + 1, 0);
-  // windows of 2^min_shift bases up to l_ref and 1 Mbase behind it, never more than the scheme addresses ((14, 5): 64 behind l_ref, at most 2^15)
-  const int64_t win = 1ll << sch.min_shift, slack = std::max<int64_t>(1, BAI_LREF_SLACK >> sch.min_shift);
-  for (int32_t t = 0; t < n_ref; ++t) {
-    const int64_t len = std::min<int64_t>(std::max<int64_t>(l_ref[t], 0), sch.max_end);
-    B->win_off[(size_t)t + 1] = B->win_off[(size_t)t] + (uint64_t)std::min<int64_t>(((len + win - 1) >> sch.min_shift) + slack, ((int64_t)sch.max_end + win - 1) >> sch.min_shift);
-  }
+  bai_windows(B->sch, n_ref, l_ref, B->win_off);
   const size_t nw = (size_t)B->win_off[(size_t)n_ref], nr = (size_t)n_ref;
   if ((rc = B->d_winoff.reserve((nr + 1) * 8)) || (rc = B->lin.reserve(nw * 8 + 16)) || (rc = B->ref_beg.reserve(nr * 8 + 16)) ||
       (rc = B->ref_end.reserve(nr * 8 + 16)) || (rc = B->ref_cnt.reserve(nr * 16 + 16)) || (rc = B->state.reserve(sizeof(BaiState))))
@@ -498,6 +453,14 @@ static int bai_setup(strl_ctx *c, int32_t n_ref, const int32_t *l_ref, const int
   STRL_HIP(hipMemcpyAsync(B->state.p, &H, sizeof H, hipMemcpyHostToDevice, st));
   STRL_HIP(hipStreamSynchronize(st));
   return STRL_OK;
+}
+// ... of a new builder on the context; replaces c->bai
+static int bai_setup(strl_ctx *c, int32_t n_ref, const int32_t *l_ref, const int32_t *csi) {
+  int rc;
+  if (csi && (rc = csi_check(csi[0], csi[1]))) return rc;
+  if (c->bai) { bai_destroy(c->bai); c->bai = nullptr; }
+  c->bai = new strl_bai();
+  return bai_tables(c, c->bai, n_ref, l_ref, csi);
 }
 
 // what a chunk's block offsets must be: ascending, behind `floor` (the end of what came before), 48 bits; ISIZE (where known) in [1, 65536]
@@ -645,58 +608,7 @@ static int bai_sort_and_pack(strl_ctx *c, strl_bai *B) {
     STRL_HIP(hipMemcpy(re.data(), B->ref_end.p, nr * 8, hipMemcpyDeviceToHost));
     STRL_HIP(hipMemcpy(cnt.data(), B->ref_cnt.p, nr * 16, hipMemcpyDeviceToHost));
   }
-  // the bytes: per reference the bins ascending with their chunks, the pseudo-bin last, n_no_coor at the end.  .bai (SAM spec
-  // 5.2): the linear index up to the last window touched behind the bins (empty windows 0).  CSI (CSIv1): no linear index, every
-  // bin carries loffset = the linear index at the bin's first window, after empty windows have taken the next filled window's
-  // value from the end towards the start (htslib's update_loff); 0 behind the last window touched.  Done here, on the host's
-  // copy of lin[]: one pass over words that are copied anyway, and a gather per bin beside the bytes being written.
-  const int ks = B->sch.key_shift, m = B->sch.min_shift, d = B->sch.depth;
-  const uint64_t bin_mask = (1ull << ks) - 1ull;
-  const uint32_t meta_bin = (uint32_t)(((1ull << (3 * (d + 1))) - 1ull) / 7ull + 1ull);      // 37450 for depth 5
-  std::vector<uint8_t> &o = B->bytes;
-  o.clear();
-  o.reserve(16 + ch.size() * 36 + (B->csi ? 0 : nw * 8) + nr * 64 + 8);
-  if (B->csi) { o.insert(o.end(), {'C', 'S', 'I', 1}); put32(o, (uint32_t)m); put32(o, (uint32_t)d); put32(o, 0); }
-  else o.insert(o.end(), {'B', 'A', 'I', 1});
-  put32(o, (uint32_t)B->n_ref);
-  size_t at = 0;
-  uint64_t n_chunks = 0;
-  for (size_t t = 0; t < nr; ++t) {
-    size_t e = at, n_bin = 0;
-    while (e < ch.size() && (ch[e].key >> ks) == t) { if (e == at || ch[e].key != ch[e - 1].key) ++n_bin; ++e; }
-    const bool meta = cnt[2 * t] + cnt[2 * t + 1] != 0;
-    const uint64_t w0 = B->win_off[t], w1 = B->win_off[t + 1];
-    uint64_t n_intv = 0;
-    for (uint64_t w = w1; w > w0; --w) if (lin[(size_t)w - 1] != ~0ull) { n_intv = w - w0; break; }
-    if (B->csi)
-      for (uint64_t w = n_intv; w > 1; --w) if (lin[(size_t)(w0 + w - 2)] == ~0ull) lin[(size_t)(w0 + w - 2)] = lin[(size_t)(w0 + w - 1)];
-    put32(o, (uint32_t)(n_bin + (meta ? 1 : 0)));
-    for (size_t a = at; a < e;) {
-      size_t b = a;
-      while (b < e && ch[b].key == ch[a].key) ++b;
-      const uint32_t bin = (uint32_t)(ch[a].key & bin_mask);
-      put32(o, bin);
-      if (B->csi) {
-        // the bin's level: the first bin of level l is (8^l - 1) / 7; its bins cover 2^(m + 3 (d - l)) bases = 8^(d - l) windows each
-        int l = 0;
-        while (l < d && bin >= (uint32_t)(((1ull << (3 * (l + 1))) - 1ull) / 7ull)) ++l;
-        const uint64_t w = (uint64_t)(bin - (uint32_t)(((1ull << (3 * l)) - 1ull) / 7ull)) << (3 * (d - l));
-        put64(o, w < n_intv ? lin[(size_t)(w0 + w)] : 0);
-      }
-      put32(o, (uint32_t)(b - a));
-      for (size_t k = a; k < b; ++k) { put64(o, ch[k].beg_v); put64(o, ch[k].end_v); }
-      n_chunks += b - a;
-      a = b;
-    }
-    if (meta) { put32(o, meta_bin); if (B->csi) put64(o, 0); put32(o, 2); put64(o, rb[t]); put64(o, re[t]); put64(o, cnt[2 * t]); put64(o, cnt[2 * t + 1]); }
-    if (!B->csi) {
-      put32(o, (uint32_t)n_intv);
-      for (uint64_t w = 0; w < n_intv; ++w) { const uint64_t v = lin[(size_t)(w0 + w)]; put64(o, v == ~0ull ? 0 : v); }
-    }
-    at = e;
-  }
-  put64(o, B->h_state->n_no_coor);
-  B->n_chunks = n_chunks;
+  B->n_chunks = bai_pack(B->sch, B->csi, B->n_ref, B->win_off, ch, lin, rb, re, cnt, B->h_state->n_no_coor, B->bytes);      // (bamindex_core.h)
   B->finished = true;
   return STRL_OK;
 }
@@ -903,5 +815,108 @@ extern "C" int strl_bamindex_end(strl_ctx *c) {
   }
   STRL_HIP(hipStreamSynchronize(c->stream));
   if (c->bai) { bai_destroy(c->bai); c->bai = nullptr; }
+  return STRL_OK;
+}
+
+// ---- the index of a sort's output from the sort's own pass (`strling sort --write-index`) ----
+// Between the last fetch and strl_bamsort_end everything an index is made of is on the device: the records (the arena), their
+// order (perm) and where each lies in the output stream (off[]).  The builder hangs off the sort, not off c->bai: a context with a
+// sort open has no index pass open.  The records go through the per-record step in launches of at most `tile` records (BaiPush::n,
+// flag[] and blk_cnt[] are 32-bit and sized per launch; BaiLast carries from one launch to the next as it does from chunk to
+// chunk), the run table grows by the per-launch read of n_heads as in bai_index_chunk, and the finish is bai_sort_and_pack.
+static uint32_t bsort_index_tile() {
+  const char *e = getenv("STRL_SORT_INDEX_TILE");             // tests: launches of a few records (wave, block and launch seams)
+  const long v = e ? atol(e) : 0;
+  return v > 0 ? (uint32_t)std::min<long>(v, 1l << 30) : 1u << 22;
+}
+
+extern "C" int strl_bamsort_index(strl_ctx *c, const int32_t *l_ref, int32_t csi_min_shift, int32_t csi_depth, const uint64_t *member_off, uint64_t n_members,
+                                  uint64_t *index_bytes, strl_bamindex_info *info) {
+  BsortView V;
+  strl_bai **slot = nullptr;
+  if (!c || bsort_view(c, &V, &slot)) { set_error("strl_bamsort_index without strl_bamsort_finish"); return STRL_ERR_ARG; }
+  if (V.n_ref && !l_ref) { set_error("strl_bamsort_index: bad argument"); return STRL_ERR_ARG; }
+  if (!bsort_member_table_ok(member_off, n_members, V.stream_bytes)) {
+    set_error("strl_bamsort_index: the member table must hold ceil(%llu / 0xFF00) + 1 = %llu file offsets that ascend and fit 48 bits (n_members given: %llu)",
+              (unsigned long long)V.stream_bytes, (unsigned long long)bsort_n_members(V.stream_bytes) + 1, (unsigned long long)n_members);
+    return STRL_ERR_ARG;
+  }
+  int rc;
+  const int32_t csi[2] = {csi_min_shift, csi_depth};
+  if (csi_min_shift >= 0 && (rc = csi_check(csi_min_shift, csi_depth))) return rc;
+  STRL_HIP(hipSetDevice(c->device));
+  if (*slot) { bai_destroy(*slot); *slot = nullptr; }
+  strl_bai *B = *slot = new strl_bai();
+  if ((rc = bai_tables(c, B, V.n_ref, l_ref, csi_min_shift >= 0 ? csi : nullptr))) return rc;
+  hipStream_t st = c->stream;
+  const uint64_t n = V.n_records;
+  const uint32_t tile = bsort_index_tile();
+  const size_t room = (size_t)std::min<uint64_t>(n, tile);
+  if ((rc = B->vt[0].reserve((size_t)(n_members + 1) * 8)) || (rc = B->flag.reserve(room + 64)) || (rc = B->blk_cnt.reserve((room / 256 + 2) * 4 + 64))) return rc;
+  STRL_HIP(hipMemcpyAsync(B->vt[0].p, member_off, (size_t)(n_members + 1) * 8, hipMemcpyHostToDevice, st));
+  const bool bai = B->bai_scheme();
+  for (uint64_t j0 = 0; j0 < n; j0 += tile) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(tile, n - j0), nblk = (m + 255u) / 256u;
+    BaiPush P{};
+    P.n = m; P.ord0 = j0;
+    P.n_ref = B->n_ref; P.win_off = B->d_winoff.as<uint64_t>();
+    P.lin = B->lin.as<uint64_t>(); P.ref_beg = B->ref_beg.as<uint64_t>(); P.ref_end = B->ref_end.as<uint64_t>(); P.ref_cnt = B->ref_cnt.as<uint64_t>();
+    P.S = B->state.as<BaiState>(); P.par = B->par; P.flag = B->flag.as<uint8_t>(); P.blk_cnt = B->blk_cnt.as<uint32_t>();
+    P.Z = BaiSorted{V, j0, B->vt[0].as<uint64_t>(), n_members};
+    P.sch = B->sch;
+    hipLaunchKernelGGL(bai ? bai_record_sorted_kernel<true> : bai_record_sorted_kernel<false>, dim3(nblk), dim3(256), 0, st, P);
+    STRL_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bai_scan_kernel, dim3(1), dim3(1024), 0, st, P.blk_cnt, nblk, &P.S->n_heads, (uint64_t *)nullptr);
+    STRL_HIP(hipGetLastError());
+    STRL_HIP(hipMemcpyAsync(B->h_state, B->state.p, sizeof(BaiState), hipMemcpyDeviceToHost, st));
+    STRL_HIP(hipStreamSynchronize(st));                 // the number of runs that start in the launch: the table grows by exactly that
+    if ((rc = bai_refuse(B, *B->h_state))) return rc;
+    const uint64_t heads = B->h_state->n_heads;
+    if (B->n_runs + heads > 0x7ffffff0ull) { set_error("more than 2^31 runs of equal (reference, bin): beyond one device sort"); return STRL_ERR_LIMIT; }
+    if (heads) {
+      if ((rc = B->runs.grow((size_t)(B->n_runs + heads) * sizeof(BaiRun), (size_t)B->n_runs * sizeof(BaiRun), st))) return rc;
+      P.runs = B->runs.as<BaiRun>(); P.run_base = B->n_runs; P.run_acc = nullptr; P.run_cap = B->runs.cap / sizeof(BaiRun);
+      hipLaunchKernelGGL(bai ? bai_emit_sorted_kernel<true> : bai_emit_sorted_kernel<false>, dim3(nblk), dim3(256), 0, st, P);
+      STRL_HIP(hipGetLastError());
+      B->n_runs += heads;
+    }
+    B->n_records += m;
+    B->par ^= 1u;
+  }
+  STRL_HIP(hipStreamSynchronize(st));
+  if ((rc = bai_sort_and_pack(c, B))) return rc;
+  if (index_bytes) *index_bytes = B->bytes.size();
+  if (info) { info->n_records = B->n_records; info->n_no_coor = B->h_state->n_no_coor; info->n_runs = B->n_runs; info->n_chunks = B->n_chunks; }
+  return STRL_OK;
+}
+
+extern "C" int strl_bamsort_index_fetch(strl_ctx *c, uint8_t *out, uint64_t cap) {
+  BsortView V;
+  strl_bai **slot = nullptr;
+  if (!c || !out || bsort_view(c, &V, &slot) || !*slot || !(*slot)->finished) { set_error("strl_bamsort_index_fetch without strl_bamsort_index"); return STRL_ERR_ARG; }
+  const std::vector<uint8_t> &b = (*slot)->bytes;
+  if (cap < b.size()) { set_error("strl_bamsort_index_fetch: %llu bytes, room for %llu", (unsigned long long)b.size(), (unsigned long long)cap); return STRL_ERR_CAPACITY; }
+  memcpy(out, b.data(), b.size());
+  return STRL_OK;
+}
+
+// the rule of the virtual offsets through the library, without a device (the Python mirror, tests): bamsort_core.h's bsort_voff over
+// a table checked by bsort_member_table_ok, and the member walk the CLI runs over the bytes it writes
+extern "C" int strl_bamsort_voff(const uint64_t *member_off, uint64_t n_members, uint64_t stream_bytes, uint64_t s, uint64_t *voff) {
+  if (!voff || s > stream_bytes || !bsort_member_table_ok(member_off, n_members, stream_bytes)) {
+    set_error("strl_bamsort_voff: the table must hold ceil(stream_bytes / 0xFF00) + 1 file offsets that ascend and fit 48 bits, s <= stream_bytes");
+    return STRL_ERR_ARG;
+  }
+  *voff = bsort_voff(member_off, n_members, stream_bytes, s);
+  return STRL_OK;
+}
+extern "C" int strl_bamsort_members(const uint8_t *bytes, uint64_t n, uint64_t file_off, uint64_t *member_off, uint64_t cap, uint64_t *n_out) {
+  if ((n && !bytes) || !n_out) { set_error("strl_bamsort_members: null argument"); return STRL_ERR_ARG; }
+  std::vector<uint64_t> m;
+  uint64_t at = file_off;
+  if (!bsort_walk_members(bytes, (size_t)n, &at, m)) { set_error("strl_bamsort_members: the bytes are not whole BGZF members"); return STRL_ERR_FORMAT; }
+  *n_out = m.size();
+  if (cap < m.size() || (m.size() && !member_off)) { set_error("strl_bamsort_members: %zu members, room for %llu", m.size(), (unsigned long long)cap); return STRL_ERR_CAPACITY; }
+  if (!m.empty()) memcpy(member_off, m.data(), m.size() * 8);
   return STRL_OK;
 }

@@ -26,8 +26,6 @@
 
 namespace strl {
 
-constexpr int BSORT_SLAB_SHIFT = 40;                         // src = slab << 40 | offset in the slab
-constexpr uint64_t BSORT_SLAB_MASK = (1ull << BSORT_SLAB_SHIFT) - 1ull;
 constexpr uint32_t BSORT_TILE = 2048;                        // ranks per workgroup of the layout: 256 lanes x 8
 constexpr uint32_t BSORT_E_TID = 0, BSORT_E_RECORD = 1;
 
@@ -235,13 +233,26 @@ struct strl_bsort {
   std::string fail;
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   strl_bamsort_info info{};
+  strl_bai *index = nullptr;                   // `sort --write-index`: the index builder over the sorted records (bamindex.hip strl_bamsort_index)
 };
 
 void bsort_destroy(strl_bsort *B) {
   if (!B) return;
+  if (B->index) bai_destroy(B->index);
   if (B->h_state) (void)hipHostFree(B->h_state);
   for (hipEvent_t e : {B->e0, B->e1, B->e2}) if (e) (void)hipEventDestroy(e);
   delete B;
+}
+
+// the finished sort of the context, for the index step; *slot: where its builder hangs (bsort_destroy destroys it)
+int bsort_view(strl_ctx *c, BsortView *v, strl_bai ***slot) {
+  if (!c || !c->bsort || !c->bsort->finished) return STRL_ERR_ARG;
+  strl_bsort *B = c->bsort;
+  const size_t ns = B->slabs.size();
+  *v = BsortView{B->off.as<uint64_t>(), B->src.as<uint64_t>(), B->perm, B->len.as<uint32_t>(), B->d_slab.as<uint8_t *>(), B->d_slab.as<uint64_t>() + ns, (uint32_t)ns, B->n_ref,
+                 B->n_records, B->stream_bytes};
+  *slot = &B->index;
+  return STRL_OK;
 }
 
 static int bsort_fail(strl_bsort *B, int rc) {

@@ -66,6 +66,55 @@ BSORT_HD inline BsortPart bsort_part(uint64_t beg, uint64_t end, uint64_t lo, ui
   return p;
 }
 
+// ---- virtual offsets of the output (`sort --write-index`) ------------------------------------------------------------------------
+// The stream is cut into members of exactly BSORT_BLK bytes, so where a stream offset lies in the file is arithmetic and one load:
+// member_off[0 .. n_members] = file offset of every member, the last entry the EOF block's; n_members = ceil(stream_bytes / 0xFF00).
+//   voff(s) = member_off[s / 0xFF00] << 16 | s % 0xFF00,  0 <= s < stream_bytes;   voff(stream_bytes) = member_off[n_members] << 16
+// A byte on a member boundary belongs to the member that starts there, and the stream's end to the EOF block (offset 0) -- whether
+// or not the stream is a multiple of 0xFF00 long: what bai_voff (bamindex.hip) gives for the byte behind the last record of a file,
+// and what htslib's bgzf_tell gives there, so the index is `strling bamindex OUT.bam`'s byte for byte.  (bamio.write_bai names the
+// last member and its ISIZE instead when the last member is short: the same place, as tests that compare structures see it.)
+BSORT_HD inline uint64_t bsort_n_members(uint64_t stream_bytes) { return (stream_bytes + BSORT_BLK - 1) / BSORT_BLK; }
+BSORT_HD inline uint64_t bsort_voff(const uint64_t *member_off, uint64_t n_members, uint64_t stream_bytes, uint64_t s) {
+  if (s >= stream_bytes) return member_off[n_members] << 16;      // (s > stream_bytes is not asked for; nothing behind the table is read)
+  const uint64_t k = s / BSORT_BLK;                                // < n_members
+  return member_off[k] << 16 | (s - k * BSORT_BLK);
+}
+// a table the rule can use: n_members as the stream's length gives it, the offsets ascending, each below 2^48
+inline bool bsort_member_table_ok(const uint64_t *member_off, uint64_t n_members, uint64_t stream_bytes) {
+  if (!member_off || n_members != bsort_n_members(stream_bytes)) return false;
+  for (uint64_t k = 0; k <= n_members; ++k)
+    if (member_off[k] >> 48 || (k && member_off[k] <= member_off[k - 1])) return false;
+  return true;
+}
+// the BGZF members in p[0, n), which the writer puts at file offset `at`: each one's file offset is appended to member_off (BSIZE
+// at byte 16 of a member: zlib's members and the device compressor's alike).  -> the file offset behind them; false: not whole members
+inline bool bsort_walk_members(const uint8_t *p, size_t n, uint64_t *at, std::vector<uint64_t> &member_off) {
+  size_t o = 0;
+  while (o < n) {
+    if (n - o < 18 || p[o] != 0x1f || p[o + 1] != 0x8b) return false;
+    const size_t bsize = ((size_t)p[o + 16] | (size_t)p[o + 17] << 8) + 1;
+    if (bsize < 26 || bsize > n - o) return false;
+    member_off.push_back(*at + o);
+    o += bsize;
+  }
+  *at += n;
+  return true;
+}
+
+// what the index step reads of a finished sort (bamsort.hip hands it to bamindex.hip): device pointers
+constexpr int BSORT_SLAB_SHIFT = 40;                         // src = slab << 40 | offset in the slab
+constexpr uint64_t BSORT_SLAB_MASK = (1ull << BSORT_SLAB_SHIFT) - 1ull;
+struct BsortView {
+  const uint64_t *off, *src;   // off[0 .. n]: stream offsets in sorted order; src[ordinal]
+  const uint32_t *perm, *len;  // perm[rank] = ordinal; len[ordinal] = 4 + block_size
+  uint8_t *const *slab;        // [n_slabs] bases
+  const uint64_t *slab_used;   // [n_slabs] bytes of records in each
+  uint32_t n_slabs;
+  int32_t n_ref;
+  uint64_t n_records, stream_bytes;
+};
+
 // ---- the header (host) ------------------------------------------------------------------------------------------------------------
 // The text of the output: the input's, with the @HD line's SO: set to coordinate (added at the end of the line when the line has
 // none), GO: and SS: dropped, the line's other fields and every other line byte for byte; a text whose first line is not @HD

@@ -31,6 +31,12 @@ int end_process(strl_ctx *ctx);             // the end of a process whose output
 // one BGZF member of `len` <= 0xFF00 input bytes: zlib at its default level (what htslib writes, and `strling pull`)
 bool bgzf_member_zlib(const uint8_t *src, size_t len, std::vector<uint8_t> &o);
 
+// --csi [-m N]: min_shift of the CSI scheme, -1 without --csi; usage errors (-m without --csi, N outside [8, 24]) end the process
+int csi_min_shift(const Args &a, const char *usage);
+// the bytes of an index to `out` through a temporary name (a failed run leaves no half index); bgzf: in BGZF blocks with the EOF
+// block, as samtools writes a .csi.  false: why
+bool write_index_file(const std::string &out, const std::vector<uint8_t> &bytes, bool bgzf, std::string &why, strl::ThreadPool *pool = nullptr);
+
 // N page-locked chunk buffers and their N block tables (chunk_feed.h), allocated on a thread per buffer: the time is the kernel's,
 // faulting and locking the pages.  Nothing is freed unless release() is called: `call` and `bamindex` leave theirs to the end of
 // the process on purpose.

@@ -334,8 +334,9 @@ static void setup_genome(strl_ctx *ctx, const Args &a, const std::vector<BamTarg
 
 static int extract_front(const Args &a, const std::string &bam, const std::string &bin, double p, uint8_t min_mapq, bool verbose);
 static bool write_bgzf(const std::string &path, const std::vector<uint8_t> &payload, ThreadPool &pool, std::string &why);
-// --csi [-m N] of `bamindex` and `extract --write-index`: min_shift of the CSI scheme, -1 without --csi; usage errors end the process
-static int csi_min_shift(const Args &a, const char *usage) {
+// --csi [-m N] of `bamindex`, `extract --write-index` and `sort --write-index`: min_shift of the CSI scheme, -1 without --csi; usage
+// errors end the process
+int csi_min_shift(const Args &a, const char *usage) {
   if (!a.flag("csi")) {
     if (a.flag("min-shift")) quit("-m / --min-shift needs --csi\n%s", usage);
     return -1;
@@ -347,7 +348,7 @@ static int csi_min_shift(const Args &a, const char *usage) {
 }
 // the bytes of an index to `out` through a temporary name (a failed run leaves no half index); bgzf: in BGZF blocks with the EOF
 // block, as samtools writes a .csi.  false: why
-static bool write_index_file(const std::string &out, const std::vector<uint8_t> &bytes, bool bgzf, std::string &why, ThreadPool *pool = nullptr) {
+bool write_index_file(const std::string &out, const std::vector<uint8_t> &bytes, bool bgzf, std::string &why, ThreadPool *pool) {
   const std::string tmp = out + ".tmp." + std::to_string((long long)getpid());
   bool ok;
   if (bgzf) {
@@ -3156,7 +3157,7 @@ int main(int argc, char **argv) {
       "  outliers :   cohort STR outlier scores from the call outputs of many samples (scripts/strling-outliers.py).\n"
       "  bamindex :   build the index (.bai, or .csi with --csi) of a coordinate-sorted BAM on the GPU (what `samtools index` writes).\n"
       "  pull     :   write a region's reads and their mates to a small BAM, for debugging (the reference's pull_region).\n"
-      "  sort     :   coordinate-sort a BAM on the GPU (what `samtools sort` writes).\n";      // strling.nim:18-24
+      "  sort     :   coordinate-sort a BAM on the GPU (what `samtools sort` writes; --write-index: its index from the same pass).\n";      // strling.nim:18-24
   if (argc < 2) { fputs(top, stdout); return 1; }
   const std::string cmd = argv[1];
   if (cmd == "extract") return extract_main(argc, argv);

@@ -7,6 +7,9 @@
 // Host path (STRL_SORT=host, or no device): the host BAM reader, std::stable_sort on the same key, the same header, the same
 // stream, the same member cuts -- with --deflate=host the two paths write the same bytes.
 // The output is written under a temporary name and renamed at the end: a failed run leaves no file.
+// --write-index: the index (.bai / .csi) from the same pass.  The members are walked as they are written (their file offsets), and
+// behind the last piece the index is built from what the sort still holds -- the device's arena, order and offsets
+// (strl_bamsort_index), or the host path's (bamindex_host.cpp) -- and written, through a temporary name, after the BAM's rename.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,6 +26,7 @@
 #include "bam_reader.h"
 #include "bgzf_feed.h"
 #include "cram_reader.h"
+#include "../bamindex_host.h"
 #include "../bamsort_core.h"
 #include "../front.h"
 
@@ -36,6 +40,10 @@ double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::
 const char *USAGE =
     "strling sort\n\nUsage:\n  strling sort [options] -o OUT.bam IN.bam\n\nArguments:\n  IN.bam           path to a bam file, in any order\n\nOptions:\n"
     "  -o, --output=OUT.bam       required; written through a temporary name, so a failed run leaves no file\n"
+    "      --write-index          also write OUT.bam's index, built from the sort's own pass: no second read, inflate and scan of the file\n"
+    "      --index-out=OUT.bai    where --write-index writes it (default: OUT.bam.bai; with --csi OUT.bam.csi)\n"
+    "      --csi                  with --write-index: a CSI index (.csi), which also holds contigs longer than 2^29 bases\n"
+    "  -m, --min-shift=N          with --csi: bases per window of the smallest bins = 2^N, N in [8, 24] (default: 14)\n"
     "      --deflate=host|device  host (default): zlib at its default level on the pool, as pull.  device: the GPU's compressor (about 1.15 x the bytes)\n"
     "  -D, --device=K             GPU to use (default: 0)\n"
     "  -v, --verbose              one JSON line on stderr\n  -h, --help                 Show this help\n";
@@ -46,6 +54,9 @@ struct Seconds { double read = 0, sort = 0, gather = 0, deflate = 0, write = 0; 
 struct SortOut {
   std::string path, tmp;
   FILE *f = nullptr;
+  bool track = false;                     // --write-index: the file offset of every member written, the EOF block's last
+  std::vector<uint64_t> member_off;
+  uint64_t at = 0;
   bool open(const std::string &out, std::string &why) {
     path = out;
     tmp = out + ".tmp." + std::to_string((long long)getpid());
@@ -55,6 +66,7 @@ struct SortOut {
   }
   bool put(const uint8_t *p, size_t n, std::string &why) {
     if (n && fwrite(p, 1, n, f) != n) { why = "cannot write " + tmp + ": " + strerror(errno); return false; }
+    if (track && !bsort_walk_members(p, n, &at, member_off)) { why = "internal error: a piece written is not whole BGZF members"; return false; }
     return true;
   }
   bool close(std::string &why) {
@@ -99,6 +111,19 @@ uint64_t piece_bytes() {
   return std::max<uint64_t>(BSORT_BLK, want / BSORT_BLK * BSORT_BLK);
 }
 
+// --write-index: what was asked for, and what the index step gave
+struct Index {
+  bool on = false;
+  int min_shift = -1;                     // >= 0: a CSI index
+  std::string out;
+  std::vector<int32_t> l_ref;
+  int rc = 0;                             // != 0: refused (the sorted file is complete all the same)
+  std::string why;
+  std::vector<uint8_t> bytes;
+  uint64_t chunks = 0;
+  double s = 0;
+};
+
 struct Result {
   uint64_t records = 0, no_ref = 0, stream_bytes = 0, slabs = 0, out_bytes = 0;
   bool already_sorted = false;
@@ -108,7 +133,7 @@ struct Result {
 };
 
 // ---- the host path ---------------------------------------------------------------------------------------------------------------
-bool sort_on_host(const std::string &bam, const std::vector<uint8_t> &header, int32_t n_ref, bool core, SortOut &out, Result &R, std::string &why, int &status) {
+bool sort_on_host(const std::string &bam, const std::vector<uint8_t> &header, int32_t n_ref, bool core, SortOut &out, Result &R, Index &X, std::string &why, int &status) {
   auto t0 = Clock::now();
   BamReader rd;
   std::string err;
@@ -175,13 +200,28 @@ bool sort_on_host(const std::string &bam, const std::vector<uint8_t> &header, in
     R.s.write += since(t0);
   }
   R.deflate = core ? "core-host" : "zlib";
+  if (X.on) {                                                   // one pass over the sorted records (bamindex_host.cpp)
+    t0 = Clock::now();
+    out.member_off.push_back(out.at);                           // the EOF block
+    const uint64_t *mo = out.member_off.data(), nm = out.member_off.size() - 1;
+    HostIndex H;
+    if (!bsort_member_table_ok(mo, nm, run)) { X.rc = STRL_ERR_ARG; X.why = "internal error: the member table does not match the stream"; }
+    else if (!H.begin(n_ref, X.l_ref.data(), X.min_shift, -1, X.why)) X.rc = STRL_ERR_ARG;
+    else {
+      for (size_t j = 0; j < n; ++j)
+        H.add(raw.data() + at[perm[j]], (uint32_t)(off[j + 1] - off[j]), bsort_voff(mo, nm, run, off[j]), bsort_voff(mo, nm, run, off[j + 1]), off[j], off[j + 1]);
+      X.rc = H.finish(X.bytes, X.why);
+      X.chunks = H.n_chunks;
+    }
+    X.s = since(t0);
+  }
   status = 0;
   return true;
 }
 
 // ---- the device path -------------------------------------------------------------------------------------------------------------
 bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::vector<uint8_t> &header, bool core, SortOut &out, Result &R,
-                    std::string &why, int &status) {
+                    Index &X, std::string &why, int &status) {
   auto t0 = Clock::now();
   status = STRL_ERR_IO;
   BgzfFeed feed;
@@ -271,6 +311,17 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
   }
   if (core) { strl_bamsort_info now; if (!strl_bamsort_info_now(ctx, &now)) { R.s.deflate = std::max(0.0, R.s.gather - now.gather_ms / 1e3); R.s.gather = now.gather_ms / 1e3; } }
   R.deflate = core ? "device" : "zlib";
+  if (X.on) {                                                   // the records, their order and their offsets are still on the device
+    t0 = Clock::now();
+    out.member_off.push_back(out.at);                           // the EOF block
+    uint64_t nbytes = 0;
+    strl_bamindex_info ii{};
+    X.rc = strl_bamsort_index(ctx, X.l_ref.data(), X.min_shift, -1, out.member_off.data(), out.member_off.size() - 1, &nbytes, &ii);
+    if (!X.rc) { X.bytes.resize((size_t)nbytes + 1); X.rc = strl_bamsort_index_fetch(ctx, X.bytes.data(), X.bytes.size()); X.bytes.resize((size_t)nbytes); }
+    if (X.rc) X.why = strl_last_error();
+    X.chunks = ii.n_chunks;
+    X.s = since(t0);
+  }
   (void)strl_bamsort_end(ctx);
   // (the page-locked buffers are left to the end of the process: unlocking them stalls the device, as `bamindex` leaves its own)
   status = 0;
@@ -281,9 +332,15 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
 
 int sort_main(int argc, char **argv) {
   if (argc <= 2) { fputs(USAGE, stdout); return 0; }
-  const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"deflate", 0, true}, {"device", 'D', true}, {"verbose", 'v', false}}, USAGE);
+  const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"deflate", 0, true}, {"device", 'D', true}, {"verbose", 'v', false},
+                                       {"write-index", 0, false}, {"index-out", 0, true}, {"csi", 0, false}, {"min-shift", 'm', true}}, USAGE);
   if (a.pos.size() != 1) quit("expected 1 argument (bam)\n%s", USAGE);
   if (!a.flag("output")) quit("[strling] sort: -o OUT.bam is required\n%s", USAGE);
+  if (a.flag("index-out") && !a.flag("write-index")) quit("--index-out needs --write-index\n%s", USAGE);
+  if (a.flag("csi") && !a.flag("write-index")) quit("--csi needs --write-index\n%s", USAGE);
+  Index X;
+  X.on = a.flag("write-index");
+  X.min_shift = csi_min_shift(a, USAGE);
   const std::string bam = a.pos[0], out_path = a.get("output", ""), form = a.get("deflate", "host");
   if (form != "host" && form != "device") quit("--deflate must be host or device (got %s)", form.c_str());
   const bool core = form == "device";
@@ -300,9 +357,24 @@ int sort_main(int argc, char **argv) {
     const std::vector<uint8_t> &h = rd.header_bytes();
     if (!bsort_header(h.data(), h.size(), header, &n_ref, nullptr, err)) quit("[strling] sort: %s (status %d)", err.c_str(), STRL_ERR_FORMAT);
   }
+  if (X.on) {                              // what no index of the kind asked for can hold is refused before anything is read
+    X.out = a.get("index-out", (out_path + (X.min_shift >= 0 ? ".csi" : ".bai")).c_str());
+    size_t at = 12 + (size_t)bsort_ld32(header.data() + 4);      // (bsort_header has walked the list)
+    for (int32_t t = 0; t < n_ref; ++t) {
+      const uint32_t l_name = bsort_ld32(header.data() + at);
+      const int32_t len = (int32_t)bsort_ld32(header.data() + at + 4 + l_name);
+      if (X.min_shift < 0 && len > BAI_MAX_POS)
+        quit("[strling] sort: --write-index: reference %s is %d bases long, past 2^29 = 536870912, which a .bai cannot address; a CSI index can: --csi (status %d)",
+             std::string(reinterpret_cast<const char *>(header.data() + at + 4), l_name ? l_name - 1 : 0).c_str(), len, STRL_ERR_LIMIT);
+      X.l_ref.push_back(len);
+      at += 8 + (size_t)l_name;
+    }
+    X.l_ref.push_back(0);                  // (n_ref = 0: the builders still get a pointer)
+  }
   const char *where = getenv("STRL_SORT");
   const bool on_host = (where && !strcmp(where, "host")) || strl_device_count() <= 0;
   SortOut out;
+  out.track = X.on;
   std::string why;
   int status = 0;
   Result R;
@@ -310,7 +382,7 @@ int sort_main(int argc, char **argv) {
   bool ok;
   if (on_host) {
     if (!out.open(out_path, why)) quit("[strling] sort: %s (status %d)", why.c_str(), STRL_ERR_IO);
-    ok = sort_on_host(bam, header, n_ref, core, out, R, why, status);
+    ok = sort_on_host(bam, header, n_ref, core, out, R, X, why, status);
   } else {
     set_device0(a.get("device", ""));
     // the HIP runtime and the context come up on a thread beside the header walk, the page-locked buffers and the first chunk's read
@@ -321,7 +393,7 @@ int sort_main(int argc, char **argv) {
     auto get_ctx = [&](std::string &w) -> strl_ctx * { if (ctx_thread.joinable()) ctx_thread.join(); if (ctx_rc) w = ctx_err; return ctx_rc ? nullptr : ctx; };
     ok = out.open(out_path, why);
     if (!ok) status = STRL_ERR_IO;
-    else ok = sort_on_device(get_ctx, bam, header, core, out, R, why, status);
+    else ok = sort_on_device(get_ctx, bam, header, core, out, R, X, why, status);
     if (ctx_thread.joinable()) ctx_thread.join();
     g_bg_init = nullptr;
   }
@@ -332,11 +404,26 @@ int sort_main(int argc, char **argv) {
     if (status == STRL_ERR_NOMEM) quit("[strling] sort: %s; sort this file with samtools, or on a device with more memory (status %d)", why.c_str(), status);
     quit("[strling] sort: %s (status %d)", why.c_str(), status);
   }
+  // the index behind the BAM's rename.  A refusal (the records' own: a negative position, a record past the end of its reference
+  // or past what the scheme addresses) leaves the sorted file, which is complete and valid, and no index
+  if (X.on && !X.rc) {
+    const auto t0 = Clock::now();
+    ThreadPool pool(std::min(decode_threads(), 4));
+    if (!write_index_file(X.out, X.bytes, X.min_shift >= 0, X.why, &pool)) X.rc = STRL_ERR_IO;
+    X.s += since(t0);
+  }
+  const bool indexed = X.on && !X.rc;
   if (a.flag("verbose"))
     fprintf(stderr,
             "{\"command\": \"sort\", \"path\": \"%s\", \"records\": %llu, \"no_reference\": %llu, \"stream_bytes\": %llu, \"out_bytes\": %llu, \"already_sorted\": %s, \"slabs\": %llu, "
-            "\"seconds\": %.3f, \"read_s\": %.3f, \"sort_s\": %.3f, \"gather_s\": %.3f, \"deflate_s\": %.3f, \"write_s\": %.3f, \"deflate\": \"%s\", \"stored\": %u}\n",
+            "\"seconds\": %.3f, \"read_s\": %.3f, \"sort_s\": %.3f, \"gather_s\": %.3f, \"deflate_s\": %.3f, \"write_s\": %.3f, \"deflate\": \"%s\", \"stored\": %u, "
+            "\"index\": \"%s\", \"index_bytes\": %llu, \"index_chunks\": %llu, \"index_s\": %.3f}\n",
             on_host ? "host" : "device", (unsigned long long)R.records, (unsigned long long)R.no_ref, (unsigned long long)R.stream_bytes, (unsigned long long)R.out_bytes,
-            R.already_sorted ? "true" : "false", (unsigned long long)R.slabs, since(t_all), R.s.read, R.s.sort, R.s.gather, R.s.deflate, R.s.write, R.deflate, R.stored);
+            R.already_sorted ? "true" : "false", (unsigned long long)R.slabs, since(t_all), R.s.read, R.s.sort, R.s.gather, R.s.deflate, R.s.write, R.deflate, R.stored,
+            !indexed ? "none" : X.min_shift >= 0 ? "csi" : "bai", (unsigned long long)(indexed ? X.bytes.size() : 0), (unsigned long long)(indexed ? X.chunks : 0), X.s);
+  if (X.on && X.rc) {
+    if (ctx) strl_ctx_destroy(ctx);
+    quit("[strling] sort: sorted file written; index refused: %s (status %d)", X.why.c_str(), X.rc);
+  }
   return end_process(ctx);
 }

@@ -161,6 +161,8 @@ size_t front_name_tiles(uint32_t cap);      // words of d_tile_sums for `cap` na
 void front_destroy(strl_front *F);
 int front_init_slots(strl_ctx *c, strl_front *F);
 int front_begin_scan(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset);   // the front end without strl_front_begin's per-read state (bamindex.hip)
+struct BsortView;
+int bsort_view(strl_ctx *c, BsortView *v, strl_bai ***slot);      // bamsort.hip: the finished sort of the context, for strl_bamsort_index
 // bamindex.hip: the index builder behind strl_front_begin's own pass (strl_front_index_*); no-ops without one.  Neither waits
 // for the device, neither can fail the extraction.
 //   bai_front_chunk   a chunk has been handed over to slot si: its block table (whole_file: no other context took the chunk before)

@@ -1,6 +1,7 @@
 """`strling sort` on a shuffled BAM: the device path with both --deflate forms beside the host path (STRL_SORT=host), JSON lines.
 
     python tools/sort_bench.py [--pairs N] [--repeats K] [--trace OUTDIR] [--dir D] [--slab-mb M] [--lanes 16,32,64]
+    python tools/sort_bench.py --write-index [--parent-cli PATH] [--pairs N] [--repeats K] [--trace OUTDIR]
 
 The input is a file of --pairs pairs from bamio.write_bam_slabs (30x geometry, qualities, aux tags), its records put into a random
 order (a seeded permutation of the whole file, the header's SO: set to unsorted) and written again at zlib level 1.  One after the
@@ -12,6 +13,10 @@ other on one box, one process at a time, K runs each (the first pays for the pag
   * one more device run with STRL_ALLOC_TIMING=1: the library's own timing of every hipMalloc of 64 MB and more, the arena's slabs among them;
   * --slab-mb: one more device run with slabs of that size (default 4096), to see what allocating the arena slab by slab costs;
   * --trace: one more run under `rocprofv3 --kernel-trace --stats` (a run of its own): OUTDIR/kernel_stats.csv.
+--write-index measures `sort --write-index` instead, in one call, alternating, K runs each (K >= 5 for a figure), for both --deflate
+forms: this build's `sort --write-index`; --parent-cli's (default: this build's) `sort` followed by its `bamindex` of the output,
+the two commands' wall times summed; this build's plain `sort` and the parent's side by side, the order swapped every repeat.  The
+index must be the bytes `bamindex` wrote.  With --trace the traced run is `sort --write-index --deflate=device`.
 `samtools sort` is not on these machines: nothing here compares with it.  No threshold is asserted.
 """
 import argparse
@@ -71,6 +76,42 @@ def _run(cmd, env=None):
     return json.loads(r.stderr.strip().splitlines()[-1]), round(time.time() - t, 3)
 
 
+def _timed(cmd):
+    t = time.time()
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
+    if r.returncode != 0:
+        sys.stderr.write(r.stderr[-4000:])
+        sys.exit(r.returncode)
+    return r, round(time.time() - t, 3)
+
+
+def write_index_runs(a, cli, src, work):
+    """`sort --write-index` against the parent's `sort` followed by `bamindex`, and plain `sort` against the parent's: alternating"""
+    parent = a.parent_cli or cli
+    ours, theirs, plain = (os.path.join(work, n) for n in ("ours.bam", "theirs.bam", "plain.bam"))
+    for form in ("host", "device"):
+        for k in range(a.repeats):
+            r, w = _timed([cli, "sort", "--write-index", "-v", f"--deflate={form}", "-o", ours, src])
+            print(json.dumps({"run": "sort --write-index", "deflate": form, "repeat": k, "wall_s": w, "says": json.loads(r.stderr.strip().splitlines()[-1])}), flush=True)
+            _, ws = _timed([parent, "sort", f"--deflate={form}", "-o", theirs, src])
+            _, wi = _timed([parent, "bamindex", theirs])
+            print(json.dumps({"run": "parent sort + bamindex", "deflate": form, "repeat": k, "wall_s": round(ws + wi, 3), "sort_wall_s": ws, "bamindex_wall_s": wi}), flush=True)
+            for who in (("sort", "parent sort") if k % 2 == 0 else ("parent sort", "sort")):      # side by side, the order swapped every repeat
+                _, wp = _timed([cli if who == "sort" else parent, "sort", f"--deflate={form}", "-o", plain, src])
+                print(json.dumps({"run": who, "deflate": form, "repeat": k, "wall_s": wp}), flush=True)
+        same = open(ours + ".bai", "rb").read() == open(theirs + ".bai", "rb").read() and open(ours, "rb").read() == open(theirs, "rb").read() == open(plain, "rb").read()
+        print(json.dumps({"check": "the index is bamindex's, the three BAMs are one", "deflate": form, "ok": same, "index_bytes": os.path.getsize(ours + ".bai")}), flush=True)
+    if a.trace:
+        os.makedirs(a.trace, exist_ok=True)
+        kt = os.path.join(work, "kt")
+        r = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", kt, "-o", "run", "--", cli, "sort", "--write-index", "--deflate=device", "-o", ours, src],
+                           capture_output=True, text=True, env=dict(os.environ, STRL_TEARDOWN="1"), timeout=900)
+        f = glob.glob(os.path.join(kt, "**", "run_kernel_stats.csv"), recursive=True)
+        if r.returncode == 0 and f:
+            shutil.copy(f[0], os.path.join(a.trace, "kernel_stats_write_index.csv"))
+        print(json.dumps({"trace": "kernel_stats_write_index.csv" if (r.returncode == 0 and f) else (r.stderr or "no kernel table")[-500:]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--pairs", type=int, default=2 ** 20)
@@ -79,6 +120,8 @@ def main():
     ap.add_argument("--dir", default=None)
     ap.add_argument("--slab-mb", default="")
     ap.add_argument("--lanes", default="16,32,64")
+    ap.add_argument("--write-index", action="store_true")
+    ap.add_argument("--parent-cli", default="")
     a = ap.parse_args()
     t0 = time.time()
     inp = e2e_bench.make_input(a.pairs, d=a.dir, level=1)
@@ -88,6 +131,10 @@ def main():
     cli = os.path.join(ROOT, "strling_amd", "lib", "strling")
     base = {"tool": "sort_bench", "reads": n, "inflated_bytes": inflated, "bam_bytes": os.path.getsize(src), "input_s": round(time.time() - t0, 1)}
     print(json.dumps(base), flush=True)
+    if a.write_index:
+        write_index_runs(a, cli, src, work)
+        shutil.rmtree(work, ignore_errors=True)
+        return
     outs = {}
     forms = (("device_zlib", ["--deflate=host"], {}), ("device_core", ["--deflate=device"], {}), ("host_zlib", ["--deflate=host"], {"STRL_SORT": "host"}))
     for k in range(a.repeats):

@@ -53,6 +53,19 @@ if command -v samtools > /dev/null 2>&1 && "$S" sort 2> /dev/null | grep -q -- -
   samtools view "$T/sort_theirs.bam" > "$T/sort_theirs.sam" 2>> "$T/sort.log"; samtools view "$T/sort_ours.bam" > "$T/sort_ours.sam" 2>> "$T/sort.log"
   check sort "$T/sort_ours.sam" "$T/sort_theirs.sam" "(reference, position, forward before reverse, then input order) is samtools sort's order"
   samtools view -H "$T/sort_ours.bam" | grep -q "^@HD.*SO:coordinate" && echo "PASS  sort_header   (@HD SO:coordinate)" || { echo "FAIL  sort_header   (no @HD SO:coordinate in strling sort's output)"; fail=1; }
+  # sort --write-index: the index from the sort's own pass against `samtools index` of the same sorted file, as region reads (the
+  # bytes may differ where a chunk ends on a block edge).  Never run either: no machine this was built on had samtools.
+  if "$S" sort 2> /dev/null | grep -q -- --write-index; then
+    "$S" sort --write-index -o "$T/sort_idx.bam" "$T/sort_in.bam" >> "$T/sort.log" 2>&1 || echo "      (sort: strling sort --write-index exited non-zero, see $T/sort.log)"
+    cp "$T/sort_idx.bam" "$T/sort_idx_theirs.bam"; samtools index "$T/sort_idx_theirs.bam" >> "$T/sort.log" 2>&1
+    : > "$T/sort_idx_ours.txt"; : > "$T/sort_idx_theirs.txt"
+    for c in $(samtools view -H "$T/sort_idx.bam" | awk -F'\t' '/^@SQ/ { sub("SN:", "", $2); print $2 }' | head -8); do
+      samtools view "$T/sort_idx.bam" "$c" >> "$T/sort_idx_ours.txt" 2>> "$T/sort.log"; samtools view "$T/sort_idx_theirs.bam" "$c" >> "$T/sort_idx_theirs.txt" 2>> "$T/sort.log"
+    done
+    check sort_index "$T/sort_idx_ours.txt" "$T/sort_idx_theirs.txt" "samtools reads the same records per contig through sort --write-index's .bai as through its own"
+  else
+    echo "SKIP  sort_index   (needs a strling with sort --write-index)"
+  fi
 else
   echo "SKIP  sort   (needs samtools and a strling with the sort command: the order stays checked against its own statement in tests/sort_bam_cases.py only)"
 fi
