@@ -896,6 +896,35 @@ int strl_bamsort_index(strl_ctx *ctx, const int32_t *l_ref, int32_t csi_min_shif
 int strl_bamsort_index_fetch(strl_ctx *ctx, uint8_t *out, uint64_t cap);
 int strl_bamsort_voff(const uint64_t *member_off, uint64_t n_members, uint64_t stream_bytes, uint64_t s, uint64_t *voff);
 int strl_bamsort_members(const uint8_t *bytes, uint64_t n, uint64_t file_off, uint64_t *member_off, uint64_t cap, uint64_t *n_out);
+/* A file larger than device memory, sorted in passes (`strling sort --windowed`).  Nothing of the records stays
+ * on the device but 12 bytes each: pass 0 keeps key and length, sorts, and leaves dest[ordinal] = the record's first byte in the
+ * output stream.  Every later pass reads the input again and scatters the records that touch the window [lo, hi) of the stream
+ * straight to their place in a window buffer, which is then a finished piece of the stream: no temporary file, no run, no merge.
+ *   strl_bamsort_begin_windowed  as strl_bamsort_begin, without an arena.  strl_bamsort_reserve / _push / _finish / _info_now /
+ *                                _end work as before; strl_bamsort_info's n_slabs, arena_bytes and gather_ms stay 0.
+ *   strl_bamsort_window_limit    the largest window the device can hold now: its free memory (the front end's slots are allocated
+ *                                by then and so outside that figure) less the 768 MiB the resident path keeps for the piece and the
+ *                                compressor.
+ *   strl_bamsort_window_begin    the window [lo, hi), lo < hi <= stream_bytes, behind strl_bamsort_finish: the window buffer (never
+ *                                shrunk between windows), the header's bytes inside it, the front end rewound to the file's start.
+ *   strl_bamsort_window_push     the same arguments and pipelining as strl_bamsort_push, over the same file from its first chunk:
+ *                                copy, inflate, CRC and record scan of chunk i, then the scatter of chunk i - 1.
+ *   strl_bamsort_window_end      the last chunk's scatter, and the checks.  STRL_ERR_FORMAT "the input changed between passes:
+ *                                record N" (the first record whose length is not pass 0's) or a record count that is not pass
+ *                                0's; STRL_ERR_ASSERT when the bytes placed and the header's do not fill the window; and the
+ *                                inflate, CRC and format errors of a push.
+ * Inside the window just ended strl_bamsort_fetch / _fetch_bgzf keep their contracts and read the window buffer; outside it they
+ * are STRL_ERR_ARG.  strl_bamsort_order and strl_bamsort_index are STRL_ERR_ARG in this mode (the order is given up for dest[], the
+ * records are never resident in sorted order).  The 2^32 - 2 record limit stays.  STRL_SORT_GATHER_LANES = 16 / 32 / 64: lanes per
+ * record of the scatter, as of the gather.  strl_bamsort_window_plan: the rule of csrc/bamsort_core.h without a device --
+ * window_bytes = max(piece_bytes, limit_bytes / piece_bytes * piece_bytes), n_windows = ceil(stream_bytes / window_bytes). */
+int strl_bamsort_begin_windowed(strl_ctx *ctx, int32_t n_ref, uint64_t first_record_offset);
+int strl_bamsort_window_limit(strl_ctx *ctx, uint64_t *bytes);
+int strl_bamsort_window_begin(strl_ctx *ctx, uint64_t lo, uint64_t hi);
+int strl_bamsort_window_push(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                             const uint32_t *crc32, uint32_t n_blocks);
+int strl_bamsort_window_end(strl_ctx *ctx);
+int strl_bamsort_window_plan(uint64_t stream_bytes, uint64_t limit_bytes, uint64_t piece_bytes, uint64_t *window_bytes, uint64_t *n_windows);
 
 /* ---- the .bai as a by-product of `strling extract`'s own pass (`strling extract --write-index`) ----
  * strl_front_push already copies, inflates, CRC-checks, record-scans and parses every block; the index needs of a record only

@@ -154,7 +154,9 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_bgzf_deflate", "strl_bgzf_deflate_bound", "strl_bgzf_deflate_host", "strl_ctx_deflate_ms",
            "strl_bamsort_begin", "strl_bamsort_reserve", "strl_bamsort_push", "strl_bamsort_finish", "strl_bamsort_fetch", "strl_bamsort_fetch_bgzf", "strl_bamsort_order",
            "strl_bamsort_info_now", "strl_bamsort_end", "strl_bamsort_key", "strl_bamsort_key_bits", "strl_bamsort_header",
-           "strl_bamsort_index", "strl_bamsort_index_fetch", "strl_bamsort_voff", "strl_bamsort_members"]
+           "strl_bamsort_index", "strl_bamsort_index_fetch", "strl_bamsort_voff", "strl_bamsort_members",
+           "strl_bamsort_begin_windowed", "strl_bamsort_window_limit", "strl_bamsort_window_begin", "strl_bamsort_window_push", "strl_bamsort_window_end",
+           "strl_bamsort_window_plan"]
 
 
 def lib_path():
@@ -295,6 +297,13 @@ def load(build_if_missing=True):
     L.strl_bamsort_voff.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     L.strl_bamsort_members.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.strl_bamsort_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_bamsort_begin_windowed.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
+    L.strl_bamsort_window_limit.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.strl_bamsort_window_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+    L.strl_bamsort_window_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.strl_bamsort_window_end.argtypes = [C.c_void_p]
+    L.strl_bamsort_window_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.strl_bamsort_window_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     L.strl_sweep_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8]
     L.strl_sweep_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
     L.strl_sweep_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
@@ -1100,6 +1109,83 @@ class Context:
         a, b = int(rng[0]), int(rng[1])
         return off, (a, b), parts[:b - a]
 
+    # ---- `strling sort --windowed` (strl_bamsort_begin_windowed / _window_*): a file larger than device memory, in passes
+    def bamsort_begin_windowed(self, n_ref, first_off):
+        _check(self.L.strl_bamsort_begin_windowed(self.h, int(n_ref), int(first_off)))
+
+    def bamsort_window_limit(self):
+        """the largest window of the stream the device can hold now, in bytes"""
+        n = C.c_uint64(0)
+        _check(self.L.strl_bamsort_window_limit(self.h, C.byref(n)))
+        return n.value
+
+    def bamsort_window_begin(self, lo, hi):
+        _check(self.L.strl_bamsort_window_begin(self.h, int(lo), int(hi)))
+
+    def bamsort_window_push(self, comp, coff, clen, isize, crc=None):
+        """one chunk of the same file again, as bamsort_push takes it"""
+        _check(self.L.strl_bamsort_window_push(self.h, comp.ctypes.data, comp.size, _ptr(coff), _ptr(clen), _ptr(isize), _ptr(crc) if crc is not None else None, len(coff)))
+
+    def bamsort_window_end(self):
+        _check(self.L.strl_bamsort_window_end(self.h))
+
+    def bamsort_window_probe(self, lens, perm, base, lo, hi):
+        """test-only (strl_bamsort_window_probe): the layout, the inversion of the permutation and the scatter's part arithmetic over
+        caller-given lengths (by input ordinal), perm[rank] = ordinal and a 64-bit base
+        -> (dest uint64[n] by ordinal, parts uint64[n, 3] = source skip, destination, bytes of each ordinal's part inside [lo, hi))"""
+        l = np.ascontiguousarray(lens, np.uint32)
+        p = np.ascontiguousarray(perm, np.uint32)
+        assert l.size == p.size
+        dest = np.zeros(max(1, l.size), np.uint64)
+        parts = np.zeros((max(1, l.size), 3), np.uint64)
+        _check(self.L.strl_bamsort_window_probe(self.h, _ptr(l) if l.size else None, _ptr(p) if p.size else None, l.size, int(base), int(lo), int(hi), dest.ctypes.data,
+                                                parts.ctypes.data))
+        return dest[:l.size], parts[:l.size]
+
+    @staticmethod
+    def _bam_chunks(B, chunk_blocks):
+        """the blocks of a file (_bam_blocks) in chunks of chunk_blocks, as a push takes them (pageable memory: the runtime stages the copy)"""
+        data, blocks = B["data"], B["blocks"]
+        for s0 in range(B["b0"], len(blocks), chunk_blocks):
+            cb = blocks[s0:s0 + chunk_blocks]
+            lo, hi = cb[0][0], cb[-1][0] + cb[-1][1]
+            yield (np.ascontiguousarray(data[lo:hi]), np.array([b[0] - lo for b in cb], np.uint64), np.array([b[1] for b in cb], np.uint32),
+                   np.array([b[2] for b in cb], np.uint32), np.array([b[3] for b in cb], np.uint32))
+
+    def bamsort_windowed(self, path, window_bytes, chunk_blocks=16384, piece_bytes=0xFF00, again=None, keep_open=False):
+        """a BAM FILE coordinate-sorted on the device in windows of the output stream (bamsort_window_plan(stream, window_bytes,
+        piece_bytes)): pass 0 over the file, then the file once more per window, every window fetched whole
+        -> (the output stream, strl_bamsort_info as a dict with "windows" and "window_bytes" added).
+        again (tests): the file the windows' passes read instead of `path` -- a changed input between passes is refused.
+        keep_open: the sort is left on the context with its last window current (bamsort_end ends it)"""
+        B = self._bam_blocks(path)
+        B2 = B if again is None else self._bam_blocks(again)
+        header = bamsort_header(B["header_raw"])
+        self.bamsort_begin_windowed(B["n_ref"], B["first_off"])
+        try:
+            keep = []
+            for ch in self._bam_chunks(B, chunk_blocks):
+                keep = (keep + [ch])[-3:]
+                self.bamsort_push(*ch)
+            info = self.bamsort_finish(header)
+            W, P = bamsort_window_plan(info["stream_bytes"], window_bytes, piece_bytes)
+            out = []
+            for w in range(P):
+                lo, hi = w * W, min(info["stream_bytes"], (w + 1) * W)
+                self.bamsort_window_begin(lo, hi)
+                for ch in self._bam_chunks(B2, chunk_blocks):
+                    keep = (keep + [ch])[-3:]
+                    self.bamsort_window_push(*ch)
+                self.bamsort_window_end()
+                out.append(self.bamsort_fetch(lo, hi - lo))
+            info = dict(self.bamsort_info(), windows=P, window_bytes=W)
+        except Exception:
+            self.bamsort_end()
+            raise
+        if not keep_open:
+            self.bamsort_end()
+        return b"".join(out), info
+
     def bamsort(self, path, chunk_blocks=16384, check_crc=True, arena_limit_bytes=0, keep_open=False, index=None):
         """a BAM FILE coordinate-sorted on the device -> (the output stream: header || records in sorted order, strl_bamsort_info as a
         dict, the permutation).  keep_open: the sort is left on the context for further fetches (bamsort_end ends it).
@@ -1481,6 +1567,14 @@ def bamsort_members(data, file_off=0):
     n = C.c_uint64(0)
     _check(load().strl_bamsort_members(_ptr(src) if src.size else None, src.size, int(file_off), out.ctypes.data, out.size, C.byref(n)))
     return [int(x) for x in out[:n.value]]
+
+
+def bamsort_window_plan(stream_bytes, limit_bytes, piece_bytes=0xFF00):
+    """the windows of `strling sort --windowed` (strl_bamsort_window_plan; csrc/bamsort_core.h) -> (window_bytes, n_windows):
+    window_bytes = max(piece_bytes, limit_bytes // piece_bytes * piece_bytes), n_windows = ceil(stream_bytes / window_bytes)"""
+    w, n = C.c_uint64(0), C.c_uint64(0)
+    _check(load().strl_bamsort_window_plan(int(stream_bytes), int(limit_bytes), int(piece_bytes), C.byref(w), C.byref(n)))
+    return w.value, n.value
 
 
 def bamsort_voff(member_off, stream_bytes, s):

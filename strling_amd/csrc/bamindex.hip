@@ -834,7 +834,9 @@ extern "C" int strl_bamsort_index(strl_ctx *c, const int32_t *l_ref, int32_t csi
                                   uint64_t *index_bytes, strl_bamindex_info *info) {
   BsortView V;
   strl_bai **slot = nullptr;
-  if (!c || bsort_view(c, &V, &slot)) { set_error("strl_bamsort_index without strl_bamsort_finish"); return STRL_ERR_ARG; }
+  const int vr = c ? bsort_view(c, &V, &slot) : STRL_ERR_ARG;
+  if (vr == 2) { set_error("strl_bamsort_index: not supported by a windowed sort, whose records are never resident in sorted order; index the file it wrote"); return STRL_ERR_ARG; }
+  if (vr) { set_error("strl_bamsort_index without strl_bamsort_finish"); return STRL_ERR_ARG; }
   if (V.n_ref && !l_ref) { set_error("strl_bamsort_index: bad argument"); return STRL_ERR_ARG; }
   if (!bsort_member_table_ok(member_off, n_members, V.stream_bytes)) {
     set_error("strl_bamsort_index: the member table must hold ceil(%llu / 0xFF00) + 1 = %llu file offsets that ascend and fit 48 bits (n_members given: %llu)",

@@ -16,6 +16,13 @@
 //   bsort_gather_kernel                a group of 16 lanes per record copies the part inside the piece with aligned 16-byte stores,
 //                                      each assembled from two aligned loads (source and destination differ mod 16)
 // and leaves as it is (strl_bamsort_fetch) or through the device BGZF compressor (deflate.hip; strl_bamsort_fetch_bgzf).
+// A file larger than device memory (`sort --windowed`; strl_bamsort_begin_windowed) keeps no arena: pass 0 is
+// the keys kernel alone (12 bytes a record stay), the finish adds
+//   bsort_dest_kernel                  dest[perm[j]] = off[j]: where every record of the INPUT starts in the stream
+// and every later pass reads the file again for one window [lo, hi) of the stream (strl_bamsort_window_begin / _push / _end)
+//   bsort_scatter_kernel               a group of 16 lanes per record of the chunk copies the part inside the window to its place,
+//                                      as the gather copies; a length that is not pass 0's is refused, the bytes placed are counted
+// after which the window buffer is a finished piece of the stream and the fetches read it.
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -70,7 +77,7 @@ __global__ __launch_bounds__(256) void bsort_keys_kernel(BsortKeys P) {
     if (bad != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(&P.S->err_ord[kind]), (unsigned long long)bad);
     P.key[P.ord0 + i] = key;
     P.len[P.ord0 + i] = len;                                  // (0 for a refused record: nothing of it is ever copied)
-    P.src[P.ord0 + i] = P.src0 + (uint64_t)(q - (len ? P.start0 : q));
+    if (P.src) P.src[P.ord0 + i] = P.src0 + (uint64_t)(q - (len ? P.start0 : q));      // (null: a windowed sort keeps no arena)
   }
   const unsigned long long m = __ballot(no_ref);
   if (m && (threadIdx.x & 63u) == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&P.S->n_no_ref), (unsigned long long)__popcll(m));
@@ -215,6 +222,88 @@ template <uint32_t G> __global__ __launch_bounds__(256) void bsort_gather_kernel
   }
 }
 
+// ---- `sort --windowed`: the file read again for every window of the stream ---------------------------------------------------------
+// dest[perm[j]] = off[j]: the permutation inverted once, so that a pass over the input reads dest[] and len[] in input order, coalesced
+__global__ __launch_bounds__(256) void bsort_dest_kernel(const uint32_t *perm, const uint64_t *off, uint32_t n, uint64_t *dest) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (j < n) { const uint32_t p = perm[j]; if (p < n) dest[p] = off[j]; }
+}
+
+struct BsortWinState {       // device words of a window's pass
+  uint64_t err_ord;          // ordinal of the first record that is not pass 0's (length, count, or outside its chunk); ~0 = none
+  uint64_t placed;           // bytes of records placed in the window
+};
+
+struct BsortScatter {
+  const uint8_t *U;          // the chunk's inflated bytes (16-byte aligned; src_cap readable bytes)
+  const uint32_t *recoff;
+  uint32_t n, start0, rec_end;
+  uint64_t src_cap;
+  uint64_t ord0, n_records;  // ordinal of the chunk's first record; records of pass 0
+  const uint64_t *dest;      // [n_records] by input ordinal
+  const uint32_t *len;
+  uint64_t lo, hi;
+  uint8_t *window;           // 16-byte aligned, hi - lo bytes
+  BsortWinState *S;
+};
+
+// G lanes per record of the chunk: the part of it inside the window goes to its place, copied as the gather copies
+template <uint32_t G> __global__ __launch_bounds__(256) void bsort_scatter_kernel(BsortScatter P) {
+  const uint64_t win_bytes = P.hi - P.lo;
+  const uint32_t g = threadIdx.x % G;
+  const uint64_t group = ((uint64_t)blockIdx.x * 256u + threadIdx.x) / G, n_groups = (uint64_t)gridDim.x * 256u / G;
+  uint64_t placed = 0;                                        // (counted by lane 0 of a group)
+  for (uint64_t i = group; i < P.n; i += n_groups) {
+    const uint64_t ord = P.ord0 + i;
+    const uint32_t q = P.recoff[i];
+    BsortPart pt{0, 0, 0};
+    bool ok = false;
+    uint32_t len = 0;
+    if (ord < P.n_records && q >= P.start0 && q <= P.rec_end && P.rec_end - q >= BSORT_MIN_REC) {      // (the chunk bounds of bsort_keys_kernel)
+      const uint32_t bs = ld32u(P.U + q);
+      len = P.len[ord];
+      ok = bs >= 32u && bs <= P.rec_end - q - 4u && bsort_scatter_part(P.dest[ord], len, bs, P.lo, P.hi, &pt);
+    }
+    if (!ok) { if (g == 0) atomicMin(reinterpret_cast<unsigned long long *>(&P.S->err_ord), (unsigned long long)ord); continue; }
+    // outside the window: nothing to do for the whole group.  Source inside the record (so inside [start0, rec_end): q + len <= rec_end
+    // by the check above), destination inside the window
+    if (!pt.bytes || pt.skip > len || pt.bytes > len - pt.skip || pt.dst > win_bytes || pt.bytes > win_bytes - pt.dst) continue;
+    const uint64_t so = (uint64_t)q + pt.skip;
+    const uint8_t *src = P.U + so;
+    uint8_t *dst = P.window + pt.dst;
+    if (g == 0) placed += pt.bytes;
+    const uint64_t to16 = (16u - (uint32_t)(pt.dst & 15u)) & 15u, head = pt.bytes < to16 ? pt.bytes : to16;
+    const uint64_t n_vec = (pt.bytes - head) >> 4;
+    const uint32_t sh = (uint32_t)((so + head) & 15u);        // (U is 16-byte aligned)
+    // the shifted copy's second aligned load reads up to 16 bytes behind the last one copied, so behind the record's end at most 16
+    // bytes: the front end leaves 256 readable bytes behind a slot's inflated end (front.hip, S.infl.reserve(end + 256)), which is
+    // what src_cap holds the loads against.  Where they do not fit the bytes go singly
+    if (n_vec && so + head - sh + (n_vec + 1u) * 16u > P.src_cap) {
+      for (uint64_t b = g; b < pt.bytes; b += G) dst[b] = src[b];
+      continue;
+    }
+    if (g < head) dst[g] = src[g];                            // (head < 16 <= G)
+    const uint4 *sa = reinterpret_cast<const uint4 *>(src + head - sh);
+    uint4 *da = reinterpret_cast<uint4 *>(dst + head);
+    if (sh) for (uint64_t v = g; v < n_vec; v += G) da[v] = bsort_load_shifted(sa + v, sh);
+    else for (uint64_t v = g; v < n_vec; v += G) da[v] = sa[v];
+    const uint64_t done = head + (n_vec << 4), tail = pt.bytes - done;
+    if (g < tail) dst[done + g] = src[done + g];              // (tail < 16)
+  }
+  // the bytes placed: summed over the wave, one vector atomic a wave
+  for (int d = 32; d > 0; d >>= 1) placed += __shfl_down(placed, d);
+  if ((threadIdx.x & 63u) == 0 && placed) atomicAdd(reinterpret_cast<unsigned long long *>(&P.S->placed), (unsigned long long)placed);
+}
+
+// test-only (strl_bamsort_window_probe): the scatter's part of every record, by ordinal, with the block_size word pass 0 saw
+__global__ void bsort_wparts_kernel(const uint64_t *dest, const uint32_t *len, uint32_t n, uint64_t lo, uint64_t hi, uint64_t *parts) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  BsortPart p{0, 0, 0};
+  if (!bsort_scatter_part(dest[i], len[i], len[i] - 4u, lo, hi, &p)) p.skip = p.dst = p.bytes = ~0ull;
+  parts[3 * i] = p.skip; parts[3 * i + 1] = p.dst; parts[3 * i + 2] = p.bytes;
+}
+
 struct BsortSlab { DevBuf buf; uint64_t bytes = 0, used = 0; };
 struct strl_bsort {
   int32_t n_ref = 0;
@@ -234,12 +323,24 @@ struct strl_bsort {
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   strl_bamsort_info info{};
   strl_bai *index = nullptr;                   // `sort --write-index`: the index builder over the sorted records (bamindex.hip strl_bamsort_index)
+  // `sort --windowed`: no arena, no src; behind the finish only dest[ordinal] and len[ordinal] stay
+  bool windowed = false;
+  DevBuf dest, window, wstate;
+  BsortWinState *h_wstate = nullptr;           // pinned
+  std::vector<uint8_t> header;                 // the output's header bytes: every window that holds some gets them again
+  uint64_t first_off = 0;                      // strl_bamsort_begin_windowed's: the front end is rewound with it
+  uint32_t res_blocks = 0;                     // strl_bamsort_reserve's, repeated for every window's front end
+  uint64_t res_comp = 0;
+  uint64_t win_lo = 0, win_hi = 0;
+  bool win_open = false, win_done = false;     // a window's pass is running | the window is complete and may be fetched from
+  uint64_t w_chunks = 0, w_done = 0, w_ord = 0;   // chunks pushed / scattered in this pass; ordinal of the next chunk's first record
 };
 
 void bsort_destroy(strl_bsort *B) {
   if (!B) return;
   if (B->index) bai_destroy(B->index);
   if (B->h_state) (void)hipHostFree(B->h_state);
+  if (B->h_wstate) (void)hipHostFree(B->h_wstate);
   for (hipEvent_t e : {B->e0, B->e1, B->e2}) if (e) (void)hipEventDestroy(e);
   delete B;
 }
@@ -248,6 +349,7 @@ void bsort_destroy(strl_bsort *B) {
 int bsort_view(strl_ctx *c, BsortView *v, strl_bai ***slot) {
   if (!c || !c->bsort || !c->bsort->finished) return STRL_ERR_ARG;
   strl_bsort *B = c->bsort;
+  if (B->windowed) return 2;                   // (a windowed sort holds no records: strl_bamsort_index says so)
   const size_t ns = B->slabs.size();
   *v = BsortView{B->off.as<uint64_t>(), B->src.as<uint64_t>(), B->perm, B->len.as<uint32_t>(), B->d_slab.as<uint8_t *>(), B->d_slab.as<uint64_t>() + ns, (uint32_t)ns, B->n_ref,
                  B->n_records, B->stream_bytes};
@@ -323,19 +425,19 @@ static int bsort_chunk(strl_ctx *c, strl_front *F, strl_bsort *B, int si) {
     const uint64_t need = B->n_records + n, bytes = rec_end - I.start0;
     if (need > B->rec_cap) {
       const uint64_t cap = std::max<uint64_t>(need + need / 2, 1u << 16);
-      if ((rc = B->key.grow((size_t)cap * 8, (size_t)B->n_records * 8, st)) || (rc = B->src.grow((size_t)cap * 8, (size_t)B->n_records * 8, st)) ||
+      if ((rc = B->key.grow((size_t)cap * 8, (size_t)B->n_records * 8, st)) || (!B->windowed && (rc = B->src.grow((size_t)cap * 8, (size_t)B->n_records * 8, st))) ||
           (rc = B->len.grow((size_t)cap * 4, (size_t)B->n_records * 4, st)))
         return rc;
       B->rec_cap = cap;
     }
     uint64_t src0 = 0;
     uint8_t *dst = nullptr;
-    if ((rc = bsort_place(B, bytes, n, &src0, &dst))) return rc;
+    if (!B->windowed && (rc = bsort_place(B, bytes, n, &src0, &dst))) return rc;
     BsortKeys P{S.infl.as<uint8_t>(), S.recoff.as<uint32_t>(), n, I.start0, rec_end, B->n_ref, B->n_records, B->rec_cap, src0,
-                B->key.as<uint64_t>(), B->src.as<uint64_t>(), B->len.as<uint32_t>(), B->state.as<BsortState>()};
+                B->key.as<uint64_t>(), B->windowed ? nullptr : B->src.as<uint64_t>(), B->len.as<uint32_t>(), B->state.as<BsortState>()};
     hipLaunchKernelGGL(bsort_keys_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, P);
     STRL_HIP(hipGetLastError());
-    STRL_HIP(hipMemcpyAsync(dst, S.infl.as<uint8_t>() + I.start0, bytes, hipMemcpyDeviceToDevice, st));
+    if (!B->windowed) STRL_HIP(hipMemcpyAsync(dst, S.infl.as<uint8_t>() + I.start0, bytes, hipMemcpyDeviceToDevice, st));      // (windowed: 12 bytes a record stay, no more)
     B->n_records += n;
   }
   STRL_HIP(hipEventRecord(S.ev_b, st));        // the slot's inflated bytes and record table may be overwritten behind this
@@ -395,6 +497,90 @@ static void bsort_gather_time(strl_bsort *B) {
   if (hipEventElapsedTime(&ms, B->e0, B->e1) == hipSuccess) B->info.gather_ms += ms; else (void)hipGetLastError();
 }
 
+// ---- `sort --windowed` ---------------------------------------------------------------------------------------------------------------
+// The finish of a windowed sort: the same radix sort and layout, then dest[perm[j]] = off[j]; everything but dest (8 B) and len
+// (4 B) goes.  The buffers come and go in steps -- the key buffers and the scratch leave before off[] and dest[] arrive -- so the
+// peak is the sort's own 28 B a record (two keys, two values, len) and its scratch.
+static int bsort_finish_windowed(strl_ctx *c, strl_bsort *B, const uint8_t *header, uint64_t header_bytes) {
+  hipStream_t st = c->stream;
+  const uint32_t n = (uint32_t)B->n_records;
+  const int bits = bsort_key_bits(B->n_ref);
+  const size_t sb = radix_sort_scratch_bytes(std::max(n, 1u), bits);
+  const uint32_t n_tiles = (n + BSORT_TILE - 1u) / BSORT_TILE;
+  int rc;
+  if ((rc = B->key.reserve(64)) || (rc = B->len.reserve(64)) || (rc = B->key_alt.reserve((size_t)n * 8 + 64)) || (rc = B->val.reserve((size_t)n * 4 + 64)) ||
+      (rc = B->val_alt.reserve((size_t)n * 4 + 64)) || (rc = B->scratch.reserve(sb + 64)))
+    return rc;
+  BsortState *S = B->state.as<BsortState>();
+  STRL_HIP(hipMemcpyAsync(&S->n, &n, 4, hipMemcpyHostToDevice, st));
+  uint64_t *ok = B->key.as<uint64_t>();
+  uint32_t *ov = B->val.as<uint32_t>();
+  STRL_HIP(hipEventRecord(B->e0, st));
+  if (n) {
+    hipLaunchKernelGGL(bsort_iota_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, B->val.as<uint32_t>(), n);
+    STRL_HIP(hipGetLastError());
+    const int se = radix_sort_pairs(st, &S->n, n, B->key.as<uint64_t>(), B->val.as<uint32_t>(), B->key_alt.as<uint64_t>(), B->val_alt.as<uint32_t>(), B->scratch.p, sb, 0, bits, &ok, &ov);
+    if (se) { set_error("radix_sort_pairs failed: %s", hipGetErrorString((hipError_t)se)); return STRL_ERR_HIP; }
+  }
+  B->perm = ov;
+  STRL_HIP(hipEventRecord(B->e1, st));
+  STRL_HIP(hipStreamSynchronize(st));
+  float a = 0.f;
+  (void)hipEventElapsedTime(&a, B->e0, B->e1);
+  B->info.sort_ms = a;
+  B->key.release(); B->key_alt.release(); B->scratch.release();
+  if (ov == B->val.as<uint32_t>()) B->val_alt.release(); else B->val.release();
+  if ((rc = B->off.reserve(((size_t)n + 1) * 8 + 64)) || (rc = B->tile.reserve((size_t)n_tiles * 8 + 64)) || (rc = B->dest.reserve((size_t)n * 8 + 64))) return rc;
+  STRL_HIP(hipEventRecord(B->e1, st));
+  if ((rc = bsort_layout(st, B->perm, B->len.as<uint32_t>(), n, B->n_records, header_bytes, B->tile.as<uint64_t>(), B->off.as<uint64_t>(), S))) return rc;
+  if (n) hipLaunchKernelGGL(bsort_dest_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, B->perm, B->off.as<uint64_t>(), n, B->dest.as<uint64_t>());
+  STRL_HIP(hipGetLastError());
+  STRL_HIP(hipEventRecord(B->e2, st));
+  STRL_HIP(hipMemcpyAsync(B->h_state, B->state.p, sizeof(BsortState), hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipStreamSynchronize(st));
+  float b = 0.f;
+  (void)hipEventElapsedTime(&b, B->e1, B->e2);
+  B->perm = nullptr;
+  B->val.release(); B->val_alt.release(); B->off.release(); B->tile.release();
+  B->header.assign(header, header + header_bytes);
+  B->header_bytes = header_bytes;
+  B->stream_bytes = header_bytes + B->h_state->total;
+  strl_bamsort_info &I = B->info;
+  I.n_records = B->n_records; I.n_no_ref = B->h_state->n_no_ref; I.stream_bytes = B->stream_bytes;
+  I.already_sorted = B->h_state->not_identity ? 0u : 1u;
+  I.n_slabs = 0; I.arena_bytes = 0;
+  I.layout_ms = b; I.gather_ms = 0;
+  B->finished = true;
+  return STRL_OK;
+}
+
+// the scatter of the chunk in slot si into the window (its record scan was enqueued by the push before)
+static int bsort_window_chunk(strl_ctx *c, strl_front *F, strl_bsort *B, int si) {
+  FrontSlot &S = F->slot[si];
+  STRL_HIP(hipEventSynchronize(S.ev_a));
+  const FrontInfo I = S.h_info[0];
+  if (I.err & FRONT_ERR_INFLATE) { set_error("invalid BGZF block (DEFLATE data or ISIZE)"); return STRL_ERR_FORMAT; }
+  if (I.err & FRONT_ERR_CRC) { set_error("CRC32 checksum mismatch in a BGZF block"); return STRL_ERR_CRC; }
+  if (I.err & FRONT_ERR_RECORD) { set_error("malformed BAM record"); return STRL_ERR_FORMAT; }
+  if (I.err & FRONT_ERR_CARRY) { set_error("BAM record of more than %u bytes", FRONT_CARRY_MAX); return STRL_ERR_FORMAT; }
+  const uint32_t n = I.n_records, rec_end = std::min(I.carry_off, I.end);
+  hipStream_t st = c->stream;
+  if (n && rec_end > I.start0 && (uint64_t)rec_end <= S.infl.cap) {
+    BsortScatter P{S.infl.as<uint8_t>(), S.recoff.as<uint32_t>(), n, I.start0, rec_end, (uint64_t)S.infl.cap, B->w_ord, B->n_records, B->dest.as<uint64_t>(), B->len.as<uint32_t>(),
+                   B->win_lo, B->win_hi, B->window.as<uint8_t>(), B->wstate.as<BsortWinState>()};
+    const uint32_t G = bsort_gather_lanes();
+    const unsigned grid = (unsigned)std::min<uint64_t>(4096, std::max<uint64_t>(1, ((uint64_t)n * G + 255u) / 256u));
+    if (G == 32) hipLaunchKernelGGL(bsort_scatter_kernel<32>, dim3(grid), dim3(256), 0, st, P);
+    else if (G == 64) hipLaunchKernelGGL(bsort_scatter_kernel<64>, dim3(grid), dim3(256), 0, st, P);
+    else hipLaunchKernelGGL(bsort_scatter_kernel<16>, dim3(grid), dim3(256), 0, st, P);
+    STRL_HIP(hipGetLastError());
+    B->w_ord += n;
+  }
+  STRL_HIP(hipEventRecord(S.ev_b, st));        // the slot's inflated bytes and record table may be overwritten behind this
+  S.b_pending = true;
+  return STRL_OK;
+}
+
 }  // namespace strl
 
 using namespace strl;
@@ -419,8 +605,8 @@ extern "C" int strl_bamsort_header(const uint8_t *in, uint64_t in_bytes, uint8_t
 }
 
 // ---- the device sort --------------------------------------------------------------------------------------------------------------
-extern "C" int strl_bamsort_begin(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset, uint64_t arena_limit_bytes) {
-  if (!c || n_ref < 0) { set_error("strl_bamsort_begin: bad argument"); return STRL_ERR_ARG; }
+static int bsort_begin(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset, uint64_t arena_limit_bytes, bool windowed) {
+  if (!c || n_ref < 0) { set_error("%s: bad argument", windowed ? "strl_bamsort_begin_windowed" : "strl_bamsort_begin"); return STRL_ERR_ARG; }
   int rc;
   if ((rc = front_begin_scan(c, n_ref, first_record_offset))) return rc;
   // one consumer of the record scan on a context: a builder or a sweep of an earlier pass ends here, as theirs end each other's
@@ -443,12 +629,24 @@ extern "C" int strl_bamsort_begin(strl_ctx *c, int32_t n_ref, uint64_t first_rec
   H.err_ord[0] = H.err_ord[1] = ~0ull;
   STRL_HIP(hipMemcpyAsync(B->state.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream));
   STRL_HIP(hipStreamSynchronize(c->stream));
+  if (windowed) {
+    B->windowed = true;
+    B->first_off = first_record_offset;
+    STRL_HIP(hipHostMalloc(reinterpret_cast<void **>(&B->h_wstate), sizeof(BsortWinState), hipHostMallocDefault));
+    if ((rc = B->wstate.reserve(sizeof(BsortWinState)))) return rc;
+  }
   return STRL_OK;
 }
+
+extern "C" int strl_bamsort_begin(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset, uint64_t arena_limit_bytes) {
+  return bsort_begin(c, n_ref, first_record_offset, arena_limit_bytes, false);
+}
+extern "C" int strl_bamsort_begin_windowed(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset) { return bsort_begin(c, n_ref, first_record_offset, 0, true); }
 
 extern "C" int strl_bamsort_reserve(strl_ctx *c, uint32_t max_blocks, uint64_t max_comp_bytes) {
   if (!c || !c->bsort || !c->front || !max_blocks) { set_error("strl_bamsort_reserve: bad argument / no strl_bamsort_begin"); return STRL_ERR_ARG; }
   STRL_HIP(hipSetDevice(c->device));
+  c->bsort->res_blocks = max_blocks; c->bsort->res_comp = max_comp_bytes;
   return front_reserve(c, c->front, max_blocks, max_comp_bytes);
 }
 
@@ -493,6 +691,11 @@ extern "C" int strl_bamsort_finish(strl_ctx *c, const uint8_t *header, uint64_t 
     STRL_HIP(hipStreamSynchronize(st));
     if (F->last_slot >= 0 && F->slot[F->last_slot].h_info[0].carry_len) { set_error("the BAM ends inside a record (truncated file)"); return bsort_fail(B, STRL_ERR_FORMAT); }
     if ((rc = bsort_refuse(B, *B->h_state))) return bsort_fail(B, rc);
+    if (B->windowed) {
+      if ((rc = bsort_finish_windowed(c, B, header, header_bytes))) return bsort_fail(B, rc);
+      if (info) *info = B->info;
+      return STRL_OK;
+    }
     const uint32_t n = (uint32_t)B->n_records;
     const int bits = bsort_key_bits(B->n_ref);
     const size_t sb = radix_sort_scratch_bytes(std::max(n, 1u), bits), ns = B->slabs.size();
@@ -555,6 +758,13 @@ static int bsort_fetch_check(strl_ctx *c, const char *who, uint64_t off, uint64_
               (unsigned long long)bytes, (unsigned long long)c->bsort->stream_bytes);
     return STRL_ERR_ARG;
   }
+  const strl_bsort *B = c->bsort;
+  if (B->windowed && bytes && (!B->win_done || off < B->win_lo || off + bytes > B->win_hi)) {
+    if (!B->win_done) set_error("%s: a windowed sort has no finished window (strl_bamsort_window_begin / _push / _end)", who);
+    else set_error("%s: [%llu, %llu + %llu) is not inside the current window [%llu, %llu) of a windowed sort", who, (unsigned long long)off, (unsigned long long)off,
+                   (unsigned long long)bytes, (unsigned long long)B->win_lo, (unsigned long long)B->win_hi);
+    return STRL_ERR_ARG;
+  }
   return STRL_OK;
 }
 
@@ -565,6 +775,11 @@ extern "C" int strl_bamsort_fetch(strl_ctx *c, uint64_t off, uint64_t bytes, uin
   if (!out) { set_error("null argument"); return STRL_ERR_ARG; }
   STRL_HIP(hipSetDevice(c->device));
   strl_bsort *B = c->bsort;
+  if (B->windowed) {                                          // the window is a finished piece of the stream: the bytes lie there
+    STRL_HIP(hipMemcpyAsync(out, B->window.as<uint8_t>() + (off - B->win_lo), bytes, hipMemcpyDeviceToHost, c->stream));
+    STRL_HIP(hipStreamSynchronize(c->stream));
+    return STRL_OK;
+  }
   if ((rc = bsort_gather(c, B, off, off + bytes))) return rc;
   STRL_HIP(hipMemcpyAsync(out, B->piece.p, bytes, hipMemcpyDeviceToHost, c->stream));
   STRL_HIP(hipStreamSynchronize(c->stream));
@@ -581,6 +796,7 @@ extern "C" int strl_bamsort_fetch_bgzf(strl_ctx *c, uint64_t off, uint64_t bytes
   if (!bytes) return STRL_OK;
   STRL_HIP(hipSetDevice(c->device));
   strl_bsort *B = c->bsort;
+  if (B->windowed) return bgzf_deflate_device(c, B->window.as<uint8_t>() + (off - B->win_lo), bytes, BSORT_BLK, out, out_cap, out_bytes, nullptr, n_stored);
   if ((rc = bsort_gather(c, B, off, off + bytes))) return rc;
   rc = bgzf_deflate_device(c, B->piece.as<uint8_t>(), bytes, BSORT_BLK, out, out_cap, out_bytes, nullptr, n_stored);      // (waits for the stream)
   if (!rc) bsort_gather_time(B);
@@ -590,9 +806,123 @@ extern "C" int strl_bamsort_fetch_bgzf(strl_ctx *c, uint64_t off, uint64_t bytes
 extern "C" int strl_bamsort_order(strl_ctx *c, uint32_t *perm, uint64_t cap) {
   if (!c || !c->bsort || !c->bsort->finished) { set_error("strl_bamsort_order without strl_bamsort_finish"); return STRL_ERR_ARG; }
   strl_bsort *B = c->bsort;
+  if (B->windowed) { set_error("strl_bamsort_order: not supported by a windowed sort, which gives the order up for the records' places in the stream"); return STRL_ERR_ARG; }
   if (cap < B->n_records || (B->n_records && !perm)) { set_error("strl_bamsort_order: %llu records, room for %llu", (unsigned long long)B->n_records, (unsigned long long)cap); return STRL_ERR_CAPACITY; }
   STRL_HIP(hipSetDevice(c->device));
   if (B->n_records) STRL_HIP(hipMemcpy(perm, B->perm, (size_t)B->n_records * 4, hipMemcpyDeviceToHost));
+  return STRL_OK;
+}
+
+// ---- `sort --windowed`: one window of the stream per pass over the input ---------------------------------------------------------------
+extern "C" int strl_bamsort_window_plan(uint64_t stream_bytes, uint64_t limit_bytes, uint64_t piece_bytes, uint64_t *window_bytes, uint64_t *n_windows) {
+  if (!piece_bytes || !window_bytes || !n_windows) { set_error("strl_bamsort_window_plan: bad argument"); return STRL_ERR_ARG; }
+  const BsortWindowPlan p = bsort_window_plan(stream_bytes, limit_bytes, piece_bytes);
+  *window_bytes = p.window_bytes; *n_windows = p.n_windows;
+  return STRL_OK;
+}
+
+static int bsort_windowed_check(strl_ctx *c, const char *who) {
+  if (!c || !c->bsort || !c->bsort->windowed || !c->bsort->finished) { set_error("%s without strl_bamsort_begin_windowed and strl_bamsort_finish", who); return STRL_ERR_ARG; }
+  if (c->bsort->fail_rc) { set_error("%s", c->bsort->fail.c_str()); return c->bsort->fail_rc; }
+  return STRL_OK;
+}
+
+extern "C" int strl_bamsort_window_limit(strl_ctx *c, uint64_t *bytes) {
+  int rc;
+  if ((rc = bsort_windowed_check(c, "strl_bamsort_window_limit"))) return rc;
+  if (!bytes) { set_error("null argument"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  size_t fr = 0, tot = 0;
+  STRL_HIP(hipMemGetInfo(&fr, &tot));
+  // the front end's slots are allocated by now (pass 0 ran through them, and a window's front end asks for the same again), so they
+  // are outside `fr` already; a window buffer of an earlier window is not, and is reused
+  const uint64_t have = (uint64_t)fr + c->bsort->window.cap, keep = (uint64_t)768 << 20;
+  *bytes = have > keep ? have - keep : 0;
+  return STRL_OK;
+}
+
+extern "C" int strl_bamsort_window_begin(strl_ctx *c, uint64_t lo, uint64_t hi) {
+  int rc;
+  if ((rc = bsort_windowed_check(c, "strl_bamsort_window_begin"))) return rc;
+  strl_bsort *B = c->bsort;
+  if (c->bai || c->sweep || c->x_open || lo >= hi || hi > B->stream_bytes) {
+    set_error("strl_bamsort_window_begin: [%llu, %llu) is not a window of the stream's %llu bytes / another pass has taken the context", (unsigned long long)lo, (unsigned long long)hi,
+              (unsigned long long)B->stream_bytes);
+    return STRL_ERR_ARG;
+  }
+  STRL_HIP(hipSetDevice(c->device));
+  B->win_open = B->win_done = false;
+  // the front end again from the start of the file (this waits for everything the last pass left in flight)
+  if ((rc = front_begin_scan(c, B->n_ref, B->first_off))) { B->front = c->front; return bsort_fail(B, rc); }
+  B->front = c->front;
+  if (B->res_blocks && (rc = front_reserve(c, c->front, B->res_blocks, B->res_comp))) return bsort_fail(B, rc);
+  if ((rc = B->window.reserve((size_t)(hi - lo) + 64))) return bsort_fail(B, rc);      // (reserve never shrinks; hipMalloc aligns far beyond 16 bytes)
+  hipStream_t st = c->stream;
+  const uint64_t hb = bsort_window_header(B->header_bytes, lo, hi);
+  if (hb) STRL_HIP(hipMemcpyAsync(B->window.p, B->header.data() + lo, hb, hipMemcpyHostToDevice, st));
+  BsortWinState &H = *B->h_wstate;
+  H.err_ord = ~0ull; H.placed = 0;
+  STRL_HIP(hipMemcpyAsync(B->wstate.p, &H, sizeof H, hipMemcpyHostToDevice, st));
+  STRL_HIP(hipStreamSynchronize(st));
+  B->win_lo = lo; B->win_hi = hi;
+  B->w_chunks = B->w_done = B->w_ord = 0;
+  B->win_open = true;
+  return STRL_OK;
+}
+
+extern "C" int strl_bamsort_window_push(strl_ctx *c, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                                        const uint32_t *crc32, uint32_t n_blocks) {
+  int rc;
+  if ((rc = bsort_windowed_check(c, "strl_bamsort_window_push"))) return rc;
+  strl_bsort *B = c->bsort;
+  if (!B->win_open || !c->front || c->front != B->front || c->bai || c->sweep || c->x_open || (n_blocks && (!comp || !coff || !clen || !isize))) {
+    set_error("strl_bamsort_window_push: bad argument / no strl_bamsort_window_begin / another pass has taken the context's front end");
+    return STRL_ERR_ARG;
+  }
+  if (!n_blocks) return STRL_OK;
+  STRL_HIP(hipSetDevice(c->device));
+  strl_front *F = c->front;
+  const int si = (int)(B->w_chunks & 1);
+  FrontSlot &S = F->slot[si];
+  if (S.b_pending) { STRL_HIP(hipEventSynchronize(S.ev_b)); S.b_pending = false; }     // the chunk two back has left the slot
+  const FrontChunkDesc d{comp, comp_bytes, coff, clen, isize, crc32, n_blocks};
+  if ((rc = front_stage_a(c, F, si, d, B->w_chunks == 0))) return bsort_fail(B, rc);
+  ++B->w_chunks;
+  // ... and beside this chunk's inflate, the scatter of the previous one
+  while (B->w_done + 1 < B->w_chunks) {
+    if ((rc = bsort_window_chunk(c, F, B, (int)(B->w_done & 1)))) return bsort_fail(B, rc);
+    ++B->w_done;
+  }
+  return STRL_OK;
+}
+
+extern "C" int strl_bamsort_window_end(strl_ctx *c) {
+  int rc;
+  if ((rc = bsort_windowed_check(c, "strl_bamsort_window_end"))) return rc;
+  strl_bsort *B = c->bsort;
+  if (!B->win_open || !c->front || c->front != B->front) { set_error("strl_bamsort_window_end without strl_bamsort_window_begin"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  strl_front *F = c->front;
+  hipStream_t st = c->stream;
+  for (; B->w_done < B->w_chunks; ++B->w_done)
+    if ((rc = bsort_window_chunk(c, F, B, (int)(B->w_done & 1)))) return bsort_fail(B, rc);
+  STRL_HIP(hipMemcpyAsync(B->h_wstate, B->wstate.p, sizeof(BsortWinState), hipMemcpyDeviceToHost, st));
+  STRL_HIP(hipStreamSynchronize(st));
+  B->win_open = false;
+  const BsortWinState &H = *B->h_wstate;
+  // (these leave the sort usable: another window_begin over the right file goes on)
+  if (H.err_ord != ~0ull && H.err_ord < B->n_records) { set_error("the input changed between passes: record %llu", (unsigned long long)H.err_ord); return STRL_ERR_FORMAT; }
+  const bool cut = F->last_slot >= 0 && F->slot[F->last_slot].h_info[0].carry_len;
+  if (B->w_ord != B->n_records || H.err_ord != ~0ull || cut) {
+    set_error("the input changed between passes: %llu records%s, pass 0 read %llu", (unsigned long long)B->w_ord, cut ? " and a part of one" : "", (unsigned long long)B->n_records);
+    return STRL_ERR_FORMAT;
+  }
+  if (!bsort_window_complete(H.placed, B->header_bytes, B->win_lo, B->win_hi)) {
+    set_error("internal error: the window [%llu, %llu) holds %llu bytes of records and %llu of the header", (unsigned long long)B->win_lo, (unsigned long long)B->win_hi,
+              (unsigned long long)H.placed, (unsigned long long)bsort_window_header(B->header_bytes, B->win_lo, B->win_hi));
+    return STRL_ERR_ASSERT;
+  }
+  B->win_done = true;
   return STRL_OK;
 }
 
@@ -606,6 +936,41 @@ extern "C" int strl_bamsort_end(strl_ctx *c) {
   }
   STRL_HIP(hipStreamSynchronize(c->stream));
   if (c->bsort) { bsort_destroy(c->bsort); c->bsort = nullptr; }
+  return STRL_OK;
+}
+
+// test-only, undeclared: the layout, bsort_dest_kernel and the scatter's part arithmetic as a windowed sort runs them, over
+// caller-given len[n] (by input ordinal), a caller-given permutation perm[n] (perm[rank] = ordinal), a 64-bit base and a window
+// [lo, hi) -- destinations beyond 2^32 without 4 GB of data.  dest_out[n] by ordinal; parts[3 i ..] = (source skip, destination,
+// bytes) of ordinal i's part inside the window (bytes 0: outside it).
+extern "C" int strl_bamsort_window_probe(strl_ctx *c, const uint32_t *len, const uint32_t *perm, uint32_t n, uint64_t base, uint64_t lo, uint64_t hi, uint64_t *dest_out,
+                                         uint64_t *parts) {
+  if (!c || (n && (!len || !perm || !dest_out || !parts)) || lo > hi) { set_error("strl_bamsort_window_probe: bad argument"); return STRL_ERR_ARG; }
+  for (uint32_t j = 0; j < n; ++j) if (perm[j] >= n) { set_error("strl_bamsort_window_probe: perm[%u] = %u is no ordinal", j, perm[j]); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const uint32_t n_tiles = (n + BSORT_TILE - 1u) / BSORT_TILE;
+  DevBuf d_len, d_perm, d_off, d_tile, d_state, d_dest, d_parts;
+  int rc;
+  if ((rc = d_len.reserve((size_t)n * 4 + 64)) || (rc = d_perm.reserve((size_t)n * 4 + 64)) || (rc = d_off.reserve(((size_t)n + 1) * 8)) || (rc = d_tile.reserve((size_t)n_tiles * 8 + 64)) ||
+      (rc = d_state.reserve(sizeof(BsortState))) || (rc = d_dest.reserve((size_t)n * 8 + 64)) || (rc = d_parts.reserve((size_t)n * 24 + 64)))
+    return rc;
+  BsortState *S = d_state.as<BsortState>();
+  STRL_HIP(hipMemsetAsync(S, 0, sizeof(BsortState), st));
+  if (n) {
+    STRL_HIP(hipMemcpyAsync(d_len.p, len, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    STRL_HIP(hipMemcpyAsync(d_perm.p, perm, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    STRL_HIP(hipMemsetAsync(d_dest.p, 0xff, (size_t)n * 8, st));
+  }
+  if ((rc = bsort_layout(st, d_perm.as<uint32_t>(), d_len.as<uint32_t>(), n, n, base, d_tile.as<uint64_t>(), d_off.as<uint64_t>(), S))) return rc;
+  if (n) {
+    hipLaunchKernelGGL(bsort_dest_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, d_perm.as<uint32_t>(), d_off.as<uint64_t>(), n, d_dest.as<uint64_t>());
+    hipLaunchKernelGGL(bsort_wparts_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, d_dest.as<uint64_t>(), d_len.as<uint32_t>(), n, lo, hi, d_parts.as<uint64_t>());
+    STRL_HIP(hipGetLastError());
+    STRL_HIP(hipMemcpyAsync(dest_out, d_dest.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    STRL_HIP(hipMemcpyAsync(parts, d_parts.p, (size_t)n * 24, hipMemcpyDeviceToHost, st));
+  }
+  STRL_HIP(hipStreamSynchronize(st));
   return STRL_OK;
 }
 

@@ -66,6 +66,36 @@ BSORT_HD inline BsortPart bsort_part(uint64_t beg, uint64_t end, uint64_t lo, ui
   return p;
 }
 
+// ---- windows of the output stream (`sort --windowed`) --------------------------------------------------------------------------------
+// A file larger than device memory: pass 0 keeps key and length of every record and sorts; dest[ordinal] = the record's first byte
+// in the stream.  Every later pass reads the input again and places the records that touch the window [lo, hi) of the stream
+// straight where they belong; the window is then a finished piece of the stream.
+//   W = max(piece_bytes, limit_bytes / piece_bytes * piece_bytes),  n_windows = ceil(stream_bytes / W),  window w = [w W, min(stream_bytes, (w + 1) W))
+// piece_bytes is a multiple of 0xFF00, so every window starts on a member boundary and no piece straddles two windows.
+struct BsortWindowPlan { uint64_t window_bytes, n_windows; };
+BSORT_HD inline BsortWindowPlan bsort_window_plan(uint64_t stream_bytes, uint64_t limit_bytes, uint64_t piece_bytes) {
+  if (!piece_bytes) piece_bytes = BSORT_BLK;
+  const uint64_t whole = limit_bytes / piece_bytes * piece_bytes;
+  BsortWindowPlan p;
+  p.window_bytes = whole > piece_bytes ? whole : piece_bytes;
+  p.n_windows = stream_bytes / p.window_bytes + (stream_bytes % p.window_bytes ? 1u : 0u);      // (no sum that could wrap)
+  return p;
+}
+// the scatter's rule for one record: dest = its first byte in the stream and len = its 4 + block_size, both from pass 0; bs_now = the
+// block_size word read in this pass -> the part inside the window.  false: bs_now + 4 != len, the file is not the one pass 0 read
+BSORT_HD inline bool bsort_scatter_part(uint64_t dest, uint32_t len, uint32_t bs_now, uint64_t lo, uint64_t hi, BsortPart *part) {
+  if ((uint64_t)bs_now + 4u != (uint64_t)len) return false;
+  *part = bsort_part(dest, dest + len, lo, hi);
+  return true;
+}
+// header bytes inside the window, and the window's completeness: the bytes the scatter placed and those of the header fill it
+BSORT_HD inline uint64_t bsort_window_header(uint64_t header_bytes, uint64_t lo, uint64_t hi) {
+  return lo < header_bytes ? (hi < header_bytes ? hi : header_bytes) - lo : 0;
+}
+BSORT_HD inline bool bsort_window_complete(uint64_t placed, uint64_t header_bytes, uint64_t lo, uint64_t hi) {
+  return hi >= lo && placed + bsort_window_header(header_bytes, lo, hi) == hi - lo;
+}
+
 // ---- virtual offsets of the output (`sort --write-index`) ------------------------------------------------------------------------
 // The stream is cut into members of exactly BSORT_BLK bytes, so where a stream offset lies in the file is arithmetic and one load:
 // member_off[0 .. n_members] = file offset of every member, the last entry the EOF block's; n_members = ceil(stream_bytes / 0xFF00).

@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <string>
 #include <thread>
@@ -60,5 +61,10 @@ struct PinnedRing {
   }
   void release() { release_except(nullptr, nullptr); }
 };
+
+// main.cpp: the index of the BAM at `bam` built on the device and written to `out` through a temporary name (`strling bamindex`;
+// `sort --windowed --write-index` runs it over the file it has just written).  csi_min_shift >= 0: a CSI index.  false: why, status
+bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::string &out, bool verbose, bool last_use, std::string &why,
+               int &status, int csi_min_shift);
 
 int sort_main(int argc, char **argv);       // sort_cli.cpp

@@ -1759,8 +1759,8 @@ static bool fragment_lengths_on_device(strl_ctx *ctx, const std::string &bam, ui
 // read: a caller brings the context up on a thread beside that.  last_use: the process ends behind this (nothing is freed).
 // csi_min_shift >= 0: the CSI index with that min_shift and samtools' depth rule instead, its payload in BGZF blocks.
 // false: `why` says what the file was refused for (status = the library's, STRL_ERR_IO for the output)
-static bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::string &out, bool verbose, bool last_use, std::string &why,
-                      int &status, int csi_min_shift = -1) {
+bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::string &out, bool verbose, bool last_use, std::string &why,
+               int &status, int csi_min_shift = -1) {
   const auto t0 = std::chrono::steady_clock::now();
   status = STRL_ERR_IO;
   BgzfFeed feed;

@@ -10,6 +10,10 @@
 // --write-index: the index (.bai / .csi) from the same pass.  The members are walked as they are written (their file offsets), and
 // behind the last piece the index is built from what the sort still holds -- the device's arena, order and offsets
 // (strl_bamsort_index), or the host path's (bamindex_host.cpp) -- and written, through a temporary name, after the BAM's rename.
+// --windowed (device path): a file larger than device memory.  Pass 0 feeds the file as above but keeps only key and length of a
+// record; the stream is then cut into windows the device can hold (strl_bamsort_window_limit, bsort_window_plan), and for every
+// window the file is fed again -- a fresh BgzfFeed and ChunkAhead over the same page-locked buffers -- and scattered into the
+// window, which then goes through the same piece loop.  With --write-index the index is build_bai's over the file just written.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,11 +48,14 @@ const char *USAGE =
     "      --index-out=OUT.bai    where --write-index writes it (default: OUT.bam.bai; with --csi OUT.bam.csi)\n"
     "      --csi                  with --write-index: a CSI index (.csi), which also holds contigs longer than 2^29 bases\n"
     "  -m, --min-shift=N          with --csi: bases per window of the smallest bins = 2^N, N in [8, 24] (default: 14)\n"
+    "      --windowed             sort a file larger than device memory: only 12 bytes a record stay on the device, and the file is read once\n"
+    "                             more for every window of the output that the device can hold; the same bytes as without it.  With\n"
+    "                             --write-index the index costs a second read of the output (it is built as `strling bamindex OUT.bam` builds it)\n"
     "      --deflate=host|device  host (default): zlib at its default level on the pool, as pull.  device: the GPU's compressor (about 1.15 x the bytes)\n"
     "  -D, --device=K             GPU to use (default: 0)\n"
     "  -v, --verbose              one JSON line on stderr\n  -h, --help                 Show this help\n";
 
-struct Seconds { double read = 0, sort = 0, gather = 0, deflate = 0, write = 0; };
+struct Seconds { double read = 0, sort = 0, gather = 0, deflate = 0, write = 0, window = 0; };      // window: the passes of --windowed behind pass 0
 
 // the output file: members appended under a temporary name, the EOF block and the rename at the end
 struct SortOut {
@@ -126,6 +133,7 @@ struct Index {
 
 struct Result {
   uint64_t records = 0, no_ref = 0, stream_bytes = 0, slabs = 0, out_bytes = 0;
+  uint64_t windows = 0, window_bytes = 0;     // --windowed on the device: passes behind pass 0, bytes of the stream each finishes
   bool already_sorted = false;
   const char *deflate = "zlib";
   uint32_t stored = 0;
@@ -220,8 +228,10 @@ bool sort_on_host(const std::string &bam, const std::vector<uint8_t> &header, in
 }
 
 // ---- the device path -------------------------------------------------------------------------------------------------------------
-bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::vector<uint8_t> &header, bool core, SortOut &out, Result &R,
-                    Index &X, std::string &why, int &status) {
+// windowed: `sort --windowed`.  Pass 0 keeps key and length of every record; the file is then read once more for every window of
+// the output stream, and each finished window goes through the piece loop the resident sort's whole stream goes through.
+bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::vector<uint8_t> &header, bool core, bool windowed, SortOut &out,
+                    Result &R, Index &X, std::string &why, int &status) {
   auto t0 = Clock::now();
   status = STRL_ERR_IO;
   BgzfFeed feed;
@@ -237,14 +247,13 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
   strl_ctx *ctx = nullptr;
   auto fail = [&](int rc) { why = strl_last_error(); status = rc; (void)strl_bamsort_end(ctx); pins.release(); return false; };
   ThreadPool pool(std::min(decode_threads(), 12));
-  {
-    ChunkAhead ring(feed, pool, pins.data.data(), pins.meta.data(), chunk_blocks, chunk_bytes);
+  // one pass over the file `fd`: every chunk through `push`, chunk ci + 1 read beside the push of chunk ci.  `begin` runs behind
+  // the first chunk's read (pass 0 takes the context there); its rc < 0 is the library's, 1 = it has said why itself
+  auto feed_pass = [&](BgzfFeed &fd, const std::function<int()> &begin, decltype(&strl_bamsort_push) push) {
+    ChunkAhead ring(fd, pool, pins.data.data(), pins.meta.data(), chunk_blocks, chunk_bytes);
     ring.stage(0, 0);
-    if (!(ctx = get_ctx(why))) { status = STRL_ERR_NO_DEVICE; pins.release(); return false; }
-    const char *cap = getenv("STRL_SORT_ARENA_MB");                // tests of the refusal
-    const uint64_t limit = cap && atof(cap) > 0 ? (uint64_t)(atof(cap) * 1048576.0) : 0;
-    int rc = strl_bamsort_begin(ctx, (int32_t)feed.targets().size(), feed.first_record_offset(), limit);
-    if (!rc) rc = strl_bamsort_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes);
+    int rc = begin();
+    if (rc > 0) { pins.release(); return false; }
     if (rc) return fail(rc);
     for (uint64_t ci = 0;; ++ci) {
       const StagedChunk cur = ring.at(ci);
@@ -252,11 +261,22 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
       if (cur.nb == 0) break;
       ring.stage_ahead(ci + 1, (ci + 1) % 3);
       const ChunkTables t = ring.tables(cur);
-      rc = strl_bamsort_push(ctx, ring.data(cur), cur.bytes(), t.coff, t.clen, t.isz, t.crc, (uint32_t)cur.nb);
+      rc = push(ctx, ring.data(cur), cur.bytes(), t.coff, t.clen, t.isz, t.crc, (uint32_t)cur.nb);
       ring.join();
       if (rc) return fail(rc);
     }
-  }
+    return true;
+  };
+  const bool read_ok = feed_pass(feed, [&]() -> int {
+    if (!(ctx = get_ctx(why))) { status = STRL_ERR_NO_DEVICE; return 1; }
+    const char *cap = getenv("STRL_SORT_ARENA_MB");                // tests of the refusal
+    const uint64_t limit = cap && atof(cap) > 0 ? (uint64_t)(atof(cap) * 1048576.0) : 0;
+    int rc = windowed ? strl_bamsort_begin_windowed(ctx, (int32_t)feed.targets().size(), feed.first_record_offset())
+                      : strl_bamsort_begin(ctx, (int32_t)feed.targets().size(), feed.first_record_offset(), limit);
+    if (!rc) rc = strl_bamsort_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes);
+    return rc;
+  }, strl_bamsort_push);
+  if (!read_ok) return false;
   R.s.read = since(t0);
   t0 = Clock::now();
   strl_bamsort_info info;
@@ -265,53 +285,86 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
   R.s.sort = since(t0);
   R.records = info.n_records; R.no_ref = info.n_no_ref; R.stream_bytes = info.stream_bytes; R.already_sorted = info.already_sorted != 0; R.slabs = info.n_slabs;
   // pieces: the fetch of piece k + 1 on a thread beside the deflate / write of piece k
-  const uint64_t piece = piece_bytes(), total = info.stream_bytes, n_pieces = (total + piece - 1) / piece;
+  const uint64_t total = info.stream_bytes;
+  uint64_t piece = piece_bytes();
+  BsortWindowPlan plan{0, 0};
+  if (windowed) {
+    uint64_t limit = 0;
+    const char *kb = getenv("STRL_SORT_WINDOW_KB");                // tests: windows of a few members (fractions allowed)
+    if (kb && atof(kb) > 0) limit = (uint64_t)(atof(kb) * 1024.0);
+    else if ((rc = strl_bamsort_window_limit(ctx, &limit))) return fail(rc);
+    // a window the device cannot hold helps nobody: where the limit is below a piece, the pieces shrink to the members that fit it
+    piece = std::min(piece, std::max<uint64_t>(BSORT_BLK, limit / BSORT_BLK * BSORT_BLK));
+    plan = bsort_window_plan(total, limit, piece);
+    R.windows = plan.n_windows; R.window_bytes = plan.window_bytes;
+  }
   const uint64_t room = core ? strl_bgzf_deflate_bound(std::min(piece, total), BSORT_BLK) : std::min(piece, total);
   uint8_t *buf[2] = {static_cast<uint8_t *>(strl_pinned_alloc(room + 64)), static_cast<uint8_t *>(strl_pinned_alloc(room + 64))};
   if (!buf[0] || !buf[1]) { why = "page-locked memory for the pieces"; status = STRL_ERR_NOMEM; (void)strl_bamsort_end(ctx); return false; }
   struct Fetched { int rc = 0; std::string err; uint64_t bytes = 0; uint32_t stored = 0; double s = 0; } got[2];
-  auto fetch = [&](uint64_t k) {
-    Fetched &F = got[k & 1];
-    const auto f0 = Clock::now();
-    const uint64_t lo = k * piece, len = std::min(piece, total - lo);
-    F = Fetched{};
-    if (core) F.rc = strl_bamsort_fetch_bgzf(ctx, lo, len, buf[k & 1], room, &F.bytes, &F.stored);
-    else { F.rc = strl_bamsort_fetch(ctx, lo, len, buf[k & 1]); F.bytes = len; }
-    if (F.rc) F.err = strl_last_error();
-    F.s = since(f0);
-  };
   std::vector<uint8_t> members;
   ThreadPool zpool(std::min(decode_threads(), 16));              // the deflate's pool, as the host path's and pull's
-  if (n_pieces) fetch(0);
-  for (uint64_t k = 0; k < n_pieces; ++k) {
-    std::thread ahead;
-    if (k + 1 < n_pieces) ahead = std::thread(fetch, k + 1);
-    const Fetched &F = got[k & 1];
-    bool ok = !F.rc;
-    if (!ok) { why = F.err; status = F.rc; }
-    R.s.gather += F.s;
-    const uint8_t *p = buf[k & 1];
-    size_t n = (size_t)F.bytes;
-    if (ok && !core) {
-      t0 = Clock::now();
-      status = STRL_ERR_IO;
-      ok = deflate_piece(p, n, false, zpool, members, R.stored, why);
-      p = members.data(); n = members.size();
-      R.s.deflate += since(t0);
-    } else if (ok) R.stored += F.stored;
-    if (ok) {
-      t0 = Clock::now();
-      status = STRL_ERR_IO;
-      ok = out.put(p, n, why);
-      R.out_bytes += n;
-      R.s.write += since(t0);
+  // the pieces of [from, to) of the stream, `from` a multiple of the piece: fetched, deflated, written
+  auto write_pieces = [&](uint64_t from, uint64_t to) {
+    const uint64_t n_pieces = (to - from + piece - 1) / piece;
+    auto fetch = [&](uint64_t k) {
+      Fetched &F = got[k & 1];
+      const auto f0 = Clock::now();
+      const uint64_t lo = from + k * piece, len = std::min(piece, to - lo);
+      F = Fetched{};
+      if (core) F.rc = strl_bamsort_fetch_bgzf(ctx, lo, len, buf[k & 1], room, &F.bytes, &F.stored);
+      else { F.rc = strl_bamsort_fetch(ctx, lo, len, buf[k & 1]); F.bytes = len; }
+      if (F.rc) F.err = strl_last_error();
+      F.s = since(f0);
+    };
+    if (n_pieces) fetch(0);
+    for (uint64_t k = 0; k < n_pieces; ++k) {
+      std::thread ahead;
+      if (k + 1 < n_pieces) ahead = std::thread(fetch, k + 1);
+      const Fetched &F = got[k & 1];
+      bool ok = !F.rc;
+      if (!ok) { why = F.err; status = F.rc; }
+      R.s.gather += F.s;
+      const uint8_t *p = buf[k & 1];
+      size_t n = (size_t)F.bytes;
+      if (ok && !core) {
+        t0 = Clock::now();
+        status = STRL_ERR_IO;
+        ok = deflate_piece(p, n, false, zpool, members, R.stored, why);
+        p = members.data(); n = members.size();
+        R.s.deflate += since(t0);
+      } else if (ok) R.stored += F.stored;
+      if (ok) {
+        t0 = Clock::now();
+        status = STRL_ERR_IO;
+        ok = out.put(p, n, why);
+        R.out_bytes += n;
+        R.s.write += since(t0);
+      }
+      if (ahead.joinable()) ahead.join();
+      if (!ok) { (void)strl_bamsort_end(ctx); return false; }
     }
-    if (ahead.joinable()) ahead.join();
-    if (!ok) { (void)strl_bamsort_end(ctx); return false; }
+    return true;
+  };
+  if (!windowed) {
+    if (!write_pieces(0, total)) return false;
+    if (core) { strl_bamsort_info now; if (!strl_bamsort_info_now(ctx, &now)) { R.s.deflate = std::max(0.0, R.s.gather - now.gather_ms / 1e3); R.s.gather = now.gather_ms / 1e3; } }
+  } else {
+    for (uint64_t w = 0; w < plan.n_windows; ++w) {
+      const uint64_t lo = w * plan.window_bytes, hi = std::min(total, lo + plan.window_bytes);
+      const auto w0 = Clock::now();
+      BgzfFeed again;                                            // the same file from its first block
+      status = STRL_ERR_IO;
+      if (!again.open(bam, err)) { why = err.empty() ? "couldn't open bam" : "couldn't open bam: " + err; (void)strl_bamsort_end(ctx); pins.release(); return false; }
+      if (!feed_pass(again, [&]() -> int { return strl_bamsort_window_begin(ctx, lo, hi); }, strl_bamsort_window_push)) return false;
+      if ((rc = strl_bamsort_window_end(ctx))) return fail(rc);
+      R.s.window += since(w0);
+      if (!write_pieces(lo, hi)) return false;
+    }
+    if (core) { R.s.deflate = R.s.gather; R.s.gather = 0; }      // (a fetch of a window's piece is the compressor's run and its copy)
   }
-  if (core) { strl_bamsort_info now; if (!strl_bamsort_info_now(ctx, &now)) { R.s.deflate = std::max(0.0, R.s.gather - now.gather_ms / 1e3); R.s.gather = now.gather_ms / 1e3; } }
   R.deflate = core ? "device" : "zlib";
-  if (X.on) {                                                   // the records, their order and their offsets are still on the device
+  if (X.on && !windowed) {                                      // the records, their order and their offsets are still on the device
     t0 = Clock::now();
     out.member_off.push_back(out.at);                           // the EOF block
     uint64_t nbytes = 0;
@@ -333,7 +386,7 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
 int sort_main(int argc, char **argv) {
   if (argc <= 2) { fputs(USAGE, stdout); return 0; }
   const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"deflate", 0, true}, {"device", 'D', true}, {"verbose", 'v', false},
-                                       {"write-index", 0, false}, {"index-out", 0, true}, {"csi", 0, false}, {"min-shift", 'm', true}}, USAGE);
+                                       {"write-index", 0, false}, {"index-out", 0, true}, {"csi", 0, false}, {"min-shift", 'm', true}, {"windowed", 0, false}}, USAGE);
   if (a.pos.size() != 1) quit("expected 1 argument (bam)\n%s", USAGE);
   if (!a.flag("output")) quit("[strling] sort: -o OUT.bam is required\n%s", USAGE);
   if (a.flag("index-out") && !a.flag("write-index")) quit("--index-out needs --write-index\n%s", USAGE);
@@ -373,12 +426,16 @@ int sort_main(int argc, char **argv) {
   }
   const char *where = getenv("STRL_SORT");
   const bool on_host = (where && !strcmp(where, "host")) || strl_device_count() <= 0;
+  // --windowed on the host path changes nothing: that path holds the file in host memory anyway.  On the device the records are
+  // never resident in sorted order, so the index comes from the builder over the file just written, behind its rename
+  const bool windowed = a.flag("windowed") && !on_host;
   SortOut out;
-  out.track = X.on;
+  out.track = X.on && !windowed;
   std::string why;
   int status = 0;
   Result R;
   strl_ctx *ctx = nullptr;
+  std::function<strl_ctx *(std::string &)> ctx_again = [&](std::string &) { return ctx; };      // the context once it is up
   bool ok;
   if (on_host) {
     if (!out.open(out_path, why)) quit("[strling] sort: %s (status %d)", why.c_str(), STRL_ERR_IO);
@@ -393,7 +450,7 @@ int sort_main(int argc, char **argv) {
     auto get_ctx = [&](std::string &w) -> strl_ctx * { if (ctx_thread.joinable()) ctx_thread.join(); if (ctx_rc) w = ctx_err; return ctx_rc ? nullptr : ctx; };
     ok = out.open(out_path, why);
     if (!ok) status = STRL_ERR_IO;
-    else ok = sort_on_device(get_ctx, bam, header, core, out, R, X, why, status);
+    else ok = sort_on_device(get_ctx, bam, header, core, windowed, out, R, X, why, status);
     if (ctx_thread.joinable()) ctx_thread.join();
     g_bg_init = nullptr;
   }
@@ -406,7 +463,15 @@ int sort_main(int argc, char **argv) {
   }
   // the index behind the BAM's rename.  A refusal (the records' own: a negative position, a record past the end of its reference
   // or past what the scheme addresses) leaves the sorted file, which is complete and valid, and no index
-  if (X.on && !X.rc) {
+  uint64_t index_bytes = 0;
+  if (X.on && windowed) {                  // a second read of the output: the bytes `strling bamindex OUT.bam` writes, by the same function
+    const auto t0 = Clock::now();
+    int st = 0;
+    if (!build_bai(ctx_again, out_path, X.out, false, false, X.why, st, X.min_shift)) X.rc = st ? st : STRL_ERR_IO;
+    else if (FILE *f = fopen(X.out.c_str(), "rb")) { fseek(f, 0, SEEK_END); index_bytes = (uint64_t)ftell(f); fclose(f); }
+    X.s = since(t0);
+  } else if (X.on && !X.rc) {
+    index_bytes = X.bytes.size();
     const auto t0 = Clock::now();
     ThreadPool pool(std::min(decode_threads(), 4));
     if (!write_index_file(X.out, X.bytes, X.min_shift >= 0, X.why, &pool)) X.rc = STRL_ERR_IO;
@@ -417,10 +482,11 @@ int sort_main(int argc, char **argv) {
     fprintf(stderr,
             "{\"command\": \"sort\", \"path\": \"%s\", \"records\": %llu, \"no_reference\": %llu, \"stream_bytes\": %llu, \"out_bytes\": %llu, \"already_sorted\": %s, \"slabs\": %llu, "
             "\"seconds\": %.3f, \"read_s\": %.3f, \"sort_s\": %.3f, \"gather_s\": %.3f, \"deflate_s\": %.3f, \"write_s\": %.3f, \"deflate\": \"%s\", \"stored\": %u, "
-            "\"index\": \"%s\", \"index_bytes\": %llu, \"index_chunks\": %llu, \"index_s\": %.3f}\n",
+            "\"index\": \"%s\", \"index_bytes\": %llu, \"index_chunks\": %llu, \"index_s\": %.3f, \"windows\": %llu, \"window_bytes\": %llu, \"window_s\": %.3f}\n",
             on_host ? "host" : "device", (unsigned long long)R.records, (unsigned long long)R.no_ref, (unsigned long long)R.stream_bytes, (unsigned long long)R.out_bytes,
             R.already_sorted ? "true" : "false", (unsigned long long)R.slabs, since(t_all), R.s.read, R.s.sort, R.s.gather, R.s.deflate, R.s.write, R.deflate, R.stored,
-            !indexed ? "none" : X.min_shift >= 0 ? "csi" : "bai", (unsigned long long)(indexed ? X.bytes.size() : 0), (unsigned long long)(indexed ? X.chunks : 0), X.s);
+            !indexed ? "none" : X.min_shift >= 0 ? "csi" : "bai", (unsigned long long)(indexed ? index_bytes : 0), (unsigned long long)(indexed ? X.chunks : 0), X.s,
+            (unsigned long long)R.windows, (unsigned long long)R.window_bytes, R.s.window);
   if (X.on && X.rc) {
     if (ctx) strl_ctx_destroy(ctx);
     quit("[strling] sort: sorted file written; index refused: %s (status %d)", X.why.c_str(), X.rc);

@@ -17,6 +17,12 @@ other on one box, one process at a time, K runs each (the first pays for the pag
 forms: this build's `sort --write-index`; --parent-cli's (default: this build's) `sort` followed by its `bamindex` of the output,
 the two commands' wall times summed; this build's plain `sort` and the parent's side by side, the order swapped every repeat.  The
 index must be the bytes `bamindex` wrote.  With --trace the traced run is `sort --write-index --deflate=device`.
+    python tools/sort_bench.py --windowed [--window-mb 1300,700,400] [--parent-cli PATH] [--pairs N] [--repeats K] [--trace OUTDIR]
+--windowed measures `sort --windowed`: --parent-cli's (default: this build's) resident `sort`, K runs (wall time and read_s); then
+`sort --windowed` with every window size of --window-mb (default: the sizes that make 1, 2 and 4 windows of this file) for both
+--deflate forms, K runs each: wall time, pass 0's time and the time of a window's pass; the --deflate=host file must be the
+resident sort's.  With --trace, runs under the profiler of their own: one window with 16 / 32 / 64 lanes a record of the scatter
+(--lanes), then 2 and 4 windows: the time of bsort_scatter_kernel and bsort_dest_kernel, and the scatter's rate in TB/s of stream.
 `samtools sort` is not on these machines: nothing here compares with it.  No threshold is asserted.
 """
 import argparse
@@ -112,6 +118,64 @@ def write_index_runs(a, cli, src, work):
         print(json.dumps({"trace": "kernel_stats_write_index.csv" if (r.returncode == 0 and f) else (r.stderr or "no kernel table")[-500:]}), flush=True)
 
 
+def _stats_csv(cmd, env, work, dest):
+    """cmd under `rocprofv3 --kernel-trace --stats`, a run of its own -> the kernel table copied to dest; its rows by kernel name"""
+    kt = os.path.join(work, "kt_" + os.path.basename(dest))
+    r = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", kt, "-o", "run", "--", *cmd], capture_output=True, text=True,
+                       env=dict(os.environ, STRL_TEARDOWN="1", **env), timeout=900)
+    f = glob.glob(os.path.join(kt, "**", "run_kernel_stats.csv"), recursive=True)
+    if r.returncode or not f:
+        return None, (r.stderr or "no kernel table")[-500:]
+    shutil.copy(f[0], dest)
+    import csv
+    rows = {}
+    for row in csv.DictReader(open(dest)):
+        rows[row["Name"]] = {"calls": int(row["Calls"]), "total_ms": round(float(row["TotalDurationNs"]) / 1e6, 3)}
+    return rows, None
+
+
+def windowed_runs(a, cli, src, work, inflated):
+    """`sort --windowed` with the windows --window-mb names (default: P = 1, 2, 4 from the inflated size) for both --deflate forms,
+    beside --parent-cli's (default: this build's) resident `sort`; and the scatter's group size, each under the profiler once"""
+    parent = a.parent_cli or cli
+    res, win = os.path.join(work, "resident.bam"), os.path.join(work, "windowed.bam")
+    for k in range(a.repeats):
+        says, wall = _run([parent, "sort", "-v", "--deflate=host", "-o", res, src])
+        print(json.dumps({"run": "parent resident sort", "deflate": "host", "repeat": k, "wall_s": wall, "read_s": says["read_s"], "says": says}), flush=True)
+    piece = (128 << 20) // 0xFF00 * 0xFF00           # the CLI's default piece: a window is a whole number of them
+
+    def mb_for(p):
+        """MiB of the smallest window limit that cuts this file's stream into p windows (the stream is the input and a few header bytes)"""
+        share = -(-(inflated + 4096) // p)
+        return -(-share // piece) * piece / 1048576.0
+
+    sizes = [float(x) for x in a.window_mb.split(",") if x] if a.window_mb else [mb_for(p) for p in (1, 2, 4)]
+    for form in ("host", "device"):
+        for mb in sizes:
+            for k in range(a.repeats):
+                says, wall = _run([cli, "sort", "--windowed", "-v", f"--deflate={form}", "-o", win, src], dict(os.environ, STRL_SORT_WINDOW_KB=str(mb * 1024)))
+                print(json.dumps({"run": "sort --windowed", "deflate": form, "window_mb": mb, "windows": says["windows"], "repeat": k, "wall_s": wall, "pass0_s": says["read_s"],
+                                  "per_window_pass_s": round(says["window_s"] / max(1, says["windows"]), 4), "says": says}), flush=True)
+            if form == "host":
+                print(json.dumps({"check": "the windowed file is the resident sort's", "window_mb": mb, "ok": open(win, "rb").read() == open(res, "rb").read()}), flush=True)
+    if a.trace:
+        os.makedirs(a.trace, exist_ok=True)
+        one = str(mb_for(1) * 1024)
+        for lanes in [x for x in a.lanes.split(",") if x]:
+            name = "kernel_stats.csv" if lanes == "16" else f"kernel_stats_lanes{lanes}.csv"
+            rows, err = _stats_csv([cli, "sort", "--windowed", "--deflate=device", "-o", win, src], {"STRL_SORT_WINDOW_KB": one, "STRL_SORT_GATHER_LANES": lanes}, work,
+                                   os.path.join(a.trace, name))
+            pick = {k.split("(")[0]: v for k, v in (rows or {}).items() if "bsort_scatter" in k or "bsort_dest" in k}
+            for v in pick.values():
+                v["TB_per_s_of_stream"] = round(inflated / (v["total_ms"] / 1e3) / 1e12, 3) if v["total_ms"] else None
+            print(json.dumps({"trace": name, "windows": 1, "lanes_per_record": int(lanes), "kernels": pick, "error": err}), flush=True)
+        for p in (2, 4):
+            name = f"kernel_stats_p{p}.csv"
+            rows, err = _stats_csv([cli, "sort", "--windowed", "--deflate=device", "-o", win, src], {"STRL_SORT_WINDOW_KB": str(mb_for(p) * 1024)}, work, os.path.join(a.trace, name))
+            pick = {k.split("(")[0]: v for k, v in (rows or {}).items() if "bsort_scatter" in k or "bsort_dest" in k}
+            print(json.dumps({"trace": name, "windows": p, "kernels": pick, "error": err}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--pairs", type=int, default=2 ** 20)
@@ -122,6 +186,8 @@ def main():
     ap.add_argument("--lanes", default="16,32,64")
     ap.add_argument("--write-index", action="store_true")
     ap.add_argument("--parent-cli", default="")
+    ap.add_argument("--windowed", action="store_true")
+    ap.add_argument("--window-mb", default="", help="with --windowed: comma-separated window sizes in MiB (default: the sizes that give 1, 2 and 4 windows)")
     a = ap.parse_args()
     t0 = time.time()
     inp = e2e_bench.make_input(a.pairs, d=a.dir, level=1)
@@ -133,6 +199,10 @@ def main():
     print(json.dumps(base), flush=True)
     if a.write_index:
         write_index_runs(a, cli, src, work)
+        shutil.rmtree(work, ignore_errors=True)
+        return
+    if a.windowed:
+        windowed_runs(a, cli, src, work, inflated)
         shutil.rmtree(work, ignore_errors=True)
         return
     outs = {}
