@@ -925,6 +925,38 @@ int strl_bamsort_window_push(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_b
                              const uint32_t *crc32, uint32_t n_blocks);
 int strl_bamsort_window_end(strl_ctx *ctx);
 int strl_bamsort_window_plan(uint64_t stream_bytes, uint64_t limit_bytes, uint64_t piece_bytes, uint64_t *window_bytes, uint64_t *n_windows);
+/* SAM text as the sort's input (`strling sort IN.sam`, `strling sort -`): a second producer of what the sort
+ * works from.  A chunk of whole lines is encoded to BAM records on the device (csrc/samparse.hip) by the rule of csrc/sam_core.h --
+ * byte for byte the records the host's encoder of that header builds -- and key, length and arena copy run over them as over an
+ * inflated chunk.  Behind the read phase nothing differs: strl_bamsort_finish, _fetch, _fetch_bgzf, _order, _index and _end.
+ *   strl_bamsort_sam_begin    as strl_bamsort_begin, without a front end: names = the n_ref reference names of the @SQ lines back
+ *                             to back without NULs, name_off[n_ref + 1] where each begins (strl_sam_header's list gives them).  The
+ *                             host builds a hash table of the names and uploads it once.  STRL_ERR_FORMAT: a name occurs twice.
+ *   strl_bamsort_sam_reserve  the slots for chunks of at most max_text_bytes (1 .. 512 MiB), before the first push.
+ *   strl_bamsort_push_sam     text[0, bytes): whole alignment lines, the last byte a newline -- else STRL_ERR_ARG, which leaves the
+ *                             sort as it was.  Key, length and arena copy of chunk i - 1, then the copy of chunk i, the line scan,
+ *                             the size kernel and the encode are enqueued; `text` may be reused on return.  A line the rule refuses
+ *                             is STRL_ERR_FORMAT "SAM line N: FIELD: ...", N counting the alignment lines from 1: the device names
+ *                             the chunk's first refused line, the host's encoder says why.  Float values in spellings the kernel
+ *                             does not convert exactly (more than 15 digits, a decimal exponent beyond 22, inf, nan) are the host's:
+ *                             it encodes those lines and copies each record over its place.
+ *   strl_bamsort_sam_info     lines, text bytes, host-finished records and chunks so far (counted when a chunk's records go into the
+ *                             arena), and the HIP-event time of the copy and of the three kernels (the sums counted with the size).
+ * STRL_SORT_SAM_LANES = 16 / 32 / 64: lanes per line of the size kernel and the encode.
+ * Without a device: strl_sam_encode, one line (a trailing newline and a \r before it are dropped) -> one record, by the same header's
+ * host function; strl_sam_header, the leading @ lines of a text -> the BAM header that text stands for (magic, l_text, the lines
+ * byte for byte, n_ref, the @SQ lines' SN and LN in order), from which strl_bamsort_header makes the output's.  STRL_ERR_FORMAT: an
+ * @SQ line without SN or with LN outside [1, 2^31 - 1], an SN that occurs twice.  Both follow strl_bamsort_header's capacity rule. */
+typedef struct {
+  uint64_t lines, text_bytes, host_finished, chunks;
+  double copy_ms, scan_ms, size_ms, encode_ms;
+} strl_bamsort_sam_figures;
+int strl_bamsort_sam_begin(strl_ctx *ctx, const uint8_t *names, const uint32_t *name_off, int32_t n_ref, uint64_t arena_limit_bytes);
+int strl_bamsort_sam_reserve(strl_ctx *ctx, uint64_t max_text_bytes);
+int strl_bamsort_push_sam(strl_ctx *ctx, const uint8_t *text, uint64_t bytes);
+int strl_bamsort_sam_info(strl_ctx *ctx, strl_bamsort_sam_figures *out);
+int strl_sam_encode(const uint8_t *line, uint64_t len, const uint8_t *names, const uint32_t *name_off, int32_t n_ref, uint8_t *out, uint64_t cap, uint64_t *out_bytes);
+int strl_sam_header(const uint8_t *text, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *out_bytes, int32_t *n_ref);
 
 /* ---- the .bai as a by-product of `strling extract`'s own pass (`strling extract --write-index`) ----
  * strl_front_push already copies, inflates, CRC-checks, record-scans and parses every block; the index needs of a record only

@@ -64,6 +64,11 @@ class BamsortInfo(C.Structure):
                 ("arena_bytes", C.c_uint64), ("sort_ms", C.c_double), ("layout_ms", C.c_double), ("gather_ms", C.c_double)]
 
 
+class BamsortSamFigures(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("text_bytes", C.c_uint64), ("host_finished", C.c_uint64), ("chunks", C.c_uint64),
+                ("copy_ms", C.c_double), ("scan_ms", C.c_double), ("size_ms", C.c_double), ("encode_ms", C.c_double)]
+
+
 class SweepInfo(C.Structure):
     _fields_ = [("n_answered", C.c_uint64), ("n_seam", C.c_uint64), ("n_passed_on", C.c_uint64), ("n_chunks", C.c_uint64), ("n_records", C.c_uint64),
                 ("sweep_ms", C.c_double), ("evidence_ms", C.c_double)]
@@ -156,7 +161,8 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_bamsort_info_now", "strl_bamsort_end", "strl_bamsort_key", "strl_bamsort_key_bits", "strl_bamsort_header",
            "strl_bamsort_index", "strl_bamsort_index_fetch", "strl_bamsort_voff", "strl_bamsort_members",
            "strl_bamsort_begin_windowed", "strl_bamsort_window_limit", "strl_bamsort_window_begin", "strl_bamsort_window_push", "strl_bamsort_window_end",
-           "strl_bamsort_window_plan"]
+           "strl_bamsort_window_plan",
+           "strl_bamsort_sam_begin", "strl_bamsort_sam_reserve", "strl_bamsort_push_sam", "strl_bamsort_sam_info", "strl_sam_encode", "strl_sam_header"]
 
 
 def lib_path():
@@ -303,6 +309,12 @@ def load(build_if_missing=True):
     L.strl_bamsort_window_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.strl_bamsort_window_end.argtypes = [C.c_void_p]
     L.strl_bamsort_window_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.strl_bamsort_sam_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64]
+    L.strl_bamsort_sam_reserve.argtypes = [C.c_void_p, C.c_uint64]
+    L.strl_bamsort_push_sam.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.strl_bamsort_sam_info.argtypes = [C.c_void_p, C.POINTER(BamsortSamFigures)]
+    L.strl_sam_encode.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.strl_sam_header.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     L.strl_bamsort_window_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     L.strl_sweep_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8]
     L.strl_sweep_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
@@ -1109,6 +1121,56 @@ class Context:
         a, b = int(rng[0]), int(rng[1])
         return off, (a, b), parts[:b - a]
 
+    # ---- SAM text as the sort's input (strl_bamsort_sam_begin / _sam_reserve / _push_sam): encoded to BAM records on the device
+    def bamsort_sam_begin(self, names, arena_limit_bytes=0):
+        """names: the @SQ names in order (str or bytes)"""
+        nm, off = _sam_names(names)
+        _check(self.L.strl_bamsort_sam_begin(self.h, _ptr(nm), off.ctypes.data, len(off) - 1, int(arena_limit_bytes)))
+
+    def bamsort_sam_reserve(self, max_text_bytes):
+        _check(self.L.strl_bamsort_sam_reserve(self.h, int(max_text_bytes)))
+
+    def bamsort_push_sam(self, text):
+        """one chunk of whole alignment lines, the last byte a newline"""
+        t = np.frombuffer(bytes(text), np.uint8)
+        _check(self.L.strl_bamsort_push_sam(self.h, _ptr(t), t.size))
+
+    def bamsort_sam_info(self):
+        f = BamsortSamFigures()
+        _check(self.L.strl_bamsort_sam_info(self.h, C.byref(f)))
+        return {k: getattr(f, k) for k, _ in BamsortSamFigures._fields_}
+
+    def bamsort_sam(self, text, chunk_bytes=1 << 20, keep_open=False):
+        """SAM TEXT (header lines and alignment lines) coordinate-sorted on the device -> (the output stream, strl_bamsort_info as a
+        dict with the SAM figures added, the permutation).  Chunks of whole lines of at most chunk_bytes, a longer line alone."""
+        text = bytes(text)
+        raw, names, _ = sam_header(text)
+        l_text = int.from_bytes(raw[4:8], "little")
+        body = text[l_text:]
+        if body and not body.endswith(b"\n"):
+            body += b"\n"
+        chunks, at = [], 0
+        while at < len(body):
+            cut = body.rfind(b"\n", at, at + chunk_bytes)
+            cut = body.index(b"\n", at) if cut < 0 else cut
+            chunks.append(body[at:cut + 1])
+            at = cut + 1
+        self.bamsort_sam_begin(names)
+        try:
+            self.bamsort_sam_reserve(max([len(c) for c in chunks] + [1]))
+            for c in chunks:
+                self.bamsort_push_sam(c)
+            info = self.bamsort_finish(bamsort_header(raw))
+            info.update(self.bamsort_sam_info())
+            stream = self.bamsort_fetch(0, info["stream_bytes"])
+            perm = self.bamsort_order(info["n_records"])
+        except Exception:
+            self.bamsort_end()
+            raise
+        if not keep_open:
+            self.bamsort_end()
+        return stream, info, perm
+
     # ---- `strling sort --windowed` (strl_bamsort_begin_windowed / _window_*): a file larger than device memory, in passes
     def bamsort_begin_windowed(self, n_ref, first_off):
         _check(self.L.strl_bamsort_begin_windowed(self.h, int(n_ref), int(first_off)))
@@ -1538,6 +1600,44 @@ def bamsort_header(raw):
     out = np.zeros(max(1, n.value), np.uint8)
     _check(load().strl_bamsort_header(_ptr(src), src.size, out.ctypes.data, out.size, C.byref(n)))
     return out[:n.value].tobytes()
+
+
+def _sam_names(names):
+    nb = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    off = np.zeros(len(nb) + 1, np.uint32)
+    off[1:] = np.cumsum([len(n) for n in nb], dtype=np.int64)
+    return np.frombuffer(b"".join(nb), np.uint8), off
+
+
+def sam_encode(line, names):
+    """one SAM alignment line -> its BAM record with the block_size word, by the rule's host function (strl_sam_encode;
+    csrc/sam_core.h).  names: the @SQ names in order.  A refusal is a StrlingError of code -6 with "FIELD: words"."""
+    src = np.frombuffer(bytes(line), np.uint8)
+    nm, off = _sam_names(names)
+    n = C.c_uint64(0)
+    out = np.zeros(2 * src.size + 64, np.uint8)
+    _check(load().strl_sam_encode(_ptr(src), src.size, _ptr(nm), off.ctypes.data, len(off) - 1, out.ctypes.data, out.size, C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+def sam_header(text):
+    """the leading @ lines of SAM text -> (the BAM header they stand for, the @SQ names, their lengths) (strl_sam_header)"""
+    src = np.frombuffer(bytes(text), np.uint8)
+    n, n_ref = C.c_uint64(0), C.c_int32(0)
+    rc = load().strl_sam_header(_ptr(src), src.size, None, 0, C.byref(n), C.byref(n_ref))
+    if rc not in (0, -4):
+        _check(rc)
+    out = np.zeros(max(1, n.value), np.uint8)
+    _check(load().strl_sam_header(_ptr(src), src.size, out.ctypes.data, out.size, C.byref(n), C.byref(n_ref)))
+    raw = out[:n.value].tobytes()
+    at = 12 + int.from_bytes(raw[4:8], "little")
+    names, lens = [], []
+    for _ in range(n_ref.value):
+        l = int.from_bytes(raw[at:at + 4], "little")
+        names.append(raw[at + 4:at + 4 + l - 1].decode())
+        lens.append(int.from_bytes(raw[at + 4 + l:at + 8 + l], "little"))
+        at += 8 + l
+    return raw, names, lens
 
 
 def bgzf_deflate_bound(n, block=0xFF00):

@@ -23,6 +23,9 @@
 //   bsort_scatter_kernel               a group of 16 lanes per record of the chunk copies the part inside the window to its place,
 //                                      as the gather copies; a length that is not pass 0's is refused, the bytes placed are counted
 // after which the window buffer is a finished piece of the stream and the fetches read it.
+// SAM text (strl_bamsort_sam_begin / strl_bamsort_push_sam) is a second producer of "records back to back plus
+// recoff[]": samparse.hip encodes a chunk of lines into a slot, and bsort_keys_kernel and the copy into the arena run over that slot
+// as they run over an inflated chunk; everything behind the read phase is the same.
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -30,6 +33,7 @@
 #include "sort.h"
 #include "device_util.h"
 #include "bamsort_core.h"
+#include "samparse.h"
 
 namespace strl {
 
@@ -334,11 +338,14 @@ struct strl_bsort {
   uint64_t win_lo = 0, win_hi = 0;
   bool win_open = false, win_done = false;     // a window's pass is running | the window is complete and may be fetched from
   uint64_t w_chunks = 0, w_done = 0, w_ord = 0;   // chunks pushed / scattered in this pass; ordinal of the next chunk's first record
+  SamParser *sam = nullptr;                    // the input is SAM text (strl_bamsort_sam_begin): no front end, samparse.hip's slots instead
 };
+static_assert(SAM_REC_MAX == FRONT_CARRY_MAX, "a record from SAM text is held to the front end's limit");
 
 void bsort_destroy(strl_bsort *B) {
   if (!B) return;
   if (B->index) bai_destroy(B->index);
+  if (B->sam) sam_parser_destroy(B->sam);
   if (B->h_state) (void)hipHostFree(B->h_state);
   if (B->h_wstate) (void)hipHostFree(B->h_wstate);
   for (hipEvent_t e : {B->e0, B->e1, B->e2}) if (e) (void)hipEventDestroy(e);
@@ -442,6 +449,37 @@ static int bsort_chunk(strl_ctx *c, strl_front *F, strl_bsort *B, int si) {
   }
   STRL_HIP(hipEventRecord(S.ev_b, st));        // the slot's inflated bytes and record table may be overwritten behind this
   S.b_pending = true;
+  return STRL_OK;
+}
+
+// keys and arena copy of the chunk of SAM text in slot si: its records were encoded behind the push before
+static int bsort_sam_chunk(strl_ctx *c, strl_bsort *B, int si) {
+  hipStream_t st = c->stream;
+  SamInfo I;
+  int rc;
+  if ((rc = sam_parser_collect(B->sam, si, st, &I))) return rc;
+  SamSlot &S = B->sam->slot[si];
+  const uint32_t n = I.n_lines;
+  const uint64_t bytes = I.total;
+  if (!n || !bytes) return STRL_OK;
+  if (B->n_records + n > BSORT_MAX_RECORDS) { set_error("more than 2^32 - 2 = %llu records: beyond one device sort", (unsigned long long)BSORT_MAX_RECORDS); return STRL_ERR_LIMIT; }
+  const uint64_t need = B->n_records + n;
+  if (need > B->rec_cap) {
+    const uint64_t cap = std::max<uint64_t>(need + need / 2, 1u << 16);
+    if ((rc = B->key.grow((size_t)cap * 8, (size_t)B->n_records * 8, st)) || (rc = B->src.grow((size_t)cap * 8, (size_t)B->n_records * 8, st)) ||
+        (rc = B->len.grow((size_t)cap * 4, (size_t)B->n_records * 4, st)))
+      return rc;
+    B->rec_cap = cap;
+  }
+  uint64_t src0 = 0;
+  uint8_t *dst = nullptr;
+  if ((rc = bsort_place(B, bytes, n, &src0, &dst))) return rc;
+  BsortKeys P{S.rec.as<uint8_t>(), S.recoff.as<uint32_t>(), n, 0u, (uint32_t)bytes, B->n_ref, B->n_records, B->rec_cap, src0, B->key.as<uint64_t>(), B->src.as<uint64_t>(),
+              B->len.as<uint32_t>(), B->state.as<BsortState>()};
+  hipLaunchKernelGGL(bsort_keys_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, P);
+  STRL_HIP(hipGetLastError());
+  STRL_HIP(hipMemcpyAsync(dst, S.rec.p, bytes, hipMemcpyDeviceToDevice, st));
+  B->n_records += n;
   return STRL_OK;
 }
 
@@ -604,11 +642,42 @@ extern "C" int strl_bamsort_header(const uint8_t *in, uint64_t in_bytes, uint8_t
   return STRL_OK;
 }
 
+extern "C" int strl_sam_encode(const uint8_t *line, uint64_t len, const uint8_t *names, const uint32_t *name_off, int32_t n_ref, uint8_t *out, uint64_t cap, uint64_t *out_bytes) {
+  if ((len && !line) || !out_bytes || n_ref < 0 || (n_ref && (!names || !name_off))) { set_error("strl_sam_encode: bad argument"); return STRL_ERR_ARG; }
+  static const uint32_t zero = 0;
+  if (!line) line = reinterpret_cast<const uint8_t *>("");
+  SamRefTable T;
+  int32_t dup = 0;
+  if (!T.build(names, n_ref ? name_off : &zero, n_ref, &dup)) { set_error("strl_sam_encode: reference name %d occurs twice", dup); return STRL_ERR_FORMAT; }
+  while (len && line[len - 1] == '\n') --len;
+  if (len > (uint64_t)SAM_LINE_MAX + 1u) len = (uint64_t)SAM_LINE_MAX + 2u;      // (refused as too long, whatever it holds)
+  std::vector<uint8_t> rec;
+  std::string why;
+  if (sam_encode_line(line, (uint32_t)len, T.view(), rec, why)) { set_error("%s", why.c_str()); return STRL_ERR_FORMAT; }
+  *out_bytes = rec.size();
+  if (cap < rec.size() || !out) { set_error("strl_sam_encode: %zu bytes, room for %llu", rec.size(), (unsigned long long)cap); return STRL_ERR_CAPACITY; }
+  memcpy(out, rec.data(), rec.size());
+  return STRL_OK;
+}
+
+extern "C" int strl_sam_header(const uint8_t *text, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *out_bytes, int32_t *n_ref) {
+  if ((len && !text) || !out_bytes) { set_error("strl_sam_header: null argument"); return STRL_ERR_ARG; }
+  SamHeader H;
+  std::string err;
+  if (!sam_header(text, (size_t)len, H, err)) { set_error("%s", err.c_str()); return STRL_ERR_FORMAT; }
+  *out_bytes = H.bam.size();
+  if (n_ref) *n_ref = (int32_t)H.l_ref.size();
+  if (cap < H.bam.size() || !out) { set_error("strl_sam_header: %zu bytes, room for %llu", H.bam.size(), (unsigned long long)cap); return STRL_ERR_CAPACITY; }
+  memcpy(out, H.bam.data(), H.bam.size());
+  return STRL_OK;
+}
+
 // ---- the device sort --------------------------------------------------------------------------------------------------------------
-static int bsort_begin(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset, uint64_t arena_limit_bytes, bool windowed) {
-  if (!c || n_ref < 0) { set_error("%s: bad argument", windowed ? "strl_bamsort_begin_windowed" : "strl_bamsort_begin"); return STRL_ERR_ARG; }
+static int bsort_begin(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset, uint64_t arena_limit_bytes, bool windowed, bool sam = false) {
+  if (!c || n_ref < 0) { set_error("%s: bad argument", sam ? "strl_bamsort_sam_begin" : windowed ? "strl_bamsort_begin_windowed" : "strl_bamsort_begin"); return STRL_ERR_ARG; }
   int rc;
-  if ((rc = front_begin_scan(c, n_ref, first_record_offset))) return rc;
+  if (sam) STRL_HIP(hipSetDevice(c->device));
+  else if ((rc = front_begin_scan(c, n_ref, first_record_offset))) return rc;
   // one consumer of the record scan on a context: a builder or a sweep of an earlier pass ends here, as theirs end each other's
   if (c->bai) { bai_destroy(c->bai); c->bai = nullptr; }
   if (c->sweep) { sweep_destroy(c->sweep); c->sweep = nullptr; }
@@ -616,7 +685,7 @@ static int bsort_begin(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset,
   strl_bsort *B = new strl_bsort();
   c->bsort = B;
   B->n_ref = n_ref;
-  B->front = c->front;
+  B->front = sam ? nullptr : c->front;          // (SAM text does not go through the front end)
   B->slab_want = bsort_slab_want();
   B->arena_limit = arena_limit_bytes;
   STRL_HIP(hipHostMalloc(reinterpret_cast<void **>(&B->h_state), sizeof(BsortState), hipHostMallocDefault));
@@ -643,8 +712,53 @@ extern "C" int strl_bamsort_begin(strl_ctx *c, int32_t n_ref, uint64_t first_rec
 }
 extern "C" int strl_bamsort_begin_windowed(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset) { return bsort_begin(c, n_ref, first_record_offset, 0, true); }
 
+extern "C" int strl_bamsort_sam_begin(strl_ctx *c, const uint8_t *names, const uint32_t *name_off, int32_t n_ref, uint64_t arena_limit_bytes) {
+  if (n_ref > 0 && (!names || !name_off)) { set_error("strl_bamsort_sam_begin: bad argument"); return STRL_ERR_ARG; }
+  int rc;
+  if ((rc = bsort_begin(c, n_ref, 0, arena_limit_bytes, false, true))) return rc;
+  static const uint32_t zero = 0;
+  return bsort_fail(c->bsort, sam_parser_create(&c->bsort->sam, names, n_ref > 0 ? name_off : &zero, n_ref, c->stream));
+}
+
+extern "C" int strl_bamsort_sam_reserve(strl_ctx *c, uint64_t max_text_bytes) {
+  if (!c || !c->bsort || !c->bsort->sam) { set_error("strl_bamsort_sam_reserve: bad argument / no strl_bamsort_sam_begin"); return STRL_ERR_ARG; }
+  strl_bsort *B = c->bsort;
+  if (B->done < B->chunks) { set_error("strl_bamsort_sam_reserve: a chunk is in flight"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  return sam_parser_reserve(B->sam, max_text_bytes);
+}
+
+extern "C" int strl_bamsort_push_sam(strl_ctx *c, const uint8_t *text, uint64_t bytes) {
+  if (!c || !c->bsort || !c->bsort->sam || c->bai || c->sweep || c->x_open || c->bsort->finished || (bytes && !text)) {
+    set_error("strl_bamsort_push_sam: bad argument / no strl_bamsort_sam_begin");
+    return STRL_ERR_ARG;
+  }
+  if (!bytes) return STRL_OK;
+  STRL_HIP(hipSetDevice(c->device));
+  strl_bsort *B = c->bsort;
+  if (B->fail_rc) { set_error("%s", B->fail.c_str()); return B->fail_rc; }
+  if (text[bytes - 1] != '\n' || bytes > B->sam->max_text) {      // (the caller's mistake, not the file's: the sort goes on)
+    set_error("strl_bamsort_push_sam: a chunk is whole lines, its last byte a newline, and at most strl_bamsort_sam_reserve's %llu bytes (got %llu)",
+              (unsigned long long)B->sam->max_text, (unsigned long long)bytes);
+    return STRL_ERR_ARG;
+  }
+  int rc;
+  // keys and arena copy of the chunk before (its kernels ran beside the caller's read of this one), then this chunk's copy and kernels
+  for (; B->done < B->chunks; ++B->done)
+    if ((rc = bsort_sam_chunk(c, B, (int)(B->done & 1)))) return bsort_fail(B, rc);
+  if ((rc = sam_parser_enqueue(B->sam, (int)(B->chunks & 1), text, bytes, B->sam->fig.lines, c->stream))) return bsort_fail(B, rc);
+  ++B->chunks;
+  return STRL_OK;
+}
+
+extern "C" int strl_bamsort_sam_info(strl_ctx *c, strl_bamsort_sam_figures *out) {
+  if (!c || !c->bsort || !c->bsort->sam || !out) { set_error("strl_bamsort_sam_info: bad argument / no strl_bamsort_sam_begin"); return STRL_ERR_ARG; }
+  *out = c->bsort->sam->fig;
+  return STRL_OK;
+}
+
 extern "C" int strl_bamsort_reserve(strl_ctx *c, uint32_t max_blocks, uint64_t max_comp_bytes) {
-  if (!c || !c->bsort || !c->front || !max_blocks) { set_error("strl_bamsort_reserve: bad argument / no strl_bamsort_begin"); return STRL_ERR_ARG; }
+  if (!c || !c->bsort || !c->front || c->bsort->sam || !max_blocks) { set_error("strl_bamsort_reserve: bad argument / no strl_bamsort_begin"); return STRL_ERR_ARG; }
   STRL_HIP(hipSetDevice(c->device));
   c->bsort->res_blocks = max_blocks; c->bsort->res_comp = max_comp_bytes;
   return front_reserve(c, c->front, max_blocks, max_comp_bytes);
@@ -652,7 +766,7 @@ extern "C" int strl_bamsort_reserve(strl_ctx *c, uint32_t max_blocks, uint64_t m
 
 extern "C" int strl_bamsort_push(strl_ctx *c, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
                                  const uint32_t *crc32, uint32_t n_blocks) {
-  if (!c || !c->bsort || !c->front || c->front != c->bsort->front || c->bai || c->sweep || c->x_open || c->bsort->finished || (n_blocks && (!comp || !coff || !clen || !isize))) {
+  if (!c || !c->bsort || c->bsort->sam || !c->front || c->front != c->bsort->front || c->bai || c->sweep || c->x_open || c->bsort->finished || (n_blocks && (!comp || !coff || !clen || !isize))) {
     set_error("strl_bamsort_push: bad argument / no strl_bamsort_begin / another pass has taken the context's front end");
     return STRL_ERR_ARG;
   }
@@ -677,7 +791,8 @@ extern "C" int strl_bamsort_push(strl_ctx *c, const uint8_t *comp, uint64_t comp
 }
 
 extern "C" int strl_bamsort_finish(strl_ctx *c, const uint8_t *header, uint64_t header_bytes, strl_bamsort_info *info) {
-  if (!c || !c->bsort || !c->front || c->front != c->bsort->front || c->bai || c->sweep || c->x_open || (header_bytes && !header)) { set_error("strl_bamsort_finish: bad argument / no strl_bamsort_begin"); return STRL_ERR_ARG; }
+  const bool sam = c && c->bsort && c->bsort->sam;
+  if (!c || !c->bsort || (!sam && (!c->front || c->front != c->bsort->front)) || c->bai || c->sweep || c->x_open || (header_bytes && !header)) { set_error("strl_bamsort_finish: bad argument / no strl_bamsort_begin"); return STRL_ERR_ARG; }
   STRL_HIP(hipSetDevice(c->device));
   strl_front *F = c->front;
   strl_bsort *B = c->bsort;
@@ -686,10 +801,10 @@ extern "C" int strl_bamsort_finish(strl_ctx *c, const uint8_t *header, uint64_t 
   int rc;
   if (!B->finished) {
     for (; B->done < B->chunks; ++B->done)
-      if ((rc = bsort_chunk(c, F, B, (int)(B->done & 1)))) return bsort_fail(B, rc);
+      if ((rc = sam ? bsort_sam_chunk(c, B, (int)(B->done & 1)) : bsort_chunk(c, F, B, (int)(B->done & 1)))) return bsort_fail(B, rc);
     STRL_HIP(hipMemcpyAsync(B->h_state, B->state.p, sizeof(BsortState), hipMemcpyDeviceToHost, st));
     STRL_HIP(hipStreamSynchronize(st));
-    if (F->last_slot >= 0 && F->slot[F->last_slot].h_info[0].carry_len) { set_error("the BAM ends inside a record (truncated file)"); return bsort_fail(B, STRL_ERR_FORMAT); }
+    if (!sam && F->last_slot >= 0 && F->slot[F->last_slot].h_info[0].carry_len) { set_error("the BAM ends inside a record (truncated file)"); return bsort_fail(B, STRL_ERR_FORMAT); }
     if ((rc = bsort_refuse(B, *B->h_state))) return bsort_fail(B, rc);
     if (B->windowed) {
       if ((rc = bsort_finish_windowed(c, B, header, header_bytes))) return bsort_fail(B, rc);

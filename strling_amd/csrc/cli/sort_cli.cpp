@@ -14,6 +14,10 @@
 // record; the stream is then cut into windows the device can hold (strl_bamsort_window_limit, bsort_window_plan), and for every
 // window the file is fed again -- a fresh BgzfFeed and ChunkAhead over the same page-locked buffers -- and scattered into the
 // window, which then goes through the same piece loop.  With --write-index the index is build_bai's over the file just written.
+// SAM text, from a file or from stdin (`-`): the format is taken from the first bytes.  SamFeed (sam_feed.h) reads chunks of whole
+// lines into page-locked buffers, chunk i + 1 beside the push of chunk i; the device encodes them to BAM records (samparse.hip) in
+// place of the inflate, and everything behind the read phase is the BAM's.  On the host path the same lines go through the same
+// header's host function (sam_core.h) into host memory and then through the host path's tail.  DESIGN section 24.2.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,8 +34,10 @@
 #include "bam_reader.h"
 #include "bgzf_feed.h"
 #include "cram_reader.h"
+#include "sam_feed.h"
 #include "../bamindex_host.h"
 #include "../bamsort_core.h"
+#include "../sam_core.h"
 #include "../front.h"
 
 using namespace strl;
@@ -42,7 +48,8 @@ using Clock = std::chrono::steady_clock;
 double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
 
 const char *USAGE =
-    "strling sort\n\nUsage:\n  strling sort [options] -o OUT.bam IN.bam\n\nArguments:\n  IN.bam           path to a bam file, in any order\n\nOptions:\n"
+    "strling sort\n\nUsage:\n  strling sort [options] -o OUT.bam IN.bam\n  strling sort [options] -o OUT.bam IN.sam\n  aligner ... | strling sort [options] -o OUT.bam -\n\n"
+    "Arguments:\n  IN.bam           path to a bam file, in any order\n  IN.sam, -        SAM text instead, from a file or from stdin (told from a BAM by its first bytes)\n\nOptions:\n"
     "  -o, --output=OUT.bam       required; written through a temporary name, so a failed run leaves no file\n"
     "      --write-index          also write OUT.bam's index, built from the sort's own pass: no second read, inflate and scan of the file\n"
     "      --index-out=OUT.bai    where --write-index writes it (default: OUT.bam.bai; with --csi OUT.bam.csi)\n"
@@ -50,7 +57,8 @@ const char *USAGE =
     "  -m, --min-shift=N          with --csi: bases per window of the smallest bins = 2^N, N in [8, 24] (default: 14)\n"
     "      --windowed             sort a file larger than device memory: only 12 bytes a record stay on the device, and the file is read once\n"
     "                             more for every window of the output that the device can hold; the same bytes as without it.  With\n"
-    "                             --write-index the index costs a second read of the output (it is built as `strling bamindex OUT.bam` builds it)\n"
+    "                             --write-index the index costs a second read of the output (it is built as `strling bamindex OUT.bam` builds it).\n"
+    "                             Not with SAM input: a pipe cannot be read again\n"
     "      --deflate=host|device  host (default): zlib at its default level on the pool, as pull.  device: the GPU's compressor (about 1.15 x the bytes)\n"
     "  -D, --device=K             GPU to use (default: 0)\n"
     "  -v, --verbose              one JSON line on stderr\n  -h, --help                 Show this help\n";
@@ -135,23 +143,47 @@ struct Result {
   uint64_t records = 0, no_ref = 0, stream_bytes = 0, slabs = 0, out_bytes = 0;
   uint64_t windows = 0, window_bytes = 0;     // --windowed on the device: passes behind pass 0, bytes of the stream each finishes
   bool already_sorted = false;
+  uint64_t lines = 0, text_bytes = 0, host_finished = 0;
+  double sam_ms[4] = {0, 0, 0, 0};            // HIP-event time of the chunks' copies, line scans, size kernels and encodes
   const char *deflate = "zlib";
   uint32_t stored = 0;
   Seconds s;
 };
 
 // ---- the host path ---------------------------------------------------------------------------------------------------------------
-bool sort_on_host(const std::string &bam, const std::vector<uint8_t> &header, int32_t n_ref, bool core, SortOut &out, Result &R, Index &X, std::string &why, int &status) {
+// SAM text on the host: what the feed reads, line by line through sam_core.h's host function
+struct SamInput { SamFeed feed; SamHeader header; };
+
+bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8_t> &header, int32_t n_ref, bool core, SortOut &out, Result &R, Index &X, std::string &why, int &status) {
   auto t0 = Clock::now();
-  BamReader rd;
   std::string err;
   status = STRL_ERR_FORMAT;
-  if (!rd.open(bam, err)) { why = err.empty() ? "couldn't open bam" : err; return false; }
   std::vector<uint8_t> raw;
-  for (;;) {
-    const int64_t got = rd.read_raw(raw, 1 << 20, err);
-    if (got < 0) { why = err.empty() ? "malformed BAM (truncated file or invalid BGZF block)" : err; return false; }
-    if (!got) break;
+  if (sam) {
+    SamRefTable table;
+    table.build(sam->header.names.data(), sam->header.name_off.data(), n_ref, nullptr);      // (sam_header has refused a name that occurs twice)
+    const SamRefs refs = table.view();
+    std::vector<uint8_t> text(sam->feed.buffer_bytes());
+    for (;;) {
+      const int64_t got = sam->feed.next_chunk(text.data(), err);
+      if (got < 0) { why = err; return false; }
+      if (!got) break;
+      R.text_bytes += (uint64_t)got;
+      for (size_t q = 0; q < (size_t)got; ++R.lines) {
+        const size_t e = (size_t)(static_cast<const uint8_t *>(memchr(text.data() + q, '\n', (size_t)got - q)) - text.data());
+        std::string w;
+        if (sam_encode_line(text.data() + q, (uint32_t)(e - q), refs, raw, w)) { why = sam_refusal(R.lines + 1, w); return false; }
+        q = e + 1;
+      }
+    }
+  } else {
+    BamReader rd;
+    if (!rd.open(bam, err)) { why = err.empty() ? "couldn't open bam" : err; return false; }
+    for (;;) {
+      const int64_t got = rd.read_raw(raw, 1 << 20, err);
+      if (got < 0) { why = err.empty() ? "malformed BAM (truncated file or invalid BGZF block)" : err; return false; }
+      if (!got) break;
+    }
   }
   std::vector<uint64_t> at, key;
   for (size_t q = 0; q < raw.size();) {
@@ -230,20 +262,22 @@ bool sort_on_host(const std::string &bam, const std::vector<uint8_t> &header, in
 // ---- the device path -------------------------------------------------------------------------------------------------------------
 // windowed: `sort --windowed`.  Pass 0 keeps key and length of every record; the file is then read once more for every window of
 // the output stream, and each finished window goes through the piece loop the resident sort's whole stream goes through.
-bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::vector<uint8_t> &header, bool core, bool windowed, SortOut &out,
-                    Result &R, Index &X, std::string &why, int &status) {
+bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, SamInput *sam, const std::vector<uint8_t> &header, bool core, bool windowed,
+                    SortOut &out, Result &R, Index &X, std::string &why, int &status) {
   auto t0 = Clock::now();
   status = STRL_ERR_IO;
   BgzfFeed feed;
   std::string err;
-  if (!feed.open(bam, err)) { why = err.empty() ? "couldn't open bam" : "couldn't open bam: " + err; return false; }
+  if (!sam && !feed.open(bam, err)) { why = err.empty() ? "couldn't open bam" : "couldn't open bam: " + err; return false; }
   static const char *env_blocks = getenv("STRL_CHUNK_BLOCKS");     // tests: tiny chunks put records across pushes
-  const size_t auto_blocks = std::min<size_t>(16384, std::max<size_t>(2048, feed.file_bytes() / 16384 / 12));
+  const size_t auto_blocks = std::min<size_t>(16384, std::max<size_t>(2048, (sam ? 0 : feed.file_bytes()) / 16384 / 12));
   const size_t chunk_blocks = env_blocks && atoi(env_blocks) > 0 ? (size_t)atoi(env_blocks) : auto_blocks;
   const size_t chunk_bytes = std::max<size_t>((size_t)1 << 20, chunk_blocks * 20000);
   PinnedRing pins;
-  pins.alloc(3, chunk_blocks, chunk_bytes);
-  if (!pins.ok()) { why = "page-locked memory for the chunks"; pins.release(); return false; }
+  if (!sam) {
+    pins.alloc(3, chunk_blocks, chunk_bytes);
+    if (!pins.ok()) { why = "page-locked memory for the chunks"; pins.release(); return false; }
+  }
   strl_ctx *ctx = nullptr;
   auto fail = [&](int rc) { why = strl_last_error(); status = rc; (void)strl_bamsort_end(ctx); pins.release(); return false; };
   ThreadPool pool(std::min(decode_threads(), 12));
@@ -267,7 +301,34 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
     }
     return true;
   };
-  const bool read_ok = feed_pass(feed, [&]() -> int {
+  // SAM text: chunks of whole lines from the feed into two page-locked buffers, chunk ci + 1 read beside the push of chunk ci (the
+  // push returns when its text has been copied, so the buffer is free again)
+  auto sam_pass = [&]() {
+    const size_t cap = sam->feed.buffer_bytes();
+    uint8_t *tb[2] = {static_cast<uint8_t *>(strl_pinned_alloc(cap)), static_cast<uint8_t *>(strl_pinned_alloc(cap))};
+    if (!tb[0] || !tb[1]) { why = "page-locked memory for the chunks"; status = STRL_ERR_NOMEM; return false; }
+    int64_t got[2] = {0, 0};
+    std::string rerr[2];
+    got[0] = sam->feed.next_chunk(tb[0], rerr[0]);
+    if (!(ctx = get_ctx(why))) { status = STRL_ERR_NO_DEVICE; return false; }
+    const char *cap_mb = getenv("STRL_SORT_ARENA_MB");
+    const uint64_t limit = cap_mb && atof(cap_mb) > 0 ? (uint64_t)(atof(cap_mb) * 1048576.0) : 0;
+    const SamHeader &H = sam->header;
+    int rc = strl_bamsort_sam_begin(ctx, H.names.data(), H.name_off.data(), (int32_t)H.l_ref.size(), limit);
+    if (!rc) rc = strl_bamsort_sam_reserve(ctx, cap);
+    if (rc) return fail(rc);
+    for (uint64_t ci = 0;; ++ci) {
+      const int b = (int)(ci & 1);
+      if (got[b] < 0) { why = rerr[b]; status = STRL_ERR_FORMAT; (void)strl_bamsort_end(ctx); return false; }
+      if (!got[b]) break;
+      std::thread ahead([&, b] { got[b ^ 1] = sam->feed.next_chunk(tb[b ^ 1], rerr[b ^ 1]); });
+      rc = strl_bamsort_push_sam(ctx, tb[b], (uint64_t)got[b]);
+      ahead.join();
+      if (rc) return fail(rc);
+    }
+    return true;
+  };
+  const bool read_ok = sam ? sam_pass() : feed_pass(feed, [&]() -> int {
     if (!(ctx = get_ctx(why))) { status = STRL_ERR_NO_DEVICE; return 1; }
     const char *cap = getenv("STRL_SORT_ARENA_MB");                // tests of the refusal
     const uint64_t limit = cap && atof(cap) > 0 ? (uint64_t)(atof(cap) * 1048576.0) : 0;
@@ -284,6 +345,10 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
   if (rc) return fail(rc);
   R.s.sort = since(t0);
   R.records = info.n_records; R.no_ref = info.n_no_ref; R.stream_bytes = info.stream_bytes; R.already_sorted = info.already_sorted != 0; R.slabs = info.n_slabs;
+  if (sam) {
+    strl_bamsort_sam_figures f{};
+    if (!strl_bamsort_sam_info(ctx, &f)) { R.lines = f.lines; R.text_bytes = f.text_bytes; R.host_finished = f.host_finished; R.sam_ms[0] = f.copy_ms; R.sam_ms[1] = f.scan_ms; R.sam_ms[2] = f.size_ms; R.sam_ms[3] = f.encode_ms; }
+  }
   // pieces: the fetch of piece k + 1 on a thread beside the deflate / write of piece k
   const uint64_t total = info.stream_bytes;
   uint64_t piece = piece_bytes();
@@ -387,7 +452,7 @@ int sort_main(int argc, char **argv) {
   if (argc <= 2) { fputs(USAGE, stdout); return 0; }
   const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"deflate", 0, true}, {"device", 'D', true}, {"verbose", 'v', false},
                                        {"write-index", 0, false}, {"index-out", 0, true}, {"csi", 0, false}, {"min-shift", 'm', true}, {"windowed", 0, false}}, USAGE);
-  if (a.pos.size() != 1) quit("expected 1 argument (bam)\n%s", USAGE);
+  if (a.pos.size() != 1) quit("expected 1 argument (bam, sam or - for SAM text on stdin)\n%s", USAGE);
   if (!a.flag("output")) quit("[strling] sort: -o OUT.bam is required\n%s", USAGE);
   if (a.flag("index-out") && !a.flag("write-index")) quit("--index-out needs --write-index\n%s", USAGE);
   if (a.flag("csi") && !a.flag("write-index")) quit("--csi needs --write-index\n%s", USAGE);
@@ -397,13 +462,27 @@ int sort_main(int argc, char **argv) {
   const std::string bam = a.pos[0], out_path = a.get("output", ""), form = a.get("deflate", "host");
   if (form != "host" && form != "device") quit("--deflate must be host or device (got %s)", form.c_str());
   const bool core = form == "device";
-  if (CramFile::is_cram(bam)) quit("[strling] sort: %s is a CRAM; sorting one is out of scope: this command sorts a BAM", bam.c_str());
-  if (!file_exists(bam)) quit("couldn't open bam");
+  const bool from_stdin = bam == "-";
+  if (!from_stdin && CramFile::is_cram(bam)) quit("[strling] sort: %s is a CRAM; sorting one is out of scope: this command sorts a BAM", bam.c_str());
+  if (!from_stdin && !file_exists(bam)) quit("couldn't open bam");
   const auto t_all = Clock::now();
+  // the format, from the first bytes: BGZF magic is a BAM (from a file), `@` or anything else printable is SAM text
+  SamInput sam_in;
+  std::string sniff_err;
+  const SamFeed::Kind kind = sam_in.feed.open(bam, sniff_err);
+  if (kind == SamFeed::KIND_ERROR && from_stdin) quit("[strling] sort: %s (status %d)", sniff_err.c_str(), STRL_ERR_IO);
+  if (from_stdin && kind == SamFeed::KIND_GZIP) quit("[strling] sort: a BAM on stdin is not read; write it to a file (status %d)", STRL_ERR_ARG);
+  if (from_stdin && kind != SamFeed::KIND_SAM) quit("[strling] sort: stdin holds no SAM text (status %d)", STRL_ERR_FORMAT);
+  SamInput *sam = kind == SamFeed::KIND_SAM ? &sam_in : nullptr;
+  if (sam && a.flag("windowed")) quit("[strling] sort: --windowed reads its input once more for every window, and SAM text is read once (a pipe cannot be read again): sort a BAM in windows (status %d)", STRL_ERR_ARG);
   // the header, by the host reader, and the output's from it
   std::vector<uint8_t> header;
   int32_t n_ref = 0;
-  {
+  if (sam) {
+    std::string err;
+    if (!sam->feed.read_header(sam->header, err)) quit("[strling] sort: %s (status %d)", err.c_str(), STRL_ERR_FORMAT);
+    if (!bsort_header(sam->header.bam.data(), sam->header.bam.size(), header, &n_ref, nullptr, err)) quit("[strling] sort: %s (status %d)", err.c_str(), STRL_ERR_FORMAT);
+  } else {
     BamReader rd;
     std::string err;
     if (!rd.open(bam, err)) quit("[strling] sort: %s (status %d)", err.empty() ? "malformed BAM header (truncated file or invalid BGZF block)" : err.c_str(), STRL_ERR_FORMAT);
@@ -439,7 +518,7 @@ int sort_main(int argc, char **argv) {
   bool ok;
   if (on_host) {
     if (!out.open(out_path, why)) quit("[strling] sort: %s (status %d)", why.c_str(), STRL_ERR_IO);
-    ok = sort_on_host(bam, header, n_ref, core, out, R, X, why, status);
+    ok = sort_on_host(bam, sam, header, n_ref, core, out, R, X, why, status);
   } else {
     set_device0(a.get("device", ""));
     // the HIP runtime and the context come up on a thread beside the header walk, the page-locked buffers and the first chunk's read
@@ -450,7 +529,7 @@ int sort_main(int argc, char **argv) {
     auto get_ctx = [&](std::string &w) -> strl_ctx * { if (ctx_thread.joinable()) ctx_thread.join(); if (ctx_rc) w = ctx_err; return ctx_rc ? nullptr : ctx; };
     ok = out.open(out_path, why);
     if (!ok) status = STRL_ERR_IO;
-    else ok = sort_on_device(get_ctx, bam, header, core, windowed, out, R, X, why, status);
+    else ok = sort_on_device(get_ctx, bam, sam, header, core, windowed, out, R, X, why, status);
     if (ctx_thread.joinable()) ctx_thread.join();
     g_bg_init = nullptr;
   }
@@ -482,11 +561,14 @@ int sort_main(int argc, char **argv) {
     fprintf(stderr,
             "{\"command\": \"sort\", \"path\": \"%s\", \"records\": %llu, \"no_reference\": %llu, \"stream_bytes\": %llu, \"out_bytes\": %llu, \"already_sorted\": %s, \"slabs\": %llu, "
             "\"seconds\": %.3f, \"read_s\": %.3f, \"sort_s\": %.3f, \"gather_s\": %.3f, \"deflate_s\": %.3f, \"write_s\": %.3f, \"deflate\": \"%s\", \"stored\": %u, "
-            "\"index\": \"%s\", \"index_bytes\": %llu, \"index_chunks\": %llu, \"index_s\": %.3f, \"windows\": %llu, \"window_bytes\": %llu, \"window_s\": %.3f}\n",
+            "\"index\": \"%s\", \"index_bytes\": %llu, \"index_chunks\": %llu, \"index_s\": %.3f, \"windows\": %llu, \"window_bytes\": %llu, \"window_s\": %.3f, "
+            "\"input\": \"%s\", \"lines\": %llu, \"text_bytes\": %llu, \"host_finished\": %llu, \"sam_copy_ms\": %.3f, \"sam_scan_ms\": %.3f, \"sam_size_ms\": %.3f, "
+            "\"sam_encode_ms\": %.3f}\n",
             on_host ? "host" : "device", (unsigned long long)R.records, (unsigned long long)R.no_ref, (unsigned long long)R.stream_bytes, (unsigned long long)R.out_bytes,
             R.already_sorted ? "true" : "false", (unsigned long long)R.slabs, since(t_all), R.s.read, R.s.sort, R.s.gather, R.s.deflate, R.s.write, R.deflate, R.stored,
             !indexed ? "none" : X.min_shift >= 0 ? "csi" : "bai", (unsigned long long)(indexed ? index_bytes : 0), (unsigned long long)(indexed ? X.chunks : 0), X.s,
-            (unsigned long long)R.windows, (unsigned long long)R.window_bytes, R.s.window);
+            (unsigned long long)R.windows, (unsigned long long)R.window_bytes, R.s.window, sam ? "sam" : "bam", (unsigned long long)R.lines, (unsigned long long)R.text_bytes,
+            (unsigned long long)R.host_finished, R.sam_ms[0], R.sam_ms[1], R.sam_ms[2], R.sam_ms[3]);
   if (X.on && X.rc) {
     if (ctx) strl_ctx_destroy(ctx);
     quit("[strling] sort: sorted file written; index refused: %s (status %d)", X.why.c_str(), X.rc);

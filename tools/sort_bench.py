@@ -23,6 +23,13 @@ index must be the bytes `bamindex` wrote.  With --trace the traced run is `sort 
 --deflate forms, K runs each: wall time, pass 0's time and the time of a window's pass; the --deflate=host file must be the
 resident sort's.  With --trace, runs under the profiler of their own: one window with 16 / 32 / 64 lanes a record of the scatter
 (--lanes), then 2 and 4 windows: the time of bsort_scatter_kernel and bsort_dest_kernel, and the scatter's rate in TB/s of stream.
+    python tools/sort_bench.py --sam [--parent-cli PATH] [--pairs N] [--repeats K] [--lanes 16,32,64]
+--sam measures SAM text as the input: the same shuffled reads printed as SAM, sorted from a file and from a pipe (`cat IN.sam |
+strling sort -`), beside --parent-cli's (default: this build's) `sort` of the shuffled BAM and beside STRL_SORT=host on the same SAM;
+K runs each: wall time and the read phase.  Then, for every group size of --lanes (STRL_SORT_SAM_LANES), one run whose JSON line
+gives the HIP-event time of the chunks' copies and of the three kernels (line scan, size with the sums, encode): GB/s of text each,
+and the kernels' time a chunk beside that chunk's copy time.  The SAM outputs must be the BAM's sort with the bin field aside (the
+benchmark's BAM writer gives every record bin 4680).
 `samtools sort` is not on these machines: nothing here compares with it.  No threshold is asserted.
 """
 import argparse
@@ -176,6 +183,113 @@ def windowed_runs(a, cli, src, work, inflated):
             print(json.dumps({"trace": name, "windows": p, "kernels": pick, "error": err}), flush=True)
 
 
+def sam_copy(src, dst):
+    """the BAM at src printed as SAM text -> dst; -> text bytes.  Table look-ups a record, not a loop a base"""
+    raw = gzip.decompress(open(src, "rb").read())
+    l_text = struct.unpack_from("<i", raw, 4)[0]
+    at = 8 + l_text
+    n_ref = struct.unpack_from("<i", raw, at)[0]
+    at += 4
+    names = []
+    for _ in range(n_ref):
+        l = struct.unpack_from("<i", raw, at)[0]
+        names.append(raw[at + 4:at + 4 + l - 1])
+        at += 8 + l
+    code = b"=ACMGRSVTWYHKDBN"
+    two = np.array([code[b >> 4] | code[b & 15] << 8 for b in range(256)], np.uint16)
+    ops = b"MIDNSHP=X"
+    mv = memoryview(raw)
+    fixed = struct.Struct("<iiiBBHHHiiii")
+    sizes = {67: ("B", 1), 99: ("b", 1), 83: ("H", 2), 115: ("h", 2), 73: ("I", 4), 105: ("i", 4)}
+    total = 0
+    with open(dst, "wb", buffering=1 << 24) as f:
+        f.write(raw[8:8 + l_text])
+        total += l_text
+        while at < len(raw):
+            bs, tid, pos, l_name, mapq, _, n_cig, flag, l_seq, mtid, mpos, tlen = fixed.unpack_from(raw, at)
+            q = at + 36
+            qname = raw[q:q + l_name - 1]; q += l_name
+            cig = b"".join(b"%d%c" % (v >> 4, ops[v & 15]) for v in struct.unpack_from(f"<{n_cig}I", raw, q)) or b"*"; q += 4 * n_cig
+            seq = two[np.frombuffer(mv[q:q + (l_seq + 1) // 2], np.uint8)].tobytes()[:l_seq] or b"*"; q += (l_seq + 1) // 2
+            ql = np.frombuffer(mv[q:q + l_seq], np.uint8); q += l_seq
+            qual = b"*" if not l_seq or ql[0] == 255 else (ql + 33).tobytes()
+            tags = []
+            end = at + 4 + bs
+            while q < end:
+                t = raw[q + 2]
+                if t in sizes:
+                    fmt, sz = sizes[t]
+                    tags.append(b"%s:i:%d" % (raw[q:q + 2], struct.unpack_from("<" + fmt, raw, q + 3)[0])); q += 3 + sz
+                elif t == 90 or t == 72:
+                    e = raw.index(b"\0", q + 3)
+                    tags.append(raw[q:q + 2] + (b":Z:" if t == 90 else b":H:") + raw[q + 3:e]); q = e + 1
+                elif t == 65:
+                    tags.append(raw[q:q + 2] + b":A:" + raw[q + 3:q + 4]); q += 4
+                elif t == 102:
+                    tags.append(b"%s:f:%s" % (raw[q:q + 2], repr(float(np.float32(struct.unpack_from("<f", raw, q + 3)[0]))).encode())); q += 7
+                else:
+                    raise ValueError(f"tag type {chr(t)} is not printed here")
+            line = b"\t".join([qname, b"%d" % flag, names[tid] if tid >= 0 else b"*", b"%d" % (pos + 1), b"%d" % mapq, cig,
+                               b"*" if mtid < 0 else b"=" if mtid == tid else names[mtid], b"%d" % (mpos + 1), b"%d" % tlen, seq, qual] + tags) + b"\n"
+            f.write(line)
+            total += len(line)
+            at = end
+    return total
+
+
+def _zero_bins(path):
+    """the file's inflated stream with every record's bin field zeroed"""
+    raw = bytearray(gzip.decompress(open(path, "rb").read()))
+    at = 8 + struct.unpack_from("<i", raw, 4)[0]
+    n_ref = struct.unpack_from("<i", raw, at)[0]
+    at += 4
+    for _ in range(n_ref):
+        at += 8 + struct.unpack_from("<i", raw, at)[0]
+    while at < len(raw):
+        raw[at + 14:at + 16] = b"\0\0"
+        at += 4 + struct.unpack_from("<i", raw, at)[0]
+    return bytes(raw)
+
+
+def sam_runs(a, cli, src, work):
+    """SAM text from a file and from a pipe beside the BAM's sort and the host path; the kernels' rates for every group size"""
+    parent = a.parent_cli or cli
+    t0 = time.time()
+    sam = os.path.join(work, "shuffled.sam")
+    text_bytes = sam_copy(src, sam)
+    print(json.dumps({"sam_text_bytes": text_bytes, "print_s": round(time.time() - t0, 1)}), flush=True)
+    out = {t: os.path.join(work, t + ".bam") for t in ("sam_file", "sam_pipe", "bam_parent", "sam_host")}
+    keys = ("seconds", "read_s", "sort_s", "gather_s", "deflate_s", "write_s", "lines", "text_bytes", "host_finished", "sam_copy_ms", "sam_scan_ms", "sam_size_ms", "sam_encode_ms")
+    for k in range(a.repeats):
+        says, wall = _run([cli, "sort", "-v", "-o", out["sam_file"], sam])
+        print(json.dumps({"run": "SAM from a file", "repeat": k, "wall_s": wall, "says": {x: says.get(x) for x in keys}}), flush=True)
+        t = time.time()
+        r = subprocess.run(f"cat {sam} | {cli} sort -v -o {out['sam_pipe']} -", shell=True, capture_output=True, text=True, timeout=1500)
+        if r.returncode:
+            sys.stderr.write(r.stderr[-2000:]); sys.exit(r.returncode)
+        says = json.loads(r.stderr.strip().splitlines()[-1])
+        print(json.dumps({"run": "SAM from a pipe", "repeat": k, "wall_s": round(time.time() - t, 3), "says": {x: says.get(x) for x in keys}}), flush=True)
+        says, wall = _run([parent, "sort", "-v", "-o", out["bam_parent"], src])
+        print(json.dumps({"run": "parent sort of the BAM", "repeat": k, "wall_s": wall, "says": {x: says.get(x) for x in keys[:6]}}), flush=True)
+    says, wall = _run([cli, "sort", "-v", "-o", out["sam_host"], sam], dict(os.environ, STRL_SORT="host"))
+    print(json.dumps({"run": "STRL_SORT=host on the SAM", "wall_s": wall, "says": {x: says.get(x) for x in keys}}), flush=True)
+    same = open(out["sam_file"], "rb").read() == open(out["sam_pipe"], "rb").read() == open(out["sam_host"], "rb").read()
+    print(json.dumps({"check": "file, pipe and host path write one file", "ok": same,
+                      "the BAM's sort with the bin field aside": _zero_bins(out["sam_file"]) == _zero_bins(out["bam_parent"])}), flush=True)
+    for lanes in [x for x in a.lanes.split(",") if x]:
+        runs = []
+        for k in range(2):
+            says, wall = _run([cli, "sort", "-v", "-o", out["sam_file"], sam], dict(os.environ, STRL_SORT_SAM_LANES=lanes))
+            runs.append(says)
+        s = runs[-1]
+        chunks = max(1, -(-s["text_bytes"] // (32 << 20)))
+        gbs = lambda ms: round(s["text_bytes"] / ms / 1e6, 1) if ms else None
+        print(json.dumps({"kernels": "HIP-event time over all chunks, second run", "lanes_per_line": int(lanes), "text_bytes": s["text_bytes"], "read_s": s["read_s"],
+                          "copy_ms": s["sam_copy_ms"], "scan_ms": s["sam_scan_ms"], "size_ms": s["sam_size_ms"], "encode_ms": s["sam_encode_ms"],
+                          "GB_per_s_of_text": {"copy": gbs(s["sam_copy_ms"]), "scan": gbs(s["sam_scan_ms"]), "size": gbs(s["sam_size_ms"]), "encode": gbs(s["sam_encode_ms"])},
+                          "per_chunk_ms": {"kernels": round((s["sam_scan_ms"] + s["sam_size_ms"] + s["sam_encode_ms"]) / chunks, 3), "copy": round(s["sam_copy_ms"] / chunks, 3)}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--pairs", type=int, default=2 ** 20)
@@ -187,6 +301,7 @@ def main():
     ap.add_argument("--write-index", action="store_true")
     ap.add_argument("--parent-cli", default="")
     ap.add_argument("--windowed", action="store_true")
+    ap.add_argument("--sam", action="store_true", help="SAM text as the input, from a file and from a pipe, beside the BAM's sort")
     ap.add_argument("--window-mb", default="", help="with --windowed: comma-separated window sizes in MiB (default: the sizes that give 1, 2 and 4 windows)")
     a = ap.parse_args()
     t0 = time.time()
@@ -199,6 +314,10 @@ def main():
     print(json.dumps(base), flush=True)
     if a.write_index:
         write_index_runs(a, cli, src, work)
+        shutil.rmtree(work, ignore_errors=True)
+        return
+    if a.sam:
+        sam_runs(a, cli, src, work)
         shutil.rmtree(work, ignore_errors=True)
         return
     if a.windowed:

@@ -66,6 +66,31 @@ if command -v samtools > /dev/null 2>&1 && "$S" sort 2> /dev/null | grep -q -- -
   else
     echo "SKIP  sort_index   (needs a strling with sort --write-index)"
   fi
+  # sort of SAM text: the records strling encodes from SAM (csrc/sam_core.h) against the records `samtools view -b` makes of the same
+  # text, record for record through `samtools view` (which prints every field, the tags with their types) and as BAM bytes behind the
+  # header (bin included).  Never run: no machine this was built on had samtools or htslib.
+  if "$S" sort 2> /dev/null | grep -q -- "IN.sam"; then
+    samtools view -h "$T/sort_in.bam" > "$T/sort_in.sam" 2>> "$T/sort.log"
+    "$S" sort -o "$T/sort_sam_ours.bam" "$T/sort_in.sam" >> "$T/sort.log" 2>&1 || echo "      (sort: strling sort of SAM text exited non-zero, see $T/sort.log)"
+    samtools view --no-PG -b "$T/sort_in.sam" 2>> "$T/sort.log" | samtools sort --no-PG -o "$T/sort_sam_theirs.bam" - >> "$T/sort.log" 2>&1
+    samtools view "$T/sort_sam_ours.bam" > "$T/sort_sam_ours.sam" 2>> "$T/sort.log"; samtools view "$T/sort_sam_theirs.bam" > "$T/sort_sam_theirs.sam" 2>> "$T/sort.log"
+    check sort_sam "$T/sort_sam_ours.sam" "$T/sort_sam_theirs.sam" "SAM text encoded by strling sort gives the records samtools view -b gives"
+    cat "$T/sort_in.sam" | "$S" sort -o "$T/sort_sam_pipe.bam" - >> "$T/sort.log" 2>&1
+    check sort_sam_stdin "$T/sort_sam_pipe.bam" "$T/sort_sam_ours.bam" "SAM text on stdin sorts to the file's bytes"
+    python3 - "$T/sort_sam_ours.bam" "$T/sort_sam_theirs.bam" > "$T/sort_sam.cmp" 2>&1 <<'PY' && echo "PASS  sort_sam_bytes   (the records' bytes, bin included, are htslib's)" || { echo "FAIL  sort_sam_bytes   (see $T/sort_sam.cmp)"; fail=1; }
+import gzip, struct, sys
+def records(p):
+    raw = gzip.decompress(open(p, "rb").read())
+    at = 8 + struct.unpack_from("<i", raw, 4)[0]
+    n = struct.unpack_from("<i", raw, at)[0]; at += 4
+    for _ in range(n): at += 8 + struct.unpack_from("<i", raw, at)[0]
+    return raw[at:]
+a, b = records(sys.argv[1]), records(sys.argv[2])
+print(len(a), len(b)); sys.exit(0 if a == b else 1)
+PY
+  else
+    echo "SKIP  sort_sam   (needs a strling whose sort reads SAM text)"
+  fi
 else
   echo "SKIP  sort   (needs samtools and a strling with the sort command: the order stays checked against its own statement in tests/sort_bam_cases.py only)"
 fi
