@@ -563,7 +563,18 @@ uint64_t strl_bgzf_deflate_bound(uint64_t in_bytes, uint32_t block_bytes);
 /* strl_bgzf_deflate on the calling thread, without a device: the same rule (csrc/deflate_core.h), the same bytes, the same refusals. */
 int strl_bgzf_deflate_host(const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
                            uint32_t *n_stored);
-/* HIP-event time (ms) of the kernels of the last strl_bgzf_deflate call (copies excluded). */
+/* The same calls with the match rule named.  STRL_DEFLATE_FAST is the rule of the calls above and gives their bytes: one
+ * candidate per position, greedy.  STRL_DEFLATE_DENSE looks at up to 16 earlier positions with the same 4-byte hash within 16128
+ * bytes and parses one step lazily (csrc/deflate_core.h: DflDense): smaller members (zlib level 5 to 6's size), more kernel time.
+ * Any other mode is STRL_ERR_ARG.  Members, refusals and strl_bgzf_deflate_bound are those of the calls above; device and host
+ * give the same bytes for a mode. */
+#define STRL_DEFLATE_FAST 0
+#define STRL_DEFLATE_DENSE 1
+int strl_bgzf_deflate_mode(strl_ctx *ctx, int mode, const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap,
+                           uint64_t *out_bytes, uint32_t *csize, uint32_t *n_stored);
+int strl_bgzf_deflate_host_mode(int mode, const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+                                uint32_t *csize, uint32_t *n_stored);
+/* HIP-event time (ms) of the kernels of the last strl_bgzf_deflate / strl_bgzf_deflate_mode call (copies excluded). */
 int strl_ctx_deflate_ms(strl_ctx *ctx, double *ms);
 
 /* ---- `strling call`'s evidence reads on the device (replaces the per-bound `for aln in ibam.query(tid, left - window,
@@ -841,6 +852,8 @@ int strl_sweep_end(strl_ctx *ctx);
  *   strl_bamsort_fetch_bgzf the same bytes as BGZF members of 0xFF00 input bytes from the device compressor (the bytes
  *                           strl_bgzf_deflate gives for them), packed; off must be a multiple of 0xFF00; out_cap >=
  *                           strl_bgzf_deflate_bound(bytes, 0xFF00).  No EOF block.
+ *   strl_bamsort_deflate_mode  the rule of the fetch_bgzf calls that follow on this sort (STRL_DEFLATE_FAST, where it is never
+ *                           called, or STRL_DEFLATE_DENSE; else STRL_ERR_ARG); between strl_bamsort_begin and strl_bamsort_end.
  *   strl_bamsort_order      perm[j] = the input ordinal of the record of output rank j.
  *   strl_bamsort_info_now   the figures again, gather_ms summed over the fetches so far.
  *   strl_bamsort_end        gives the sort up (also after an error): what it had in flight has completed on return, arena and
@@ -862,6 +875,7 @@ int strl_bamsort_push(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, c
 int strl_bamsort_finish(strl_ctx *ctx, const uint8_t *header, uint64_t header_bytes, strl_bamsort_info *info);
 int strl_bamsort_fetch(strl_ctx *ctx, uint64_t off, uint64_t bytes, uint8_t *out);
 int strl_bamsort_fetch_bgzf(strl_ctx *ctx, uint64_t off, uint64_t bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *n_stored);
+int strl_bamsort_deflate_mode(strl_ctx *ctx, int mode);
 int strl_bamsort_order(strl_ctx *ctx, uint32_t *perm, uint64_t cap);
 int strl_bamsort_info_now(strl_ctx *ctx, strl_bamsort_info *info);
 int strl_bamsort_end(strl_ctx *ctx);

@@ -156,7 +156,8 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_front_index_begin", "strl_front_index_blocks", "strl_front_index_finish", "strl_bamindex_begin_csi", "strl_front_index_begin_csi",
            "strl_sweep_begin", "strl_sweep_reserve", "strl_sweep_push", "strl_sweep_finish", "strl_sweep_end",
            "strl_pull_select", "strl_pull_mates", "strl_pull_select_host", "strl_pull_counts_host", "strl_pull_mates_host", "strl_pull_order",
-           "strl_bgzf_deflate", "strl_bgzf_deflate_bound", "strl_bgzf_deflate_host", "strl_ctx_deflate_ms",
+           "strl_bgzf_deflate", "strl_bgzf_deflate_bound", "strl_bgzf_deflate_host", "strl_ctx_deflate_ms", "strl_bgzf_deflate_mode", "strl_bgzf_deflate_host_mode",
+           "strl_bamsort_deflate_mode",
            "strl_bamsort_begin", "strl_bamsort_reserve", "strl_bamsort_push", "strl_bamsort_finish", "strl_bamsort_fetch", "strl_bamsort_fetch_bgzf", "strl_bamsort_order",
            "strl_bamsort_info_now", "strl_bamsort_end", "strl_bamsort_key", "strl_bamsort_key_bits", "strl_bamsort_header",
            "strl_bamsort_index", "strl_bamsort_index_fetch", "strl_bamsort_voff", "strl_bamsort_members",
@@ -251,6 +252,9 @@ def load(build_if_missing=True):
     L.strl_ctx_inflate_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.strl_bgzf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint32)]
     L.strl_bgzf_deflate_host.argtypes = L.strl_bgzf_deflate.argtypes[1:]
+    L.strl_bgzf_deflate_mode.argtypes = [C.c_void_p, C.c_int] + L.strl_bgzf_deflate.argtypes[1:]
+    L.strl_bgzf_deflate_host_mode.argtypes = [C.c_int] + L.strl_bgzf_deflate.argtypes[1:]
+    L.strl_bamsort_deflate_mode.argtypes = [C.c_void_p, C.c_int]
     L.strl_bgzf_deflate_bound.argtypes = [C.c_uint64, C.c_uint32]
     L.strl_bgzf_deflate_bound.restype = C.c_uint64
     L.strl_ctx_deflate_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -1321,9 +1325,13 @@ class Context:
             self.L.strl_sweep_end(self.h)
         return res, {k: getattr(info, k) for k, _ in SweepInfo._fields_}
 
-    def bgzf_deflate(self, data, block=0xFF00, out=None):
-        """bytes -> (BGZF members back to back, without the EOF block; csize uint32[members]; members that went out stored), on the device (strl_bgzf_deflate)"""
-        return _bgzf_deflate(lambda *a: self.L.strl_bgzf_deflate(self.h, *a), data, block, out)
+    def bgzf_deflate(self, data, block=0xFF00, out=None, mode=None):
+        """bytes -> (BGZF members back to back, without the EOF block; csize uint32[members]; members that went out stored), on the
+        device (strl_bgzf_deflate).  mode = "fast" (the default's rule and bytes) or "dense" (strl_bgzf_deflate_mode)"""
+        if mode is None:
+            return _bgzf_deflate(lambda *a: self.L.strl_bgzf_deflate(self.h, *a), data, block, out)
+        m = _deflate_mode(mode)
+        return _bgzf_deflate(lambda *a: self.L.strl_bgzf_deflate_mode(self.h, m, *a), data, block, out)
 
     def deflate_ms(self):
         """kernel time (ms) of the last bgzf_deflate call"""
@@ -1686,9 +1694,25 @@ def bamsort_voff(member_off, stream_bytes, s):
     return int(v.value)
 
 
-def bgzf_deflate_host(data, block=0xFF00, out=None):
-    """Context.bgzf_deflate without a device: the same rule on the calling thread, the same bytes (strl_bgzf_deflate_host)"""
-    return _bgzf_deflate(load().strl_bgzf_deflate_host, data, block, out)
+DEFLATE_MODES = {"fast": 0, "dense": 1}        # STRL_DEFLATE_FAST, STRL_DEFLATE_DENSE
+
+
+def _deflate_mode(mode):
+    """the C value of a mode's name; an integer goes through as it is (the library refuses what it does not know)"""
+    if isinstance(mode, str):
+        if mode not in DEFLATE_MODES:
+            raise ValueError(f"bgzf_deflate: mode must be one of {sorted(DEFLATE_MODES)}, not {mode!r}")
+        return DEFLATE_MODES[mode]
+    return int(mode)
+
+
+def bgzf_deflate_host(data, block=0xFF00, out=None, mode=None):
+    """Context.bgzf_deflate without a device: the same rule on the calling thread, the same bytes (strl_bgzf_deflate_host;
+    with a mode, "fast" or "dense", strl_bgzf_deflate_host_mode)"""
+    if mode is None:
+        return _bgzf_deflate(load().strl_bgzf_deflate_host, data, block, out)
+    m = _deflate_mode(mode)
+    return _bgzf_deflate(lambda *a: load().strl_bgzf_deflate_host_mode(m, *a), data, block, out)
 
 
 def pull_select_host(raw, tile, base_off=0):

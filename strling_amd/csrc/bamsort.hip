@@ -329,6 +329,7 @@ struct strl_bsort {
   strl_bai *index = nullptr;                   // `sort --write-index`: the index builder over the sorted records (bamindex.hip strl_bamsort_index)
   // `sort --windowed`: no arena, no src; behind the finish only dest[ordinal] and len[ordinal] stay
   bool windowed = false;
+  int deflate_mode = STRL_DEFLATE_FAST;        // the rule of strl_bamsort_fetch_bgzf (strl_bamsort_deflate_mode)
   DevBuf dest, window, wstate;
   BsortWinState *h_wstate = nullptr;           // pinned
   std::vector<uint8_t> header;                 // the output's header bytes: every window that holds some gets them again
@@ -911,11 +912,18 @@ extern "C" int strl_bamsort_fetch_bgzf(strl_ctx *c, uint64_t off, uint64_t bytes
   if (!bytes) return STRL_OK;
   STRL_HIP(hipSetDevice(c->device));
   strl_bsort *B = c->bsort;
-  if (B->windowed) return bgzf_deflate_device(c, B->window.as<uint8_t>() + (off - B->win_lo), bytes, BSORT_BLK, out, out_cap, out_bytes, nullptr, n_stored);
+  if (B->windowed) return bgzf_deflate_device(c, B->deflate_mode, B->window.as<uint8_t>() + (off - B->win_lo), bytes, BSORT_BLK, out, out_cap, out_bytes, nullptr, n_stored);
   if ((rc = bsort_gather(c, B, off, off + bytes))) return rc;
-  rc = bgzf_deflate_device(c, B->piece.as<uint8_t>(), bytes, BSORT_BLK, out, out_cap, out_bytes, nullptr, n_stored);      // (waits for the stream)
+  rc = bgzf_deflate_device(c, B->deflate_mode, B->piece.as<uint8_t>(), bytes, BSORT_BLK, out, out_cap, out_bytes, nullptr, n_stored);      // (waits for the stream)
   if (!rc) bsort_gather_time(B);
   return rc;
+}
+
+extern "C" int strl_bamsort_deflate_mode(strl_ctx *c, int mode) {
+  if (!c || !c->bsort) { set_error("strl_bamsort_deflate_mode without strl_bamsort_begin"); return STRL_ERR_ARG; }
+  if (mode != STRL_DEFLATE_FAST && mode != STRL_DEFLATE_DENSE) { set_error("strl_bamsort_deflate_mode: mode %d is neither STRL_DEFLATE_FAST nor STRL_DEFLATE_DENSE", mode); return STRL_ERR_ARG; }
+  c->bsort->deflate_mode = mode;
+  return STRL_OK;
 }
 
 extern "C" int strl_bamsort_order(strl_ctx *c, uint32_t *perm, uint64_t cap) {

@@ -2775,11 +2775,11 @@ static bool write_bgzf(const std::string &path, const std::vector<uint8_t> &payl
   return write_members(path, blocks, why);
 }
 
-// --deflate=device: the output's members from the BGZF compressor of deflate.hip on pull's context, at most `batch` bytes of
+// --deflate=device|dense: the output's members from the BGZF compressor of deflate.hip on pull's context, at most `batch` bytes of
 // payload a call (whole blocks of 0xFF00, so the cuts fall where one call's would); from its host twin -- the same bytes -- when
-// there is no context or a call runs out of device memory.
+// there is no context or a call runs out of device memory.  `mode` is the compressor's rule (STRL_DEFLATE_FAST / _DENSE).
 struct DeflateStats { const char *form = "zlib"; uint32_t stored = 0; double kernel_ms = 0; };
-static bool write_bgzf_core(const std::string &path, const std::vector<uint8_t> &payload, strl_ctx *ctx, bool verbose, DeflateStats &D, std::string &why) {
+static bool write_bgzf_core(const std::string &path, const std::vector<uint8_t> &payload, strl_ctx *ctx, int mode, bool verbose, DeflateStats &D, std::string &why) {
   const uint64_t BLK = 0xFF00;
   // (STRL_DEFLATE_BATCH_MB: a smaller cut, fractions allowed, for tests of the seam between two calls)
   const double mb = getenv("STRL_DEFLATE_BATCH_MB") ? atof(getenv("STRL_DEFLATE_BATCH_MB")) : 128.0;
@@ -2796,7 +2796,7 @@ static bool write_bgzf_core(const std::string &path, const std::vector<uint8_t> 
     uint32_t stored = 0;
     int rc = STRL_ERR_NOMEM;
     if (on_device) {
-      rc = strl_bgzf_deflate(ctx, payload.data() + off, len, (uint32_t)BLK, out.data() + at, out.size() - at, &got, nullptr, &stored);
+      rc = strl_bgzf_deflate_mode(ctx, mode, payload.data() + off, len, (uint32_t)BLK, out.data() + at, out.size() - at, &got, nullptr, &stored);
       if (rc == STRL_ERR_NOMEM) {
         on_device = false;
         if (verbose) fprintf(stderr, "[strling] pull: the device has no memory for the output's deflate (%s), deflating on the host\n", strl_last_error());
@@ -2807,14 +2807,14 @@ static bool write_bgzf_core(const std::string &path, const std::vector<uint8_t> 
         D.kernel_ms += ms;
       }
     }
-    if (rc == STRL_ERR_NOMEM && (rc = strl_bgzf_deflate_host(payload.data() + off, len, (uint32_t)BLK, out.data() + at, out.size() - at, &got, nullptr, &stored)) != STRL_OK) {
+    if (rc == STRL_ERR_NOMEM && (rc = strl_bgzf_deflate_host_mode(mode, payload.data() + off, len, (uint32_t)BLK, out.data() + at, out.size() - at, &got, nullptr, &stored)) != STRL_OK) {
       why = std::string("deflate: ") + strl_last_error();
       return false;
     }
     at += got;
     D.stored += stored;
   }
-  D.form = on_device ? "device" : "core-host";
+  D.form = mode == STRL_DEFLATE_DENSE ? (on_device ? "device-dense" : "core-host-dense") : on_device ? "device" : "core-host";
   out.resize((size_t)at);
   return write_members(path, pieces, why);
 }
@@ -2825,15 +2825,16 @@ static int pull_main(int argc, char **argv) {
       "  region           NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive)\n\nOptions:\n"
       "  -o, --output-bam=OUT.bam   path to output bam (default: extracted.bam)\n  -L, --regions=BED          regions as BED rows: chrom start end\n"
       "  -f, --fasta=FASTA          accepted for the reference's command line; a bam needs none\n"
-      "      --deflate=host|device  who compresses the output.  host (default): zlib at its default level.  device: the GPU's BGZF\n"
-      "                             compressor, whose greedy parse gives about zlib level 1's bytes; level 6 gives 0.86 of those,\n"
-      "                             so the file is about 1.15 x as large (same records)\n"
+      "      --deflate=host|device|dense  who compresses the output.  host (default): zlib at its default level.  device: the GPU's\n"
+      "                             BGZF compressor, whose greedy parse gives about zlib level 1's bytes; level 6 gives 0.86 of those,\n"
+      "                             so the file is about 1.15 x as large (same records).  dense: the GPU's compressor with its\n"
+      "                             chained, lazy match search: a file of the default's size class, more kernel time than device\n"
       "  -v, --verbose\n  -h, --help                 Show this help\n";
   if (argc <= 2) { fputs(usage, stdout); return 0; }
   const Args a = parse(argc, argv, 2, {{"output-bam", 'o', true}, {"regions", 'L', true}, {"fasta", 'f', true}, {"verbose", 'v', false}, {"deflate", 0, true}}, usage);
   if (a.pos.empty()) quit("expected a bam\n%s", usage);
   const std::string deflate = a.get("deflate", "host");
-  if (deflate != "host" && deflate != "device") quit("--deflate must be host or device\n%s", usage);
+  if (deflate != "host" && deflate != "device" && deflate != "dense") quit("--deflate must be host or device, or dense (the device with its dense rule)\n%s", usage);
   const std::string bam = a.pos[0], out_path = a.get("output-bam", "extracted.bam");
   const bool verbose = a.flag("verbose");
   if (!file_exists(bam)) quit("could not open bam");                                                   // :41
@@ -3112,10 +3113,10 @@ static int pull_main(int argc, char **argv) {
   }
   std::string why;
   DeflateStats DS;
-  if (deflate == "device") {
+  if (deflate != "host") {
     if (!ctx && verbose)
       fprintf(stderr, "[strling] pull: deflating the output on the host (%s)\n", mode && !strcmp(mode, "host") ? "STRL_PULL=host" : strl_device_count() > 0 ? "no context" : "no device");
-    if (!write_bgzf_core(out_path, payload, ctx, verbose, DS, why)) quit("couldn't open output bam: %s", why.c_str());
+    if (!write_bgzf_core(out_path, payload, ctx, deflate == "dense" ? STRL_DEFLATE_DENSE : STRL_DEFLATE_FAST, verbose, DS, why)) quit("couldn't open output bam: %s", why.c_str());
   } else if (!write_bgzf(out_path, payload, pool, why)) quit("couldn't open output bam: %s", why.c_str());       // :72-73
   if (verbose)
     fprintf(stderr,

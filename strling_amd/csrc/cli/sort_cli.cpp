@@ -59,7 +59,8 @@ const char *USAGE =
     "                             more for every window of the output that the device can hold; the same bytes as without it.  With\n"
     "                             --write-index the index costs a second read of the output (it is built as `strling bamindex OUT.bam` builds it).\n"
     "                             Not with SAM input: a pipe cannot be read again\n"
-    "      --deflate=host|device  host (default): zlib at its default level on the pool, as pull.  device: the GPU's compressor (about 1.15 x the bytes)\n"
+    "      --deflate=host|device|dense  host (default): zlib at its default level on the pool, as pull.  device: the GPU's compressor (about\n"
+    "                             1.15 x the bytes).  dense: the GPU's compressor with its chained, lazy match search (the default's size class)\n"
     "  -D, --device=K             GPU to use (default: 0)\n"
     "  -v, --verbose              one JSON line on stderr\n  -h, --help                 Show this help\n";
 
@@ -96,8 +97,9 @@ struct SortOut {
   void drop() { if (f) { fclose(f); f = nullptr; } if (!tmp.empty()) unlink(tmp.c_str()); }
 };
 
-// the members of a piece of the stream (whole 0xFF00 blocks but for the stream's last), on the pool: zlib, or the compressor's host twin
-bool deflate_piece(const uint8_t *p, size_t n, bool core, ThreadPool &pool, std::vector<uint8_t> &out, uint32_t &stored, std::string &why) {
+// the members of a piece of the stream (whole 0xFF00 blocks but for the stream's last), on the pool: zlib, or the compressor's host
+// twin with the rule `mode` (STRL_DEFLATE_FAST / _DENSE)
+bool deflate_piece(const uint8_t *p, size_t n, bool core, int mode, ThreadPool &pool, std::vector<uint8_t> &out, uint32_t &stored, std::string &why) {
   const size_t nb = (n + BSORT_BLK - 1) / BSORT_BLK;
   std::vector<std::vector<uint8_t>> blocks(nb);
   std::vector<uint32_t> st(nb, 0);
@@ -108,7 +110,7 @@ bool deflate_piece(const uint8_t *p, size_t n, bool core, ThreadPool &pool, std:
     if (!core) { bad[k] = !bgzf_member_zlib(src, len, blocks[k]); return; }
     blocks[k].resize((size_t)strl_bgzf_deflate_bound(len, BSORT_BLK));
     uint64_t got = 0;
-    bad[k] = strl_bgzf_deflate_host(src, len, BSORT_BLK, blocks[k].data(), blocks[k].size(), &got, nullptr, &st[k]) != 0;
+    bad[k] = strl_bgzf_deflate_host_mode(mode, src, len, BSORT_BLK, blocks[k].data(), blocks[k].size(), &got, nullptr, &st[k]) != 0;
     blocks[k].resize((size_t)got);
   });
   out.clear();
@@ -154,7 +156,7 @@ struct Result {
 // SAM text on the host: what the feed reads, line by line through sam_core.h's host function
 struct SamInput { SamFeed feed; SamHeader header; };
 
-bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8_t> &header, int32_t n_ref, bool core, SortOut &out, Result &R, Index &X, std::string &why, int &status) {
+bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8_t> &header, int32_t n_ref, bool core, int mode, SortOut &out, Result &R, Index &X, std::string &why, int &status) {
   auto t0 = Clock::now();
   std::string err;
   status = STRL_ERR_FORMAT;
@@ -232,14 +234,14 @@ bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8
     }
     R.s.gather += since(t0);
     t0 = Clock::now();
-    if (!deflate_piece(buf.data(), buf.size(), core, pool, members, R.stored, why)) return false;
+    if (!deflate_piece(buf.data(), buf.size(), core, mode, pool, members, R.stored, why)) return false;
     R.s.deflate += since(t0);
     t0 = Clock::now();
     if (!out.put(members.data(), members.size(), why)) return false;
     R.out_bytes += members.size();
     R.s.write += since(t0);
   }
-  R.deflate = core ? "core-host" : "zlib";
+  R.deflate = !core ? "zlib" : mode == STRL_DEFLATE_DENSE ? "core-host-dense" : "core-host";
   if (X.on) {                                                   // one pass over the sorted records (bamindex_host.cpp)
     t0 = Clock::now();
     out.member_off.push_back(out.at);                           // the EOF block
@@ -262,7 +264,7 @@ bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8
 // ---- the device path -------------------------------------------------------------------------------------------------------------
 // windowed: `sort --windowed`.  Pass 0 keeps key and length of every record; the file is then read once more for every window of
 // the output stream, and each finished window goes through the piece loop the resident sort's whole stream goes through.
-bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, SamInput *sam, const std::vector<uint8_t> &header, bool core, bool windowed,
+bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, SamInput *sam, const std::vector<uint8_t> &header, bool core, int mode, bool windowed,
                     SortOut &out, Result &R, Index &X, std::string &why, int &status) {
   auto t0 = Clock::now();
   status = STRL_ERR_IO;
@@ -344,6 +346,7 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
   int rc = strl_bamsort_finish(ctx, header.data(), header.size(), &info);
   if (rc) return fail(rc);
   R.s.sort = since(t0);
+  if (core && (rc = strl_bamsort_deflate_mode(ctx, mode))) return fail(rc);      // the rule of every fetch_bgzf below
   R.records = info.n_records; R.no_ref = info.n_no_ref; R.stream_bytes = info.stream_bytes; R.already_sorted = info.already_sorted != 0; R.slabs = info.n_slabs;
   if (sam) {
     strl_bamsort_sam_figures f{};
@@ -395,7 +398,7 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
       if (ok && !core) {
         t0 = Clock::now();
         status = STRL_ERR_IO;
-        ok = deflate_piece(p, n, false, zpool, members, R.stored, why);
+        ok = deflate_piece(p, n, false, mode, zpool, members, R.stored, why);
         p = members.data(); n = members.size();
         R.s.deflate += since(t0);
       } else if (ok) R.stored += F.stored;
@@ -428,7 +431,7 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
     }
     if (core) { R.s.deflate = R.s.gather; R.s.gather = 0; }      // (a fetch of a window's piece is the compressor's run and its copy)
   }
-  R.deflate = core ? "device" : "zlib";
+  R.deflate = !core ? "zlib" : mode == STRL_DEFLATE_DENSE ? "device-dense" : "device";
   if (X.on && !windowed) {                                      // the records, their order and their offsets are still on the device
     t0 = Clock::now();
     out.member_off.push_back(out.at);                           // the EOF block
@@ -460,8 +463,9 @@ int sort_main(int argc, char **argv) {
   X.on = a.flag("write-index");
   X.min_shift = csi_min_shift(a, USAGE);
   const std::string bam = a.pos[0], out_path = a.get("output", ""), form = a.get("deflate", "host");
-  if (form != "host" && form != "device") quit("--deflate must be host or device (got %s)", form.c_str());
-  const bool core = form == "device";
+  if (form != "host" && form != "device" && form != "dense") quit("--deflate must be host or device, or dense (the device with its dense rule) (got %s)", form.c_str());
+  const bool core = form != "host";
+  const int mode = form == "dense" ? STRL_DEFLATE_DENSE : STRL_DEFLATE_FAST;
   const bool from_stdin = bam == "-";
   if (!from_stdin && CramFile::is_cram(bam)) quit("[strling] sort: %s is a CRAM; sorting one is out of scope: this command sorts a BAM", bam.c_str());
   if (!from_stdin && !file_exists(bam)) quit("couldn't open bam");
@@ -518,7 +522,7 @@ int sort_main(int argc, char **argv) {
   bool ok;
   if (on_host) {
     if (!out.open(out_path, why)) quit("[strling] sort: %s (status %d)", why.c_str(), STRL_ERR_IO);
-    ok = sort_on_host(bam, sam, header, n_ref, core, out, R, X, why, status);
+    ok = sort_on_host(bam, sam, header, n_ref, core, mode, out, R, X, why, status);
   } else {
     set_device0(a.get("device", ""));
     // the HIP runtime and the context come up on a thread beside the header walk, the page-locked buffers and the first chunk's read
@@ -529,7 +533,7 @@ int sort_main(int argc, char **argv) {
     auto get_ctx = [&](std::string &w) -> strl_ctx * { if (ctx_thread.joinable()) ctx_thread.join(); if (ctx_rc) w = ctx_err; return ctx_rc ? nullptr : ctx; };
     ok = out.open(out_path, why);
     if (!ok) status = STRL_ERR_IO;
-    else ok = sort_on_device(get_ctx, bam, sam, header, core, windowed, out, R, X, why, status);
+    else ok = sort_on_device(get_ctx, bam, sam, header, core, mode, windowed, out, R, X, why, status);
     if (ctx_thread.joinable()) ctx_thread.join();
     g_bg_init = nullptr;
   }

@@ -209,8 +209,8 @@ struct strl_ctx : TailSet, HeadSet {
   strl_assign_info as_info{};
 };
 
-// deflate.hip: strl_bgzf_deflate over input that lies on the device already (bamsort.hip's gathered pieces); the same kernels, the same bytes
-namespace strl { int bgzf_deflate_device(strl_ctx *c, const uint8_t *d_in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
+// deflate.hip: strl_bgzf_deflate_mode over input that lies on the device already (bamsort.hip's gathered pieces); the same kernels, the same bytes
+namespace strl { int bgzf_deflate_device(strl_ctx *c, int mode, const uint8_t *d_in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
                                          uint32_t *n_stored); }
 // pair.hip: enqueue the device pair logic behind a scoring pass of the same batch
 int strl_pair_order(strl_ctx *c, hipStream_t on_stream = nullptr);   // nullptr = the main stream (after a side_join)

@@ -1,6 +1,7 @@
 // deflate.hip -- the BGZF compressor on the GPU (gfx950): the output side of `strling pull --deflate=device`
 // (extract_region.nim:70-80 writes its BAM through htslib, i.e. zlib on the host).
 //
+//   deflate_dense_kernel : the same with the dense rule (DflDense: chains in a head table and a ring of links, ~125 KB of LDS)
 //   deflate_kernel : ONE WORKGROUP of 256 per BGZF block of <= 0xFF00 input bytes, the whole rule of deflate_core.h with the
 //                    block's bytes, the hash table, the histograms and the code tables in LDS (DflWork: ~107 KB, one
 //                    workgroup per CU).  The tokens of the greedy parse go to a scratch in HBM, one slice per workgroup; the
@@ -19,6 +20,7 @@ constexpr uint32_t DFL_MAX_GRID = 512;          // workgroups of a launch (each 
 
 struct DflGroup {
   static constexpr uint32_t N = DFL_THREADS;
+  static constexpr bool IN_ORDER = false;      // lanes side by side
   __device__ __forceinline__ uint32_t tid() const { return threadIdx.x; }
   __device__ __forceinline__ void sync() const { __syncthreads(); }
   __device__ __forceinline__ void max_u32(uint32_t *p, uint32_t v) const { atomicMax(p, v); }
@@ -38,8 +40,9 @@ struct DeflateParams {
   const DflCrc *crc;
 };
 
-__global__ __launch_bounds__(DFL_THREADS) void deflate_kernel(DeflateParams P) {
-  __shared__ DflWork W;
+template <class Rule>
+__device__ __forceinline__ void deflate_blocks(const DeflateParams &P) {
+  __shared__ DflWorkT<Rule> W;
   const DflGroup T;
   for (uint32_t k = blockIdx.x; k < P.n_blocks; k += gridDim.x) {
     const uint64_t off = (uint64_t)k * P.block_bytes;
@@ -52,6 +55,8 @@ __global__ __launch_bounds__(DFL_THREADS) void deflate_kernel(DeflateParams P) {
     __syncthreads();
   }
 }
+__global__ __launch_bounds__(DFL_THREADS) void deflate_kernel(DeflateParams P) { deflate_blocks<DflFast>(P); }
+__global__ __launch_bounds__(DFL_THREADS) void deflate_dense_kernel(DeflateParams P) { deflate_blocks<DflDense>(P); }
 
 __global__ __launch_bounds__(256) void deflate_pack_kernel(const uint8_t *slots, uint64_t stride, const uint32_t *csize, const uint64_t *at, uint32_t n_blocks, uint8_t *out,
                                                            uint64_t out_bytes) {
@@ -78,15 +83,27 @@ static int deflate_refusal(int rc, uint64_t in_bytes, uint32_t block_bytes, uint
   return rc;
 }
 
+static bool deflate_mode_ok(int mode) {
+  if (mode == STRL_DEFLATE_FAST || mode == STRL_DEFLATE_DENSE) return true;
+  set_error("bgzf deflate: mode %d is neither STRL_DEFLATE_FAST nor STRL_DEFLATE_DENSE", mode);
+  return false;
+}
+
 extern "C" int strl_bgzf_deflate_host(const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
                                       uint32_t *n_stored) {
   return deflate_refusal(dfl_deflate_host(in, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored), in_bytes, block_bytes, out_cap);
 }
+extern "C" int strl_bgzf_deflate_host_mode(int mode, const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+                                           uint32_t *csize, uint32_t *n_stored) {
+  if (!deflate_mode_ok(mode)) return STRL_ERR_ARG;
+  return deflate_refusal(dfl_deflate_host_mode(mode, in, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored), in_bytes, block_bytes, out_cap);
+}
 
 // strl_bgzf_deflate; on_device: `in` lies on the context's device already (written on its stream): no copy in
-static int deflate_run(strl_ctx *c, const uint8_t *in, bool on_device, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+static int deflate_run(strl_ctx *c, int mode, const uint8_t *in, bool on_device, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
                        uint32_t *csize, uint32_t *n_stored) {
   if (!c) { set_error("null argument"); return STRL_ERR_ARG; }
+  if (!deflate_mode_ok(mode)) return STRL_ERR_ARG;
   if (block_bytes < 1u || block_bytes > DFL_MAX_BLOCK || !out_bytes || (in_bytes && (!in || !out))) return deflate_refusal(STRL_ERR_ARG, in_bytes, block_bytes, out_cap);
   if (out_cap < dfl_bound(in_bytes, block_bytes)) return deflate_refusal(STRL_ERR_CAPACITY, in_bytes, block_bytes, out_cap);
   *out_bytes = 0;
@@ -117,7 +134,8 @@ static int deflate_run(strl_ctx *c, const uint8_t *in, bool on_device, uint64_t 
   if (!on_device && (he = hipMemcpyAsync(c->dfl_in.p, in, in_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(he, "copy in");
   DeflateParams P{on_device ? in : c->dfl_in.as<uint8_t>(), in_bytes, block_bytes, nb, c->dfl_tok.as<uint32_t>(), c->dfl_slots.as<uint8_t>(), stride, d_csize, c->dfl_crc.as<DflCrc>()};
   (void)hipEventRecord(ev[0], st);
-  hipLaunchKernelGGL(deflate_kernel, dim3(grid), dim3(DFL_THREADS), 0, st, P);
+  if (mode == STRL_DEFLATE_DENSE) hipLaunchKernelGGL(deflate_dense_kernel, dim3(grid), dim3(DFL_THREADS), 0, st, P);
+  else hipLaunchKernelGGL(deflate_kernel, dim3(grid), dim3(DFL_THREADS), 0, st, P);
   if ((he = hipGetLastError()) != hipSuccess) return fail(he, "deflate_kernel");
   (void)hipEventRecord(ev[1], st);
   std::vector<uint32_t> cs(nb);
@@ -155,11 +173,15 @@ static int deflate_run(strl_ctx *c, const uint8_t *in, bool on_device, uint64_t 
 
 extern "C" int strl_bgzf_deflate(strl_ctx *c, const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
                                  uint32_t *csize, uint32_t *n_stored) {
-  return deflate_run(c, in, false, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
+  return deflate_run(c, STRL_DEFLATE_FAST, in, false, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
 }
-int strl::bgzf_deflate_device(strl_ctx *c, const uint8_t *d_in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
-                              uint32_t *n_stored) {
-  return deflate_run(c, d_in, true, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
+extern "C" int strl_bgzf_deflate_mode(strl_ctx *c, int mode, const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap,
+                                      uint64_t *out_bytes, uint32_t *csize, uint32_t *n_stored) {
+  return deflate_run(c, mode, in, false, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
+}
+int strl::bgzf_deflate_device(strl_ctx *c, int mode, const uint8_t *d_in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+                              uint32_t *csize, uint32_t *n_stored) {
+  return deflate_run(c, mode, d_in, true, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
 }
 
 // HIP-event time (ms) of the kernels of the last strl_bgzf_deflate call on this context (copies excluded).

@@ -14,6 +14,8 @@
 //   - the CRC-32 is linear over GF(2) (bgzf.hip has the argument): slices may be dealt to the lanes in any way.
 // The DEFLATE block is dynamic Huffman (BTYPE=10) with the run-length symbols 16 to 18 in its header; when that form would be no
 // smaller than the stored one (BTYPE=00: 5 + n bytes) the block is stored.  Either way a member is at most n + 31 bytes.
+// Two match rules share everything behind the tokens: DflFast (the text above: one candidate, a batch old, greedy) and DflDense
+// (chains of depth 16 in a window of 16128 with a one-step lazy parse; DESIGN.md 23.1, stated at the struct below).
 // The same source compiles for the host without HIP (tests/emu/deflate_emu.cpp, tests/emu/deflate_cases_main.cpp: a
 // stand-alone program under AddressSanitizer and UBSan).  No wave intrinsics for that reason.
 #pragma once
@@ -60,11 +62,12 @@ inline void dfl_crc_make(DflCrc &T) {
     }
 }
 
-// Everything a team needs for one block (the device keeps it in LDS: ~107 KB of the CU's 160 KB)
-struct DflWork {
+// Everything a team needs for one block (the device keeps it in LDS: ~107 KB of the CU's 160 KB with DflFast's tables, ~125 KB
+// with DflDense's)
+template <class Rule>
+struct DflWorkT {
   uint32_t buf[DFL_BUF_WORDS];          // the block's bytes; after the parse, the bits of the dynamic form
-  uint32_t tab[1u << DFL_HASH_BITS];    // hash of 4 bytes -> 1 + the largest inserted position with it (0: none)
-  uint32_t cand[DFL_BATCH];             // the batch's candidates: length << 16 | distance, 0 = no match
+  typename Rule::Search s;              // the match rule's tables
   uint32_t part[DFL_BATCH];             // per-lane sums of the emit pass
   uint32_t lit_hist[288], dist_hist[32], cl_hist[20];
   uint16_t lit_code[288], dist_code[32], cl_code[20];      // bit-reversed: ready to be OR-ed in
@@ -76,10 +79,14 @@ struct DflWork {
   DflCrc crc;
   uint32_t ntok, n_cl, hlit, hdist, hclen, header_bits, total_bits, crc_acc, dynamic;
 };
+struct DflFast;
+struct DflDense;
+using DflWork = DflWorkT<DflFast>;
 
 // a team of one: the host twin.  (deflate.hip has the workgroup.)
 struct DflSerial {
   static constexpr uint32_t N = 1;
+  static constexpr bool IN_ORDER = true;       // its loops visit a batch's positions in ascending order
   DFL_FN uint32_t tid() const { return 0; }
   DFL_FN void sync() const {}
   DFL_FN void max_u32(uint32_t *p, uint32_t v) const { if (*p < v) *p = v; }
@@ -140,8 +147,8 @@ DFL_FN void dfl_put(const Team &T, uint32_t *buf, uint32_t at, uint32_t v, uint3
 // length is taken away and the longest shorter code is made one bit longer with a sibling beside it (the Kraft sum falls by
 // 2^-limit each time, the number of codes stays).  The lengths, longest first, go to the symbols in the order above.
 // The team must have made hist[] visible (a sync) before the call; len[] is visible to all after it.
-template <class Team>
-DFL_FN void dfl_code_lengths(const Team &T, DflWork &W, const uint32_t *hist, uint32_t nsym, uint32_t limit, uint8_t *len) {
+template <class Team, class Work>
+DFL_FN void dfl_code_lengths(const Team &T, Work &W, const uint32_t *hist, uint32_t nsym, uint32_t limit, uint8_t *len) {
   const uint32_t tid = T.tid();
   if (nsym > 288u) nsym = 288u;
   for (uint32_t s = tid; s < nsym; s += Team::N) {
@@ -214,17 +221,190 @@ DFL_FN uint32_t dfl_cl_order(uint32_t i) {
   return o[i < 19u ? i : 18u];
 }
 
+// One token of lane 0's parse at `pos`, c = length << 16 | distance of the match taken there or 0 for the literal b[pos]:
+// counted in the histograms, written to tok[nt] (nt < n); returns the input bytes it covers.
+template <class Work>
+DFL_FN uint32_t dfl_token(Work &W, const uint8_t *b, uint32_t pos, uint32_t c, uint32_t *tok, uint32_t nt, uint32_t n) {
+  uint32_t t, step;
+  if (c) {
+    const uint32_t l = (c >> 16) - 3u, d = (c & 0xffffu) - 1u;
+    uint32_t sym, eb, ev;
+    dfl_len_sym(l, sym, eb, ev);
+    W.lit_hist[sym < 288u ? sym : 287u]++;
+    dfl_dist_sym(d, sym, eb, ev);
+    W.dist_hist[sym & 31u]++;
+    t = 0x80000000u | l << 16 | d;
+    step = c >> 16;
+  } else {
+    t = b[pos];
+    W.lit_hist[t]++;
+    step = 1u;
+  }
+  if (nt < n) tok[nt] = t;
+  return step;
+}
+
+// The fast rule: the tokens of b[0, n) from one candidate per position, at least a batch old, parsed greedily (the text at the
+// top of this file).  tokens() leaves them in tok[0, W.ntok) and their counts in the histograms; every lane makes the call.
+struct DflFast {
+  struct Search {
+    uint32_t tab[1u << DFL_HASH_BITS];    // hash of 4 bytes -> 1 + the largest inserted position with it (0: none)
+    uint32_t cand[DFL_BATCH];             // the batch's candidates: length << 16 | distance, 0 = no match
+  };
+  template <class Team>
+  static DFL_FN void reset(const Team &T, Search &S) {
+    for (uint32_t i = T.tid(); i < (1u << DFL_HASH_BITS); i += Team::N) S.tab[i] = 0;
+  }
+  template <class Team, class Work>
+  static DFL_FN void tokens(const Team &T, Work &W, const uint8_t *b, uint32_t n, uint32_t *tok) {
+    const uint32_t tid = T.tid();
+    Search &S = W.s;
+    uint32_t pos = 0, nt = 0;             // lane 0's: where the last token ends, tokens so far
+    for (uint32_t base = 0; base < n; base += DFL_BATCH) {
+      for (uint32_t t = tid; t < DFL_BATCH; t += Team::N) {
+        const uint32_t p = base + t;
+        uint32_t c = 0;
+        if (p + DFL_MIN_MATCH <= n) {
+          const uint32_t e = S.tab[dfl_hash(b + p)];
+          if (e && e <= base && p - (e - 1u) <= DFL_MAX_DIST) {     // (e - 1 < base: only earlier batches have been inserted)
+            const uint32_t q = e - 1u, maxl = n - p < DFL_MAX_MATCH ? n - p : DFL_MAX_MATCH;
+            uint32_t l = 0;
+            while (l < maxl && b[q + l] == b[p + l]) ++l;
+            if (l >= DFL_MIN_MATCH) c = l << 16 | (p - q);
+          }
+        }
+        S.cand[t] = c;
+      }
+      T.sync();
+      for (uint32_t t = tid; t < DFL_BATCH; t += Team::N) {
+        const uint32_t p = base + t;
+        if (p + DFL_MIN_MATCH <= n) T.max_u32(&S.tab[dfl_hash(b + p)], p + 1u);
+      }
+      if (tid == 0) {
+        const uint32_t end = base + DFL_BATCH < n ? base + DFL_BATCH : n;
+        while (pos < end) {
+          pos += dfl_token(W, b, pos, S.cand[pos - base], tok, nt, n);
+          ++nt;
+        }
+      }
+      T.sync();
+    }
+    if (tid == 0) W.ntok = nt < n ? nt : n;
+  }
+};
+
+// The dense rule, a function of the block's bytes alone:
+//   chain(p)  the positions q < p with hash4(q) == hash4(p) and p - q <= WINDOW, nearest first; its first DEPTH entries are
+//             looked at, those whose bytes differ (the hash is 12 bits of four bytes) among them;
+//   match(p)  the longest common prefix with one of them, at most 258 bytes and the block's end, the nearest of equal lengths;
+//             below 4 bytes, and where fewer than four bytes are left, none.  Source and copy may overlap;
+//   parse     in position order: where match(pos + 1) is strictly longer than match(pos), the literal b[pos]; else the match.
+// How it is kept: head[h] is 1 + the largest inserted position with hash h, ring[q % RING] is 1 + the nearest position before q
+// with q's hash: q's link, written when q is inserted.  A batch of 256 positions is inserted at a time, so the slot of q is
+// written again by q + RING at the earliest when the batch of q + RING is inserted: no position of that batch is within
+// WINDOW = RING - 256 of q.  Every slot a walk may follow is therefore the link of the position it is followed from.
+// A walk takes at most DEPTH steps, each to a strictly smaller position within WINDOW, else it ends: whatever a slot holds.
+struct DflDense {
+  static constexpr uint32_t HASH_BITS = 12, DEPTH = 16, RING = 16384, WINDOW = RING - DFL_BATCH;
+  struct Search {
+    uint32_t head[1u << HASH_BITS];
+    uint16_t ring[RING];
+    uint32_t cand[2u * DFL_BATCH];        // match(p) at p % 512, length << 16 | distance, 0 = none: this batch's and the one before
+    uint16_t hb[DFL_BATCH];               // the batch's hashes; NO_HASH where fewer than four bytes are left
+  };
+  static constexpr uint32_t NO_HASH = 0xffffu;
+  static DFL_FN uint32_t hash(const uint8_t *p) { return (dfl_ld32(p) * 2654435761u) >> (32 - HASH_BITS); }
+  static DFL_FN uint32_t ld32u(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }      // (both sides little-endian)
+  // the common prefix of b + q and b + p, at most maxl bytes; four bytes at a time (reads stay below p + maxl + 3 < 65536)
+  static DFL_FN uint32_t prefix(const uint8_t *b, uint32_t q, uint32_t p, uint32_t maxl) {
+    uint32_t l = 0;
+    while (l + 4u <= maxl) {
+      const uint32_t x = ld32u(b + q + l) ^ ld32u(b + p + l);
+      if (x) return l + ((uint32_t)__builtin_ctz(x) >> 3);
+      l += 4u;
+    }
+    while (l < maxl && b[q + l] == b[p + l]) ++l;
+    return l;
+  }
+  // match(p) from p's link e (1 + the nearest earlier position with p's hash, 0: none); p + 4 <= n
+  static DFL_FN uint32_t match(const Search &S, const uint8_t *b, uint32_t n, uint32_t p, uint32_t e) {
+    const uint32_t maxl = n - p < DFL_MAX_MATCH ? n - p : DFL_MAX_MATCH;
+    uint32_t best = DFL_MIN_MATCH - 1u, dist = 0, last = p;
+    for (uint32_t step = 0; step < DEPTH && e; ++step) {
+      const uint32_t q = e - 1u;
+      if (q >= last || p - q > WINDOW) break;
+      last = q;
+      if (b[q + best] == b[p + best]) {            // (best < maxl: q + best < p + best < n) only then can q be longer than the best
+        const uint32_t l = prefix(b, q, p, maxl);
+        if (l > best) { best = l; dist = p - q; }
+        if (best >= maxl) break;
+      }
+      e = S.ring[q & (RING - 1u)];
+    }
+    return dist ? best << 16 | dist : 0u;
+  }
+  template <class Team>
+  static DFL_FN void reset(const Team &T, Search &S) {
+    for (uint32_t i = T.tid(); i < (1u << HASH_BITS); i += Team::N) S.head[i] = 0;
+  }
+  template <class Team, class Work>
+  static DFL_FN void tokens(const Team &T, Work &W, const uint8_t *b, uint32_t n, uint32_t *tok) {
+    const uint32_t tid = T.tid();
+    Search &S = W.s;
+    uint32_t pos = 0, nt = 0;             // lane 0's: the position to parse next, tokens so far
+    for (uint32_t base = 0; base < n; base += DFL_BATCH) {
+      for (uint32_t t = tid; t < DFL_BATCH; t += Team::N) S.hb[t] = (uint16_t)(base + t + DFL_MIN_MATCH <= n ? hash(b + base + t) : NO_HASH);
+      T.sync();
+      // every position's link.  A team that visits the positions in order inserts as it goes; lanes side by side look for the
+      // nearest predecessor among the batch's own hashes first, then in the table, which holds earlier batches only
+      for (uint32_t t = tid; t < DFL_BATCH; t += Team::N) {
+        const uint32_t p = base + t, h = S.hb[t];
+        if (h == NO_HASH) continue;
+        uint32_t e = 0;
+        if (Team::IN_ORDER) {
+          e = S.head[h];
+          S.head[h] = p + 1u;
+        } else {
+          for (uint32_t u = t; u-- > 0u;)
+            if (S.hb[u] == h) { e = base + u + 1u; break; }
+          if (!e) e = S.head[h];
+        }
+        S.ring[p & (RING - 1u)] = (uint16_t)e;                        // (e <= 0xFF00)
+      }
+      T.sync();
+      for (uint32_t t = tid; t < DFL_BATCH; t += Team::N) {
+        const uint32_t p = base + t, h = S.hb[t];
+        S.cand[p & (2u * DFL_BATCH - 1u)] = h == NO_HASH ? 0u : match(S, b, n, p, S.ring[p & (RING - 1u)]);
+        if (!Team::IN_ORDER && h != NO_HASH) T.max_u32(&S.head[h], p + 1u);
+      }
+      T.sync();
+      // lane 0 parses what has its look-ahead: all but the batch's last position, which waits for the next batch
+      if (tid == 0) {
+        const uint32_t end = base + DFL_BATCH < n ? base + DFL_BATCH : n, lim = end == n ? n : end - 1u;
+        while (pos < lim) {
+          uint32_t c = S.cand[pos & (2u * DFL_BATCH - 1u)];
+          if (c && pos + 1u < n && (S.cand[(pos + 1u) & (2u * DFL_BATCH - 1u)] >> 16) > (c >> 16)) c = 0;
+          pos += dfl_token(W, b, pos, c, tok, nt, n);
+          ++nt;
+        }
+      }
+    }
+    if (tid == 0) W.ntok = nt < n ? nt : n;
+  }
+};
+static_assert(DflDense::RING >= DflDense::WINDOW + DFL_BATCH && (DflDense::RING & (DflDense::RING - 1u)) == 0 && DflDense::WINDOW <= DFL_MAX_DIST, "the ring holds a window and a batch");
+
 // One block.  in[0, n), 1 <= n <= 0xFF00; tok[0, n) is scratch (the tokens); out has room for n + 31 bytes.
 // Returns the member's size; *stored = 1 when the block went out stored.  Every lane of the team makes the call, with the
-// same arguments, and every lane returns the same values.
-template <class Team>
-DFL_FN uint32_t dfl_block(const Team &T, DflWork &W, const DflCrc &crc, const uint8_t *in, uint32_t n, uint32_t *tok, uint8_t *out, uint32_t *stored) {
+// same arguments, and every lane returns the same values.  The work area's type names the match rule.
+template <class Team, class Rule>
+DFL_FN uint32_t dfl_block(const Team &T, DflWorkT<Rule> &W, const DflCrc &crc, const uint8_t *in, uint32_t n, uint32_t *tok, uint8_t *out, uint32_t *stored) {
   const uint32_t tid = T.tid();
   uint8_t *b = reinterpret_cast<uint8_t *>(W.buf);
   if (n > DFL_MAX_BLOCK) n = DFL_MAX_BLOCK;
   // ---- the block's bytes, empty tables
   for (uint32_t i = tid; i < n; i += Team::N) b[i] = in[i];
-  for (uint32_t i = tid; i < (1u << DFL_HASH_BITS); i += Team::N) W.tab[i] = 0;
+  Rule::reset(T, W.s);
   for (uint32_t i = tid; i < 288u; i += Team::N) W.lit_hist[i] = 0;
   for (uint32_t i = tid; i < 32u; i += Team::N) W.dist_hist[i] = 0;
   for (uint32_t i = tid; i < 20u; i += Team::N) W.cl_hist[i] = 0;
@@ -244,57 +424,9 @@ DFL_FN uint32_t dfl_block(const Team &T, DflWork &W, const DflCrc &crc, const ui
       if (c) T.xor_u32(&W.crc_acc, c);
     }
   }
-  // ---- match search and greedy parse, a batch of positions at a time
-  uint32_t pos = 0, nt = 0;             // lane 0's: where the last token ends, tokens so far
-  for (uint32_t base = 0; base < n; base += DFL_BATCH) {
-    for (uint32_t t = tid; t < DFL_BATCH; t += Team::N) {
-      const uint32_t p = base + t;
-      uint32_t c = 0;
-      if (p + DFL_MIN_MATCH <= n) {
-        const uint32_t e = W.tab[dfl_hash(b + p)];
-        if (e && e <= base && p - (e - 1u) <= DFL_MAX_DIST) {     // (e - 1 < base: only earlier batches have been inserted)
-          const uint32_t q = e - 1u, maxl = n - p < DFL_MAX_MATCH ? n - p : DFL_MAX_MATCH;
-          uint32_t l = 0;
-          while (l < maxl && b[q + l] == b[p + l]) ++l;
-          if (l >= DFL_MIN_MATCH) c = l << 16 | (p - q);
-        }
-      }
-      W.cand[t] = c;
-    }
-    T.sync();
-    for (uint32_t t = tid; t < DFL_BATCH; t += Team::N) {
-      const uint32_t p = base + t;
-      if (p + DFL_MIN_MATCH <= n) T.max_u32(&W.tab[dfl_hash(b + p)], p + 1u);
-    }
-    if (tid == 0) {
-      const uint32_t end = base + DFL_BATCH < n ? base + DFL_BATCH : n;
-      while (pos < end) {
-        const uint32_t c = W.cand[pos - base];
-        uint32_t t;
-        if (c) {
-          const uint32_t l = (c >> 16) - 3u, d = (c & 0xffffu) - 1u;
-          uint32_t sym, eb, ev;
-          dfl_len_sym(l, sym, eb, ev);
-          W.lit_hist[sym < 288u ? sym : 287u]++;
-          dfl_dist_sym(d, sym, eb, ev);
-          W.dist_hist[sym & 31u]++;
-          t = 0x80000000u | l << 16 | d;
-          pos += c >> 16;
-        } else {
-          t = b[pos];
-          W.lit_hist[t]++;
-          pos += 1u;
-        }
-        if (nt < n) tok[nt] = t;
-        ++nt;
-      }
-    }
-    T.sync();
-  }
-  if (tid == 0) {
-    W.lit_hist[256] = 1;
-    W.ntok = nt < n ? nt : n;
-  }
+  // ---- the tokens: the rule's match search and parse
+  Rule::tokens(T, W, b, n, tok);
+  if (tid == 0) W.lit_hist[256] = 1;
   T.sync();
   const uint32_t ntok = W.ntok, crc32 = ~W.crc_acc;
   // ---- code lengths and codes
@@ -449,18 +581,20 @@ inline const DflCrc &dfl_crc_tables() {
   return T;
 }
 
-// strl_bgzf_deflate_host without the error text: the members of in[0, in_bytes) back to back on the calling thread
-inline int dfl_deflate_host(const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
-                            uint32_t *n_stored) {
+// strl_bgzf_deflate_host without the error text: the members of in[0, in_bytes) back to back on the calling thread;
+// with the rule and the team named (the tests run the lanes' side of the dense rule on one thread this way)
+template <class Rule, class Team = DflSerial>
+inline int dfl_deflate_host_as(const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
+                               uint32_t *n_stored) {
   if (block_bytes < 1u || block_bytes > DFL_MAX_BLOCK || !out_bytes || (in_bytes && (!in || !out))) return STRL_ERR_ARG;
   if (out_cap < dfl_bound(in_bytes, block_bytes)) return STRL_ERR_CAPACITY;
   *out_bytes = 0;
   if (n_stored) *n_stored = 0;
   if (!in_bytes) return STRL_OK;
-  std::unique_ptr<DflWork> W(new DflWork);
+  std::unique_ptr<DflWorkT<Rule>> W(new DflWorkT<Rule>);
   std::vector<uint32_t> tok(block_bytes);
   std::vector<uint8_t> slot((size_t)block_bytes + DFL_MEMBER_EXTRA);
-  const DflSerial T;
+  const Team T;
   uint64_t at = 0, k = 0;
   for (uint64_t off = 0; off < in_bytes; off += block_bytes, ++k) {
     const uint32_t n = (uint32_t)(in_bytes - off < block_bytes ? in_bytes - off : block_bytes);
@@ -473,6 +607,17 @@ inline int dfl_deflate_host(const uint8_t *in, uint64_t in_bytes, uint32_t block
   }
   *out_bytes = at;
   return STRL_OK;
+}
+inline int dfl_deflate_host(const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, uint32_t *csize,
+                            uint32_t *n_stored) {
+  return dfl_deflate_host_as<DflFast>(in, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
+}
+// ... with the rule as a value: STRL_DEFLATE_FAST or STRL_DEFLATE_DENSE, any other is STRL_ERR_ARG
+inline int dfl_deflate_host_mode(int mode, const uint8_t *in, uint64_t in_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+                                 uint32_t *csize, uint32_t *n_stored) {
+  if (mode == STRL_DEFLATE_FAST) return dfl_deflate_host_as<DflFast>(in, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
+  if (mode == STRL_DEFLATE_DENSE) return dfl_deflate_host_as<DflDense>(in, in_bytes, block_bytes, out, out_cap, out_bytes, csize, n_stored);
+  return STRL_ERR_ARG;
 }
 
 }  // namespace strl

@@ -1,6 +1,6 @@
 """`strling sort` on a shuffled BAM: the device path with both --deflate forms beside the host path (STRL_SORT=host), JSON lines.
 
-    python tools/sort_bench.py [--pairs N] [--repeats K] [--trace OUTDIR] [--dir D] [--slab-mb M] [--lanes 16,32,64]
+    python tools/sort_bench.py [--pairs N] [--repeats K] [--trace OUTDIR] [--dir D] [--slab-mb M] [--lanes 16,32,64] [--dense [--parent-cli PATH]]
     python tools/sort_bench.py --write-index [--parent-cli PATH] [--pairs N] [--repeats K] [--trace OUTDIR]
 
 The input is a file of --pairs pairs from bamio.write_bam_slabs (30x geometry, qualities, aux tags), its records put into a random
@@ -13,6 +13,9 @@ other on one box, one process at a time, K runs each (the first pays for the pag
   * one more device run with STRL_ALLOC_TIMING=1: the library's own timing of every hipMalloc of 64 MB and more, the arena's slabs among them;
   * --slab-mb: one more device run with slabs of that size (default 4096), to see what allocating the arena slab by slab costs;
   * --trace: one more run under `rocprofv3 --kernel-trace --stats` (a run of its own): OUTDIR/kernel_stats.csv.
+  * --dense: `strling sort -v --deflate=dense` beside the three, and --parent-cli's `sort --deflate=host` (the bar the dense mode is
+    measured against), alternating with them; the dense output must inflate to the same stream; the gather runs and the allocation
+    run are left out; --trace then traces `sort --deflate=dense` (OUTDIR/kernel_stats_dense.csv).
 --write-index measures `sort --write-index` instead, in one call, alternating, K runs each (K >= 5 for a figure), for both --deflate
 forms: this build's `sort --write-index`; --parent-cli's (default: this build's) `sort` followed by its `bamindex` of the output,
 the two commands' wall times summed; this build's plain `sort` and the parent's side by side, the order swapped every repeat.  The
@@ -301,6 +304,7 @@ def main():
     ap.add_argument("--write-index", action="store_true")
     ap.add_argument("--parent-cli", default="")
     ap.add_argument("--windowed", action="store_true")
+    ap.add_argument("--dense", action="store_true", help="the plain runs with --deflate=dense (and --parent-cli's --deflate=host) beside them")
     ap.add_argument("--sam", action="store_true", help="SAM text as the input, from a file and from a pipe, beside the BAM's sort")
     ap.add_argument("--window-mb", default="", help="with --windowed: comma-separated window sizes in MiB (default: the sizes that give 1, 2 and 4 windows)")
     a = ap.parse_args()
@@ -325,16 +329,29 @@ def main():
         shutil.rmtree(work, ignore_errors=True)
         return
     outs = {}
-    forms = (("device_zlib", ["--deflate=host"], {}), ("device_core", ["--deflate=device"], {}), ("host_zlib", ["--deflate=host"], {"STRL_SORT": "host"}))
+    forms = [("device_zlib", cli, ["--deflate=host"], {}), ("device_core", cli, ["--deflate=device"], {}), ("host_zlib", cli, ["--deflate=host"], {"STRL_SORT": "host"})]
+    if a.dense:
+        forms.insert(2, ("device_dense", cli, ["--deflate=dense"], {}))
+        if a.parent_cli:
+            forms.insert(0, ("parent_device_zlib", a.parent_cli, ["--deflate=host"], {}))
     for k in range(a.repeats):
-        for tag, opts, env in forms:
+        for tag, exe, opts, env in forms:
             outs[tag] = os.path.join(work, tag + ".bam")
-            says, wall = _run([cli, "sort", "-v", *opts, "-o", outs[tag], src], dict(os.environ, **env))
+            says, wall = _run([exe, "sort", "-v", *opts, "-o", outs[tag], src], dict(os.environ, **env))
             print(json.dumps({"run": tag, "repeat": k, "wall_s": wall, "says": says}), flush=True)
     same_file = open(outs["device_zlib"], "rb").read() == open(outs["host_zlib"], "rb").read()
     same_stream = gzip.decompress(open(outs["device_core"], "rb").read()) == gzip.decompress(open(outs["host_zlib"], "rb").read())
     print(json.dumps({"check": "outputs", "device_zlib_file_equals_host_file": same_file, "device_core_stream_equals_host_stream": same_stream,
                       "out_bytes": {t: os.path.getsize(p) for t, p in outs.items()}}), flush=True)
+    if a.dense:
+        same = gzip.decompress(open(outs["device_dense"], "rb").read()) == gzip.decompress(open(outs["host_zlib"], "rb").read())
+        print(json.dumps({"check": "dense", "device_dense_stream_equals_host_stream": same}), flush=True)
+        if a.trace:
+            os.makedirs(a.trace, exist_ok=True)
+            rows, err = _stats_csv([cli, "sort", "--deflate=dense", "-o", outs["device_dense"], src], {}, work, os.path.join(a.trace, "kernel_stats_dense.csv"))
+            print(json.dumps({"trace": "kernel_stats_dense.csv" if rows else err}), flush=True)
+        shutil.rmtree(work, ignore_errors=True)
+        return
     # what allocating the arena costs: the library's own timing of every hipMalloc of 64 MB and more (STRL_ALLOC_TIMING)
     r = subprocess.run([cli, "sort", "-v", "-o", outs["device_zlib"], src], capture_output=True, text=True, env=dict(os.environ, STRL_ALLOC_TIMING="1"), timeout=1500)
     print(json.dumps({"run": "device_zlib", "STRL_ALLOC_TIMING": 1, "hipMalloc": [x for x in r.stderr.splitlines() if "hipMalloc" in x], "says": json.loads(r.stderr.strip().splitlines()[-1])}), flush=True)
