@@ -230,6 +230,8 @@ def load(build_if_missing=True):
     L.strl_extract_device.argtypes = [C.c_void_p, C.POINTER(CReadSoa), C.POINTER(CPairSoa), C.c_int64, C.c_uint64, C.c_uint64]
     L.strl_treads_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(ScoreStats)]
     L.strl_ctx_pair_times.argtypes = [C.c_void_p, C.POINTER(C.c_double * 5)]
+    if hasattr(L, "strl_pair_items_probe"):      # (STRL_LIB may name a build from before the entry point)
+        L.strl_pair_items_probe.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.strl_cluster_resident.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_uint32, C.c_int32, C.c_uint16, C.c_uint16, C.c_uint16,
                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                         C.POINTER(ClusterStats)]
@@ -633,6 +635,13 @@ class Context:
         if want and no.value:
             _check(self.L.strl_treads_fetch(self.h, out.ctypes.data, out.size, C.byref(no), None))
         return out[:no.value], st
+
+    def pair_items(self):
+        """join items of the context's last pair pass, after a sync (strl_pair_items_probe, test-only): the reads the probe let
+        through the Bloom bitmap plus the hot soft-clip records, clamped to the pass' item capacity"""
+        n = C.c_uint64(0)
+        _check(self.L.strl_pair_items_probe(self.h, C.byref(n)))
+        return n.value
 
     def pair_times(self):
         ms = (C.c_double * 5)()

@@ -2,20 +2,19 @@
 #pragma once
 #include <algorithm>
 #include "common.h"
+#include "bloom_layout.h"
 
 namespace strl {
 
-// Bloom bitmap over mixed qname hashes (pair.hip): two bits per key
+// Bloom bitmap over mixed qname hashes (pair.hip): BLOOM_K bits per key, all in one aligned 64-bit word (bloom_layout.h holds
+// the index arithmetic).  The bitmap is allocated, zeroed and OR-merged as 32-bit words (hipMalloc'd: 8-byte aligned); a mark
+// is ONE 64-bit atomic, a test one 8-byte load.
 __device__ __forceinline__ void bloom_set(uint32_t *bloom, uint32_t mask, uint64_t m) {
-  const uint32_t b0 = (uint32_t)m & mask, b1 = (uint32_t)(m >> 32) & mask;
-  atomicOr(&bloom[b0 >> 5], 1u << (b0 & 31u));
-  atomicOr(&bloom[b1 >> 5], 1u << (b1 & 31u));
+  atomicOr(reinterpret_cast<unsigned long long *>(bloom) + bloom_word(m, mask), (unsigned long long)bloom_pattern(m));
 }
 __device__ __forceinline__ bool bloom_test(const uint32_t *bloom, uint32_t mask, uint64_t m) {
-  const uint32_t b0 = (uint32_t)m & mask;
-  if (!((bloom[b0 >> 5] >> (b0 & 31u)) & 1u)) return false;
-  const uint32_t b1 = (uint32_t)(m >> 32) & mask;
-  return (bloom[b1 >> 5] >> (b1 & 31u)) & 1u;
+  const uint64_t pat = bloom_pattern(m);
+  return (reinterpret_cast<const uint64_t *>(bloom)[bloom_word(m, mask)] & pat) == pat;
 }
 
 

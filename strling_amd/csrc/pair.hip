@@ -7,11 +7,12 @@
 //      being processed), and
 //   2. a group none of whose records carries a repeat (whole-read count 0 and no soft-clip result) emits nothing.
 // So the device joins only the HOT groups -- a few per cent of the reads:
-//   mark   : every scored read / soft-clip record with a non-zero count sets two bits of a Bloom bitmap keyed by the
-//            64-bit qname hash (whole reads: inside score_kernel; soft-clip records: pair_soft_items_kernel, which also
-//            turns each such record into a join item),
+//   mark   : every scored read / soft-clip record with a non-zero count sets the four bits of its key in a Bloom bitmap
+//            keyed by the 64-bit qname hash -- all four in one 64-bit word, one atomic OR (bloom_layout.h; whole reads:
+//            inside score_kernel; soft-clip records: pair_soft_items_kernel, which also turns each such record into a
+//            join item),
 //   probe  : one streaming pass over the qname hashes of ALL reads (8 B per read -- the only full pass the pair logic
-//            adds) tests the bitmap (2 MB, L2 resident) and turns the hits into join items,
+//            adds) tests the bitmap (2 MB, L2 resident), one 8-byte gather per read, and turns the hits into join items,
 //   join   : the items are radix-sorted by hash (sort.hip); a run of equal hashes = one qname group (reads + its hot
 //            soft-clip records),
 //   replay : one lane per run replays Cache.add over the group's records in file order -- first pass over all records,
@@ -133,7 +134,9 @@ __global__ __launch_bounds__(1024) void pair_soft_items_kernel(PairParams P) {
 // The one full pass of the pair logic: qname hash of every read against the bitmap.  Each wave owns a contiguous range
 // of reads and stages its hits in LDS; a flush reserves item space with ONE atomic (same-address atomics run at ~88 per
 // microsecond on the L2, so a wave flushes once, at the end, unless its stage fills) and gathers the hashes of the
-// staged reads again.
+// staged reads again.  A turn of the loop (512 reads per wave) is one dependent round trip: eight unconditional gathers
+// of the keys' 64-bit words, one wait, the test in registers, with the next turn's eight stream loads in flight behind
+// them.  What is left is the L2's request rate: one 8-byte request per read into a 2 MB bitmap (profiles/pair_probe).
 constexpr int PR_STAGE = 1024, PR_ILP = 8;
 __global__ __launch_bounds__(256) void pair_probe_kernel(PairParams P) {
   __shared__ uint32_t stage[4][PR_STAGE + 64 * PR_ILP];
@@ -165,37 +168,41 @@ __global__ __launch_bounds__(256) void pair_probe_kernel(PairParams P) {
       cnt = 0;
     }
   };
+  if (r0 >= r1) return;   // a wave that owns no read (nothing below synchronises across waves)
+  const uint64_t *bloom_words = reinterpret_cast<const uint64_t *>(P.bloom);
   uint64_t cur[PR_ILP], nxt[PR_ILP];
+  // A lane past the wave's end reads the wave's LAST hash, not nothing: an unconditional load has no join the compiler must
+  // wait at (a conditional load's result is copied at the join -- a use, a wait), so the next turn's eight loads stay in flight
+  // across this turn.  What such a lane loaded never becomes an item: validity goes into the hit flag alone.
   auto load = [&](uint64_t base, uint64_t (&x)[PR_ILP]) {
 #pragma unroll
     for (int j = 0; j < PR_ILP; ++j) {
       const uint64_t r = base + 64ull * j + lane;
-      x[j] = r < r1 ? P.qhash[r] : 0ull;
+      x[j] = P.qhash[r < r1 ? r : r1 - 1];
     }
   };
   load(r0, cur);
   for (uint64_t base = r0; base < r1; base += 64 * PR_ILP) {
-    load(base + 64 * PR_ILP, nxt);
-    // first bit of all PR_ILP reads (independent loads), then the second bit of the few that passed
-    uint64_t m[PR_ILP];
-    uint32_t w0[PR_ILP];
+    // one gather per read, the key's word (bloom_layout.h): PR_ILP independent loads issued back to back, the BLOOM_K-bit test
+    // in registers
+    uint64_t pat[PR_ILP], w[PR_ILP];
 #pragma unroll
     for (int j = 0; j < PR_ILP; ++j) {
-      m[j] = fmix64(cur[j]);
-      w0[j] = P.bloom[((uint32_t)m[j] & P.bloom_mask) >> 5];
+      const uint64_t m = fmix64(cur[j]);
+      pat[j] = bloom_pattern(m);
+      w[j] = bloom_words[bloom_word(m, P.bloom_mask)];
     }
+    // The next turn's hashes are requested BEHIND the gathers and the scheduler is kept from moving them: loads return in the
+    // order of their issue, so the wait for the gathers (vmcnt(8)) leaves these eight in flight through the test, the ballots
+    // and the staging below.  Issued in front of the gathers they would have to land first (5 us of the launch).
+    __builtin_amdgcn_sched_barrier(0);
+    load(base + 64 * PR_ILP, nxt);
+    __builtin_amdgcn_sched_barrier(0);
     bool hit[PR_ILP];
 #pragma unroll
     for (int j = 0; j < PR_ILP; ++j) {
       const uint64_t r = base + 64ull * j + lane;
-      hit[j] = r < r1 && ((w0[j] >> ((uint32_t)m[j] & 31u)) & 1u);
-    }
-#pragma unroll
-    for (int j = 0; j < PR_ILP; ++j) {
-      if (hit[j]) {
-        const uint32_t b1 = (uint32_t)(m[j] >> 32) & P.bloom_mask;
-        hit[j] = (P.bloom[b1 >> 5] >> (b1 & 31u)) & 1u;
-      }
+      hit[j] = (r < r1) & ((w[j] & pat[j]) == pat[j]);
     }
 #pragma unroll
     for (int j = 0; j < PR_ILP; ++j) {
@@ -790,6 +797,21 @@ extern "C" int strl_pair_rules_device(strl_ctx *c, int op, strl_tread *A, const 
 extern "C" int strl_pair_rule_device(strl_ctx *c, int op, strl_tread *A, const strl_tread *B, const strl_opts *o, uint32_t B_position, int *result) {
   if (!A || !B || !result) { set_error("bad argument"); return STRL_ERR_ARG; }
   return strl_pair_rules_device(c, op, A, B, &B_position, 1, o, result);
+}
+
+// test-only, undeclared (the strl_sort_probe precedent): the join items of the context's last pair pass -- the reads the probe
+// let through plus the hot soft-clip records, clamped to the pass' item capacity -- after a sync.  What the Bloom bitmap lets
+// through beside the hot groups shows here and nowhere else: a false item emits nothing.
+extern "C" int strl_pair_items_probe(strl_ctx *c, uint64_t *n_items) {
+  if (!c || !n_items) { set_error("strl_pair_items_probe: bad argument"); return STRL_ERR_ARG; }
+  if (!c->pair_item_cap || !c->pair_cnt.p) { set_error("strl_pair_items_probe: no pair pass on this context"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  { const int rc = side_join(c); if (rc) return rc; }
+  uint32_t v = 0;
+  STRL_HIP(hipMemcpyAsync(&v, c->pair_cnt.as<uint32_t>() + PC_ITEMS, 4, hipMemcpyDeviceToHost, c->stream));
+  STRL_HIP(hipStreamSynchronize(c->stream));
+  *n_items = std::min(v, c->pair_item_cap);
+  return STRL_OK;
 }
 
 // Treads of the last strl_pair_device call into the order of the reference's .bin file (c->treads); idempotent.

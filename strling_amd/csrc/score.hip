@@ -785,7 +785,8 @@ int compact_grid(int dflt) {
 
 using namespace strl;
 
-// Bloom bitmap of the hot qname groups: ~n/2 bits (2 MB for 2^25 reads: L2 resident), two bits per key
+// Bloom bitmap of the hot qname groups: ~n/2 bits (2 MB for 2^25 reads: L2 resident), four bits per key in one 64-bit word
+// (bloom_layout.h; the size rule does not depend on the layout)
 int bloom_reset(strl_ctx *c, uint64_t n) {
   uint64_t bits = 1ull << 16;
   while (bits < n / 2 && bits < (1ull << 27)) bits <<= 1;
