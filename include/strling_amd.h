@@ -971,6 +971,32 @@ int strl_bamsort_push_sam(strl_ctx *ctx, const uint8_t *text, uint64_t bytes);
 int strl_bamsort_sam_info(strl_ctx *ctx, strl_bamsort_sam_figures *out);
 int strl_sam_encode(const uint8_t *line, uint64_t len, const uint8_t *names, const uint32_t *name_off, int32_t n_ref, uint8_t *out, uint64_t cap, uint64_t *out_bytes);
 int strl_sam_header(const uint8_t *text, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *out_bytes, int32_t *n_ref);
+/* `strling sort --markdup` (csrc/markdup.hip, the rule in csrc/markdup_core.h): flag 0x400 set or cleared on the
+ * records of a resident sort, before the first piece is gathered.  The reference drops records that carry the flag when it collects
+ * spanning evidence (collect.nim:140: `if aln.flag.secondary or aln.flag.supplementary or aln.flag.dup: continue`), and an aligner
+ * never sets it.  Picard's rule as `samtools markdup` applies it in template mode, without optical duplicates; mates are joined by
+ * NAME on the device, so no fixmate, MC or ms tag is needed.
+ *   strl_bamsort_markdup_mode  behind strl_bamsort_begin / _sam_begin and before the first push (else STRL_ERR_ARG): the pushes' arena
+ *                              limit then leaves the step's 41 bytes a record free.  STRL_ERR_ARG on a windowed sort.
+ *   strl_bamsort_markdup       behind strl_bamsort_finish and before the first fetch, once: the record kernel (signature, score,
+ *                              name hash, class), the join by name, the pairs' and the fragments' chained sorts, and the flag bytes
+ *                              written into the arena.  STRL_ERR_ARG before the finish, after a fetch, a second time, on a windowed
+ *                              sort.  STRL_ERR_FORMAT: a record whose name, CIGAR, bases and qualities do not fit its block_size, or
+ *                              whose unclipped end is no 32-bit position (the message names the record's ordinal).  STRL_ERR_LIMIT:
+ *                              more than 512 eligible records under one name hash (the message names the count; the host path,
+ *                              STRL_SORT=host, has no such limit).  After a refusal the sort is failed: only strl_bamsort_end.
+ *   strl_markdup_host          the same rule without a device: records[0, bytes) = records back to back in input order, each with
+ *                              its block_size word; flags[i] = the flag word record i leaves with (cap >= the number of records, else
+ *                              STRL_ERR_CAPACITY with *n_records set).  The times of `info` stay 0.
+ * STRL_MARKDUP_HASH_BITS = 1 .. 63 (tests; read once per process): the name hash cut to that many bits, so that different names
+ * share a hash as a rule; the output does not change. */
+typedef struct {
+  uint64_t n_pairs, n_dup_pairs, n_fragments, n_dup_fragments, n_ineligible;
+  double record_ms, join_ms, pairs_ms, fragments_ms, flag_ms;      /* HIP-event time of the step's five parts (sorts included) */
+} strl_markdup_info;
+int strl_bamsort_markdup_mode(strl_ctx *ctx, int on);
+int strl_bamsort_markdup(strl_ctx *ctx, strl_markdup_info *info);
+int strl_markdup_host(const uint8_t *records, uint64_t bytes, uint16_t *flags, uint64_t cap, uint64_t *n_records, strl_markdup_info *info);
 
 /* ---- the .bai as a by-product of `strling extract`'s own pass (`strling extract --write-index`) ----
  * strl_front_push already copies, inflates, CRC-checks, record-scans and parses every block; the index needs of a record only

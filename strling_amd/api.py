@@ -64,6 +64,12 @@ class BamsortInfo(C.Structure):
                 ("arena_bytes", C.c_uint64), ("sort_ms", C.c_double), ("layout_ms", C.c_double), ("gather_ms", C.c_double)]
 
 
+class MarkdupInfo(C.Structure):
+    """strl_markdup_info: the counts of `sort --markdup` and the HIP-event time of the device step's parts"""
+    _fields_ = [("n_pairs", C.c_uint64), ("n_dup_pairs", C.c_uint64), ("n_fragments", C.c_uint64), ("n_dup_fragments", C.c_uint64), ("n_ineligible", C.c_uint64),
+                ("record_ms", C.c_double), ("join_ms", C.c_double), ("pairs_ms", C.c_double), ("fragments_ms", C.c_double), ("flag_ms", C.c_double)]
+
+
 class BamsortSamFigures(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("text_bytes", C.c_uint64), ("host_finished", C.c_uint64), ("chunks", C.c_uint64),
                 ("copy_ms", C.c_double), ("scan_ms", C.c_double), ("size_ms", C.c_double), ("encode_ms", C.c_double)]
@@ -163,7 +169,8 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_bamsort_index", "strl_bamsort_index_fetch", "strl_bamsort_voff", "strl_bamsort_members",
            "strl_bamsort_begin_windowed", "strl_bamsort_window_limit", "strl_bamsort_window_begin", "strl_bamsort_window_push", "strl_bamsort_window_end",
            "strl_bamsort_window_plan",
-           "strl_bamsort_sam_begin", "strl_bamsort_sam_reserve", "strl_bamsort_push_sam", "strl_bamsort_sam_info", "strl_sam_encode", "strl_sam_header"]
+           "strl_bamsort_sam_begin", "strl_bamsort_sam_reserve", "strl_bamsort_push_sam", "strl_bamsort_sam_info", "strl_sam_encode", "strl_sam_header",
+           "strl_bamsort_markdup_mode", "strl_bamsort_markdup", "strl_markdup_host"]
 
 
 def lib_path():
@@ -319,6 +326,9 @@ def load(build_if_missing=True):
     L.strl_bamsort_sam_reserve.argtypes = [C.c_void_p, C.c_uint64]
     L.strl_bamsort_push_sam.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.strl_bamsort_sam_info.argtypes = [C.c_void_p, C.POINTER(BamsortSamFigures)]
+    L.strl_bamsort_markdup_mode.argtypes = [C.c_void_p, C.c_int]
+    L.strl_bamsort_markdup.argtypes = [C.c_void_p, C.POINTER(MarkdupInfo)]
+    L.strl_markdup_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(MarkdupInfo)]
     L.strl_sam_encode.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.strl_sam_header.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     L.strl_bamsort_window_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -1123,6 +1133,18 @@ class Context:
     def bamsort_end(self):
         self.L.strl_bamsort_end(self.h)
 
+    # ---- `strling sort --markdup` (strl_bamsort_markdup_mode / strl_bamsort_markdup): flag 0x400 on the resident records; the reference
+    # drops records that carry it (collect.nim:140)
+    def bamsort_markdup_mode(self, on=True):
+        """behind bamsort_begin / bamsort_sam_begin and before the first push: the arena's limit leaves room for the step"""
+        _check(self.L.strl_bamsort_markdup_mode(self.h, 1 if on else 0))
+
+    def bamsort_markdup(self):
+        """behind bamsort_finish and before the first fetch, once -> dict of strl_markdup_info"""
+        info = MarkdupInfo()
+        _check(self.L.strl_bamsort_markdup(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in MarkdupInfo._fields_}
+
     def bamsort_probe(self, lens, base, lo, hi):
         """test-only (strl_bamsort_probe): the layout and the piece search over caller-given lengths and a 64-bit base
         -> (off uint64[n + 1], (first, end) of the touched records, parts uint64[touched, 3] = source skip, destination, bytes)"""
@@ -1261,16 +1283,19 @@ class Context:
             self.bamsort_end()
         return b"".join(out), info
 
-    def bamsort(self, path, chunk_blocks=16384, check_crc=True, arena_limit_bytes=0, keep_open=False, index=None):
+    def bamsort(self, path, chunk_blocks=16384, check_crc=True, arena_limit_bytes=0, keep_open=False, index=None, markdup=False):
         """a BAM FILE coordinate-sorted on the device -> (the output stream: header || records in sorted order, strl_bamsort_info as a
         dict, the permutation).  keep_open: the sort is left on the context for further fetches (bamsort_end ends it).
         index = "bai" or ("csi", min_shift, depth): the stream is also deflated here (the compressor's host twin, members of 0xFF00
         bytes, the EOF block) and indexed from the sort (bamsort_index) -> a fourth item (the file's bytes, the index's bytes, its
-        info); a refusal of the index raises, with the sort ended unless keep_open."""
+        info); a refusal of the index raises, with the sort ended unless keep_open.
+        markdup: flag 0x400 decided on the device before the stream is fetched (bamsort_markdup); info["markdup"] = its dict."""
         B = self._bam_blocks(path)
         header = bamsort_header(B["header_raw"])
         self.bamsort_begin(B["n_ref"], B["first_off"], arena_limit_bytes)
         try:
+            if markdup:
+                self.bamsort_markdup_mode(True)
             data, blocks, keep = B["data"], B["blocks"], []
             for s0 in range(B["b0"], len(blocks), chunk_blocks):
                 cb = blocks[s0:s0 + chunk_blocks]
@@ -1283,6 +1308,8 @@ class Context:
                 keep = (keep + [(comp, coff, clen, isz, crc)])[-3:]      # pageable memory: the copy is staged by the runtime
                 self.bamsort_push(comp, coff, clen, isz, crc if check_crc else None)
             info = self.bamsort_finish(header)
+            if markdup:
+                info["markdup"] = self.bamsort_markdup()
             stream = self.bamsort_fetch(0, info["stream_bytes"])
             perm = self.bamsort_order(info["n_records"])
         except Exception:
@@ -1601,6 +1628,17 @@ def bamsort_key(rec20, n_ref):
     key = C.c_uint64(0)
     _check(load().strl_bamsort_key(b.ctypes.data, int(n_ref), C.byref(key)))
     return key.value
+
+
+def markdup_host(records):
+    """the rule of `strling sort --markdup` without a device (strl_markdup_host; csrc/markdup_core.h): records = BAM records back to
+    back in input order, each with its block_size word -> (the flag word every record leaves with, dict of the five counts)"""
+    src = np.frombuffer(bytes(records), np.uint8)
+    n = C.c_uint64(0)
+    info = MarkdupInfo()
+    flags = np.zeros(max(src.size // 36, 1), np.uint16)
+    _check(load().strl_markdup_host(_ptr(src) if src.size else None, src.size, flags.ctypes.data, flags.size, C.byref(n), C.byref(info)))
+    return flags[:n.value].copy(), {k: int(getattr(info, k)) for k, _ in MarkdupInfo._fields_[:5]}
 
 
 def bamsort_key_bits(n_ref):

@@ -34,6 +34,7 @@
 #include "device_util.h"
 #include "bamsort_core.h"
 #include "samparse.h"
+#include "markdup_core.h"
 
 namespace strl {
 
@@ -340,6 +341,8 @@ struct strl_bsort {
   bool win_open = false, win_done = false;     // a window's pass is running | the window is complete and may be fetched from
   uint64_t w_chunks = 0, w_done = 0, w_ord = 0;   // chunks pushed / scattered in this pass; ordinal of the next chunk's first record
   SamParser *sam = nullptr;                    // the input is SAM text (strl_bamsort_sam_begin): no front end, samparse.hip's slots instead
+  // `sort --markdup` (markdup.hip): asked for before the first push | ran | a piece has been gathered: the flags can no longer change
+  bool markdup_on = false, markdup_done = false, fetched = false;
 };
 static_assert(SAM_REC_MAX == FRONT_CARRY_MAX, "a record from SAM text is held to the front end's limit");
 
@@ -388,7 +391,8 @@ static int bsort_place(strl_bsort *B, uint64_t bytes, uint64_t n_more, uint64_t 
       // for the records still to come, and the sort's scratch, the piece and the compressor's buffers
       size_t fr = 0, tot = 0;
       if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = ~(size_t)0 >> 1; }
-      const uint64_t keep = (B->n_records + n_more) * 30ull + ((uint64_t)768 << 20);
+      // (`sort --markdup`: MDUP_RECORD_BYTES more for the step between the finish and the first fetch)
+      const uint64_t keep = (B->n_records + n_more) * (30ull + (B->markdup_on ? MDUP_RECORD_BYTES : 0ull)) + ((uint64_t)768 << 20);
       limit = B->arena_bytes + (fr > keep ? (uint64_t)fr - keep : 0);
       what = "the device's free memory less the finish step's needs";
     }
@@ -896,6 +900,7 @@ extern "C" int strl_bamsort_fetch(strl_ctx *c, uint64_t off, uint64_t bytes, uin
     STRL_HIP(hipStreamSynchronize(c->stream));
     return STRL_OK;
   }
+  B->fetched = true;
   if ((rc = bsort_gather(c, B, off, off + bytes))) return rc;
   STRL_HIP(hipMemcpyAsync(out, B->piece.p, bytes, hipMemcpyDeviceToHost, c->stream));
   STRL_HIP(hipStreamSynchronize(c->stream));
@@ -913,6 +918,7 @@ extern "C" int strl_bamsort_fetch_bgzf(strl_ctx *c, uint64_t off, uint64_t bytes
   STRL_HIP(hipSetDevice(c->device));
   strl_bsort *B = c->bsort;
   if (B->windowed) return bgzf_deflate_device(c, B->deflate_mode, B->window.as<uint8_t>() + (off - B->win_lo), bytes, BSORT_BLK, out, out_cap, out_bytes, nullptr, n_stored);
+  B->fetched = true;
   if ((rc = bsort_gather(c, B, off, off + bytes))) return rc;
   rc = bgzf_deflate_device(c, B->deflate_mode, B->piece.as<uint8_t>(), bytes, BSORT_BLK, out, out_cap, out_bytes, nullptr, n_stored);      // (waits for the stream)
   if (!rc) bsort_gather_time(B);
@@ -924,6 +930,30 @@ extern "C" int strl_bamsort_deflate_mode(strl_ctx *c, int mode) {
   if (mode != STRL_DEFLATE_FAST && mode != STRL_DEFLATE_DENSE) { set_error("strl_bamsort_deflate_mode: mode %d is neither STRL_DEFLATE_FAST nor STRL_DEFLATE_DENSE", mode); return STRL_ERR_ARG; }
   c->bsort->deflate_mode = mode;
   return STRL_OK;
+}
+
+// ---- `sort --markdup`: flag 0x400 decided on the resident records, between the finish and the first fetch (markdup.hip) -----------------
+extern "C" int strl_bamsort_markdup_mode(strl_ctx *c, int on) {
+  if (!c || !c->bsort || c->bsort->chunks || c->bsort->finished) { set_error("strl_bamsort_markdup_mode: behind strl_bamsort_begin / _sam_begin and before the first push"); return STRL_ERR_ARG; }
+  if (c->bsort->windowed && on) { set_error("strl_bamsort_markdup_mode: a windowed sort holds no records to mark"); return STRL_ERR_ARG; }
+  c->bsort->markdup_on = on != 0;
+  return STRL_OK;
+}
+
+extern "C" int strl_bamsort_markdup(strl_ctx *c, strl_markdup_info *out) {
+  if (!c || !c->bsort || !c->bsort->finished) { set_error("strl_bamsort_markdup without strl_bamsort_finish"); return STRL_ERR_ARG; }
+  strl_bsort *B = c->bsort;
+  if (B->windowed) { set_error("strl_bamsort_markdup: a windowed sort holds no records to mark"); return STRL_ERR_ARG; }
+  if (B->fail_rc) { set_error("%s", B->fail.c_str()); return B->fail_rc; }
+  if (B->fetched) { set_error("strl_bamsort_markdup: a piece of the stream has been fetched already"); return STRL_ERR_ARG; }
+  if (B->markdup_done) { set_error("strl_bamsort_markdup: the step has run on this sort already"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  const size_t ns = B->slabs.size();
+  const BsortView V{B->off.as<uint64_t>(), B->src.as<uint64_t>(), B->perm, B->len.as<uint32_t>(), B->d_slab.as<uint8_t *>(), B->d_slab.as<uint64_t>() + ns, (uint32_t)ns, B->n_ref,
+                    B->n_records, B->stream_bytes};
+  B->markdup_done = true;
+  // (a refusal fails the sort: the arena may hold flags of a step that did not end)
+  return bsort_fail(B, markdup_run(c, V, out));
 }
 
 extern "C" int strl_bamsort_order(strl_ctx *c, uint32_t *perm, uint64_t cap) {

@@ -18,6 +18,9 @@
 // lines into page-locked buffers, chunk i + 1 beside the push of chunk i; the device encodes them to BAM records (samparse.hip) in
 // place of the inflate, and everything behind the read phase is the BAM's.  On the host path the same lines go through the same
 // header's host function (sam_core.h) into host memory and then through the host path's tail.  DESIGN section 24.2.
+// --markdup: flag 0x400 on duplicate pairs and fragments (csrc/markdup_core.h; the reference drops such records, collect.nim:140).
+// On the device the step runs over the resident records between the finish and the first fetch (strl_bamsort_markdup); the host path
+// applies the same header's rule to its records before it writes.  DESIGN section 24.3.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,6 +40,7 @@
 #include "sam_feed.h"
 #include "../bamindex_host.h"
 #include "../bamsort_core.h"
+#include "../markdup_core.h"
 #include "../sam_core.h"
 #include "../front.h"
 
@@ -59,6 +63,9 @@ const char *USAGE =
     "                             more for every window of the output that the device can hold; the same bytes as without it.  With\n"
     "                             --write-index the index costs a second read of the output (it is built as `strling bamindex OUT.bam` builds it).\n"
     "                             Not with SAM input: a pipe cannot be read again\n"
+    "      --markdup              set flag 0x400 on duplicate pairs and fragments (and clear it elsewhere), as samtools markdup does in\n"
+    "                             template mode: mates are joined by name on the device, no fixmate, MC or ms tag is needed.  One line on\n"
+    "                             stderr gives the counts.  Not with --windowed: the records are not resident\n"
     "      --deflate=host|device|dense  host (default): zlib at its default level on the pool, as pull.  device: the GPU's compressor (about\n"
     "                             1.15 x the bytes).  dense: the GPU's compressor with its chained, lazy match search (the default's size class)\n"
     "  -D, --device=K             GPU to use (default: 0)\n"
@@ -150,6 +157,9 @@ struct Result {
   const char *deflate = "zlib";
   uint32_t stored = 0;
   Seconds s;
+  bool markdup = false;                       // --markdup: asked for | the counts, and on the device the step's times
+  strl_markdup_info md{};
+  double markdup_s = 0;
 };
 
 // ---- the host path ---------------------------------------------------------------------------------------------------------------
@@ -203,6 +213,17 @@ bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8
   }
   R.s.read = since(t0);
   t0 = Clock::now();
+  if (R.markdup) {                                              // the rule over the records in input order; the decided words into them
+    std::vector<uint16_t> flags;
+    MdupCounts C{};
+    std::string w;
+    const int64_t bad = mdup_host(raw.data(), raw.size(), flags, &C, w);
+    if (bad >= 0) { why = "malformed BAM record " + std::to_string(bad) + ": " + w; return false; }
+    for (size_t i = 0; i < at.size(); ++i) { raw[at[i] + MDUP_FLAG_AT] = (uint8_t)flags[i]; raw[at[i] + MDUP_FLAG_AT + 1] = (uint8_t)(flags[i] >> 8); }
+    R.md.n_pairs = C.pairs; R.md.n_dup_pairs = C.dup_pairs; R.md.n_fragments = C.fragments; R.md.n_dup_fragments = C.dup_fragments; R.md.n_ineligible = C.ineligible;
+    R.markdup_s = since(t0);
+    t0 = Clock::now();
+  }
   const size_t n = at.size();
   std::vector<uint32_t> perm(n);
   std::iota(perm.begin(), perm.end(), 0u);
@@ -317,6 +338,7 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
     const uint64_t limit = cap_mb && atof(cap_mb) > 0 ? (uint64_t)(atof(cap_mb) * 1048576.0) : 0;
     const SamHeader &H = sam->header;
     int rc = strl_bamsort_sam_begin(ctx, H.names.data(), H.name_off.data(), (int32_t)H.l_ref.size(), limit);
+    if (!rc && R.markdup) rc = strl_bamsort_markdup_mode(ctx, 1);
     if (!rc) rc = strl_bamsort_sam_reserve(ctx, cap);
     if (rc) return fail(rc);
     for (uint64_t ci = 0;; ++ci) {
@@ -336,6 +358,7 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
     const uint64_t limit = cap && atof(cap) > 0 ? (uint64_t)(atof(cap) * 1048576.0) : 0;
     int rc = windowed ? strl_bamsort_begin_windowed(ctx, (int32_t)feed.targets().size(), feed.first_record_offset())
                       : strl_bamsort_begin(ctx, (int32_t)feed.targets().size(), feed.first_record_offset(), limit);
+    if (!rc && R.markdup) rc = strl_bamsort_markdup_mode(ctx, 1);
     if (!rc) rc = strl_bamsort_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes);
     return rc;
   }, strl_bamsort_push);
@@ -346,6 +369,11 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
   int rc = strl_bamsort_finish(ctx, header.data(), header.size(), &info);
   if (rc) return fail(rc);
   R.s.sort = since(t0);
+  if (R.markdup) {                                              // every record lies on the device: the flags before the first piece is gathered
+    t0 = Clock::now();
+    if ((rc = strl_bamsort_markdup(ctx, &R.md))) return fail(rc);
+    R.markdup_s = since(t0);
+  }
   if (core && (rc = strl_bamsort_deflate_mode(ctx, mode))) return fail(rc);      // the rule of every fetch_bgzf below
   R.records = info.n_records; R.no_ref = info.n_no_ref; R.stream_bytes = info.stream_bytes; R.already_sorted = info.already_sorted != 0; R.slabs = info.n_slabs;
   if (sam) {
@@ -454,11 +482,12 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
 int sort_main(int argc, char **argv) {
   if (argc <= 2) { fputs(USAGE, stdout); return 0; }
   const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"deflate", 0, true}, {"device", 'D', true}, {"verbose", 'v', false},
-                                       {"write-index", 0, false}, {"index-out", 0, true}, {"csi", 0, false}, {"min-shift", 'm', true}, {"windowed", 0, false}}, USAGE);
+                                       {"write-index", 0, false}, {"index-out", 0, true}, {"csi", 0, false}, {"min-shift", 'm', true}, {"windowed", 0, false}, {"markdup", 0, false}}, USAGE);
   if (a.pos.size() != 1) quit("expected 1 argument (bam, sam or - for SAM text on stdin)\n%s", USAGE);
   if (!a.flag("output")) quit("[strling] sort: -o OUT.bam is required\n%s", USAGE);
   if (a.flag("index-out") && !a.flag("write-index")) quit("--index-out needs --write-index\n%s", USAGE);
   if (a.flag("csi") && !a.flag("write-index")) quit("--csi needs --write-index\n%s", USAGE);
+  if (a.flag("markdup") && a.flag("windowed")) quit("[strling] sort: --markdup --windowed: the records are not resident; sort without --windowed or mark with samtools (status %d)", STRL_ERR_ARG);
   Index X;
   X.on = a.flag("write-index");
   X.min_shift = csi_min_shift(a, USAGE);
@@ -517,6 +546,7 @@ int sort_main(int argc, char **argv) {
   std::string why;
   int status = 0;
   Result R;
+  R.markdup = a.flag("markdup");
   strl_ctx *ctx = nullptr;
   std::function<strl_ctx *(std::string &)> ctx_again = [&](std::string &) { return ctx; };      // the context once it is up
   bool ok;
@@ -561,18 +591,23 @@ int sort_main(int argc, char **argv) {
     X.s += since(t0);
   }
   const bool indexed = X.on && !X.rc;
+  if (R.markdup)
+    fprintf(stderr, "[strling] sort: markdup: %llu pairs, %llu duplicate pairs, %llu fragments, %llu duplicate fragments, %llu ineligible records\n", (unsigned long long)R.md.n_pairs,
+            (unsigned long long)R.md.n_dup_pairs, (unsigned long long)R.md.n_fragments, (unsigned long long)R.md.n_dup_fragments, (unsigned long long)R.md.n_ineligible);
   if (a.flag("verbose"))
     fprintf(stderr,
             "{\"command\": \"sort\", \"path\": \"%s\", \"records\": %llu, \"no_reference\": %llu, \"stream_bytes\": %llu, \"out_bytes\": %llu, \"already_sorted\": %s, \"slabs\": %llu, "
             "\"seconds\": %.3f, \"read_s\": %.3f, \"sort_s\": %.3f, \"gather_s\": %.3f, \"deflate_s\": %.3f, \"write_s\": %.3f, \"deflate\": \"%s\", \"stored\": %u, "
             "\"index\": \"%s\", \"index_bytes\": %llu, \"index_chunks\": %llu, \"index_s\": %.3f, \"windows\": %llu, \"window_bytes\": %llu, \"window_s\": %.3f, "
             "\"input\": \"%s\", \"lines\": %llu, \"text_bytes\": %llu, \"host_finished\": %llu, \"sam_copy_ms\": %.3f, \"sam_scan_ms\": %.3f, \"sam_size_ms\": %.3f, "
-            "\"sam_encode_ms\": %.3f}\n",
+            "\"sam_encode_ms\": %.3f, \"markdup\": %s, \"markdup_s\": %.3f, \"markdup_record_ms\": %.3f, \"markdup_join_ms\": %.3f, \"markdup_pairs_ms\": %.3f, "
+            "\"markdup_fragments_ms\": %.3f, \"markdup_flag_ms\": %.3f}\n",
             on_host ? "host" : "device", (unsigned long long)R.records, (unsigned long long)R.no_ref, (unsigned long long)R.stream_bytes, (unsigned long long)R.out_bytes,
             R.already_sorted ? "true" : "false", (unsigned long long)R.slabs, since(t_all), R.s.read, R.s.sort, R.s.gather, R.s.deflate, R.s.write, R.deflate, R.stored,
             !indexed ? "none" : X.min_shift >= 0 ? "csi" : "bai", (unsigned long long)(indexed ? index_bytes : 0), (unsigned long long)(indexed ? X.chunks : 0), X.s,
             (unsigned long long)R.windows, (unsigned long long)R.window_bytes, R.s.window, sam ? "sam" : "bam", (unsigned long long)R.lines, (unsigned long long)R.text_bytes,
-            (unsigned long long)R.host_finished, R.sam_ms[0], R.sam_ms[1], R.sam_ms[2], R.sam_ms[3]);
+            (unsigned long long)R.host_finished, R.sam_ms[0], R.sam_ms[1], R.sam_ms[2], R.sam_ms[3], R.markdup ? "true" : "false", R.markdup_s, R.md.record_ms, R.md.join_ms,
+            R.md.pairs_ms, R.md.fragments_ms, R.md.flag_ms);
   if (X.on && X.rc) {
     if (ctx) strl_ctx_destroy(ctx);
     quit("[strling] sort: sorted file written; index refused: %s (status %d)", X.why.c_str(), X.rc);

@@ -163,6 +163,7 @@ int front_init_slots(strl_ctx *c, strl_front *F);
 int front_begin_scan(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset);   // the front end without strl_front_begin's per-read state (bamindex.hip)
 struct BsortView;
 int bsort_view(strl_ctx *c, BsortView *v, strl_bai ***slot);      // bamsort.hip: the finished sort of the context, for strl_bamsort_index
+int markdup_run(strl_ctx *c, const BsortView &V, strl_markdup_info *out);      // markdup.hip: flag 0x400 on the records of a finished resident sort
 // bamindex.hip: the index builder behind strl_front_begin's own pass (strl_front_index_*); no-ops without one.  Neither waits
 // for the device, neither can fail the extraction.
 //   bai_front_chunk   a chunk has been handed over to slot si: its block table (whole_file: no other context took the chunk before)

@@ -33,6 +33,12 @@ K runs each: wall time and the read phase.  Then, for every group size of --lane
 gives the HIP-event time of the chunks' copies and of the three kernels (line scan, size with the sums, encode): GB/s of text each,
 and the kernels' time a chunk beside that chunk's copy time.  The SAM outputs must be the BAM's sort with the bin field aside (the
 benchmark's BAM writer gives every record bin 4680).
+    python tools/sort_bench.py --markdup [--parent-cli PATH] [--pairs N] [--repeats K]
+--markdup measures `sort --markdup`: alternating with --parent-cli's (default: this build's) plain `sort` of
+the same file, K runs each, for both --deflate forms: wall time, the step's wall time (markdup_s) and the HIP-event time of its five
+parts -- the record kernel, the join by name (a sort and the runs kernel), the pairs' and the fragments' chained sorts, the flag
+kernel -- and the time added as a share of the parent's command; then STRL_SORT=host with the option.  The device file with
+--deflate=host must be the host path's, and the counts must agree.
 `samtools sort` is not on these machines: nothing here compares with it.  No threshold is asserted.
 """
 import argparse
@@ -142,6 +148,41 @@ def _stats_csv(cmd, env, work, dest):
     for row in csv.DictReader(open(dest)):
         rows[row["Name"]] = {"calls": int(row["Calls"]), "total_ms": round(float(row["TotalDurationNs"]) / 1e6, 3)}
     return rows, None
+
+
+def markdup_runs(a, cli, src, work):
+    """`sort --markdup` against the parent's plain `sort` of the same file, alternating; then the host path"""
+    parent = a.parent_cli or cli
+    ours, theirs, host = (os.path.join(work, n) for n in ("markdup.bam", "parent.bam", "markdup_host.bam"))
+    keys = ("markdup_s", "markdup_record_ms", "markdup_join_ms", "markdup_pairs_ms", "markdup_fragments_ms", "markdup_flag_ms", "read_s", "sort_s")
+    counts = {}
+    for form in ("host", "device"):
+        walls = {"sort --markdup": [], "parent sort": []}
+        for k in range(a.repeats):
+            for who in (("sort --markdup", "parent sort") if k % 2 == 0 else ("parent sort", "sort --markdup")):      # the order swapped every repeat
+                if who == "parent sort":
+                    _, w = _timed([parent, "sort", f"--deflate={form}", "-o", theirs, src])
+                    print(json.dumps({"run": who, "deflate": form, "repeat": k, "wall_s": w}), flush=True)
+                else:
+                    r, w = _timed([cli, "sort", "--markdup", "-v", f"--deflate={form}", "-o", ours, src])
+                    says = json.loads(r.stderr.strip().splitlines()[-1])
+                    counts[form] = [l for l in r.stderr.splitlines() if "markdup:" in l][-1]
+                    print(json.dumps({"run": who, "deflate": form, "repeat": k, "wall_s": w, **{x: says.get(x) for x in keys}}), flush=True)
+                walls[who].append(w)
+        med = {who: sorted(v)[len(v) // 2] for who, v in walls.items()}
+        print(json.dumps({"summary": "markdup", "deflate": form, "median_wall_s": med,
+                          "added_share_of_parent": round((med["sort --markdup"] - med["parent sort"]) / med["parent sort"], 4)}), flush=True)
+    r, w = _timed([cli, "sort", "--markdup", "--deflate=host", "-o", ours, src])
+    e = dict(os.environ, STRL_SORT="host")
+    t = time.time()
+    h = subprocess.run([cli, "sort", "--markdup", "-v", "-o", host, src], capture_output=True, text=True, env=e, timeout=3000)
+    if h.returncode != 0:
+        sys.stderr.write(h.stderr[-4000:])
+        sys.exit(h.returncode)
+    hc = [l for l in h.stderr.splitlines() if "markdup:" in l][-1]
+    print(json.dumps({"run": "STRL_SORT=host sort --markdup", "wall_s": round(time.time() - t, 3), "markdup_s": json.loads(h.stderr.strip().splitlines()[-1]).get("markdup_s")}), flush=True)
+    print(json.dumps({"check": "markdup", "device_file_equals_host_file": open(ours, "rb").read() == open(host, "rb").read(), "counts_agree": counts.get("host") == hc == counts.get("device"),
+                      "counts": hc}), flush=True)
 
 
 def windowed_runs(a, cli, src, work, inflated):
@@ -306,6 +347,7 @@ def main():
     ap.add_argument("--windowed", action="store_true")
     ap.add_argument("--dense", action="store_true", help="the plain runs with --deflate=dense (and --parent-cli's --deflate=host) beside them")
     ap.add_argument("--sam", action="store_true", help="SAM text as the input, from a file and from a pipe, beside the BAM's sort")
+    ap.add_argument("--markdup", action="store_true", help="`sort --markdup` beside --parent-cli's plain sort: the step's times and the time added")
     ap.add_argument("--window-mb", default="", help="with --windowed: comma-separated window sizes in MiB (default: the sizes that give 1, 2 and 4 windows)")
     a = ap.parse_args()
     t0 = time.time()
@@ -318,6 +360,10 @@ def main():
     print(json.dumps(base), flush=True)
     if a.write_index:
         write_index_runs(a, cli, src, work)
+        shutil.rmtree(work, ignore_errors=True)
+        return
+    if a.markdup:
+        markdup_runs(a, cli, src, work)
         shutil.rmtree(work, ignore_errors=True)
         return
     if a.sam:

@@ -91,6 +91,22 @@ PY
   else
     echo "SKIP  sort_sam   (needs a strling whose sort reads SAM text)"
   fi
+  # sort --markdup: flag 0x400 per (name, read number) against samtools' own pipeline over the same records -- collate, fixmate -m,
+  # sort, markdup in template mode (its default; no optical distance, no library split: -l is not given and the input has one
+  # library).  Secondary, supplementary, QC-fail and unmapped records are left out of the comparison's lines only when samtools
+  # itself leaves their flag alone.  Never run: no machine this was built on had samtools.
+  if "$S" sort 2> /dev/null | grep -q -- "--markdup"; then
+    "$S" sort --markdup -o "$T/markdup_ours.bam" "$T/sort_in.bam" >> "$T/sort.log" 2>&1 || echo "      (sort: strling sort --markdup exited non-zero, see $T/sort.log)"
+    samtools collate -O -u "$T/sort_in.bam" "$T/collate_tmp" 2>> "$T/sort.log" | samtools fixmate -m -u - - 2>> "$T/sort.log" | samtools sort -u - 2>> "$T/sort.log" |
+      samtools markdup --no-PG - "$T/markdup_theirs.bam" >> "$T/sort.log" 2>&1
+    for w in ours theirs; do
+      samtools view "$T/markdup_$w.bam" 2>> "$T/sort.log" | awk -F'\t' '{ f = $2; rn = int(f / 64) % 4; sup = int(f / 256) % 2 + int(f / 2048) % 2 * 2; print $1 "\t" rn "\t" sup "\t" $3 "\t" $4 "\t" int(f / 1024) % 2 }' |
+        LC_ALL=C sort > "$T/markdup_$w.txt"
+    done
+    check sort_markdup "$T/markdup_ours.txt" "$T/markdup_theirs.txt" "sort --markdup sets 0x400 where samtools collate | fixmate -m | sort | markdup sets it"
+  else
+    echo "SKIP  sort_markdup   (needs a strling with sort --markdup)"
+  fi
 else
   echo "SKIP  sort   (needs samtools and a strling with the sort command: the order stays checked against its own statement in tests/sort_bam_cases.py only)"
 fi
