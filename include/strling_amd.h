@@ -997,6 +997,44 @@ typedef struct {
 int strl_bamsort_markdup_mode(strl_ctx *ctx, int on);
 int strl_bamsort_markdup(strl_ctx *ctx, strl_markdup_info *info);
 int strl_markdup_host(const uint8_t *records, uint64_t bytes, uint16_t *flags, uint64_t cap, uint64_t *n_records, strl_markdup_info *info);
+/* `strling fastq` (csrc/fastq.hip, the rule in csrc/fastq_core.h): the reads of a resident sort back to paired
+ * FASTQ, the step in front of the aligner (what `samtools collate | samtools fastq` is used for).  Mates are joined by NAME on the
+ * device; three byte streams come out: 0 = p1 (R1 entries, or R1 R2 R1 R2 ... when interleaved), 1 = p2 (R2 entries; empty when
+ * interleaved), 2 = s (singles; empty unless opts.singles).  Agreement with samtools is unverified.
+ *   strl_bamsort_fastq_mode   behind strl_bamsort_begin / _sam_begin and before the first push (else STRL_ERR_ARG): the pushes' arena
+ *                             limit then leaves the step's 57 bytes a record free.  STRL_ERR_ARG on a windowed sort and together
+ *                             with strl_bamsort_markdup_mode.
+ *   strl_bamsort_fastq        behind strl_bamsort_finish, once: the record kernel (field check, class, name hash, entry length), the
+ *                             join by name, and one 64-bit prefix sum a stream; fills the counts and the three streams' lengths.
+ *                             STRL_ERR_ARG before the finish, a second time, without the mode, on a windowed sort.  STRL_ERR_FORMAT: a
+ *                             record whose name, CIGAR, bases and qualities do not fit its block_size (the message names its
+ *                             ordinal).  STRL_ERR_LIMIT: more than 512 kept records under one name hash (the message names the count
+ *                             and the host path, STRL_FASTQ=host, which has no such limit).
+ *   strl_bamsort_fastq_fetch  behind strl_bamsort_fastq: bytes [lo, lo + len) of a stream to dst, any lo and any len inside the
+ *                             stream (len < 4 GiB); nothing outside dst[0, len) is written.  STRL_ERR_ARG otherwise.
+ *   strl_bamsort_fastq_info_now  the info again, text_ms and text_bytes summed over the fetches so far.
+ *   strl_fastq_host           the same rule without a device: records[0, bytes) = records back to back in input order, each with its
+ *                             block_size word.  info (not null) gets the counts and the streams' lengths; a stream is copied to
+ *                             out[k] when cap[k] holds it, else STRL_ERR_CAPACITY (call with cap = {0, 0, 0} for the lengths).
+ * STRL_FASTQ_HASH_BITS = 1 .. 63 (tests; read once per process): the name hash cut to that many bits. */
+typedef struct {
+  uint32_t filter;        /* -F: records with any of these flag bits are left out (default 0x900) */
+  uint32_t suffix;        /* -N: /1 and /2 behind the names of reads with read number 1 and 2 */
+  uint32_t default_qual;  /* -v: the quality of every base of a read without qualities (default 1) */
+  uint32_t interleaved;   /* -o: each R2 behind its R1 in stream 0 */
+  uint32_t singles;       /* -s: stream 2 is laid out; else singles are counted as not written */
+} strl_fastq_opts;
+typedef struct {
+  uint64_t n_kept, n_filtered, n_empty, n_pairs, n_singles, n_singles_unwritten;
+  uint64_t stream_bytes[3];
+  uint64_t text_bytes;                                /* bytes the text kernel has written so far */
+  double record_ms, join_ms, layout_ms, text_ms;      /* HIP-event time of the step's parts; text_ms over the fetches so far */
+} strl_fastq_info;
+int strl_bamsort_fastq_mode(strl_ctx *ctx, int on);
+int strl_bamsort_fastq(strl_ctx *ctx, const strl_fastq_opts *opts, strl_fastq_info *info);
+int strl_bamsort_fastq_fetch(strl_ctx *ctx, int stream, uint64_t lo, uint64_t len, uint8_t *dst);
+int strl_bamsort_fastq_info_now(strl_ctx *ctx, strl_fastq_info *info);
+int strl_fastq_host(const uint8_t *records, uint64_t bytes, const strl_fastq_opts *opts, uint8_t *const out[3], const uint64_t cap[3], strl_fastq_info *info);
 
 /* ---- the .bai as a by-product of `strling extract`'s own pass (`strling extract --write-index`) ----
  * strl_front_push already copies, inflates, CRC-checks, record-scans and parses every block; the index needs of a record only

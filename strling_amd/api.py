@@ -70,6 +70,27 @@ class MarkdupInfo(C.Structure):
                 ("record_ms", C.c_double), ("join_ms", C.c_double), ("pairs_ms", C.c_double), ("fragments_ms", C.c_double), ("flag_ms", C.c_double)]
 
 
+class FastqOpts(C.Structure):
+    """strl_fastq_opts: -F, -N, -v, interleaved (-o) or split (-1 -2), and whether the singles' stream is laid out (-s)"""
+    _fields_ = [("filter", C.c_uint32), ("suffix", C.c_uint32), ("default_qual", C.c_uint32), ("interleaved", C.c_uint32), ("singles", C.c_uint32)]
+
+
+class FastqInfo(C.Structure):
+    """strl_fastq_info: the six counts of `strling fastq`, the three streams' lengths and the HIP-event time of the device step's parts"""
+    _fields_ = [("n_kept", C.c_uint64), ("n_filtered", C.c_uint64), ("n_empty", C.c_uint64), ("n_pairs", C.c_uint64), ("n_singles", C.c_uint64), ("n_singles_unwritten", C.c_uint64),
+                ("stream_bytes", C.c_uint64 * 3), ("text_bytes", C.c_uint64), ("record_ms", C.c_double), ("join_ms", C.c_double), ("layout_ms", C.c_double), ("text_ms", C.c_double)]
+
+
+def _fastq_opts(filter=0x900, suffix=False, default_qual=1, interleaved=True, singles=False):
+    return FastqOpts(int(filter), int(bool(suffix)), int(default_qual), int(bool(interleaved)), int(bool(singles)))
+
+
+def _fastq_info(info):
+    d = {k: getattr(info, k) for k, _ in FastqInfo._fields_ if k != "stream_bytes"}
+    d["stream_bytes"] = [int(x) for x in info.stream_bytes]
+    return d
+
+
 class BamsortSamFigures(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("text_bytes", C.c_uint64), ("host_finished", C.c_uint64), ("chunks", C.c_uint64),
                 ("copy_ms", C.c_double), ("scan_ms", C.c_double), ("size_ms", C.c_double), ("encode_ms", C.c_double)]
@@ -170,7 +191,8 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_bamsort_begin_windowed", "strl_bamsort_window_limit", "strl_bamsort_window_begin", "strl_bamsort_window_push", "strl_bamsort_window_end",
            "strl_bamsort_window_plan",
            "strl_bamsort_sam_begin", "strl_bamsort_sam_reserve", "strl_bamsort_push_sam", "strl_bamsort_sam_info", "strl_sam_encode", "strl_sam_header",
-           "strl_bamsort_markdup_mode", "strl_bamsort_markdup", "strl_markdup_host"]
+           "strl_bamsort_markdup_mode", "strl_bamsort_markdup", "strl_markdup_host",
+           "strl_bamsort_fastq_mode", "strl_bamsort_fastq", "strl_bamsort_fastq_fetch", "strl_bamsort_fastq_info_now", "strl_fastq_host"]
 
 
 def lib_path():
@@ -329,6 +351,11 @@ def load(build_if_missing=True):
     L.strl_bamsort_markdup_mode.argtypes = [C.c_void_p, C.c_int]
     L.strl_bamsort_markdup.argtypes = [C.c_void_p, C.POINTER(MarkdupInfo)]
     L.strl_markdup_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(MarkdupInfo)]
+    L.strl_bamsort_fastq_mode.argtypes = [C.c_void_p, C.c_int]
+    L.strl_bamsort_fastq.argtypes = [C.c_void_p, C.POINTER(FastqOpts), C.POINTER(FastqInfo)]
+    L.strl_bamsort_fastq_fetch.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.strl_bamsort_fastq_info_now.argtypes = [C.c_void_p, C.POINTER(FastqInfo)]
+    L.strl_fastq_host.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(FastqOpts), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(FastqInfo)]
     L.strl_sam_encode.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.strl_sam_header.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     L.strl_bamsort_window_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -1145,6 +1172,32 @@ class Context:
         _check(self.L.strl_bamsort_markdup(self.h, C.byref(info)))
         return {k: getattr(info, k) for k, _ in MarkdupInfo._fields_}
 
+    # ---- `strling fastq` (strl_bamsort_fastq_mode / _fastq / _fastq_fetch): the resident records as FASTQ text
+    def bamsort_fastq_mode(self, on=True):
+        """behind bamsort_begin / bamsort_sam_begin and before the first push; not together with bamsort_markdup_mode"""
+        _check(self.L.strl_bamsort_fastq_mode(self.h, 1 if on else 0))
+
+    def bamsort_fastq(self, **opts):
+        """behind bamsort_finish, once: the join and the layout.  opts: filter, suffix, default_qual, interleaved, singles
+        -> dict of strl_fastq_info (stream_bytes = the lengths of p1, p2 and s)"""
+        o, info = _fastq_opts(**opts), FastqInfo()
+        _check(self.L.strl_bamsort_fastq(self.h, C.byref(o), C.byref(info)))
+        return _fastq_info(info)
+
+    def bamsort_fastq_fetch(self, stream, lo, nbytes, canary=0):
+        """bytes [lo, lo + nbytes) of stream 0 (p1), 1 (p2) or 2 (s).  canary > 0 (tests): that many guard bytes on either side of
+        the destination, checked to be untouched"""
+        out = np.full(max(1, nbytes) + 2 * canary, 0xA5, np.uint8)
+        _check(self.L.strl_bamsort_fastq_fetch(self.h, int(stream), int(lo), int(nbytes), out.ctypes.data + canary))
+        if canary and not ((out[:canary] == 0xA5).all() and (out[canary + nbytes:][-canary:] == 0xA5).all()):
+            raise AssertionError("strl_bamsort_fastq_fetch wrote outside its destination")
+        return out[canary:canary + nbytes].tobytes()
+
+    def bamsort_fastq_info(self):
+        info = FastqInfo()
+        _check(self.L.strl_bamsort_fastq_info_now(self.h, C.byref(info)))
+        return _fastq_info(info)
+
     def bamsort_probe(self, lens, base, lo, hi):
         """test-only (strl_bamsort_probe): the layout and the piece search over caller-given lengths and a 64-bit base
         -> (off uint64[n + 1], (first, end) of the touched records, parts uint64[touched, 3] = source skip, destination, bytes)"""
@@ -1639,6 +1692,21 @@ def markdup_host(records):
     flags = np.zeros(max(src.size // 36, 1), np.uint16)
     _check(load().strl_markdup_host(_ptr(src) if src.size else None, src.size, flags.ctypes.data, flags.size, C.byref(n), C.byref(info)))
     return flags[:n.value].copy(), {k: int(getattr(info, k)) for k, _ in MarkdupInfo._fields_[:5]}
+
+
+def fastq_host(records, **opts):
+    """the rule of `strling fastq` without a device (strl_fastq_host; csrc/fastq_core.h): records = BAM records back to back in input
+    order, each with its block_size word; opts as Context.bamsort_fastq's -> ([p1, p2, s] as bytes, dict of the six counts)"""
+    src = np.frombuffer(bytes(records), np.uint8)
+    o, info = _fastq_opts(**opts), FastqInfo()
+    L = load()
+    ptr = _ptr(src) if src.size else None
+    rc = L.strl_fastq_host(ptr, src.size, C.byref(o), None, (C.c_uint64 * 3)(0, 0, 0), C.byref(info))
+    if rc not in (0, -4):
+        _check(rc)
+    bufs = [np.zeros(max(1, int(n)), np.uint8) for n in info.stream_bytes]
+    _check(L.strl_fastq_host(ptr, src.size, C.byref(o), (C.c_void_p * 3)(*[b.ctypes.data for b in bufs]), (C.c_uint64 * 3)(*[b.size for b in bufs]), C.byref(info)))
+    return [b[:int(n)].tobytes() for b, n in zip(bufs, info.stream_bytes)], {k: int(getattr(info, k)) for k, _ in FastqInfo._fields_[:6]}
 
 
 def bamsort_key_bits(n_ref):

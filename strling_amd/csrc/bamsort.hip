@@ -35,6 +35,7 @@
 #include "bamsort_core.h"
 #include "samparse.h"
 #include "markdup_core.h"
+#include "fastq_core.h"
 
 namespace strl {
 
@@ -343,12 +344,16 @@ struct strl_bsort {
   SamParser *sam = nullptr;                    // the input is SAM text (strl_bamsort_sam_begin): no front end, samparse.hip's slots instead
   // `sort --markdup` (markdup.hip): asked for before the first push | ran | a piece has been gathered: the flags can no longer change
   bool markdup_on = false, markdup_done = false, fetched = false;
+  // `strling fastq` (fastq.hip): asked for before the first push | the plan of the three streams, once strl_bamsort_fastq has run
+  bool fastq_on = false;
+  FastqPlan *fastq = nullptr;
 };
 static_assert(SAM_REC_MAX == FRONT_CARRY_MAX, "a record from SAM text is held to the front end's limit");
 
 void bsort_destroy(strl_bsort *B) {
   if (!B) return;
   if (B->index) bai_destroy(B->index);
+  fastq_destroy(B->fastq);
   if (B->sam) sam_parser_destroy(B->sam);
   if (B->h_state) (void)hipHostFree(B->h_state);
   if (B->h_wstate) (void)hipHostFree(B->h_wstate);
@@ -392,7 +397,8 @@ static int bsort_place(strl_bsort *B, uint64_t bytes, uint64_t n_more, uint64_t 
       size_t fr = 0, tot = 0;
       if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = ~(size_t)0 >> 1; }
       // (`sort --markdup`: MDUP_RECORD_BYTES more for the step between the finish and the first fetch)
-      const uint64_t keep = (B->n_records + n_more) * (30ull + (B->markdup_on ? MDUP_RECORD_BYTES : 0ull)) + ((uint64_t)768 << 20);
+      // (`strling fastq`: FASTQ_RECORD_BYTES more for its plan)
+      const uint64_t keep = (B->n_records + n_more) * (30ull + (B->markdup_on ? MDUP_RECORD_BYTES : 0ull) + (B->fastq_on ? FASTQ_RECORD_BYTES : 0ull)) + ((uint64_t)768 << 20);
       limit = B->arena_bytes + (fr > keep ? (uint64_t)fr - keep : 0);
       what = "the device's free memory less the finish step's needs";
     }
@@ -936,6 +942,7 @@ extern "C" int strl_bamsort_deflate_mode(strl_ctx *c, int mode) {
 extern "C" int strl_bamsort_markdup_mode(strl_ctx *c, int on) {
   if (!c || !c->bsort || c->bsort->chunks || c->bsort->finished) { set_error("strl_bamsort_markdup_mode: behind strl_bamsort_begin / _sam_begin and before the first push"); return STRL_ERR_ARG; }
   if (c->bsort->windowed && on) { set_error("strl_bamsort_markdup_mode: a windowed sort holds no records to mark"); return STRL_ERR_ARG; }
+  if (c->bsort->fastq_on && on) { set_error("strl_bamsort_markdup_mode: not together with strl_bamsort_fastq_mode"); return STRL_ERR_ARG; }
   c->bsort->markdup_on = on != 0;
   return STRL_OK;
 }
@@ -954,6 +961,54 @@ extern "C" int strl_bamsort_markdup(strl_ctx *c, strl_markdup_info *out) {
   B->markdup_done = true;
   // (a refusal fails the sort: the arena may hold flags of a step that did not end)
   return bsort_fail(B, markdup_run(c, V, out));
+}
+
+// ---- `strling fastq`: the resident records as FASTQ text, behind the finish (fastq.hip) ---------------------------------------------------
+extern "C" int strl_bamsort_fastq_mode(strl_ctx *c, int on) {
+  if (!c || !c->bsort || c->bsort->chunks || c->bsort->finished) { set_error("strl_bamsort_fastq_mode: behind strl_bamsort_begin / _sam_begin and before the first push"); return STRL_ERR_ARG; }
+  if (c->bsort->windowed && on) { set_error("strl_bamsort_fastq_mode: a windowed sort holds no records to write"); return STRL_ERR_ARG; }
+  if (c->bsort->markdup_on && on) { set_error("strl_bamsort_fastq_mode: not together with strl_bamsort_markdup_mode"); return STRL_ERR_ARG; }
+  c->bsort->fastq_on = on != 0;
+  return STRL_OK;
+}
+
+static BsortView bsort_view_of(strl_bsort *B) {
+  const size_t ns = B->slabs.size();
+  return BsortView{B->off.as<uint64_t>(), B->src.as<uint64_t>(), B->perm, B->len.as<uint32_t>(), B->d_slab.as<uint8_t *>(), B->d_slab.as<uint64_t>() + ns, (uint32_t)ns, B->n_ref,
+                   B->n_records, B->stream_bytes};
+}
+
+extern "C" int strl_bamsort_fastq(strl_ctx *c, const strl_fastq_opts *opts, strl_fastq_info *out) {
+  if (!c || !c->bsort || !c->bsort->finished || !opts) { set_error("strl_bamsort_fastq without strl_bamsort_finish"); return STRL_ERR_ARG; }
+  strl_bsort *B = c->bsort;
+  if (B->windowed) { set_error("strl_bamsort_fastq: a windowed sort holds no records to write"); return STRL_ERR_ARG; }
+  if (B->fail_rc) { set_error("%s", B->fail.c_str()); return B->fail_rc; }
+  if (!B->fastq_on) { set_error("strl_bamsort_fastq without strl_bamsort_fastq_mode before the first push"); return STRL_ERR_ARG; }
+  if (B->fastq) { set_error("strl_bamsort_fastq: the step has run on this sort already"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  // (a refusal fails the sort: its plan is no plan)
+  return bsort_fail(B, fastq_plan(c, bsort_view_of(B), opts, &B->fastq, out));
+}
+
+static int bsort_fastq_check(strl_ctx *c, const char *who) {
+  if (!c || !c->bsort || !c->bsort->finished || !c->bsort->fastq) { set_error("%s without strl_bamsort_fastq", who); return STRL_ERR_ARG; }
+  if (c->bsort->fail_rc) { set_error("%s", c->bsort->fail.c_str()); return c->bsort->fail_rc; }
+  return STRL_OK;
+}
+
+extern "C" int strl_bamsort_fastq_fetch(strl_ctx *c, int stream, uint64_t lo, uint64_t len, uint8_t *dst) {
+  int rc;
+  if ((rc = bsort_fastq_check(c, "strl_bamsort_fastq_fetch"))) return rc;
+  STRL_HIP(hipSetDevice(c->device));
+  return fastq_fetch(c, c->bsort->fastq, bsort_view_of(c->bsort), stream, lo, len, dst);
+}
+
+extern "C" int strl_bamsort_fastq_info_now(strl_ctx *c, strl_fastq_info *info) {
+  int rc;
+  if ((rc = bsort_fastq_check(c, "strl_bamsort_fastq_info_now"))) return rc;
+  if (!info) { set_error("null argument"); return STRL_ERR_ARG; }
+  *info = *fastq_info(c->bsort->fastq);
+  return STRL_OK;
 }
 
 extern "C" int strl_bamsort_order(strl_ctx *c, uint32_t *perm, uint64_t cap) {

@@ -68,3 +68,4 @@ bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, const st
                int &status, int csi_min_shift);
 
 int sort_main(int argc, char **argv);       // sort_cli.cpp
+int fastq_main(int argc, char **argv);      // sort_cli.cpp: `strling fastq`, a mode of sort's driver

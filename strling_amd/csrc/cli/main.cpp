@@ -3158,7 +3158,8 @@ int main(int argc, char **argv) {
       "  outliers :   cohort STR outlier scores from the call outputs of many samples (scripts/strling-outliers.py).\n"
       "  bamindex :   build the index (.bai, or .csi with --csi) of a coordinate-sorted BAM on the GPU (what `samtools index` writes).\n"
       "  pull     :   write a region's reads and their mates to a small BAM, for debugging (the reference's pull_region).\n"
-      "  sort     :   coordinate-sort a BAM on the GPU (what `samtools sort` writes; --write-index: its index from the same pass).\n";      // strling.nim:18-24
+      "  sort     :   coordinate-sort a BAM on the GPU (what `samtools sort` writes; --write-index: its index from the same pass).\n"
+      "  fastq    :   a BAM's reads back to paired FASTQ on the GPU, mates joined by name (the step in front of the aligner).\n";      // strling.nim:18-24
   if (argc < 2) { fputs(top, stdout); return 1; }
   const std::string cmd = argv[1];
   if (cmd == "extract") return extract_main(argc, argv);
@@ -3169,6 +3170,7 @@ int main(int argc, char **argv) {
   if (cmd == "bamindex") return bamindex_main(argc, argv);
   if (cmd == "pull") return pull_main(argc, argv);
   if (cmd == "sort") return sort_main(argc, argv);
+  if (cmd == "fastq") return fastq_main(argc, argv);
   if (cmd == "_dump") return dump_main(argc, argv);
   if (cmd == "_decode") return decode_main(argc, argv);
   if (cmd == "_region") return region_main(argc, argv);

@@ -21,6 +21,9 @@
 // --markdup: flag 0x400 on duplicate pairs and fragments (csrc/markdup_core.h; the reference drops such records, collect.nim:140).
 // On the device the step runs over the resident records between the finish and the first fetch (strl_bamsort_markdup); the host path
 // applies the same header's rule to its records before it writes.  DESIGN section 24.3.
+// `strling fastq` (fastq_main below) is a mode of this driver: the same feeds fill the same arena, and behind the finish the reads go
+// out as FASTQ text (strl_bamsort_fastq / _fastq_fetch; the rule is csrc/fastq_core.h's) instead of as a sorted BAM.  The host path
+// (STRL_FASTQ=host, or no device) applies the same header's rule to its records.  DESIGN section 24.4.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,6 +44,7 @@
 #include "../bamindex_host.h"
 #include "../bamsort_core.h"
 #include "../markdup_core.h"
+#include "../fastq_core.h"
 #include "../sam_core.h"
 #include "../front.h"
 
@@ -162,11 +166,122 @@ struct Result {
   double markdup_s = 0;
 };
 
+// ---- `strling fastq`: what was asked for, where the three streams go, what the step gave ------------------------------------------------
+// one output: a file written under a temporary name and renamed at the end (a failed run leaves no file), or stdout
+struct FastqOut {
+  std::string path, tmp;
+  FILE *f = nullptr;
+  bool on = false, to_stdout = false;
+  bool open(std::string &why) {
+    if (to_stdout) { f = stdout; return true; }
+    tmp = path + ".tmp." + std::to_string((long long)getpid());
+    f = fopen(tmp.c_str(), "wb");
+    if (!f) why = "cannot write " + tmp + ": " + strerror(errno);
+    return f != nullptr;
+  }
+  bool put(const uint8_t *p, size_t n, std::string &why) {
+    if (n && fwrite(p, 1, n, f) != n) { why = "cannot write " + (to_stdout ? std::string("stdout") : tmp) + ": " + strerror(errno); return false; }
+    return true;
+  }
+  bool close(std::string &why) {
+    if (!f) return true;
+    bool ok = to_stdout ? fflush(stdout) == 0 : fclose(f) == 0;
+    f = nullptr;
+    if (ok && !to_stdout && rename(tmp.c_str(), path.c_str()) != 0) ok = false;
+    if (!ok) { if (why.empty()) why = "cannot write " + (to_stdout ? std::string("stdout") : path) + ": " + strerror(errno); if (!to_stdout) unlink(tmp.c_str()); }
+    return ok;
+  }
+  void drop() { if (f && !to_stdout) fclose(f); f = nullptr; if (!to_stdout && !tmp.empty()) unlink(tmp.c_str()); }
+};
+struct Fastq {
+  strl_fastq_opts opts{FASTQ_FILTER_DEFAULT, 0, 1, 0, 0};
+  FastqOut out[3];                            // by stream: p1 (or the interleaved pairs), p2, s
+  strl_fastq_info info{};
+  double plan_s = 0, fetch_s = 0, write_s = 0;
+};
+
+uint64_t fastq_piece_bytes() {
+  const char *e = getenv("STRL_FASTQ_PIECE_KB");               // tests: pieces that cut entries anywhere
+  return e && atof(e) > 0 ? std::max<uint64_t>(1, (uint64_t)(atof(e) * 1024.0)) : (uint64_t)128 << 20;
+}
+
+// the host path's: the rule over the records in input order, the three streams written whole
+bool fastq_on_host(const std::vector<uint8_t> &raw, Fastq &Q, std::string &why, int &status) {
+  auto t0 = Clock::now();
+  const FastqOpts o{Q.opts.filter, Q.opts.suffix, Q.opts.default_qual, Q.opts.interleaved, Q.opts.singles};
+  std::vector<uint8_t> stream[3];
+  FastqCounts C{};
+  std::string w;
+  static const uint8_t none = 0;
+  const int64_t bad = fastq_host(raw.empty() ? &none : raw.data(), raw.size(), o, stream, &C, w);
+  if (bad >= 0) { why = "malformed BAM record " + std::to_string(bad) + ": " + w; status = STRL_ERR_FORMAT; return false; }
+  Q.info.n_kept = C.kept; Q.info.n_filtered = C.filtered; Q.info.n_empty = C.empty; Q.info.n_pairs = C.pairs; Q.info.n_singles = C.singles; Q.info.n_singles_unwritten = C.singles_unwritten;
+  for (int s = 0; s < 3; ++s) Q.info.stream_bytes[s] = stream[s].size();
+  Q.plan_s = since(t0);
+  t0 = Clock::now();
+  status = STRL_ERR_IO;
+  for (int s = 0; s < 3; ++s)
+    if (Q.out[s].on && !Q.out[s].put(stream[s].data(), stream[s].size(), why)) return false;
+  Q.write_s = since(t0);
+  status = 0;
+  return true;
+}
+
+// the device path's, behind strl_bamsort_finish: the plan, then every stream in pieces -- the fetch of piece k + 1 into one of two
+// page-locked buffers on a thread beside the write of piece k, as the sorted stream's pieces go
+bool fastq_on_device(strl_ctx *ctx, Fastq &Q, std::string &why, int &status) {
+  auto t0 = Clock::now();
+  int rc = strl_bamsort_fastq(ctx, &Q.opts, &Q.info);
+  if (rc) { why = strl_last_error(); status = rc; return false; }
+  Q.plan_s = since(t0);
+  const uint64_t piece = fastq_piece_bytes();
+  uint64_t room = 0;
+  for (int s = 0; s < 3; ++s) if (Q.out[s].on) room = std::max(room, std::min(piece, (uint64_t)Q.info.stream_bytes[s]));
+  uint8_t *buf[2] = {static_cast<uint8_t *>(strl_pinned_alloc(room + 64)), static_cast<uint8_t *>(strl_pinned_alloc(room + 64))};
+  if (!buf[0] || !buf[1]) { why = "page-locked memory for the pieces"; status = STRL_ERR_NOMEM; return false; }
+  struct Fetched { int rc = 0; std::string err; uint64_t bytes = 0; double s = 0; } got[2];
+  for (int s = 0; s < 3; ++s) {
+    if (!Q.out[s].on) continue;
+    const uint64_t total = Q.info.stream_bytes[s], n_pieces = (total + piece - 1) / piece;
+    auto fetch = [&](uint64_t k) {
+      Fetched &F = got[k & 1];
+      const auto f0 = Clock::now();
+      const uint64_t lo = k * piece;
+      F = Fetched{};
+      F.bytes = std::min(piece, total - lo);
+      F.rc = strl_bamsort_fastq_fetch(ctx, s, lo, F.bytes, buf[k & 1]);
+      if (F.rc) F.err = strl_last_error();
+      F.s = since(f0);
+    };
+    if (n_pieces) fetch(0);
+    for (uint64_t k = 0; k < n_pieces; ++k) {
+      std::thread ahead;
+      if (k + 1 < n_pieces) ahead = std::thread(fetch, k + 1);
+      const Fetched &F = got[k & 1];
+      bool ok = !F.rc;
+      if (!ok) { why = F.err; status = F.rc; }
+      Q.fetch_s += F.s;
+      if (ok) {
+        t0 = Clock::now();
+        status = STRL_ERR_IO;
+        ok = Q.out[s].put(buf[k & 1], (size_t)F.bytes, why);
+        Q.write_s += since(t0);
+      }
+      if (ahead.joinable()) ahead.join();
+      if (!ok) return false;
+    }
+  }
+  (void)strl_bamsort_fastq_info_now(ctx, &Q.info);             // (the text kernel's time over the fetches)
+  status = 0;
+  return true;
+}
+
 // ---- the host path ---------------------------------------------------------------------------------------------------------------
 // SAM text on the host: what the feed reads, line by line through sam_core.h's host function
 struct SamInput { SamFeed feed; SamHeader header; };
 
-bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8_t> &header, int32_t n_ref, bool core, int mode, SortOut &out, Result &R, Index &X, std::string &why, int &status) {
+bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8_t> &header, int32_t n_ref, bool core, int mode, SortOut &out, Result &R, Index &X, std::string &why, int &status,
+                  Fastq *fq = nullptr) {
   auto t0 = Clock::now();
   std::string err;
   status = STRL_ERR_FORMAT;
@@ -212,6 +327,7 @@ bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8
     q += 4 + (size_t)bs;
   }
   R.s.read = since(t0);
+  if (fq) { R.records = at.size(); return fastq_on_host(raw, *fq, why, status); }      // `strling fastq`: the records in input order are all it needs
   t0 = Clock::now();
   if (R.markdup) {                                              // the rule over the records in input order; the decided words into them
     std::vector<uint16_t> flags;
@@ -286,7 +402,7 @@ bool sort_on_host(const std::string &bam, SamInput *sam, const std::vector<uint8
 // windowed: `sort --windowed`.  Pass 0 keeps key and length of every record; the file is then read once more for every window of
 // the output stream, and each finished window goes through the piece loop the resident sort's whole stream goes through.
 bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, SamInput *sam, const std::vector<uint8_t> &header, bool core, int mode, bool windowed,
-                    SortOut &out, Result &R, Index &X, std::string &why, int &status) {
+                    SortOut &out, Result &R, Index &X, std::string &why, int &status, Fastq *fq = nullptr) {
   auto t0 = Clock::now();
   status = STRL_ERR_IO;
   BgzfFeed feed;
@@ -339,6 +455,7 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
     const SamHeader &H = sam->header;
     int rc = strl_bamsort_sam_begin(ctx, H.names.data(), H.name_off.data(), (int32_t)H.l_ref.size(), limit);
     if (!rc && R.markdup) rc = strl_bamsort_markdup_mode(ctx, 1);
+    if (!rc && fq) rc = strl_bamsort_fastq_mode(ctx, 1);
     if (!rc) rc = strl_bamsort_sam_reserve(ctx, cap);
     if (rc) return fail(rc);
     for (uint64_t ci = 0;; ++ci) {
@@ -359,6 +476,7 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
     int rc = windowed ? strl_bamsort_begin_windowed(ctx, (int32_t)feed.targets().size(), feed.first_record_offset())
                       : strl_bamsort_begin(ctx, (int32_t)feed.targets().size(), feed.first_record_offset(), limit);
     if (!rc && R.markdup) rc = strl_bamsort_markdup_mode(ctx, 1);
+    if (!rc && fq) rc = strl_bamsort_fastq_mode(ctx, 1);
     if (!rc) rc = strl_bamsort_reserve(ctx, (uint32_t)chunk_blocks, chunk_bytes);
     return rc;
   }, strl_bamsort_push);
@@ -369,6 +487,13 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
   int rc = strl_bamsort_finish(ctx, header.data(), header.size(), &info);
   if (rc) return fail(rc);
   R.s.sort = since(t0);
+  if (fq) {                                                     // `strling fastq`: every record lies on the device; the text instead of the sorted stream
+    R.records = info.n_records; R.slabs = info.n_slabs;
+    const bool ok = fastq_on_device(ctx, *fq, why, status);
+    (void)strl_bamsort_end(ctx);
+    if (!ok) pins.release();
+    return ok;
+  }
   if (R.markdup) {                                              // every record lies on the device: the flags before the first piece is gathered
     t0 = Clock::now();
     if ((rc = strl_bamsort_markdup(ctx, &R.md))) return fail(rc);
@@ -477,6 +602,31 @@ bool sort_on_device(const std::function<strl_ctx *(std::string &)> &get_ctx, con
   return true;
 }
 
+// the input's format, from its first bytes: BGZF magic is a BAM (from a file), `@` or anything else printable is SAM text
+// -> sam_in opened as the SAM feed, or null for a BAM; `cmd` names the command in the refusals
+SamInput *sniff_input(const char *cmd, const std::string &bam, bool from_stdin, SamInput &sam_in) {
+  std::string sniff_err;
+  const SamFeed::Kind kind = sam_in.feed.open(bam, sniff_err);
+  if (kind == SamFeed::KIND_ERROR && from_stdin) quit("[strling] %s: %s (status %d)", cmd, sniff_err.c_str(), STRL_ERR_IO);
+  if (from_stdin && kind == SamFeed::KIND_GZIP) quit("[strling] %s: a BAM on stdin is not read; write it to a file (status %d)", cmd, STRL_ERR_ARG);
+  if (from_stdin && kind != SamFeed::KIND_SAM) quit("[strling] %s: stdin holds no SAM text (status %d)", cmd, STRL_ERR_FORMAT);
+  return kind == SamFeed::KIND_SAM ? &sam_in : nullptr;
+}
+// the header, by the host reader, and the output's from it
+void read_header(const char *cmd, const std::string &bam, SamInput *sam, std::vector<uint8_t> &header, int32_t &n_ref) {
+  if (sam) {
+    std::string err;
+    if (!sam->feed.read_header(sam->header, err)) quit("[strling] %s: %s (status %d)", cmd, err.c_str(), STRL_ERR_FORMAT);
+    if (!bsort_header(sam->header.bam.data(), sam->header.bam.size(), header, &n_ref, nullptr, err)) quit("[strling] %s: %s (status %d)", cmd, err.c_str(), STRL_ERR_FORMAT);
+  } else {
+    BamReader rd;
+    std::string err;
+    if (!rd.open(bam, err)) quit("[strling] %s: %s (status %d)", cmd, err.empty() ? "malformed BAM header (truncated file or invalid BGZF block)" : err.c_str(), STRL_ERR_FORMAT);
+    const std::vector<uint8_t> &h = rd.header_bytes();
+    if (!bsort_header(h.data(), h.size(), header, &n_ref, nullptr, err)) quit("[strling] %s: %s (status %d)", cmd, err.c_str(), STRL_ERR_FORMAT);
+  }
+}
+
 }  // namespace
 
 int sort_main(int argc, char **argv) {
@@ -499,29 +649,12 @@ int sort_main(int argc, char **argv) {
   if (!from_stdin && CramFile::is_cram(bam)) quit("[strling] sort: %s is a CRAM; sorting one is out of scope: this command sorts a BAM", bam.c_str());
   if (!from_stdin && !file_exists(bam)) quit("couldn't open bam");
   const auto t_all = Clock::now();
-  // the format, from the first bytes: BGZF magic is a BAM (from a file), `@` or anything else printable is SAM text
   SamInput sam_in;
-  std::string sniff_err;
-  const SamFeed::Kind kind = sam_in.feed.open(bam, sniff_err);
-  if (kind == SamFeed::KIND_ERROR && from_stdin) quit("[strling] sort: %s (status %d)", sniff_err.c_str(), STRL_ERR_IO);
-  if (from_stdin && kind == SamFeed::KIND_GZIP) quit("[strling] sort: a BAM on stdin is not read; write it to a file (status %d)", STRL_ERR_ARG);
-  if (from_stdin && kind != SamFeed::KIND_SAM) quit("[strling] sort: stdin holds no SAM text (status %d)", STRL_ERR_FORMAT);
-  SamInput *sam = kind == SamFeed::KIND_SAM ? &sam_in : nullptr;
+  SamInput *sam = sniff_input("sort", bam, from_stdin, sam_in);
   if (sam && a.flag("windowed")) quit("[strling] sort: --windowed reads its input once more for every window, and SAM text is read once (a pipe cannot be read again): sort a BAM in windows (status %d)", STRL_ERR_ARG);
-  // the header, by the host reader, and the output's from it
   std::vector<uint8_t> header;
   int32_t n_ref = 0;
-  if (sam) {
-    std::string err;
-    if (!sam->feed.read_header(sam->header, err)) quit("[strling] sort: %s (status %d)", err.c_str(), STRL_ERR_FORMAT);
-    if (!bsort_header(sam->header.bam.data(), sam->header.bam.size(), header, &n_ref, nullptr, err)) quit("[strling] sort: %s (status %d)", err.c_str(), STRL_ERR_FORMAT);
-  } else {
-    BamReader rd;
-    std::string err;
-    if (!rd.open(bam, err)) quit("[strling] sort: %s (status %d)", err.empty() ? "malformed BAM header (truncated file or invalid BGZF block)" : err.c_str(), STRL_ERR_FORMAT);
-    const std::vector<uint8_t> &h = rd.header_bytes();
-    if (!bsort_header(h.data(), h.size(), header, &n_ref, nullptr, err)) quit("[strling] sort: %s (status %d)", err.c_str(), STRL_ERR_FORMAT);
-  }
+  read_header("sort", bam, sam, header, n_ref);
   if (X.on) {                              // what no index of the kind asked for can hold is refused before anything is read
     X.out = a.get("index-out", (out_path + (X.min_shift >= 0 ? ".csi" : ".bai")).c_str());
     size_t at = 12 + (size_t)bsort_ld32(header.data() + 4);      // (bsort_header has walked the list)
@@ -612,5 +745,104 @@ int sort_main(int argc, char **argv) {
     if (ctx) strl_ctx_destroy(ctx);
     quit("[strling] sort: sorted file written; index refused: %s (status %d)", X.why.c_str(), X.rc);
   }
+  return end_process(ctx);
+}
+
+// ---- `strling fastq` -----------------------------------------------------------------------------------------------------------------
+namespace {
+const char *FASTQ_USAGE =
+    "strling fastq\n\nUsage:\n  strling fastq [options] -o OUT.fq|- IN.bam|IN.sam|-\n  strling fastq [options] -1 R1.fq -2 R2.fq IN.bam|IN.sam|-\n"
+    "  strling fastq -o - old.bam | bwa mem -p ref.fa - | strling sort --markdup --write-index -o new.bam -\n\n"
+    "A BAM's reads back to paired FASTQ, for realignment: mates are joined by name on the GPU, whatever the order of the file (what\n"
+    "`samtools collate | samtools fastq` is used for).  A name with exactly two kept records, one first (0x40) and one last (0x80) read,\n"
+    "is a pair; every other kept record is a single.  Pairs stand in the order of first appearance, R1 before R2.\n\n"
+    "Arguments:\n  IN.bam           path to a bam file, in any order\n  IN.sam, -        SAM text instead, from a file or from stdin (told from a BAM by its first bytes)\n\nOptions:\n"
+    "  -o, --output=FILE|-        the pairs interleaved (R1, R2, R1, R2 ...), to a file or to stdout: what `bwa mem -p` reads\n"
+    "  -1 FILE -2 FILE            instead of -o: first reads to one file, last reads to the other\n"
+    "  -s, --singles=FILE         the singles; without it they are counted and reported as left out, never mixed into the pairs\n"
+    "  -F, --filter=INT           leave out records with any of these flag bits (default: 0x900, secondary and supplementary)\n"
+    "  -N, --suffix               /1 and /2 behind the names of first and last reads\n"
+    "  -v, --default-qual=INT     the quality of every base of a read that has none (default: 1)\n"
+    "  -D, --device=K             GPU to use (default: 0)\n"
+    "      --verbose              one JSON line on stderr with the step's times\n  -h, --help                 Show this help\n\n"
+    "Out of scope: tags and barcodes in the header line (samtools' -T, CASAVA), compressed output (pipe through a compressor), CRAM\n"
+    "input, and files larger than device memory (sort's --windowed has no counterpart here).  Reads without a sequence (l_seq 0) are\n"
+    "counted and left out.  STRL_FASTQ=host (or a machine without a GPU) takes the host path: the same bytes.\n";
+}  // namespace
+
+int fastq_main(int argc, char **argv) {
+  if (argc <= 2) { fputs(FASTQ_USAGE, stdout); return 0; }
+  const Args a = parse(argc, argv, 2, {{"output", 'o', true}, {"out1", '1', true}, {"out2", '2', true}, {"singles", 's', true}, {"filter", 'F', true}, {"suffix", 'N', false},
+                                       {"default-qual", 'v', true}, {"device", 'D', true}, {"verbose", 0, false}}, FASTQ_USAGE);
+  if (a.pos.size() != 1) quit("expected 1 argument (bam, sam or - for SAM text on stdin)\n%s", FASTQ_USAGE);
+  if (a.flag("output") && (a.flag("out1") || a.flag("out2"))) quit("[strling] fastq: -o writes the pairs interleaved and -1 / -2 write them to two files: give one or the other (status %d)", STRL_ERR_ARG);
+  if (a.flag("out1") != a.flag("out2")) quit("[strling] fastq: -1 and -2 go together (status %d)", STRL_ERR_ARG);
+  if (!a.flag("output") && !a.flag("out1")) quit("[strling] fastq: -o FILE|- or -1 FILE -2 FILE is required\n%s", FASTQ_USAGE);
+  auto number = [&](const char *k, const char *dflt, unsigned long max) {
+    const std::string v = a.get(k, dflt);
+    char *end = nullptr;
+    const unsigned long x = strtoul(v.c_str(), &end, 0);
+    if (v.empty() || *end || v[0] == '-' || x > max) quit("[strling] fastq: --%s must be an integer in [0, %lu] (got %s) (status %d)", k, max, v.c_str(), STRL_ERR_ARG);
+    return (uint32_t)x;
+  };
+  Fastq Q;
+  Q.opts.filter = number("filter", "0x900", 0xffff);
+  Q.opts.default_qual = number("default-qual", "1", 255);
+  Q.opts.suffix = a.flag("suffix");
+  Q.opts.interleaved = a.flag("output");
+  Q.opts.singles = a.flag("singles");
+  const std::string names[3] = {Q.opts.interleaved ? a.get("output", "") : a.get("out1", ""), a.get("out2", ""), a.get("singles", "")};
+  for (int s = 0; s < 3; ++s) { Q.out[s].on = !names[s].empty(); Q.out[s].path = names[s]; }
+  Q.out[0].to_stdout = Q.opts.interleaved && names[0] == "-";
+  const std::string bam = a.pos[0];
+  const bool from_stdin = bam == "-";
+  if (!from_stdin && CramFile::is_cram(bam)) quit("[strling] fastq: %s is a CRAM; reading one is out of scope: this command reads a BAM", bam.c_str());
+  if (!from_stdin && !file_exists(bam)) quit("couldn't open bam");
+  const auto t_all = Clock::now();
+  SamInput sam_in;
+  SamInput *sam = sniff_input("fastq", bam, from_stdin, sam_in);
+  std::vector<uint8_t> header;
+  int32_t n_ref = 0;
+  read_header("fastq", bam, sam, header, n_ref);
+  const char *where = getenv("STRL_FASTQ");
+  const bool on_host = (where && !strcmp(where, "host")) || strl_device_count() <= 0;
+  std::string why;
+  int status = 0;
+  bool ok = true;
+  for (int s = 0; s < 3 && ok; ++s) if (Q.out[s].on && !Q.out[s].open(why)) { ok = false; status = STRL_ERR_IO; }
+  SortOut none;
+  Result R;
+  Index X;
+  strl_ctx *ctx = nullptr;
+  if (ok && on_host) ok = sort_on_host(bam, sam, header, n_ref, false, STRL_DEFLATE_FAST, none, R, X, why, status, &Q);
+  else if (ok) {
+    set_device0(a.get("device", ""));
+    int ctx_rc = 0;
+    std::string ctx_err;
+    std::thread ctx_thread([&] { ctx_rc = strl_ctx_create(device_of(0), &ctx); if (ctx_rc) ctx_err = strl_last_error(); });
+    g_bg_init = &ctx_thread;
+    auto get_ctx = [&](std::string &w) -> strl_ctx * { if (ctx_thread.joinable()) ctx_thread.join(); if (ctx_rc) w = ctx_err; return ctx_rc ? nullptr : ctx; };
+    ok = sort_on_device(get_ctx, bam, sam, header, false, STRL_DEFLATE_FAST, false, none, R, X, why, status, &Q);
+    if (ctx_thread.joinable()) ctx_thread.join();
+    g_bg_init = nullptr;
+  }
+  for (int s = 0; s < 3 && ok; ++s) if (Q.out[s].on && !Q.out[s].close(why)) { ok = false; status = STRL_ERR_IO; }
+  if (!ok) {
+    for (FastqOut &o : Q.out) o.drop();
+    if (ctx) strl_ctx_destroy(ctx);
+    if (status == STRL_ERR_NOMEM) quit("[strling] fastq: %s; the records of this file do not fit the device: STRL_FASTQ=host writes it on the host (status %d)", why.c_str(), status);
+    quit("[strling] fastq: %s (status %d)", why.c_str(), status);
+  }
+  const strl_fastq_info &I = Q.info;
+  fprintf(stderr, "[strling] fastq: %llu records kept, %llu filtered, %llu empty, %llu pairs, %llu singles, %llu singles not written\n", (unsigned long long)I.n_kept,
+          (unsigned long long)I.n_filtered, (unsigned long long)I.n_empty, (unsigned long long)I.n_pairs, (unsigned long long)I.n_singles, (unsigned long long)I.n_singles_unwritten);
+  if (a.flag("verbose"))
+    fprintf(stderr,
+            "{\"command\": \"fastq\", \"path\": \"%s\", \"input\": \"%s\", \"records\": %llu, \"slabs\": %llu, \"p1_bytes\": %llu, \"p2_bytes\": %llu, \"s_bytes\": %llu, \"seconds\": %.3f, "
+            "\"read_s\": %.3f, \"sort_s\": %.3f, \"plan_s\": %.3f, \"fetch_s\": %.3f, \"write_s\": %.3f, \"record_ms\": %.3f, \"join_ms\": %.3f, \"layout_ms\": %.3f, \"text_ms\": %.3f, "
+            "\"text_bytes\": %llu}\n",
+            on_host ? "host" : "device", sam ? "sam" : "bam", (unsigned long long)R.records, (unsigned long long)R.slabs, (unsigned long long)I.stream_bytes[0],
+            (unsigned long long)I.stream_bytes[1], (unsigned long long)I.stream_bytes[2], since(t_all), R.s.read, R.s.sort, Q.plan_s, Q.fetch_s, Q.write_s, I.record_ms, I.join_ms,
+            I.layout_ms, I.text_ms, (unsigned long long)I.text_bytes);
   return end_process(ctx);
 }

@@ -164,6 +164,13 @@ int front_begin_scan(strl_ctx *c, int32_t n_ref, uint64_t first_record_offset); 
 struct BsortView;
 int bsort_view(strl_ctx *c, BsortView *v, strl_bai ***slot);      // bamsort.hip: the finished sort of the context, for strl_bamsort_index
 int markdup_run(strl_ctx *c, const BsortView &V, strl_markdup_info *out);      // markdup.hip: flag 0x400 on the records of a finished resident sort
+// fastq.hip: the records of a finished resident sort as FASTQ text.  fastq_plan joins the mates and lays the three streams out (*slot:
+// where the plan hangs; bsort_destroy destroys it); fastq_fetch writes a piece of a stream
+struct FastqPlan;
+int fastq_plan(strl_ctx *c, const BsortView &V, const strl_fastq_opts *opts, FastqPlan **slot, strl_fastq_info *out);
+int fastq_fetch(strl_ctx *c, FastqPlan *F, const BsortView &V, int stream, uint64_t lo, uint64_t len, uint8_t *dst);
+const strl_fastq_info *fastq_info(const FastqPlan *F);
+void fastq_destroy(FastqPlan *F);
 // bamindex.hip: the index builder behind strl_front_begin's own pass (strl_front_index_*); no-ops without one.  Neither waits
 // for the device, neither can fail the extraction.
 //   bai_front_chunk   a chunk has been handed over to slot si: its block table (whole_file: no other context took the chunk before)

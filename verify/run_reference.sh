@@ -107,6 +107,21 @@ PY
   else
     echo "SKIP  sort_markdup   (needs a strling with sort --markdup)"
   fi
+  # fastq: the entries of `strling fastq` against samtools' own pipeline over the same records -- collate, then fastq -n (no /1 /2)
+  # with the same filter.  Both sides as one line an entry (name, read number by stream, bases, qualities), sorted: samtools' order of
+  # the pairs is collate's, not the order of first appearance.  Never run: no machine this was built on had samtools (DESIGN.md
+  # section 24.4).
+  if "$S" 2> /dev/null | grep -q "fastq "; then
+    "$S" fastq -1 "$T/fq_ours_1.fq" -2 "$T/fq_ours_2.fq" -s "$T/fq_ours_s.fq" "$T/sort_in.bam" >> "$T/sort.log" 2>&1 || echo "      (fastq: strling fastq exited non-zero, see $T/sort.log)"
+    samtools collate -O -u "$T/sort_in.bam" "$T/collate_fq_tmp" 2>> "$T/sort.log" | samtools fastq -n -F 0x900 -1 "$T/fq_theirs_1.fq" -2 "$T/fq_theirs_2.fq" -s "$T/fq_theirs_s.fq" -0 "$T/fq_theirs_0.fq" - >> "$T/sort.log" 2>&1
+    cat "$T/fq_theirs_0.fq" >> "$T/fq_theirs_s.fq" 2> /dev/null
+    for w in ours theirs; do
+      for k in 1 2 s; do paste - - - - < "$T/fq_${w}_$k.fq" | awk -v k=$k '{ print k "\t" $0 }'; done | LC_ALL=C sort > "$T/fq_$w.txt"
+    done
+    check fastq "$T/fq_ours.txt" "$T/fq_theirs.txt" "strling fastq writes the entries samtools collate | fastq -n writes, pairs and singles alike"
+  else
+    echo "SKIP  fastq   (needs a strling with the fastq command)"
+  fi
 else
   echo "SKIP  sort   (needs samtools and a strling with the sort command: the order stays checked against its own statement in tests/sort_bam_cases.py only)"
 fi
