@@ -1036,6 +1036,58 @@ int strl_bamsort_fastq_fetch(strl_ctx *ctx, int stream, uint64_t lo, uint64_t le
 int strl_bamsort_fastq_info_now(strl_ctx *ctx, strl_fastq_info *info);
 int strl_fastq_host(const uint8_t *records, uint64_t bytes, const strl_fastq_opts *opts, uint8_t *const out[3], const uint64_t cap[3], strl_fastq_info *info);
 
+/* `strling view` (csrc/view.hip, the rule in csrc/view_core.h): a BAM's records as SAM text, one line a kept
+ * record, what `samtools view` is used for.  Agreement with htslib is unverified.  names / name_off[n_ref + 1]: the references' names
+ * back to back, name r = names[name_off[r], name_off[r + 1]).
+ *   strl_view_begin    the front end up to the record table (copy + inflate + CRC + record scan) with the view behind it; the names and
+ *                      the options are uploaded once.
+ *   strl_view_reserve  buffers for chunks of at most max_blocks blocks / max_comp_bytes compressed bytes.
+ *   strl_view_push     a chunk of whole BGZF blocks (the block arrays of strl_bamindex_push).  The chunk is copied and its inflate is
+ *                      enqueued; beside that the chunk pushed BEFORE is sized (view_size_kernel, a 64-bit prefix sum), written
+ *                      (view_text_kernel) and copied to page-locked memory: *text / *text_bytes name its lines (null / 0 on the first
+ *                      push and for a chunk without a kept record).  The bytes stay valid through the next call and no longer.
+ *   strl_view_finish   the last chunk's lines the same way, the totals, and the check that the file does not end inside a record.
+ *   strl_view_end      gives everything up.
+ *                      Calls out of order (a push or finish without a begin, a push behind the finish, a second finish) are
+ *                      STRL_ERR_ARG.  STRL_ERR_FORMAT: a refused record ("malformed BAM record N: FIELD ...", N its ordinal in the
+ *                      file; nothing of its chunk or behind it is handed out), invalid DEFLATE data; STRL_ERR_CRC; STRL_ERR_NOMEM.
+ *   strl_view_records  records[0, bytes) = records back to back in host memory, each with its block_size word, through the same two
+ *                      kernels: their lines to out[0, *out_bytes).  STRL_ERR_CAPACITY leaves the bytes needed in *out_bytes and
+ *                      writes nothing; nothing outside out[0, *out_bytes) is ever written.  Serves regions (opts->tid, beg, end).
+ *   strl_view_records_at  the same with the ordinal of the first record given, for a caller that feeds a region in batches: refusals
+ *                      name first_ordinal + the record's place in the call.  The context keeps the call's buffers for the next call.
+ *   strl_view_count_only  between strl_view_begin and the first push: the pushes and the finish count (info->written) and hand out no
+ *                      text -- the size kernel and the prefix sum run, the text kernel and the copy do not.
+ *                      strl_view_records with out = NULL and cap = 0 does the same for records in host memory (and leaves the need
+ *                      in *out_bytes, STRL_ERR_CAPACITY unless it is 0; with a hard chunk the need is the host twin's).
+ *   strl_view_host     the same rule without a device (csrc/view_host.cpp): the same bytes.
+ * A chunk that holds a float outside the range view_core.h's integer %g answers is formatted by the host twin (host_chunks). */
+typedef struct {
+  uint32_t require;       /* -f: every one of these flag bits is set */
+  uint32_t exclude;       /* -F: none of these is set */
+  uint32_t exclude_all;   /* -G: not all of these are set (0: no such filter) */
+  uint32_t min_mapq;      /* -q */
+  int32_t tid, beg, end;  /* a region, 0-based and half-open: the records that overlap it; tid = -2: no region */
+} strl_view_opts;
+typedef struct {
+  uint64_t records, written, dropped, text_bytes;
+  uint64_t chunks, host_chunks;      /* chunks (or calls) sized on the device | of those, formatted by the host twin */
+  double size_ms, text_ms;           /* HIP-event time of the size kernel with its prefix sum | of the text kernel */
+} strl_view_info;
+int strl_view_begin(strl_ctx *ctx, int32_t n_ref, uint64_t first_record_offset, const uint8_t *names, const uint32_t *name_off, const strl_view_opts *opts);
+int strl_view_reserve(strl_ctx *ctx, uint32_t max_blocks, uint64_t max_comp_bytes);
+int strl_view_push(strl_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const uint64_t *coff, const uint32_t *clen, const uint32_t *isize, const uint32_t *crc32,
+                   uint32_t n_blocks, const uint8_t **text, uint64_t *text_bytes);
+int strl_view_finish(strl_ctx *ctx, const uint8_t **text, uint64_t *text_bytes, strl_view_info *info);
+int strl_view_end(strl_ctx *ctx);
+int strl_view_records(strl_ctx *ctx, const uint8_t *records, uint64_t bytes, const uint8_t *names, const uint32_t *name_off, int32_t n_ref, const strl_view_opts *opts,
+                      uint8_t *out, uint64_t cap, uint64_t *out_bytes, strl_view_info *info);
+int strl_view_records_at(strl_ctx *ctx, const uint8_t *records, uint64_t bytes, const uint8_t *names, const uint32_t *name_off, int32_t n_ref, const strl_view_opts *opts,
+                         uint64_t first_ordinal, uint8_t *out, uint64_t cap, uint64_t *out_bytes, strl_view_info *info);
+int strl_view_count_only(strl_ctx *ctx, int on);
+int strl_view_host(const uint8_t *records, uint64_t bytes, const uint8_t *names, const uint32_t *name_off, int32_t n_ref, const strl_view_opts *opts, uint8_t *out,
+                   uint64_t cap, uint64_t *out_bytes, strl_view_info *info);
+
 /* ---- the .bai as a by-product of `strling extract`'s own pass (`strling extract --write-index`) ----
  * strl_front_push already copies, inflates, CRC-checks, record-scans and parses every block; the index needs of a record only
  * where it starts, refID, pos, end and flag, and the parse has just written those as dense columns.  A builder attached to the

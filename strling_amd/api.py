@@ -81,6 +81,25 @@ class FastqInfo(C.Structure):
                 ("stream_bytes", C.c_uint64 * 3), ("text_bytes", C.c_uint64), ("record_ms", C.c_double), ("join_ms", C.c_double), ("layout_ms", C.c_double), ("text_ms", C.c_double)]
 
 
+class ViewOpts(C.Structure):
+    """strl_view_opts: -f, -F, -G, -q and a region (tid = -2: none)"""
+    _fields_ = [("require", C.c_uint32), ("exclude", C.c_uint32), ("exclude_all", C.c_uint32), ("min_mapq", C.c_uint32), ("tid", C.c_int32), ("beg", C.c_int32), ("end", C.c_int32)]
+
+
+class ViewInfo(C.Structure):
+    """strl_view_info: the counts of `strling view`, the chunks and the HIP-event time of the two kernels"""
+    _fields_ = [("records", C.c_uint64), ("written", C.c_uint64), ("dropped", C.c_uint64), ("text_bytes", C.c_uint64), ("chunks", C.c_uint64), ("host_chunks", C.c_uint64),
+                ("size_ms", C.c_double), ("text_ms", C.c_double)]
+
+
+def _view_opts(require=0, exclude=0, exclude_all=0, min_mapq=0, tid=-2, beg=0, end=0):
+    return ViewOpts(int(require), int(exclude), int(exclude_all), int(min_mapq), int(tid), int(beg), int(end))
+
+
+def _view_info(info):
+    return {k: getattr(info, k) for k, _ in ViewInfo._fields_}
+
+
 def _fastq_opts(filter=0x900, suffix=False, default_qual=1, interleaved=True, singles=False):
     return FastqOpts(int(filter), int(bool(suffix)), int(default_qual), int(bool(interleaved)), int(bool(singles)))
 
@@ -192,7 +211,8 @@ EXPORTS = ["strl_dev_alloc", "strl_dev_free", "strl_copy", "strl_outliers_row_me
            "strl_bamsort_window_plan",
            "strl_bamsort_sam_begin", "strl_bamsort_sam_reserve", "strl_bamsort_push_sam", "strl_bamsort_sam_info", "strl_sam_encode", "strl_sam_header",
            "strl_bamsort_markdup_mode", "strl_bamsort_markdup", "strl_markdup_host",
-           "strl_bamsort_fastq_mode", "strl_bamsort_fastq", "strl_bamsort_fastq_fetch", "strl_bamsort_fastq_info_now", "strl_fastq_host"]
+           "strl_bamsort_fastq_mode", "strl_bamsort_fastq", "strl_bamsort_fastq_fetch", "strl_bamsort_fastq_info_now", "strl_fastq_host",
+           "strl_view_begin", "strl_view_reserve", "strl_view_push", "strl_view_finish", "strl_view_end", "strl_view_records", "strl_view_host", "strl_view_records_at", "strl_view_count_only"]
 
 
 def lib_path():
@@ -361,6 +381,15 @@ def load(build_if_missing=True):
     L.strl_bamsort_window_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     L.strl_sweep_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint8]
     L.strl_sweep_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    L.strl_view_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(ViewOpts)]
+    L.strl_view_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    L.strl_view_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.strl_view_finish.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(ViewInfo)]
+    L.strl_view_end.argtypes = [C.c_void_p]
+    L.strl_view_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ViewOpts), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(ViewInfo)]
+    L.strl_view_records_at.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ViewOpts), C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(ViewInfo)]
+    L.strl_view_count_only.argtypes = [C.c_void_p, C.c_int]
+    L.strl_view_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ViewOpts), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(ViewInfo)]
     L.strl_sweep_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
     L.strl_sweep_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SweepInfo)]
     L.strl_sweep_end.argtypes = [C.c_void_p]
@@ -1414,6 +1443,59 @@ class Context:
             self.L.strl_sweep_end(self.h)
         return res, {k: getattr(info, k) for k, _ in SweepInfo._fields_}
 
+    def view(self, path, chunk_blocks=16384, check_crc=True, **opts):
+        """the records of a BAM FILE as SAM text (strl_view_begin / _push / _finish; csrc/view.hip): opts as strl_view_opts ->
+        (the alignment lines as bytes, dict of strl_view_info)"""
+        B = self._bam_blocks(path)
+        names, off = _sam_names([t[0] for t in B["targets"]])
+        names = np.concatenate([names, np.zeros(1, np.uint8)])
+        o = _view_opts(**opts)
+        _check(self.L.strl_view_begin(self.h, B["n_ref"], B["first_off"], names.ctypes.data, off.ctypes.data, C.byref(o)))
+        out, info = [], ViewInfo()
+        try:
+            data, blocks, keep = B["data"], B["blocks"], []
+            text, nb = C.c_void_p(), C.c_uint64(0)
+            for s0 in range(B["b0"], len(blocks), chunk_blocks):
+                cb = blocks[s0:s0 + chunk_blocks]
+                lo, hi = cb[0][0], cb[-1][0] + cb[-1][1]
+                comp = np.ascontiguousarray(data[lo:hi])
+                coff = np.array([b[0] - lo for b in cb], np.uint64)
+                clen = np.array([b[1] for b in cb], np.uint32)
+                isz = np.array([b[2] for b in cb], np.uint32)
+                crc = np.array([b[3] for b in cb], np.uint32)
+                keep = (keep + [(comp, coff, clen, isz, crc)])[-3:]      # pageable memory: the copy is staged by the runtime
+                _check(self.L.strl_view_push(self.h, comp.ctypes.data, comp.size, _ptr(coff), _ptr(clen), _ptr(isz), _ptr(crc) if check_crc else None, len(cb),
+                                             C.byref(text), C.byref(nb)))
+                if nb.value:
+                    out.append(C.string_at(text.value, nb.value))
+            _check(self.L.strl_view_finish(self.h, C.byref(text), C.byref(nb), C.byref(info)))
+            if nb.value:
+                out.append(C.string_at(text.value, nb.value))
+        finally:
+            self.L.strl_view_end(self.h)
+        return b"".join(out), _view_info(info)
+
+    def view_records(self, records, names, cap=None, guard=0, **opts):
+        """records back to back in host memory, each with its block_size word, as SAM text through the device's two kernels
+        (strl_view_records).  names: the references' names in order.  cap: the room given (default: what is needed); guard: bytes
+        of 0xA5 on both sides of the room, returned as they are found afterwards -> (text, dict of strl_view_info[, before, behind])"""
+        src = np.frombuffer(bytes(records), np.uint8)
+        nm, off = _sam_names(names)
+        nm = np.concatenate([nm, np.zeros(1, np.uint8)])
+        o, info, need = _view_opts(**opts), ViewInfo(), C.c_uint64(0)
+        ptr = _ptr(src) if src.size else None
+        if cap is None:
+            rc = self.L.strl_view_records(self.h, ptr, src.size, nm.ctypes.data, off.ctypes.data, len(names), C.byref(o), None, 0, C.byref(need), C.byref(info))
+            if rc not in (0, -4):
+                _check(rc)
+            cap = need.value
+        buf = np.full(int(cap) + 2 * guard + 1, 0xA5, np.uint8)
+        _check(self.L.strl_view_records(self.h, ptr, src.size, nm.ctypes.data, off.ctypes.data, len(names), C.byref(o), buf.ctypes.data + guard, int(cap), C.byref(need), C.byref(info)))
+        text = buf[guard:guard + need.value].tobytes()
+        if guard:
+            return text, _view_info(info), buf[:guard].tobytes(), buf[guard + need.value:guard + need.value + guard].tobytes()
+        return text, _view_info(info)
+
     def bgzf_deflate(self, data, block=0xFF00, out=None, mode=None):
         """bytes -> (BGZF members back to back, without the EOF block; csize uint32[members]; members that went out stored), on the
         device (strl_bgzf_deflate).  mode = "fast" (the default's rule and bytes) or "dense" (strl_bgzf_deflate_mode)"""
@@ -1707,6 +1789,31 @@ def fastq_host(records, **opts):
     bufs = [np.zeros(max(1, int(n)), np.uint8) for n in info.stream_bytes]
     _check(L.strl_fastq_host(ptr, src.size, C.byref(o), (C.c_void_p * 3)(*[b.ctypes.data for b in bufs]), (C.c_uint64 * 3)(*[b.size for b in bufs]), C.byref(info)))
     return [b[:int(n)].tobytes() for b, n in zip(bufs, info.stream_bytes)], {k: int(getattr(info, k)) for k, _ in FastqInfo._fields_[:6]}
+
+
+def view_host(records, names, cap=None, **opts):
+    """the rule of `strling view` without a device (strl_view_host; csrc/view_core.h): records = BAM records back to back, each with
+    its block_size word; names: the references' names in order; opts as strl_view_opts -> (text, dict of strl_view_info).  cap: the
+    room given (default: what is needed); too little is a StrlingError of code -4 whose `need` holds the bytes needed"""
+    src = np.frombuffer(bytes(records), np.uint8)
+    nm, off = _sam_names(names)
+    nm = np.concatenate([nm, np.zeros(1, np.uint8)])
+    o, info, need = _view_opts(**opts), ViewInfo(), C.c_uint64(0)
+    L = load()
+    ptr = _ptr(src) if src.size else None
+    if cap is None:
+        rc = L.strl_view_host(ptr, src.size, nm.ctypes.data, off.ctypes.data, len(names), C.byref(o), None, 0, C.byref(need), C.byref(info))
+        if rc not in (0, -4):
+            _check(rc)
+        cap = need.value
+    buf = np.zeros(int(cap) + 1, np.uint8)
+    rc = L.strl_view_host(ptr, src.size, nm.ctypes.data, off.ctypes.data, len(names), C.byref(o), buf.ctypes.data, int(cap), C.byref(need), C.byref(info))
+    if rc == -4:
+        e = StrlingError(L.strl_last_error().decode())
+        e.code, e.need = -4, need.value
+        raise e
+    _check(rc)
+    return buf[:need.value].tobytes(), _view_info(info)
 
 
 def bamsort_key_bits(n_ref):

@@ -344,7 +344,7 @@ int64_t BamReader::read_region(RecordBatch &b, int32_t tid, int64_t beg, int64_t
   return read_until(b, INT64_MAX, tid, (int32_t)std::min<int64_t>(end, INT32_MAX), err);
 }
 
-int64_t BamReader::read_region_raw(std::vector<uint8_t> &out, int32_t tid, int64_t beg, int64_t end, std::string &err) {
+int BamReader::region_seek(int32_t tid, int64_t beg, int64_t end, std::string &err) {
   if (cram_) { err = "raw records of a CRAM"; return -1; }
   if (tid < 0 || (size_t)tid >= ref_beg_.size() || ref_beg_[(size_t)tid] == 0 || end <= beg) return 0;
   const std::vector<uint64_t> &lin = lin_[(size_t)tid];
@@ -353,8 +353,16 @@ int64_t BamReader::read_region_raw(std::vector<uint8_t> &out, int32_t tid, int64
   if (w >= (int64_t)lin.size()) w = (int64_t)lin.size() - 1;
   for (; w >= 0 && off == 0; --w) off = lin[(size_t)w];
   if (off == 0) off = ref_beg_[(size_t)tid];
-  if (!seek(Pos{off >> 16, (uint32_t)(off & 0xffff)}, err)) return -1;
-  return read_raw_until(out, INT64_MAX, tid, (int32_t)std::min<int64_t>(end, INT32_MAX), err);
+  return seek(Pos{off >> 16, (uint32_t)(off & 0xffff)}, err) ? 1 : -1;
+}
+
+int64_t BamReader::region_next(std::vector<uint8_t> &out, int64_t max_records, int32_t tid, int64_t end, std::string &err) {
+  return read_raw_until(out, max_records, tid, (int32_t)std::min<int64_t>(end, INT32_MAX), err);
+}
+
+int64_t BamReader::read_region_raw(std::vector<uint8_t> &out, int32_t tid, int64_t beg, int64_t end, std::string &err) {
+  const int at = region_seek(tid, beg, end, err);
+  return at <= 0 ? at : region_next(out, INT64_MAX, tid, end, err);
 }
 
 bool BamReader::seek_tail(std::string &err) {

@@ -157,6 +157,11 @@ class BamReader {
   // call (0 at the end of the file).  header_bytes: magic, text and reference list, byte for byte.  index_windows: 16 KiB
   // windows of the reference's linear index (no record overlaps a later one).  The reads return the records appended, -1 on error.
   int64_t read_region_raw(std::vector<uint8_t> &out, int32_t tid, int64_t beg, int64_t end, std::string &err);
+  // read_region_raw in pieces (`strling view` holds a bounded batch of a region at a time): region_seek goes where read_region_raw
+  // starts (1; 0: the region holds nothing; -1: err), region_next appends up to max_records of the region's records -- fewer than
+  // asked for: the region is over.
+  int region_seek(int32_t tid, int64_t beg, int64_t end, std::string &err);
+  int64_t region_next(std::vector<uint8_t> &out, int64_t max_records, int32_t tid, int64_t end, std::string &err);
   bool seek_tail(std::string &err);
   int64_t read_raw(std::vector<uint8_t> &out, int64_t max_records, std::string &err) { return read_raw_until(out, max_records, INT32_MIN, 0, err); }
   const std::vector<uint8_t> &header_bytes() const { return hdr_raw_; }

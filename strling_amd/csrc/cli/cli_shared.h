@@ -67,5 +67,12 @@ struct PinnedRing {
 bool build_bai(const std::function<strl_ctx *(std::string &)> &get_ctx, const std::string &bam, const std::string &out, bool verbose, bool last_use, std::string &why,
                int &status, int csi_min_shift);
 
+// main.cpp: htslib's region forms as `strling pull` takes them (NAME, NAME:BEG, NAME:BEG-END, 1-based and inclusive) -> 0-based, half-open;
+// what cannot be read ends the process with a message that names `cmd`
+namespace strl { struct BamTarget; }
+struct PullRegion { int32_t tid; int64_t beg, end; };
+PullRegion parse_pull_region(const std::string &s, const std::vector<strl::BamTarget> &targets, const char *cmd = "pull");
+
 int sort_main(int argc, char **argv);       // sort_cli.cpp
 int fastq_main(int argc, char **argv);      // sort_cli.cpp: `strling fastq`, a mode of sort's driver
+int view_main(int argc, char **argv);       // view_cli.cpp

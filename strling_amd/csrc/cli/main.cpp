@@ -2706,23 +2706,22 @@ static int shares_main(int argc, char **argv) {
 }
 
 // ---- `strling pull` (extract_region.nim): a region's primary records and the mates that lie elsewhere, as a BAM --------------
-struct PullRegion { int32_t tid; int64_t beg, end; };
 // htslib's region forms (hts_parse_reg behind `ibam.query(opts.region)`, extract_region.nim:46): NAME, NAME:BEG, NAME:BEG-END,
 // 1-based and inclusive, commas allowed in the numbers; a string that is a reference's name as a whole is that reference
-static PullRegion parse_pull_region(const std::string &s, const std::vector<BamTarget> &targets) {
+PullRegion parse_pull_region(const std::string &s, const std::vector<BamTarget> &targets, const char *cmd) {
   int tid = get_tid(s, targets);
   if (tid >= 0) return PullRegion{tid, 0, INT32_MAX};
   const size_t colon = s.rfind(':');
   if (colon == std::string::npos || (tid = get_tid(s.substr(0, colon), targets)) < 0)
-    quit("[strling] pull: unknown reference in region %s", s.c_str());
+    quit("[strling] %s: unknown reference in region %s", cmd, s.c_str());
   std::string num;
   for (char ch : s.substr(colon + 1)) if (ch != ',') num += ch;
   const size_t dash = num.find('-');
   const std::string b = num.substr(0, dash), e = dash == std::string::npos ? "" : num.substr(dash + 1);
   auto digits = [](const std::string &x) { return !x.empty() && x.size() <= 10 && x.find_first_not_of("0123456789") == std::string::npos; };
-  if (!digits(b) || (!e.empty() && !digits(e))) quit("[strling] pull: cannot read the coordinates of region %s", s.c_str());
+  if (!digits(b) || (!e.empty() && !digits(e))) quit("[strling] %s: cannot read the coordinates of region %s", cmd, s.c_str());
   const int64_t beg = std::max<int64_t>(0, atoll(b.c_str()) - 1), end = e.empty() ? INT32_MAX : std::min<int64_t>(atoll(e.c_str()), INT32_MAX);
-  if (end <= beg) quit("[strling] pull: region %s is empty", s.c_str());
+  if (end <= beg) quit("[strling] %s: region %s is empty", cmd, s.c_str());
   return PullRegion{tid, beg, end};
 }
 
@@ -3159,7 +3158,8 @@ int main(int argc, char **argv) {
       "  bamindex :   build the index (.bai, or .csi with --csi) of a coordinate-sorted BAM on the GPU (what `samtools index` writes).\n"
       "  pull     :   write a region's reads and their mates to a small BAM, for debugging (the reference's pull_region).\n"
       "  sort     :   coordinate-sort a BAM on the GPU (what `samtools sort` writes; --write-index: its index from the same pass).\n"
-      "  fastq    :   a BAM's reads back to paired FASTQ on the GPU, mates joined by name (the step in front of the aligner).\n";      // strling.nim:18-24
+      "  fastq    :   a BAM's reads back to paired FASTQ on the GPU, mates joined by name (the step in front of the aligner).\n"
+      "  view     :   a BAM's records as SAM text, written on the GPU; flag and MAPQ filters, regions through the index.\n";      // strling.nim:18-24
   if (argc < 2) { fputs(top, stdout); return 1; }
   const std::string cmd = argv[1];
   if (cmd == "extract") return extract_main(argc, argv);
@@ -3171,6 +3171,7 @@ int main(int argc, char **argv) {
   if (cmd == "pull") return pull_main(argc, argv);
   if (cmd == "sort") return sort_main(argc, argv);
   if (cmd == "fastq") return fastq_main(argc, argv);
+  if (cmd == "view") return view_main(argc, argv);
   if (cmd == "_dump") return dump_main(argc, argv);
   if (cmd == "_decode") return decode_main(argc, argv);
   if (cmd == "_region") return region_main(argc, argv);

@@ -95,7 +95,7 @@ inline uint64_t strl_record_limit() {
   return v;
 }
 
-namespace strl { struct strl_front; struct strl_comm; void comm_destroy(strl_comm *m); struct strl_bai; void bai_destroy(strl_bai *b); struct strl_sweep; void sweep_destroy(strl_sweep *w); struct strl_bsort; void bsort_destroy(strl_bsort *b); }
+namespace strl { struct strl_front; struct strl_comm; void comm_destroy(strl_comm *m); struct strl_bai; void bai_destroy(strl_bai *b); struct strl_sweep; void sweep_destroy(strl_sweep *w); struct strl_bsort; void bsort_destroy(strl_bsort *b); struct strl_view; void view_destroy(strl_view *v); }
 struct strl_ctx;
 int side_join(strl_ctx *c);   // main stream waits for the side streams' pending work (context.hip)
 int side_streams(strl_ctx *c);   // the side streams of the overlapped mode, made at its first use (context.hip)
@@ -201,6 +201,8 @@ struct strl_ctx : TailSet, HeadSet {
   strl::strl_bai *bai = nullptr;       // BAI builder behind the front end's record scan (bamindex.hip), created by strl_bamindex_begin
   strl::strl_sweep *sweep = nullptr;   // `call --sweep`: the evidence of many bounds behind the front end's record scan (sweep.hip), created by strl_sweep_begin
   strl::strl_bsort *bsort = nullptr;   // `strling sort`: keys, arena and layout of a coordinate sort behind the front end's record scan (bamsort.hip), created by strl_bamsort_begin
+  strl::strl_view *view = nullptr;     // `strling view`: records to SAM text behind the front end's record scan (view.hip), created by strl_view_begin
+  strl::strl_view *view_rec = nullptr; // ... and the buffers strl_view_records keeps between its calls
   strl::strl_comm *comm = nullptr;     // multi-GPU exchange (comm.hip): RCCL communicator / local group of this context
   // staging of the pairing arrays for host-memory batches
   strl::DevBuf st_mtid, st_qhash;

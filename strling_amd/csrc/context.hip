@@ -209,6 +209,8 @@ void strl_ctx_destroy(strl_ctx *c) {
   if (c->x_soft_seen) (void)hipHostFree(c->x_soft_seen);
   if (c->bai) { strl::bai_destroy(c->bai); c->bai = nullptr; }
   if (c->sweep) { strl::sweep_destroy(c->sweep); c->sweep = nullptr; }
+  if (c->view) { strl::view_destroy(c->view); c->view = nullptr; }
+  if (c->view_rec) { strl::view_destroy(c->view_rec); c->view_rec = nullptr; }
   if (c->bsort) { strl::bsort_destroy(c->bsort); c->bsort = nullptr; }
   if (c->front) { if (c->front->st_c) (void)hipStreamSynchronize(c->front->st_c); for (hipStream_t q : c->front->st_i) if (q) (void)hipStreamSynchronize(q); if (c->front->st_a) (void)hipStreamSynchronize(c->front->st_a); strl::front_destroy(c->front); c->front = nullptr; }
   for (auto &r : c->rg)

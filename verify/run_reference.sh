@@ -122,6 +122,16 @@ PY
   else
     echo "SKIP  fastq   (needs a strling with the fastq command)"
   fi
+  # view: the text of `strling view -h` against `samtools view -h --no-PG` over the same file, whole and for a region.  Never run: no
+  # machine this was built on had samtools.  Unverified with it: %g of float tags against htslib's kputd
+  # (which is not printf), the spelling of an empty name, and qualities above 93 (clamped here, not by htslib).
+  if "$S" 2> /dev/null | grep -q "view "; then
+    "$S" view -h "$T/sort_ours.bam" > "$T/view_ours.sam" 2>> "$T/sort.log" || echo "      (view: strling view exited non-zero, see $T/sort.log)"
+    samtools view -h --no-PG "$T/sort_ours.bam" > "$T/view_theirs.sam" 2>> "$T/sort.log"
+    check view "$T/view_ours.sam" "$T/view_theirs.sam" "strling view -h writes the text samtools view -h writes"
+  else
+    echo "SKIP  view   (needs a strling with the view command)"
+  fi
 else
   echo "SKIP  sort   (needs samtools and a strling with the sort command: the order stays checked against its own statement in tests/sort_bam_cases.py only)"
 fi
