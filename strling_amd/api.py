@@ -279,6 +279,8 @@ def load(build_if_missing=True):
     L.strl_extract_device.argtypes = [C.c_void_p, C.POINTER(CReadSoa), C.POINTER(CPairSoa), C.c_int64, C.c_uint64, C.c_uint64]
     L.strl_treads_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(ScoreStats)]
     L.strl_ctx_pair_times.argtypes = [C.c_void_p, C.POINTER(C.c_double * 5)]
+    if hasattr(L, "strl_score_queue_probe"):     # (likewise)
+        L.strl_score_queue_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     if hasattr(L, "strl_pair_items_probe"):      # (STRL_LIB may name a build from before the entry point)
         L.strl_pair_items_probe.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.strl_cluster_resident.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_uint32, C.c_int32, C.c_uint16, C.c_uint16, C.c_uint16,
@@ -701,6 +703,14 @@ class Context:
         if want and no.value:
             _check(self.L.strl_treads_fetch(self.h, out.ctypes.data, out.size, C.byref(no), None))
         return out[:no.value], st
+
+    def score_queue_ids(self, cap):
+        """the read ids the skip-predicate pass queued in the context's last scoring pass, in queue order, after a sync
+        (strl_score_queue_probe, test-only); `cap`: the batch's reads -> (ids, their number)"""
+        out = np.zeros(max(1, int(cap)), np.uint32)
+        n = C.c_uint64(0)
+        _check(self.L.strl_score_queue_probe(self.h, out.ctypes.data, int(cap), C.byref(n)))
+        return out[:min(int(n.value), int(cap))], int(n.value)
 
     def pair_items(self):
         """join items of the context's last pair pass, after a sync (strl_pair_items_probe, test-only): the reads the probe let

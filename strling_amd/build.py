@@ -14,7 +14,7 @@ LIB = os.path.join(LIBDIR, "libstrling_amd.so")
 CLI = os.path.join(LIBDIR, "strling")
 SOURCES = ["context.hip", "score.hip", "extract.hip", "pair.hip", "sort.hip", "outliers.hip", "cluster.hip", "bgzf.hip", "deflate.hip", "evidence.hip", "pull.hip", "front.hip", "front_abi.hip", "bamindex.hip", "bamsort.hip", "markdup.hip", "fastq.hip", "view.hip", "samparse.hip", "sweep.hip", "assign.hip", "comm.hip", "host_logic.cpp", "host_score.cpp", "call_logic.cpp", "pull_logic.cpp", "markdup_host.cpp", "fastq_host.cpp", "view_host.cpp", "nim_tables.cpp"]
 CLI_SOURCES = ["cli/main.cpp", "cli/outliers_cli.cpp", "cli/sort_cli.cpp", "cli/view_cli.cpp", "cli/sam_feed.cpp", "bamindex_host.cpp", "cli/bam_reader.cpp", "cli/fast_inflate.cpp", "cli/bgzf_feed.cpp", "cli/chunk_feed.cpp", "cli/region_feed.cpp", "cli/cram_reader.cpp", "cli/cram_codecs.cpp"]
-HEADERS = ["common.h", "device_util.h", "bloom_layout.h","sort.h", "inflate_wave.h", "inflate_group.h", "front.h", "regions.h", "bam_rec.h", "sweep_core.h", "evidence_core.h", "assign_core.h", "deflate_core.h", "bamsort_core.h", "markdup_core.h", "fastq_core.h", "view_core.h", "sam_core.h", "samparse.h", "bamindex_core.h", "bamindex_host.h", "pull_rec.h", "score.h", "score_core.h", "score_tables.h", "nim_tables.h", "host_score.h", "cli/bam_reader.h", "cli/fast_inflate.h", "cli/bgzf_feed.h", "cli/chunk_feed.h", "cli/region_feed.h", "cli/sam_feed.h", "cli/cram_reader.h", "cli/cram_codecs.h", "cli/cli_shared.h", "../../include/strling_amd.h"]
+HEADERS = ["common.h", "device_util.h", "bloom_layout.h", "classify_turn.h", "sort.h", "inflate_wave.h", "inflate_group.h", "front.h", "regions.h", "bam_rec.h", "sweep_core.h", "evidence_core.h", "assign_core.h", "deflate_core.h", "bamsort_core.h", "markdup_core.h", "fastq_core.h", "view_core.h", "sam_core.h", "samparse.h", "bamindex_core.h", "bamindex_host.h", "pull_rec.h", "score.h", "score_core.h", "score_tables.h", "nim_tables.h", "host_score.h", "cli/bam_reader.h", "cli/fast_inflate.h", "cli/bgzf_feed.h", "cli/chunk_feed.h", "cli/region_feed.h", "cli/sam_feed.h", "cli/cram_reader.h", "cli/cram_codecs.h", "cli/cli_shared.h", "../../include/strling_amd.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 # the grouped form of the device inflate (csrc/inflate_group.h): an experiment that measured slower (profiles/r05/inflate_group/);
 # not in the shipped library unless asked for

@@ -5,7 +5,12 @@
 //                    extract.nim:30-34 against the genome STR intervals (a wave-level merge join against a
 //                    window of {start, running max stop} entries; bin directory + short scan for reads
 //                    outside it), writes the "skipped" result word or stages the read for the scoring
-//                    queue (one queue atomic per 512 staged reads).  HBM-bound.
+//                    queue (one queue atomic per 512 staged reads).  A turn that lies, with the turn behind it, wholly
+//                    inside the wave's range is FULL (classify_turn.h): no bounds test, no exec mask on a load or a
+//                    store, and the next turn's eight loads stay in flight for the whole turn -- two register sets
+//                    swap roles instead of a copy, the wait for the current vectors is a counted one.  The last two
+//                    turns of a range, ragged ends and the scalar variant take the GENERAL turn.  Bound by neither
+//                    HBM (3.6 TB/s) nor vector issue (profiles/classify).
 //  score_kernel<0> : one queued read per lane -> utils.get_repeat on the whole read
 //                    (score_core.h), writes the packed result, queues the soft-clipped ends
 //                    add_soft (extract.nim:93-106) would look at.  Bound by integer VALU issue (0.75-0.87 of
@@ -18,8 +23,10 @@
 #include <string.h>
 #include <algorithm>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include "common.h"
+#include "classify_turn.h"
 #include "host_score.h"
 #include "device_util.h"
 #include "score_core.h"
@@ -107,14 +114,17 @@ struct JoinState {
   int2 e[JOIN_WIN];
 };
 
-template <int N>
-__device__ __forceinline__ void skip_predicate_n(const ScoreParams &P, JoinState &J, const uint32_t (&cg)[N], const int32_t (&t)[N],
+// ALL_IN: every one of the N reads exists (a full turn, classify_turn.h): `in` is not looked at.  n_tid: max(P.n_tid, 0).
+template <int N, bool ALL_IN>
+__device__ __forceinline__ void skip_predicate_n(const ScoreParams &P, JoinState &J, uint32_t n_tid, const uint32_t (&cg)[N], const int32_t (&t)[N],
                                                  const int32_t (&start)[N], const int32_t (&stop)[N], const bool (&in)[N], bool (&skip)[N]) {
   bool cand[N];
   bool any = false;
 #pragma unroll
   for (int j = 0; j < N; ++j) {
-    cand[j] = in[j] && (cg[j] & STRL_CIG_SINGLE_M) && t[j] >= 0 && t[j] < P.n_tid;
+    // one unsigned compare for 0 <= t < n_tid, and no short circuit: a branch per read put a wait for every load in flight
+    // (the next turn's prefetch included) in front of each of the N tests
+    cand[j] = (ALL_IN | in[j]) & ((cg[j] & STRL_CIG_SINGLE_M) != 0) & ((uint32_t)t[j] < n_tid);
     any |= cand[j];
   }
   // lapper.find(start, stop) <=> any interval with iv.start < stop and iv.stop > start.
@@ -186,7 +196,7 @@ __device__ __forceinline__ void skip_predicate_n(const ScoreParams &P, JoinState
         int32_t pm = J.e[0].y;
 #pragma unroll
         for (int q = 0; q + 1 < WIN; ++q) pm = J.e[q].x < stop[j] ? J.e[q + 1].y : pm;   // starts ascend: the last true one decides
-        skip[j] = cand[j] && !(pm > start[j]);
+        skip[j] = cand[j] & !(pm > start[j]);
       }
       return;
     }
@@ -203,29 +213,32 @@ __global__ __launch_bounds__(256, 4) void classify_kernel(ScoreParams P) {
   // space with ONE global atomic (one same-address atomic per wave-iteration ran into the ~88 ops/us limit of
   // the L2 atomic unit: 12 ms per 2^25 reads) and gathers the reads' metadata into self-contained 16-byte items.
   __shared__ uint32_t stage[4][CL_STAGE + 64 * CL_ILP];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  static_assert(CL_ILP == (int)CT_ILP, "classify_turn.h restates the turn");
+  // the wave index in a scalar register: the range and every test on it (a full turn?) are scalar arithmetic
+  const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   uint32_t *buf = stage[wave];
   const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
   const uint64_t gw = (uint64_t)blockIdx.x * 4u + wave;
   const uint64_t per = (((P.n + n_waves - 1) / n_waves) + 255ull) & ~255ull;
-  const uint64_t r0 = gw * per;
-  const uint64_t r1 = r0 + per < P.n ? r0 + per : P.n;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const ClassifyRange R = classify_range(P.n, per, gw);
+  if (!classify_owns(R)) return;            // a wave without a read: before its first load (the kernel has no block-wide barrier)
+  const uint64_t r0 = R.r0, r1 = R.r1;
+  const uint32_t len = classify_len(R);
   uint32_t cnt = 0, nskip = 0;
   // read handled by this lane as sub-item j of the iteration starting at `base`
-  auto ridx = [&](uint64_t base, int j) -> uint64_t {
+  auto ridx = [&](uint64_t base, int j, int lane) -> uint64_t {
     return VEC ? base + 256ull * (uint64_t)(j >> 2) + 4ull * (uint64_t)lane + (uint64_t)(j & 3) : base + 64ull * (uint64_t)j + (uint64_t)lane;
   };
   auto flush = [&]() {
     if (cnt) {
       uint32_t b = 0;
-      if (lane == 0) b = atomicAdd(&P.counters[CNT_QUEUE], cnt);
+      if (lane0 == 0) b = atomicAdd(&P.counters[CNT_QUEUE], cnt);
       b = __shfl(b, 0);
       __builtin_amdgcn_wave_barrier();
       // Only the ids leave this kernel: it is the one launch of the step that HBM bounds, and gathering the kept reads' rows
       // here (8.5 % of the reads: three quarters of every 64-byte line fetched for nothing) was 160 MB of its 800 MB.
       // Stage A of the scorer, which integer issue bounds, gathers them beside its arithmetic and writes the entries.
-      for (uint32_t i = lane; i < cnt; i += 64) P.queue_id[b + i] = buf[i];
+      for (uint32_t i = lane0; i < cnt; i += 64) P.queue_id[b + i] = buf[i];
       __builtin_amdgcn_wave_barrier();
       cnt = 0;
     }
@@ -235,7 +248,7 @@ __global__ __launch_bounds__(256, 4) void classify_kernel(ScoreParams P) {
   // right behind the loads and serialised every prefetch with its own latency.
   struct In { int4 t, s, e; uint32_t c; };                    // VEC: 4 reads; scalar variant: .x / low byte only
   constexpr int NIN = VEC ? CL_ILP / 4 : CL_ILP;
-  auto load = [&](uint64_t base, In (&x)[NIN]) {
+  auto load = [&](uint64_t base, int lane, In (&x)[NIN]) {
     if (VEC) {
 #pragma unroll
       for (int gq = 0; gq < NIN; ++gq) {
@@ -271,18 +284,54 @@ __global__ __launch_bounds__(256, 4) void classify_kernel(ScoreParams P) {
     }
   };
   auto comp = [](const int4 &v, int q) -> int32_t { return q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w; };
-  In cur[NIN], nxt[NIN];
+  // The vectors of a turn that lies wholly inside the range (classify_turn.h; vector variant only): no bounds test, no exec
+  // mask, a scalar base + the lane's 32-bit byte offset + an immediate per group.
+  // (the turn's offset goes into the scalar base, classify_group_off(0, lane, gq) is the lane's part: reads, i.e. bytes of the
+  // cigar column and a quarter of the bytes of a 4-byte column)
+  auto load_full = [&](uint32_t off, int lane, In (&x)[NIN]) {
+    const char *pt = reinterpret_cast<const char *>(P.tid + r0 + off), *ps = reinterpret_cast<const char *>(P.pos + r0 + off);
+    const char *pe = reinterpret_cast<const char *>(P.end + r0 + off), *pc = reinterpret_cast<const char *>(P.cig + r0 + off);
+#pragma unroll
+    for (int gq = 0; gq < NIN; ++gq) {
+      const uint32_t g = classify_group_off(0u, (uint32_t)lane, (uint32_t)gq);
+      x[gq].t = *reinterpret_cast<const int4 *>(pt + 4u * g);
+      x[gq].s = *reinterpret_cast<const int4 *>(ps + 4u * g);
+      x[gq].e = *reinterpret_cast<const int4 *>(pe + 4u * g);
+      x[gq].c = *reinterpret_cast<const uint32_t *>(pc + g);
+    }
+  };
   JoinState join;
   join.t = -2; join.valid = 0; join.lo = 0;
-  load(r0, cur);
-  for (uint64_t base = r0; base < r1; base += 64 * CL_ILP) {
-    load(base + 64 * CL_ILP, nxt);   // next iteration's streaming loads fly while this one chases the interval table
+  // One turn: the reads of `cur`, while `nxt` is requested.  FULL (std::true_type): this turn and the next lie wholly inside the
+  // range, wave-uniformly; nothing in it is loaded, tested or stored under an exec mask, and the next turn's eight loads, issued
+  // first, stay in flight through the predicate, the ballots, the staging and the stores: what waits for `cur` is a counted
+  // wait (vmcnt(8) in one copy of the turn, vmcnt(10) in the other) that leaves them outstanding.  The general turn is the loop body as it always was.
+  auto turn = [&](auto full_c, uint64_t base, In (&cur)[NIN], In (&nxt)[NIN]) {
+    constexpr bool FULL = decltype(full_c)::value;
+    const uint32_t off = (uint32_t)(base - r0);
+    // The lane index anew in every turn: what derives from it alone (byte offsets, the general turn's 64-bit addresses) is
+    // invariant, was hoisted out of the loop for all four copies of the turn at once, and spilled.
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    if constexpr (FULL) load_full(off + CT_TURN, lane, nxt);
+    else load(base + 64 * CL_ILP, lane, nxt);   // next iteration's streaming loads fly while this one chases the interval table
+    __builtin_amdgcn_sched_barrier(0);    // the loads stay in front of everything that waits for `cur`
+    uint32_t n_tid_u = (uint32_t)(P.n_tid > 0 ? P.n_tid : 0);
+    if constexpr (FULL) {
+      // `cur` is first looked at HERE: without this, what the two kinds of turn do alike with it (the first compares, the cigar
+      // bytes) is hoisted above their common branch, in front of the loads, with a wait for everything outstanding
+      // (the cigar words themselves, and the table size the contig ids are compared with: enough to make the first uses differ)
+#pragma unroll
+      for (int gq = 0; gq < NIN; ++gq) asm volatile("" : "+v"(cur[gq].c));
+      asm volatile("" : "+s"(n_tid_u));
+      __builtin_amdgcn_sched_barrier(0);
+    }
     bool need[CL_ILP], skipped[CL_ILP], inr[CL_ILP];
     uint32_t cgs[CL_ILP];
     int32_t ts[CL_ILP], sts[CL_ILP], ens[CL_ILP];
 #pragma unroll
     for (int j = 0; j < CL_ILP; ++j) {
-      inr[j] = ridx(base, j) < r1;
+      inr[j] = FULL || ridx(base, j, lane) < r1;
       if (VEC) {
         const In &g4 = cur[j >> 2];
         cgs[j] = (g4.c >> (8 * (j & 3))) & 0xffu; ts[j] = comp(g4.t, j & 3); sts[j] = comp(g4.s, j & 3); ens[j] = comp(g4.e, j & 3);
@@ -290,22 +339,27 @@ __global__ __launch_bounds__(256, 4) void classify_kernel(ScoreParams P) {
         cgs[j] = cur[j].c; ts[j] = cur[j].t.x; sts[j] = cur[j].s.x; ens[j] = cur[j].e.x;
       }
     }
-    skip_predicate_n<CL_ILP>(P, join, cgs, ts, sts, ens, inr, skipped);
+    skip_predicate_n<CL_ILP, FULL>(P, join, n_tid_u, cgs, ts, sts, ens, inr, skipped);
 #pragma unroll
     for (int j = 0; j < CL_ILP; ++j) {
       need[j] = inr[j] && !skipped[j];
-      if (!VEC && skipped[j]) P.whole[ridx(base, j)] = STRL_RES_SKIPPED;
+      if (!VEC && skipped[j]) P.whole[ridx(base, j, lane)] = STRL_RES_SKIPPED;
     }
     if (VEC) {   // one 16-byte store per group; kept reads get 0 here and their real word from the scorer later
 #pragma unroll
       for (int gq = 0; gq < CL_ILP / 4; ++gq) {
-        const uint64_t r = base + 256ull * gq + 4ull * lane;
-        if (r + 3 < r1) {
-          reinterpret_cast<uint4 *>(P.whole)[r >> 2] = make_uint4(skipped[4 * gq] ? STRL_RES_SKIPPED : 0u, skipped[4 * gq + 1] ? STRL_RES_SKIPPED : 0u,
-                                                                 skipped[4 * gq + 2] ? STRL_RES_SKIPPED : 0u, skipped[4 * gq + 3] ? STRL_RES_SKIPPED : 0u);
+        const uint4 w4 = make_uint4(skipped[4 * gq] ? STRL_RES_SKIPPED : 0u, skipped[4 * gq + 1] ? STRL_RES_SKIPPED : 0u,
+                                    skipped[4 * gq + 2] ? STRL_RES_SKIPPED : 0u, skipped[4 * gq + 3] ? STRL_RES_SKIPPED : 0u);
+        if constexpr (FULL) {
+          *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(P.whole + r0 + off) + 4u * classify_group_off(0u, (uint32_t)lane, (uint32_t)gq)) = w4;
         } else {
+          const uint64_t r = base + 256ull * gq + 4ull * lane;
+          if (r + 3 < r1) {
+            reinterpret_cast<uint4 *>(P.whole)[r >> 2] = w4;
+          } else {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) if (skipped[4 * gq + q]) P.whole[r + q] = STRL_RES_SKIPPED;
+            for (int q = 0; q < 4; ++q) if (skipped[4 * gq + q]) P.whole[r + q] = STRL_RES_SKIPPED;
+          }
         }
       }
     }
@@ -313,15 +367,36 @@ __global__ __launch_bounds__(256, 4) void classify_kernel(ScoreParams P) {
     for (int j = 0; j < CL_ILP; ++j) {
       const unsigned long long m = __ballot(need[j]);
       nskip += (uint32_t)__popcll(__ballot(skipped[j]));
-      if (need[j]) buf[cnt + __popcll(m & below)] = (uint32_t)ridx(base, j);
+      // (the lanes below this one that keep their read: mbcnt, two instructions)
+      const uint32_t slot = cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      if (need[j]) buf[slot] = FULL ? (uint32_t)r0 + classify_read_off(off, (uint32_t)lane, (uint32_t)j) : (uint32_t)ridx(base, j, lane);
       cnt += (uint32_t)__popcll(m);
     }
     if (cnt >= CL_STAGE) flush();
-#pragma unroll
-    for (int j = 0; j < NIN; ++j) cur[j] = nxt[j];
+  };
+  auto step = [&](uint64_t base, In (&cur)[NIN], In (&nxt)[NIN]) {
+    if constexpr (VEC) {
+      if (classify_full((uint32_t)(base - r0), len)) { turn(std::true_type{}, base, cur, nxt); return; }
+    }
+    turn(std::false_type{}, base, cur, nxt);
+  };
+  // Two register sets that swap roles from turn to turn: handing `nxt` over by copying it is a use of the loads just issued, and
+  // a wait for them (and for the stores behind them, which the same counter counts) in the turn that issued them.
+  In va[NIN], vb[NIN];
+  bool first_full = false;
+  if constexpr (VEC) first_full = classify_full(0u, len);
+  if (first_full) { if constexpr (VEC) load_full(0u, lane0, va); }
+  else load(r0, lane0, va);
+  // ONE ITERATION IS A PAIR OF TURNS: the turn at `base` (va -> vb), then, if the range goes on, the turn 64 * CL_ILP reads
+  // further (vb -> va), which advances `base` itself.  Every turn still starts at r0 + k * 64 * CL_ILP.
+  for (uint64_t base = r0; base < r1; base += 64 * CL_ILP) {
+    step(base, va, vb);
+    base += 64 * CL_ILP;          // the second turn of the pair: the sets the other way round
+    if (!(base < r1)) break;
+    step(base, vb, va);
   }
   flush();
-  if (lane == 0 && nskip) atomicAdd(&P.counters[CNT_SKIP], nskip);
+  if (lane0 == 0 && nskip) atomicAdd(&P.counters[CNT_SKIP], nskip);
 }
 
 // Order-preserving-within-block compaction of a dense array with EMPTY holes into a queue: one global atomic
@@ -1131,6 +1206,24 @@ int strl_score_reads(strl_ctx *c, const strl_read_soa *s, uint32_t *whole, strl_
   if (soft && ns) std::sort(soft, soft + ns, [](const strl_soft_rec &a, const strl_soft_rec &b) { return a.read_side < b.read_side; });
   if (n_soft) *n_soft = ns;
   if (stats) *stats = st;
+  return STRL_OK;
+}
+
+// test-only, undeclared (the strl_sort_probe precedent): the read ids classify_kernel queued in the context's last scoring pass,
+// in queue order, after a sync -> their number (all of them are counted, at most `cap` are copied)
+int strl_score_queue_probe(strl_ctx *c, uint32_t *ids, uint64_t cap, uint64_t *n_ids) {
+  if (!c || !n_ids || (cap && !ids)) { set_error("strl_score_queue_probe: bad argument"); return STRL_ERR_ARG; }
+  if (!c->counters.p || !c->queue_r.p) { set_error("strl_score_queue_probe: no scoring pass on this context"); return STRL_ERR_ARG; }
+  STRL_HIP(hipSetDevice(c->device));
+  uint32_t v = 0;
+  STRL_HIP(hipMemcpyAsync(&v, c->counters.as<uint32_t>() + CNT_QUEUE, 4, hipMemcpyDeviceToHost, c->stream));
+  STRL_HIP(hipStreamSynchronize(c->stream));
+  *n_ids = v;
+  const uint64_t m = std::min<uint64_t>(v, cap);
+  if (m) {
+    STRL_HIP(hipMemcpyAsync(ids, c->queue_r.p, m * 4, hipMemcpyDeviceToHost, c->stream));
+    STRL_HIP(hipStreamSynchronize(c->stream));
+  }
   return STRL_OK;
 }
 
